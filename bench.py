@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: mel-frames/s and 24 kHz RTF of the full synthesis path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2], the one the metric is quoted on): full text encoder -> flow decoder (CFM Euler/CFG,
 n_timesteps = 10) -> HiFT vocoder, batch 32 utterances per GPU, 150 tokens -> 300 mel frames = 6.0 s of 24 kHz audio
@@ -9,16 +9,21 @@ each, synthetic key-hashed weights and seeded inputs; fp32 data
 the 16-bit matrix cores at fp32-level accuracy: fp16x3 (operands scaled by an exact power of two and split into two fp16
 planes = 22 significant bits, three MFMA products) wherever an upper bound of the operand is proven at load time or
 measured on the device, bf16x6 (three bf16 planes = 24 bits, six products) elsewhere.  `value` is measured
-in that default mode; `value_exact_range` repeats the timed loop with every contraction on bf16x6
-(jv_flow_set_contraction(1)), and `parity` carries the default mode's measured error against the CPU oracle on the
-utterances the CPU baseline synthesises anyway.
+in that default mode.
 One "step" = one pass of that path over one batch; inputs are resident in HBM before the timed region.
 With N > 1 (launched by torch.distributed.run, one rank per GPU) each rank synthesises its own 32 utterances (weak
 scaling, no data-path collective) and the generated mels are all-gathered over RCCL at the end of every step.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel, measured with HIP events on the launch stream
-inside the timed region (jv_profile_*); `cpu_baseline` is the CPU oracle (a plain-PyTorch port of the reference path)
-timed on this box's host cores on a bounded sample -- reported, not a target.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): the headline and what follows from
+its wall time alone (`ms_per_step`, `rtf`, `roofline_path`).  --dump-outputs DIR writes what the last timed step returned
+(rank 0's mel, mel_lengths, waveform and source signal) as DIR/<name>.npy; the inputs depend on the arguments only.
+--full adds what needs work of its own: `roofline`, `kernels` and `conv_stack` from per-launch HIP events on the launch
+stream in the first timed step (jv_profile_*; `value` then carries their cost; --no-profile leaves them out),
+`value_exact_range` (the timed loop repeated with every contraction on bf16x6, jv_flow_set_contraction(1);
+--no-exact-range), `stage_ms` (three passes with events at the stage boundaries), `cpu_baseline` (the CPU oracle, a
+plain-PyTorch port of the reference path, timed on this box's host cores on a bounded sample -- reported, not a target;
+--no-cpu-baseline) and `parity` (the default mode's measured error against the CPU oracle on the utterances the CPU
+baseline synthesises anyway; a run outside the tolerance exits with status 3).
 """
 import argparse
 import json
@@ -191,6 +196,27 @@ def cpu_baseline(n_tokens: int, n_timesteps: int, repeats: int, hip=None):
     return out, parity
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """arrays {name: numpy array} -> out_dir/<name>.npy, floating point as float32 (float64 kept), integers as float64.
+    When they hold more than DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its elements: a sample of flat
+    indices drawn from a generator seeded with `seed` and the array's size, sorted -- the same elements on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: (v.astype(np.float64) if v.dtype.kind in "iub" or v.dtype == np.float64 else v.astype(np.float32))
+              for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    keep = min(1.0, (DUMP_LIMIT_BYTES - (1 << 16)) / total)      # (room for the .npy headers)
+    for name, v in arrays.items():
+        if keep < 1.0:
+            flat = v.reshape(-1)
+            idx = np.random.default_rng([seed, flat.size]).choice(flat.size, int(flat.size * keep), replace=False)
+            v = flat[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -202,12 +228,17 @@ def main():
     ap.add_argument("--workload", choices=("c3", "c2"), default="c3",
                     help="c3 (default, the headline): full encoder -> flow -> HiFT; c2: the CFM Euler loop alone on [B,80,T] "
                          "N(0,1) mu (BASELINE.json configs[1]: --workload c2 --batch 8 --tokens 256)")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what needs work of its own: per-kernel profile, bf16x6 loop, per-stage times, "
+                         "CPU baseline and parity against the CPU oracle (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MiB in all)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not record per-kernel HIP events in the timed region")
     ap.add_argument("--profile-steps", type=int, default=1,
                     help="how many of the K timed steps carry the per-launch HIP events (each event pair costs GPU time: all "
                          "steps instrumented lowers `value` by ~5 %%; one step gives ~1700 launches of the dominant kernel)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-exact-range", action="store_true", help="skip the second timed loop (bf16x6 everywhere)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no parity check")
+    ap.add_argument("--no-exact-range", action="store_true", help="with --full: skip the second timed loop (bf16x6 everywhere)")
     ap.add_argument("--cpu-utts", type=int, default=5, help="CPU-baseline runs per configuration (median of)")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --total-batch utterances over ALL ranks (BASELINE.json configs[4] as written: 256 over 8 "
@@ -218,6 +249,8 @@ def main():
                          "--tokens, so the padded shape is the equal-length run's); `value` counts VALID frames only")
     ap.add_argument("--ragged-min", type=int, default=60)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -314,7 +347,7 @@ def main():
     for _ in range(args.warmup):
         step()
 
-    profile = not args.no_profile
+    profile = args.full and not args.no_profile
     torch.cuda.synchronize(device)
     if profile:
         engine.profile_report()          # drop anything recorded during warm-up
@@ -332,12 +365,18 @@ def main():
         pair = kern.pop("_empty_event_pair", None)      # what an event pair measures around nothing
         if pair:
             event_overhead_us = 1e3 * pair["ms"]
+    dump = None
+    if args.dump_outputs and rank == 0:      # copied now: the passes below reuse the engine's output buffers
+        dump = {"mel": res["mel"]}
+        if args.workload == "c3":
+            dump.update(mel_lengths=res["mel_lengths"], wav=wav, source=src["s"])
+        dump = {k: v.detach().cpu().numpy() for k, v in dump.items()}
     hip_out = None
-    if args.workload == "c3" and rank == 0:
+    if args.full and args.workload == "c3" and rank == 0:
         hip_out = {"mel": res["mel"].float().cpu(), "wav": wav.float().cpu(), "s": src["s"].float().cpu()}
     # the same loop with every contraction on bf16x6 (24-bit operands): what the fp16x3 engine buys, measured, not claimed
     elapsed_exact = None
-    if not args.no_exact_range and not os.environ.get("JV_EXACT_RANGE"):
+    if args.full and not args.no_exact_range and not os.environ.get("JV_EXACT_RANGE"):
         rt_eng = get_runtime(device).ensure(B, T, Tt)
         rt_eng.set_exact_range(True)
         step()
@@ -354,7 +393,7 @@ def main():
     # per-stage GPU time (encoder + duration predictor + length regulation | CFM loop | HiFT): three more passes, outside the
     # timed region, with events on the launch stream at the stage boundaries; median
     stage_ms = None
-    if args.workload == "c3" and rank == 0:
+    if args.full and args.workload == "c3" and rank == 0:
         import statistics
         runs = []
         for _ in range(3):
@@ -497,11 +536,13 @@ def main():
             out["exact_range_note"] = ("the same timed loop, under the same conditions (first step instrumented), with every "
                                        "contraction on bf16x6 (24-bit operands, jv_flow_set_contraction(1)); `value` is the default fp16x3 mode")
         parity_ok = True
-        if world == 1 and not args.no_cpu_baseline and args.cpu_utts > 0 and args.workload == "c3" and not args.ragged:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.cpu_utts > 0 and args.workload == "c3" and not args.ragged:
             out["cpu_baseline"], parity = cpu_baseline(Tt, n_steps, args.cpu_utts, hip_out)
             if parity:
                 out["parity"] = parity
                 parity_ok = parity["ok"]
+        if dump is not None:
+            dump_outputs(args.dump_outputs, dump)
         print(json.dumps(out), flush=True)
         if not parity_ok:      # a throughput measured on results outside the tolerance is not a result
             sys.stderr.write("bench.py: parity against the CPU oracle is outside the tolerance -- see `parity` on the JSON line\n")

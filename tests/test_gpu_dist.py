@@ -85,7 +85,7 @@ def test_bench_script_runs_with_two_ranks(strong):
         pytest.fail("no GPU visible: the -m gpu tests must run on the MI355X box")
     import json
     port = _free_port()
-    flags = ["--gpus", "2", "--tokens", "20", "--timesteps", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-exact-range"]
+    flags = ["--gpus", "2", "--tokens", "20", "--timesteps", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-exact-range"]
     flags += ["--strong", "--total-batch", "6"] if strong else ["--batch", "3"]
     procs = []
     for rank in range(2):

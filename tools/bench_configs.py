@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py lines of the other configurations on ONE box (through gpurun, repo root):
     python tools/bench_configs.py [tag]      -> gpurun_out/bench_configs_<tag>.json   (committed as profiles/rNN_bench_configs.json)
-Every run is --no-cpu-baseline --no-exact-range --no-profile; a failed run is recorded with its stderr tail."""
+Every run is --full --no-cpu-baseline --no-exact-range --no-profile (for `stage_ms`); a failed run is recorded with its stderr tail."""
 import json
 import subprocess
 import sys
@@ -27,7 +27,7 @@ def main():
         env = dict(os.environ)
         if key == "ragged_uniform":
             env["JV_NO_COMPACT"] = "1"
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-exact-range", "--no-profile"] + flags.split()
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-exact-range", "--no-profile"] + flags.split()
         r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT)
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if r.returncode != 0 or not lines:
@@ -44,7 +44,7 @@ def main():
     dst = os.path.join(ROOT, "gpurun_out", f"bench_configs_{tag}.json")
     os.makedirs(os.path.dirname(dst), exist_ok=True)
     with open(dst, "w") as fh:
-        json.dump({"note": "bench.py lines of one build on one box, back to back; --no-cpu-baseline --no-exact-range --no-profile", "configs": out}, fh, indent=1)
+        json.dump({"note": "bench.py lines of one build on one box, back to back; --full --no-cpu-baseline --no-exact-range --no-profile", "configs": out}, fh, indent=1)
 
 
 if __name__ == "__main__":

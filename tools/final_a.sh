@@ -1,8 +1,9 @@
 #!/bin/bash
 # round artefacts, call A: the whole GPU suite on the final build, then the headline bench line
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
-mkdir -p gpurun_out/final
-(time timeout -k 10 1000 python -m pytest tests -m gpu -x -q) > gpurun_out/final/gputests.log 2>&1 || { tail -n 40 gpurun_out/final/gputests.log; exit 1; }
-tail -n 5 gpurun_out/final/gputests.log
-python bench.py > gpurun_out/final/bench.json 2> gpurun_out/final/bench.err || { tail -n 5 gpurun_out/final/bench.err; exit 1; }
-tail -c 1500 gpurun_out/final/bench.json
+OUT=${JV_OUT:-out}/final
+mkdir -p $OUT
+(time timeout -k 10 1000 python -m pytest tests -m gpu -x -q) > $OUT/gputests.log 2>&1 || { tail -n 40 $OUT/gputests.log; exit 1; }
+tail -n 5 $OUT/gputests.log
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -n 5 $OUT/bench.err; exit 1; }
+tail -c 1500 $OUT/bench.json

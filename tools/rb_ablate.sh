@@ -13,7 +13,7 @@ VALS=${@:-0 1 2 4 8 16 26}
 LIB=${JV_LIB:-$PWD/jyutvoice_amd/libjyutvoice_hip.tune.so}
 OUT=gpurun_out/rb_ablate_$TAG.txt
 : > $OUT
-B="--workload c2 --batch ${JV_BATCH:-32} --tokens 150 --timesteps 2 --steps 2 --warmup 1 --no-cpu-baseline --no-exact-range"
+B="--workload c2 --batch ${JV_BATCH:-32} --tokens 150 --timesteps 2 --steps 2 --warmup 1 --full --no-cpu-baseline --no-exact-range"
 for v in $VALS; do
   JYUTVOICE_HIP_LIB=$LIB JV_RB_ABLATE=$v python bench.py $B > gpurun_out/rb_ab.json 2> gpurun_out/rb_ab.err || { tail -5 gpurun_out/rb_ab.err; }
   python - $v >> $OUT <<'PY'
