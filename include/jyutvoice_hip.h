@@ -123,6 +123,19 @@ int jv_flow_contraction_info(const jv_context* ctx, int32_t* out, int n);
  * per-utterance loop of the batch-1-only reference. */
 int jv_cfm_solve(jv_context* ctx, const float* mu, const int32_t* lens, const float* spks, const float* cond, int B, int T,
                  int n_timesteps, float temperature, const float* t_span_host, float* mel, void* stream);
+/* jv_cfm_solve_prompted: the voice-cloning glue of JyutVoiceTTS.synthesise (jyutvoice_tts.py:213-244: mu = [prompt_h | mu_y],
+ * cond = [prompt_feat | 0], the solve over all p + y frames, `decoder_outputs[:, :, mel_len1:]`) around the same solver, for a
+ * batch in which EVERY utterance has a prompt of its own length -- defined as the batch-1 reference looped over the utterances,
+ * utterance b called with prompt_h[b, :p_b] and prompt_feat[b, :p_b].  Its sequence is p_b + y_b frames, the noise column j
+ * belongs to frame j of its own sequence, and mel[b, :, :y_b] receives frames p_b .. p_b + y_b - 1 (zeros behind y_b).
+ * mu_y, mel: [B,80,Ty]; y_lens, prompt_lens: [B] int32; prompt_h: [B,Ph,80], prompt_feat: [B,Pf,80] (batch, time, channel;
+ * 16-byte aligned; what lies behind p_b is not read); spks: [B,80].  All device pointers except t_span_host (as jv_cfm_solve).
+ * 0 <= prompt_lens[b] <= min(Ph, Pf) and 0 <= y_lens[b] <= Ty, else JV_ERR_ARG naming the utterance, before anything is
+ * launched (both vectors come down with the solve's one synchronisation); p_b = 0 is the unprompted solve of that utterance.
+ * The capacity of jv_create / jv_reserve applies to T = max_b(p_b + y_b). */
+int jv_cfm_solve_prompted(jv_context* ctx, const float* mu_y, const int32_t* y_lens, const float* prompt_h,
+                          const float* prompt_feat, const int32_t* prompt_lens, const float* spks, int B, int Ty, int Ph, int Pf,
+                          int n_timesteps, float temperature, const float* t_span_host, float* mel, void* stream);
 
 /* ---- prompt (voice-cloning) branch ---------------------------------------------------------------------
  * jv_prompt_encoder_fwd: FlowEncoder.forward of the reference's infer.py:35-83 -- Embedding(clamp(token, 0)) * mask ->
@@ -141,6 +154,15 @@ int jv_prompt_encoder_fwd(jv_context* ctx, const int64_t* tokens, const int64_t*
  * T = 1 + (n_samples - 480) / 480. */
 int jv_load_mel_basis(jv_context* ctx, const float* basis, int64_t numel, int on_device, void* stream);
 int jv_mel_spectrogram(jv_context* ctx, const float* wav, int B, int n_samples, float* mel, void* stream);
+/* jv_mel_spectrogram_ragged: the same front-end for recordings of different durations in one call -- the per-utterance loop of
+ * infer.py:166-186 (the reference extracts one prompt at a time).  wav: [B, n_samples], recording b is wav[b, :wav_lens[b]]
+ * (what lies behind it is not read); wav_lens: [B] int32 on the device, 720 < wav_lens[b] <= n_samples (else JV_ERR_ARG, naming
+ * the recording).  The reflect padding of 720 samples is taken at each recording's own end.  mel: [B, 80, Tmax],
+ * Tmax = 1 + (n_samples - 480) / 480, recording b in [:T_b], T_b = 1 + (wav_lens[b] - 480) / 480, zeros behind it;
+ * mel_lens: [B] int32 on the device, receives T_b.  The STFT / mel GEMMs run on the valid frames only.  Synchronises the
+ * stream once (the lengths are validated on the host). */
+int jv_mel_spectrogram_ragged(jv_context* ctx, const float* wav, const int32_t* wav_lens, int B, int n_samples, float* mel,
+                              int32_t* mel_lens, void* stream);
 
 /* ---- text encoder + duration predictor + length regulation ---------------------------------------------
  * jv_encoder_fwd: spk_embed_affine_layer(normalize(spk)) + TextEncoder.forward + DurationPredictor.forward

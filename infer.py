@@ -19,6 +19,10 @@ mel extractor.  Instead this CLI takes their outputs directly:
                              "prompt_wav_24k": "ref_24k.wav" (16-bit mono; its mel is extracted on the GPU as
                              infer.py:386 does) -- what infer.py:386-392 gets from --ref_audio; the prompt encoder
                              (--flow_encoder) then runs on the GPU exactly as infer.py:390-392 runs it
+                             A JSON *list* of such objects is synthesised as ONE batch, every utterance with its own
+                             prompt of its own length (or none); the results go to OUTPUT with _000, _001, ... before the
+                             extension.  Each utterance's prompt_h (2 frames per prompt token) and prompt mel are trimmed
+                             to the shorter of the two first: the batch takes one prompt length per utterance
     --synthetic N            no checkpoint / no tokens: N synthetic tokens, key-hashed weights (smoke / demo)
     --synthetic-prompt K     with --synthetic: also a synthetic K-token voice prompt through the prompt encoder
 
@@ -64,6 +68,73 @@ def read_wav_24k(path: str):
     if fmt is None or pcm is None or fmt[0] != 1 or fmt[1] != 1 or fmt[2] != 24000 or fmt[5] != 16:
         raise SystemExit(f"{path}: need 16-bit PCM, mono, 24 kHz (resample with the reference's front-end first)")
     return (torch.frombuffer(bytearray(pcm), dtype=torch.int16).float() / 32768.0).unsqueeze(0)
+
+
+def synthesise_list(toks, args, tts, hift, device):
+    """--tokens with a JSON list: all utterances in one batch through synthesise(batched=True, prompt_lengths=...)"""
+    import torch
+
+    from jyutvoice_amd.utils.prompt import pad_prompts
+    from jyutvoice_amd.utils.text import FIELDS, load_tokens_json
+    B = len(toks)
+    if B == 0:
+        raise SystemExit(f"{args.tokens}: empty list")
+    try:
+        ids = [load_tokens_json(t) for t in toks]
+    except ValueError as e:
+        raise SystemExit(str(e))
+    x_lengths = torch.cat([i["x_lengths"] for i in ids])
+    Tt = int(x_lengths.max())
+    batch = {k: torch.zeros(B, Tt, dtype=torch.int64) for k in FIELDS}
+    for b, i in enumerate(ids):
+        for k in FIELDS:
+            batch[k][b, : i[k].shape[1]] = i[k][0]
+    spk = torch.cat([torch.tensor(t["spk_embed"], dtype=torch.float32).view(1, 192) if "spk_embed" in t else torch.randn(1, 192)
+                     for t in toks])
+    # prompts: the prompt encoder on the ragged token batch, the prompt mels of all recordings in one ragged pass
+    empty = torch.zeros(0, 80)
+    feats, hs = [empty] * B, [empty] * B
+    with_prompt = [b for b, t in enumerate(toks) if "prompt_token" in t and ("prompt_feat" in t or "prompt_wav_24k" in t)]
+    if with_prompt:
+        from jyutvoice_amd.flow.encoder import load_flow_encoder
+        from jyutvoice_amd.utils.audio import extract_speech_feat_batch
+        print(f"Loading flow encoder from {args.flow_encoder}...")
+        flow_encoder = load_flow_encoder(args.flow_encoder, device)
+        plens = torch.tensor([len(toks[b]["prompt_token"]) for b in with_prompt], dtype=torch.int64)
+        ptok = torch.zeros(len(with_prompt), int(plens.max()), dtype=torch.int64)
+        for i, b in enumerate(with_prompt):
+            ptok[i, : plens[i]] = torch.tensor(toks[b]["prompt_token"], dtype=torch.int64)
+        h, h_len = flow_encoder(ptok, plens)
+        from_wav = [b for b in with_prompt if "prompt_wav_24k" in toks[b]]
+        if from_wav:
+            mel, mel_len = extract_speech_feat_batch([read_wav_24k(toks[b]["prompt_wav_24k"]) for b in from_wav], device)
+        for i, b in enumerate(with_prompt):
+            if b in from_wav:
+                j = from_wav.index(b)
+                f = mel[j, : int(mel_len[j])]
+            else:
+                f = torch.tensor(toks[b]["prompt_feat"], dtype=torch.float32).view(-1, 80)
+            n_h, n_f = 2 * int(plens[i]), f.shape[0]
+            p = min(n_h, n_f)
+            if n_h != n_f:
+                print(f"utterance {b}: prompt_h has {n_h} frames, the prompt mel {n_f}: both trimmed to {p}")
+            feats[b], hs[b] = f[:p].cpu(), h[i, :p].cpu()
+    prompt_feat, prompt_h, prompt_lengths = pad_prompts(feats, hs)
+
+    print(f"Running TTS synthesis of {B} utterances as one batch...")
+    start = time.time()
+    result = tts.synthesise(x=batch["x"], x_lengths=x_lengths, lang=batch["lang"], tone=batch["tone"], word_pos=batch["word_pos"],
+                            syllable_pos=batch["syllable_pos"], prompt_feat=prompt_feat, prompt_h=prompt_h, spk_embed=spk,
+                            n_timesteps=args.n_timesteps, length_scale=args.length_scale, batched=True,
+                            prompt_lengths=prompt_lengths)
+    wav, _ = hift.inference(result["mel"], lengths=result["mel_lengths"])
+    torch.cuda.synchronize()
+    print(f"Synthesis time: {time.time() - start:.2f} s (rtf of synthesise(): {result['rtf']:.4f})")
+    stem, ext = os.path.splitext(args.output)
+    for b, frames in enumerate(result["mel_lengths"].tolist()):
+        path = f"{stem}_{b:03d}{ext}"
+        write_wav(path, wav[b, : frames * 480])
+        print(f"Generated audio saved to: {path} ({frames * 480 / 24000:.2f} seconds)")
 
 
 def main(argv=None):
@@ -123,6 +194,9 @@ def main(argv=None):
         hift.load_state_dict(torch.load(args.hift, map_location="cpu"))
         from jyutvoice_amd.utils.text import load_tokens_json
         tok = json.load(open(args.tokens))
+        if isinstance(tok, list):
+            hift.manual_seed(args.seed)
+            return synthesise_list(tok, args, tts.eval().to(device), hift.eval().to(device), device)
         try:      # the contract of get_text (infer.py:189-206): equal lengths, ids inside the embedding tables, blanks in place
             ids = load_tokens_json(tok)
         except ValueError as e:

@@ -334,6 +334,16 @@ int jv_cfm_solve(jv_context* ctx, const float* mu, const int32_t* lens, const fl
                        static_cast<hipStream_t>(stream));
 }
 
+int jv_cfm_solve_prompted(jv_context* ctx, const float* mu_y, const int32_t* y_lens, const float* prompt_h,
+                          const float* prompt_feat, const int32_t* prompt_lens, const float* spks, int B, int Ty, int Ph, int Pf,
+                          int n_timesteps, float temperature, const float* t_span_host, float* mel, void* stream) {
+  CTX_GUARD(ctx);
+  if (!mu_y || !y_lens || !prompt_lens || !spks || !mel) return jv::fail(JV_ERR_ARG, "jv_cfm_solve_prompted: null tensor");
+  if ((Ph > 0 && !prompt_h) || (Pf > 0 && !prompt_feat)) return jv::fail(JV_ERR_ARG, "jv_cfm_solve_prompted: null prompt tensor");
+  return jv::cfm_solve_prompted(ctx->c, mu_y, y_lens, prompt_h, prompt_feat, prompt_lens, spks, B, Ty, Ph, Pf, n_timesteps,
+                                temperature, t_span_host, mel, static_cast<hipStream_t>(stream));
+}
+
 // ---- operator-level entry points -------------------------------------------------------------------
 int jv_op_conv_gemm(const float* A, int64_t a_rows, int M, int Cin, int ntaps, int tap_row0, int dil, const float* W, int N,
                     const float* bias, int act, int prologue, const float* alpha, float slope, const float* ln_g,

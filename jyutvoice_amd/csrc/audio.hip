@@ -7,6 +7,7 @@
 // [961 -> 80] mel projection with the log in its epilogue.  The mel filterbank is data supplied by the host
 // (jv_load_mel_basis): in the reference it comes from librosa, which is not part of this build.
 #include <math.h>
+#include <stdio.h>
 
 #include "../../include/jyutvoice_hip.h"
 #include "jv_model.h"
@@ -26,12 +27,17 @@ struct AudioWs {
   long rows = 0;
   std::vector<void*> allocs, ws;
   float *frames = nullptr, *spec = nullptr, *mag = nullptr, *out = nullptr;
+  // jv_mel_spectrogram_ragged: [nb] frame counts and [nb + 1] first rows, pinned host staging and their device copies
+  int meta_nb = 0;
+  int *h_meta = nullptr, *d_meta = nullptr;
 };
 
 void audio_ws_destroy(Context& c) {
   if (!c.aws) return;
   for (void* p : c.aws->allocs) (void)hipFree(p);
   for (void* p : c.aws->ws) (void)hipFree(p);
+  if (c.aws->h_meta) (void)hipHostFree(c.aws->h_meta);
+  if (c.aws->d_meta) (void)hipFree(c.aws->d_meta);
   delete c.aws;
   c.aws = nullptr;
 }
@@ -66,6 +72,26 @@ __global__ __launch_bounds__(256) void frame_rows_kernel(const float* __restrict
   if (j < 0) j = -j;
   if (j >= n) j = 2 * (n - 1) - j;
   frames[idx] = wav[(long)b * n + j];
+}
+
+// the ragged form: recording b is wav[b, :lens[b]] and owns rows off[b] .. off[b + 1] - 1 (its own frames, back to back); the
+// reflect padding is taken at ITS end.  lens were validated on the host (720 < lens[b] <= n); the index is clamped all the same.
+__global__ __launch_bounds__(256) void frame_rows_ragged_kernel(const float* __restrict__ wav, float* __restrict__ frames, int B,
+                                                                int n, const int* __restrict__ lens, const int* __restrict__ off) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)off[B] * A_NFFT) return;
+  const int i = (int)(idx % A_NFFT);
+  const int row = (int)(idx / A_NFFT);
+  int lo = 0, hi = B - 1;      // the last recording whose first row is <= row (recordings without frames do not exist: T_b >= 1)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= row) lo = mid; else hi = mid - 1;
+  }
+  const int nb = min(lens[lo], n);
+  int j = (row - off[lo]) * A_HOP + i - A_PAD;
+  if (j < 0) j = -j;
+  if (j >= nb) j = 2 * (nb - 1) - j;
+  frames[idx] = wav[(long)lo * n + min(max(j, 0), n - 1)];
 }
 
 // mag[row][k] = sqrt(re^2 + im^2 + 1e-9) for k < 961, zero for the K padding 961 <= k < 992
@@ -129,15 +155,11 @@ int load_mel_basis(Context& c, const float* data, bool on_device, hipStream_t st
   return JV_OK;
 }
 
-int mel_spectrogram(Context& c, const float* wav, int B, int n, float* mel, hipStream_t st) {
-  AudioWs& w = get(c);
-  if (!w.mel_loaded) return fail(JV_ERR_STATE, "mel filterbank not loaded (jv_load_mel_basis)");
-  if (B < 1 || n <= A_PAD || n < A_NFFT - 2 * A_PAD)
-    return fail(JV_ERR_ARG, "jv_mel_spectrogram: need more than 720 samples per utterance (reflect padding)");
-  const int T = 1 + (n + 2 * A_PAD - A_NFFT) / A_HOP;
-  const long rows = (long)B * T;
-  if (rows > (1L << 22)) return fail(JV_ERR_SHAPE, "jv_mel_spectrogram: too many frames");
-  if (!w.dft.w) {      // first call: build the windowed DFT basis and its bf16x6 planes
+namespace {
+
+// first call: the windowed DFT basis and its bf16x6 planes; workspace for `rows` frames
+int mel_prepare(AudioWs& w, long rows, hipStream_t st) {
+  if (!w.dft.w) {
     void* d = nullptr;
     JV_TRY(dev_alloc(w, w.allocs, &d, sizeof(float) * A_NDFT * A_NFFT));
     hipLaunchKernelGGL(dft_basis_kernel, dim3((unsigned)cdivl((long)A_NDFT * A_NFFT, 256)), dim3(256), 0, st,
@@ -157,7 +179,11 @@ int mel_spectrogram(Context& c, const float* wav, int B, int n, float* mel, hipS
     JV_TRY(dev_alloc(w, w.ws, reinterpret_cast<void**>(&w.out), R * A_NMEL * sizeof(float)));
     w.rows = (long)R;
   }
-  hipLaunchKernelGGL(frame_rows_kernel, dim3((unsigned)cdivl(rows * A_NFFT, 256)), dim3(256), 0, st, wav, w.frames, B, n, T);
+  return JV_OK;
+}
+
+// w.frames [rows, 1920] -> w.out [rows, 80]: DFT GEMM, magnitude, mel GEMM with the log in its epilogue
+int mel_rows(AudioWs& w, long rows, hipStream_t st) {
   ConvGemmArgs a;
   conv_gemm_defaults(a);
   a.A = w.frames; a.lda = A_NFFT; a.a_rows = rows; a.M = (int)rows; a.Cin = A_NFFT; a.ntaps = 1;
@@ -172,7 +198,72 @@ int mel_spectrogram(Context& c, const float* wav, int B, int n, float* mel, hipS
   a.act = ACT_LOGCLIP;
   JV_TRY(conv_gemm(a, 1, st));
   JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
+}  // namespace
+
+int mel_spectrogram(Context& c, const float* wav, int B, int n, float* mel, hipStream_t st) {
+  AudioWs& w = get(c);
+  if (!w.mel_loaded) return fail(JV_ERR_STATE, "mel filterbank not loaded (jv_load_mel_basis)");
+  if (B < 1 || n <= A_PAD || n < A_NFFT - 2 * A_PAD)
+    return fail(JV_ERR_ARG, "jv_mel_spectrogram: need more than 720 samples per utterance (reflect padding)");
+  const int T = 1 + (n + 2 * A_PAD - A_NFFT) / A_HOP;
+  const long rows = (long)B * T;
+  if (rows > (1L << 22)) return fail(JV_ERR_SHAPE, "jv_mel_spectrogram: too many frames");
+  JV_TRY(mel_prepare(w, rows, st));
+  hipLaunchKernelGGL(frame_rows_kernel, dim3((unsigned)cdivl(rows * A_NFFT, 256)), dim3(256), 0, st, wav, w.frames, B, n, T);
+  JV_TRY(mel_rows(w, rows, st));
   return rows_to_cf(w.out, A_NMEL, 0, 0, T, mel, (long)A_NMEL * T, B, A_NMEL, T, nullptr, st);
+}
+
+// Recordings of different durations in one [B, n] buffer: recording b is wav[b, :n_b] and yields T_b = 1 + (n_b - 480) / 480
+// frames, the reflect padding taken at its own end; the GEMMs run on the valid frames' rows only (recording b's rows follow
+// recording b - 1's).  mel is [B, 80, Tmax], Tmax = 1 + (n - 480) / 480, zero behind T_b; mel_lens receives T_b.
+// One synchronisation: the lengths come down to be validated and to lay out the rows.
+int mel_spectrogram_ragged(Context& c, const float* wav, const int* wav_lens, int B, int n, float* mel, int* mel_lens,
+                           hipStream_t st) {
+  AudioWs& w = get(c);
+  if (!w.mel_loaded) return fail(JV_ERR_STATE, "mel filterbank not loaded (jv_load_mel_basis)");
+  if (B < 1 || n <= A_PAD || n < A_NFFT - 2 * A_PAD)
+    return fail(JV_ERR_ARG, "jv_mel_spectrogram_ragged: need more than 720 samples per utterance (reflect padding)");
+  const int Tmax = 1 + (n + 2 * A_PAD - A_NFFT) / A_HOP;
+  if ((long)B * Tmax > (1L << 22)) return fail(JV_ERR_SHAPE, "jv_mel_spectrogram_ragged: too many frames");
+  if (B > w.meta_nb) {
+    JV_HIP(hipDeviceSynchronize());
+    if (w.h_meta) (void)hipHostFree(w.h_meta);
+    if (w.d_meta) (void)hipFree(w.d_meta);
+    w.h_meta = w.d_meta = nullptr;
+    w.meta_nb = 0;
+    JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w.h_meta), (size_t)(3 * B + 1) * sizeof(int), hipHostMallocDefault));
+    JV_HIP(hipMalloc(reinterpret_cast<void**>(&w.d_meta), (size_t)(2 * B + 1) * sizeof(int)));
+    w.meta_nb = B;
+  }
+  // h_meta: [B] frame counts | [B + 1] first rows | [B] the sample counts as they came down
+  int *h_T = w.h_meta, *h_off = w.h_meta + B, *h_n = w.h_meta + 2 * B + 1;
+  JV_HIP(hipMemcpyAsync(h_n, wav_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  JV_HIP(hipStreamSynchronize(st));      // (also: the previous call's upload from h_meta has been consumed)
+  long rows = 0;
+  for (int b = 0; b < B; ++b) {
+    if (h_n[b] <= A_PAD || h_n[b] > n) {
+      char msg[160];
+      snprintf(msg, sizeof msg, "jv_mel_spectrogram_ragged: recording %d: %d samples, need more than 720 (reflect padding) and at most n = %d",
+               b, h_n[b], n);
+      return fail(JV_ERR_ARG, msg);
+    }
+    h_T[b] = 1 + (h_n[b] + 2 * A_PAD - A_NFFT) / A_HOP;
+    h_off[b] = (int)rows;
+    rows += h_T[b];
+  }
+  h_off[B] = (int)rows;
+  JV_TRY(mel_prepare(w, rows, st));
+  int *d_T = w.d_meta, *d_off = w.d_meta + B;
+  JV_HIP(hipMemcpyAsync(w.d_meta, w.h_meta, sizeof(int) * (2 * B + 1), hipMemcpyHostToDevice, st));      // (pinned: stays valid)
+  JV_HIP(hipMemcpyAsync(mel_lens, d_T, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(frame_rows_ragged_kernel, dim3((unsigned)cdivl(rows * A_NFFT, 256)), dim3(256), 0, st, wav, w.frames, B, n,
+                     wav_lens, d_off);
+  JV_TRY(mel_rows(w, rows, st));
+  return rows_to_cf(w.out, A_NMEL, 0, 0, 0, mel, (long)A_NMEL * Tmax, B, A_NMEL, Tmax, d_T, st, d_off);
 }
 
 }  // namespace jv
@@ -190,6 +281,13 @@ int jv_mel_spectrogram(jv_context* ctx, const float* wav, int B, int n_samples, 
   if (!ctx || !wav || !mel) return jv::fail(JV_ERR_ARG, "jv_mel_spectrogram: null argument");
   JV_HIP(hipSetDevice(ctx->c.device));
   return jv::mel_spectrogram(ctx->c, wav, B, n_samples, mel, static_cast<hipStream_t>(stream));
+}
+
+int jv_mel_spectrogram_ragged(jv_context* ctx, const float* wav, const int32_t* wav_lens, int B, int n_samples, float* mel,
+                              int32_t* mel_lens, void* stream) {
+  if (!ctx || !wav || !wav_lens || !mel || !mel_lens) return jv::fail(JV_ERR_ARG, "jv_mel_spectrogram_ragged: null argument");
+  JV_HIP(hipSetDevice(ctx->c.device));
+  return jv::mel_spectrogram_ragged(ctx->c, wav, wav_lens, B, n_samples, mel, mel_lens, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -63,6 +63,7 @@ struct FlowWs {
   // h_lens / h_uoff: pinned host staging (the lengths come down with the solve's one synchronisation, the offsets go up async)
   int* uoff = nullptr;
   int *h_lens = nullptr, *h_uoff = nullptr;
+  int* h_sum = nullptr;     // cfm_solve_prompted: p_b + y_b of every utterance and its CFG twin, [2*maxB] (pinned; goes up to lens2)
   int max_steps = 1024;
   // One Euler step (step scalars -> input assembly -> estimator -> CFG update) captured as a hipGraph per (B, T,
   // attention mode): the step reads its (t, dt) through a device-side counter, so one executable graph replays for
@@ -123,6 +124,7 @@ int flow_ws_create(Context& c) {
   JV_TRY(ws_alloc(c, (size_t)(B2 + 1) * sizeof(int), reinterpret_cast<void**>(&w->uoff)));
   JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->h_lens), (size_t)B2 * sizeof(int), hipHostMallocDefault));
   JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->h_uoff), (size_t)(B2 + 1) * sizeof(int), hipHostMallocDefault));
+  JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->h_sum), (size_t)B2 * sizeof(int), hipHostMallocDefault));
   JV_TRY(ws_alloc(c, sizeof(int), reinterpret_cast<void**>(&w->step_ctr)));
   JV_TRY(F(&w->t_cur, 1));
   JV_TRY(F(&w->dt_cur, 1));
@@ -766,18 +768,19 @@ int flow_estimator(Context& c, const float* x, const int* lens_dev, const float*
   return rows_to_cf(w.d, 80, 0, FLOW_G, g.S, out, 80L * T, B2, 80, T, nullptr, st);
 }
 
-int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spks, const float* cond, int B, int T,
-              int n_timesteps, float temperature, const float* t_span_host, float* mel, hipStream_t st) {
-  JV_TRY(check_shape(c, 2 * B, T));
-  if (!c.noise_loaded) return fail(JV_ERR_STATE, "CFM noise tensor not loaded (jv_load_noise)");
-  if (T > NOISE_FRAMES) return fail(JV_ERR_SHAPE, "more frames than the fixed noise tensor holds (15000)");
-  FlowWs& w = *c.flow;
-  if (n_timesteps < 1 || n_timesteps > w.max_steps) return fail(JV_ERR_ARG, "n_timesteps out of range");
-  const int B2 = 2 * B;
-  Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, nullptr, 0};
+namespace {
 
+// ---- the three parts of a solve that cfm_solve and cfm_solve_prompted share: schedule, geometry, Euler loop ----------------
+// The entries differ in what they pack into the row buffers before the loop and in what they unpack after it.
+
+// (t, dt) of every step -> w.t_table / w.dt_table.  tt / dts are the caller's: pageable staging that must live until the
+// solve's one synchronisation has consumed the copies.
+int solve_schedule(FlowWs& w, int n_timesteps, const float* t_span_host, std::vector<float>& tt, std::vector<float>& dts,
+                   hipStream_t st) {
+  std::vector<float> ts(n_timesteps + 1);
+  tt.resize(n_timesteps);
+  dts.resize(n_timesteps);
   // cosine schedule and the reference's running (t, dt) recurrence, in fp32 (flow_matching.py:230,260-263,387-389)
-  std::vector<float> ts(n_timesteps + 1), tt(n_timesteps), dts(n_timesteps);
   if (t_span_host) {
     for (int i = 0; i <= n_timesteps; ++i) ts[i] = t_span_host[i];
   } else {
@@ -799,43 +802,34 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
   }
   JV_HIP(hipMemcpyAsync(w.t_table, tt.data(), sizeof(float) * n_timesteps, hipMemcpyHostToDevice, st));
   JV_HIP(hipMemcpyAsync(w.dt_table, dts.data(), sizeof(float) * n_timesteps, hipMemcpyHostToDevice, st));
-  // Ragged batch?  The lengths come down with the synchronisation below (which the staging vectors need anyway): B ints.
-  const bool ragged_candidate = lens_dev && B > 1 && flow_compact_ok(c, g.M);
-  if (ragged_candidate) JV_HIP(hipMemcpyAsync(w.h_lens, lens_dev, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-  // pageable-host staging vectors die at scope exit: make sure the copies have been consumed
-  JV_HIP(hipStreamSynchronize(st));
-  // COMPACT geometry: every utterance (and its CFG twin) gets its own frames + the gap, nothing is padded to the longest;
-  // taken when it saves at least 8 % of the rows and the shorter batch still fills the row-owning kernels.  All per-row
-  // arithmetic is the uniform geometry's (a row's sums do not depend on where the row sits): the same bits per utterance.
-  if (ragged_candidate) {
-    long r = FLOW_G, frames = 0;
-    for (int b2 = 0; b2 < B2; ++b2) {
-      const int len = std::min(std::max(w.h_lens[b2 % B], 0), T);
-      w.h_uoff[b2] = (int)r;
-      r += len + FLOW_GAP;
-      frames += len;
-    }
-    w.h_uoff[B2] = (int)r;
-    if (r * 100 <= g.M * 92 && flow_compact_ok(c, r)) {
-      JV_HIP(hipMemcpyAsync(w.uoff, w.h_uoff, sizeof(int) * (B2 + 1), hipMemcpyHostToDevice, st));      // (pinned: stays valid)
-      g.M = r; g.uoff = w.uoff; g.alg_rows = frames;
-    }
-  }
+  return JV_OK;
+}
 
-  // per-solve preparation: lengths (duplicated for the CFG twin rows), masks, row-layout mu / cond / z
-  if (lens_dev) {
-    JV_HIP(hipMemcpyAsync(w.lens2, lens_dev, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
-    JV_HIP(hipMemcpyAsync(w.lens2 + B, lens_dev, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
-  } else {
-    JV_TRY(fill_int(w.lens2, T, B2, st));
+// COMPACT geometry: every utterance (and its CFG twin) gets its own frames + the gap, nothing is padded to the longest;
+// taken when it saves at least 8 % of the rows and the shorter batch still fills the row-owning kernels.  All per-row
+// arithmetic is the uniform geometry's (a row's sums do not depend on where the row sits): the same bits per utterance.
+// h_lens: the B sequence lengths on the host (after the solve's synchronisation).
+int solve_compact(Context& c, Geo& g, const int* h_lens, int B, int T, hipStream_t st) {
+  FlowWs& w = *c.flow;
+  const int B2 = 2 * B;
+  long r = FLOW_G, frames = 0;
+  for (int b2 = 0; b2 < B2; ++b2) {
+    const int len = std::min(std::max(h_lens[b2 % B], 0), T);
+    w.h_uoff[b2] = (int)r;
+    r += len + FLOW_GAP;
+    frames += len;
   }
-  const int* const clens = g.uoff ? w.lens2 : nullptr;      // (compact: only an utterance's own frames are written)
-  JV_TRY(row_meta(w.rowmask, w.row_sample, w.lens2, B2, 1, FLOW_G, g.S, T, w.rows_alloc, 1, 0, st, g.uoff));
-  JV_TRY(cf_to_rows(mu, 80L * T, T, B, 80, T, w.mu, 80, 0, FLOW_G, g.S, 1.f, clens, st, g.uoff));
-  JV_TRY(cf_to_rows(cond, 80L * T, T, B, 80, T, w.cond, 80, 0, FLOW_G, g.S, 1.f, clens, st, g.uoff));
-  // z = rand_noise[:, :, :T] * temperature, the same prefix for every utterance (flow_matching.py:385)
-  JV_TRY(cf_to_rows(c.noise, 0, NOISE_FRAMES, B, 80, T, w.x, 80, 0, FLOW_G, g.S, temperature, clens, st, g.uoff));
+  w.h_uoff[B2] = (int)r;
+  if (r * 100 <= g.M * 92 && flow_compact_ok(c, r)) {
+    JV_HIP(hipMemcpyAsync(w.uoff, w.h_uoff, sizeof(int) * (B2 + 1), hipMemcpyHostToDevice, st));      // (pinned: stays valid)
+    g.M = r; g.uoff = w.uoff; g.alg_rows = frames;
+  }
+  return JV_OK;
+}
 
+// the Euler loop on packed row buffers (w.mu, w.cond, w.x = z, w.lens2, row metadata): the result is left in w.x
+int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timesteps, hipStream_t st) {
+  FlowWs& w = *c.flow;
   JV_HIP(hipMemsetAsync(w.step_ctr, 0, sizeof(int), st));
   JV_HIP(hipMemsetAsync(w.amax, 0, sizeof(float) * 3 * w.amax_stride, st));      // trunk bounds: maxima over the whole solve
   JV_HIP(hipMemcpyAsync(w.spks, spks, sizeof(float) * 80 * B, hipMemcpyDeviceToDevice, st));
@@ -929,7 +923,105 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
       fprintf(stderr, "\n");
     }
   }
+  return JV_OK;
+}
+
+}  // namespace
+
+int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spks, const float* cond, int B, int T,
+              int n_timesteps, float temperature, const float* t_span_host, float* mel, hipStream_t st) {
+  JV_TRY(check_shape(c, 2 * B, T));
+  if (!c.noise_loaded) return fail(JV_ERR_STATE, "CFM noise tensor not loaded (jv_load_noise)");
+  if (T > NOISE_FRAMES) return fail(JV_ERR_SHAPE, "more frames than the fixed noise tensor holds (15000)");
+  FlowWs& w = *c.flow;
+  if (n_timesteps < 1 || n_timesteps > w.max_steps) return fail(JV_ERR_ARG, "n_timesteps out of range");
+  const int B2 = 2 * B;
+  Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, nullptr, 0};
+
+  std::vector<float> tt, dts;
+  JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
+  // Ragged batch?  The lengths come down with the synchronisation below (which the staging vectors need anyway): B ints.
+  const bool ragged_candidate = lens_dev && B > 1 && flow_compact_ok(c, g.M);
+  if (ragged_candidate) JV_HIP(hipMemcpyAsync(w.h_lens, lens_dev, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  // pageable-host staging vectors die at scope exit: make sure the copies have been consumed
+  JV_HIP(hipStreamSynchronize(st));
+  if (ragged_candidate) JV_TRY(solve_compact(c, g, w.h_lens, B, T, st));
+
+  // pack: lengths (duplicated for the CFG twin rows), masks, row-layout mu / cond / z
+  if (lens_dev) {
+    JV_HIP(hipMemcpyAsync(w.lens2, lens_dev, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
+    JV_HIP(hipMemcpyAsync(w.lens2 + B, lens_dev, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
+  } else {
+    JV_TRY(fill_int(w.lens2, T, B2, st));
+  }
+  const int* const clens = g.uoff ? w.lens2 : nullptr;      // (compact: only an utterance's own frames are written)
+  JV_TRY(row_meta(w.rowmask, w.row_sample, w.lens2, B2, 1, FLOW_G, g.S, T, w.rows_alloc, 1, 0, st, g.uoff));
+  JV_TRY(cf_to_rows(mu, 80L * T, T, B, 80, T, w.mu, 80, 0, FLOW_G, g.S, 1.f, clens, st, g.uoff));
+  JV_TRY(cf_to_rows(cond, 80L * T, T, B, 80, T, w.cond, 80, 0, FLOW_G, g.S, 1.f, clens, st, g.uoff));
+  // z = rand_noise[:, :, :T] * temperature, the same prefix for every utterance (flow_matching.py:385)
+  JV_TRY(cf_to_rows(c.noise, 0, NOISE_FRAMES, B, 80, T, w.x, 80, 0, FLOW_G, g.S, temperature, clens, st, g.uoff));
+
+  JV_TRY(solve_loop(c, g, spks, B, T, n_timesteps, st));
+  // unpack
   return rows_to_cf(w.x, 80, 0, FLOW_G, g.S, mel, 80L * T, B, 80, T, lens_dev ? w.lens2 : nullptr, st, g.uoff);
+}
+
+// The voice-cloning batch: utterance b's sequence is [prompt_b | text_b], p_b + y_b frames, with its own split point
+// (jyutvoice_tts.py:213-244 looped over the utterances).  The same schedule, geometry rule and Euler loop as cfm_solve on the
+// summed lengths; only the pack (prompt rows copied frame-major, text rows transposed from mu_y, cond zero behind the prompt)
+// and the unpack (frames p_b .. p_b + y_b - 1, left-aligned) are its own.
+int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const float* prompt_h, const float* prompt_feat,
+                       const int* prompt_lens, const float* spks, int B, int Ty, int Ph, int Pf, int n_timesteps,
+                       float temperature, const float* t_span_host, float* mel, hipStream_t st) {
+  if (!c.ready[MODEL_TTS]) return fail(JV_ERR_STATE, "tts weights not finalized");
+  if (B < 1 || Ty < 1 || Ph < 0 || Pf < 0) return fail(JV_ERR_ARG, "jv_cfm_solve_prompted: B, Ty must be positive, Ph, Pf non-negative");
+  if (B > c.max_batch) return fail(JV_ERR_SHAPE, "batch/frames exceed the capacity given to jv_create");
+  if (!c.noise_loaded) return fail(JV_ERR_STATE, "CFM noise tensor not loaded (jv_load_noise)");
+  FlowWs& w = *c.flow;
+  if (n_timesteps < 1 || n_timesteps > w.max_steps) return fail(JV_ERR_ARG, "n_timesteps out of range");
+  if ((reinterpret_cast<uintptr_t>(prompt_h) | reinterpret_cast<uintptr_t>(prompt_feat)) & 15)
+    return fail(JV_ERR_ARG, "jv_cfm_solve_prompted: prompt_h / prompt_feat must be 16-byte aligned");
+  const int B2 = 2 * B, Pmax = std::min(Ph, Pf);
+
+  std::vector<float> tt, dts;
+  JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
+  // both length vectors always come down (2B ints): they are validated here, before anything is launched on them
+  JV_HIP(hipMemcpyAsync(w.h_lens, y_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  JV_HIP(hipMemcpyAsync(w.h_lens + B, prompt_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  JV_HIP(hipStreamSynchronize(st));
+  // An over-long length would put one utterance's prompt rows into its neighbour's causal context (row_meta's compact
+  // branch does not clamp lens[b] > T): rejected here, on the host.
+  int T = 0;
+  for (int b = 0; b < B; ++b) {
+    const int y = w.h_lens[b], p = w.h_lens[B + b];
+    char msg[160];
+    if (p < 0 || p > Pmax) {
+      snprintf(msg, sizeof msg, "jv_cfm_solve_prompted: utterance %d: prompt length %d outside [0, min(Ph, Pf) = %d]", b, p, Pmax);
+      return fail(JV_ERR_ARG, msg);
+    }
+    if (y < 0 || y > Ty) {
+      snprintf(msg, sizeof msg, "jv_cfm_solve_prompted: utterance %d: %d frames outside [0, Ty = %d]", b, y, Ty);
+      return fail(JV_ERR_ARG, msg);
+    }
+    w.h_sum[b] = w.h_sum[B + b] = p + y;
+    T = std::max(T, p + y);
+  }
+  JV_TRY(check_shape(c, B2, T));
+  if (T > NOISE_FRAMES) return fail(JV_ERR_SHAPE, "more frames than the fixed noise tensor holds (15000)");
+  Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, nullptr, 0};
+  if (B > 1 && flow_compact_ok(c, g.M)) JV_TRY(solve_compact(c, g, w.h_sum, B, T, st));
+
+  // pack
+  JV_HIP(hipMemcpyAsync(w.lens2, w.h_sum, sizeof(int) * B2, hipMemcpyHostToDevice, st));      // (pinned: stays valid)
+  const int* const clens = g.uoff ? w.lens2 : nullptr;
+  JV_TRY(row_meta(w.rowmask, w.row_sample, w.lens2, B2, 1, FLOW_G, g.S, T, w.rows_alloc, 1, 0, st, g.uoff));
+  JV_TRY(pack_prompted(mu_y, Ty, prompt_h, Ph, prompt_feat, Pf, prompt_lens, w.lens2, B, T, w.mu, w.cond, FLOW_G, g.S, st, g.uoff));
+  // z = rand_noise[:, :, :p_b + y_b] * temperature: column j is frame j of the utterance's own sequence (flow_matching.py:385)
+  JV_TRY(cf_to_rows(c.noise, 0, NOISE_FRAMES, B, 80, T, w.x, 80, 0, FLOW_G, g.S, temperature, clens, st, g.uoff));
+
+  JV_TRY(solve_loop(c, g, spks, B, T, n_timesteps, st));
+  // unpack: the generated frames only (jyutvoice_tts.py:244 `decoder_outputs[:, :, mel_len1:]`), zeros behind y_b
+  return rows_to_cf_from(w.x, 80, FLOW_G, g.S, prompt_lens, y_lens, mel, 80L * Ty, B, 80, Ty, st, g.uoff);
 }
 
 }  // namespace jv
@@ -943,6 +1035,7 @@ void flow_ws_destroy(Context& c) {
     if (c.flow->ev_out) (void)hipEventDestroy(c.flow->ev_out);
     if (c.flow->h_lens) (void)hipHostFree(c.flow->h_lens);
     if (c.flow->h_uoff) (void)hipHostFree(c.flow->h_uoff);
+    if (c.flow->h_sum) (void)hipHostFree(c.flow->h_sum);
   }
   delete c.flow;
   c.flow = nullptr;

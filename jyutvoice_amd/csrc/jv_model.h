@@ -191,6 +191,9 @@ int flow_estimator(Context& c, const float* x, const int* lens_dev, const float*
                    const float* cond, int B2, int T, float* out, hipStream_t st, const float* mask_f32 = nullptr);
 int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spks, const float* cond, int B, int T,
               int n_timesteps, float temperature, const float* t_span_host, float* mel, hipStream_t st);
+int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const float* prompt_h, const float* prompt_feat,
+                       const int* prompt_lens, const float* spks, int B, int Ty, int Ph, int Pf, int n_timesteps,
+                       float temperature, const float* t_span_host, float* mel, hipStream_t st);
 
 // prompt.hip
 int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int Tk, float* h_out, hipStream_t st);

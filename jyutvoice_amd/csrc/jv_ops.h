@@ -13,6 +13,12 @@ int cf_to_rows(const float* src, long src_bstride, long pitch, int B, int C, int
                int S, float scale, const int* lens, hipStream_t st, const int* uoff = nullptr);
 int rows_to_cf(const float* src, int ld, int col0, int G, int S, float* dst, long dst_bstride, int B, int C, int T,
                const int* lens, hipStream_t st, const int* uoff = nullptr);
+// cfm_solve_prompted's pack and unpack (rowops.hip): row-layout mu / cond of [prompt_b | text_b] sequences in one launch; the
+// generated frames first[b] .. first[b] + lens[b] - 1 back to channels-first, zero-filled to T
+int pack_prompted(const float* mu_y, int Ty, const float* prompt_h, int Ph, const float* prompt_feat, int Pf, const int* plens,
+                  const int* sums, int B, int T, float* mu, float* cond, int G, int S, hipStream_t st, const int* uoff = nullptr);
+int rows_to_cf_from(const float* src, int ld, int G, int S, const int* first, const int* lens, float* dst, long dst_bstride,
+                    int B, int C, int T, hipStream_t st, const int* uoff = nullptr);
 int assemble_xin(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int G, int S,
                  int L, long rows2, hipStream_t st, const int* uoff = nullptr, const int* row_sample = nullptr,
                  const unsigned char* rowmask = nullptr);

@@ -404,6 +404,88 @@ int rows_to_cf(const float* src, int ld, int col0, int G, int S, float* dst, lon
   return JV_OK;
 }
 
+// ---- voice-cloning batch (flow.hip cfm_solve_prompted): utterance b's sequence is [prompt_b | text_b] ----------------------
+// pack: one launch writes the row-layout mu AND cond of all utterances.  Frame t < p_b copies prompt_h[b, t, :] and
+// prompt_feat[b, t, :] (frame-major already: 16-byte row copies); frame p_b <= t < sums[b] takes mu_y[b, :, t - p_b] through an
+// LDS tile (read along t, written along c) and zeros in cond; frames behind sums[b] are zero (uniform geometry only: in the
+// compact one they are the next utterance's).  Every index is clamped by the extents given as arguments, whatever the
+// length vectors hold.
+__global__ __launch_bounds__(256) void pack_prompted_kernel(const float* __restrict__ mu_y, int Ty, const float* __restrict__ prompt_h,
+                                                            int Ph, const float* __restrict__ prompt_feat, int Pf,
+                                                            const int* __restrict__ plens, const int* __restrict__ sums, int T,
+                                                            float* __restrict__ mu, float* __restrict__ cond, int G, int S,
+                                                            const int* __restrict__ uoff) {
+  __shared__ float tile[32][81];
+  const int b = blockIdx.y, t0 = blockIdx.x * 32;
+  const int p = min(max(plens[b], 0), min(min(Ph, Pf), T));
+  const int len = min(max(sums[b], p), min(T, p + Ty));      // p <= len <= T, len - p <= Ty
+  const long row0 = uoff ? (long)uoff[b] : (long)G + (long)b * S;
+  const int twr = uoff ? len : T;
+  if (t0 >= twr) return;      // (uniform over the block)
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+  if (t0 + 32 > p && t0 < len) {      // (uniform over the block) some text frames here
+    const int t = t0 + tx;
+    const bool text = t >= p && t < len;
+    for (int c = ty; c < 80; c += 8) tile[tx][c] = text ? mu_y[((long)b * 80 + c) * Ty + (t - p)] : 0.f;
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < 32 * 20; idx += 256) {
+    const int r = idx / 20, q = idx - r * 20, t = t0 + r;
+    if (t >= twr) continue;
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f), cd = m;
+    if (t < p) {
+      m = *reinterpret_cast<const float4*>(prompt_h + ((long)b * Ph + t) * 80 + 4 * q);
+      cd = *reinterpret_cast<const float4*>(prompt_feat + ((long)b * Pf + t) * 80 + 4 * q);
+    } else if (t < len) {
+      m = make_float4(tile[r][4 * q], tile[r][4 * q + 1], tile[r][4 * q + 2], tile[r][4 * q + 3]);
+    }
+    *reinterpret_cast<float4*>(mu + (row0 + t) * 80 + 4 * q) = m;
+    *reinterpret_cast<float4*>(cond + (row0 + t) * 80 + 4 * q) = cd;
+  }
+}
+
+int pack_prompted(const float* mu_y, int Ty, const float* prompt_h, int Ph, const float* prompt_feat, int Pf, const int* plens,
+                  const int* sums, int B, int T, float* mu, float* cond, int G, int S, hipStream_t st, const int* uoff) {
+  if (B <= 0 || T <= 0) return JV_OK;
+  hipLaunchKernelGGL(pack_prompted_kernel, dim3(cdiv(T, 32), B), dim3(256), 0, st, mu_y, Ty, prompt_h, Ph, prompt_feat, Pf, plens,
+                     sums, T, mu, cond, G, S, uoff);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
+// unpack: rows_to_cf with a per-utterance first row and length -- dst[b, c, t] = src[row0(b) + first[b] + t][c] for t < lens[b],
+// zero for lens[b] <= t < T
+__global__ __launch_bounds__(256) void rows_to_cf_from_kernel(const float* __restrict__ src, int ld, int G, int S,
+                                                              const int* __restrict__ first, const int* __restrict__ lens,
+                                                              float* __restrict__ dst, long dst_bstride, int C, int T,
+                                                              const int* __restrict__ uoff) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int tmax = min(max(lens[b], 0), T);
+  const long row0 = (uoff ? (long)uoff[b] : (long)G + (long)b * S) + max(first[b], 0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int t = t0 + ty + 8 * i, c = c0 + tx;
+    tile[ty + 8 * i][tx] = (t < tmax && c < C) ? src[(row0 + t) * ld + c] : 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = c0 + ty + 8 * i, t = t0 + tx;
+    if (c < C && t < T) dst[b * dst_bstride + (long)c * T + t] = tile[tx][ty + 8 * i];
+  }
+}
+
+int rows_to_cf_from(const float* src, int ld, int G, int S, const int* first, const int* lens, float* dst, long dst_bstride,
+                    int B, int C, int T, hipStream_t st, const int* uoff) {
+  if (B <= 0 || T <= 0) return JV_OK;
+  hipLaunchKernelGGL(rows_to_cf_from_kernel, dim3(cdiv(T, 32), cdiv(C, 32), B), dim3(256), 0, st, src, ld, G, S, first, lens, dst,
+                     dst_bstride, C, T, uoff);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
 // ---- flow estimator input: [x | mu | spks | cond] per row, CFG rows appended ---------------------------
 // rows of utterance b' < B are conditional; b' >= B are the unconditional twin of b' - B (mu = spks = cond = 0),
 // jyutvoice/flow/flow_matching.py:246-251.  x/mu/cond are row buffers of 80 columns with geometry (G,S).

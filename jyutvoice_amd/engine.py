@@ -152,17 +152,46 @@ class Engine:
                                     float(temperature), ts, _ptr(mel), _stream(self.device)))
         return mel
 
+    def cfm_solve_prompted(self, mu_y, y_lens, prompt_h, prompt_feat, prompt_lens, spks, n_timesteps, temperature=1.0,
+                           t_span=None):
+        """jv_cfm_solve_prompted: mu_y [B,80,Ty], prompt_h [B,Ph,80], prompt_feat [B,Pf,80] (batch, time, channel, as the
+        prompt encoder and extract_speech_feat return them), y_lens / prompt_lens [B] -> the generated frames [B,80,Ty],
+        utterance b in [:y_lens[b]], zeros behind.  The tensors go to the library as they are: no assembly here."""
+        B, _, Ty = mu_y.shape
+        mu_y, spks = _f32(mu_y, self.device), _f32(spks, self.device)
+        prompt_h, prompt_feat = _f32(prompt_h, self.device), _f32(prompt_feat, self.device)
+        yl = y_lens.to(device=self.device, dtype=torch.int32).contiguous()
+        pl = prompt_lens.to(device=self.device, dtype=torch.int32).contiguous()
+        mel = torch.empty_like(mu_y)
+        ts = None
+        if t_span is not None:
+            ts_host = t_span.detach().to("cpu", torch.float32).contiguous()
+            ts = (C.c_float * ts_host.numel())(*ts_host.tolist())
+        check(self.lib.jv_cfm_solve_prompted(self._h, _ptr(mu_y), _ptr(yl), _ptr(prompt_h), _ptr(prompt_feat), _ptr(pl), _ptr(spks),
+                                             B, Ty, prompt_h.shape[1], prompt_feat.shape[1], int(n_timesteps), float(temperature),
+                                             ts, _ptr(mel), _stream(self.device)))
+        return mel
+
     # ---- prompt mel front-end --------------------------------------------------------------------------
     def load_mel_basis(self, basis: torch.Tensor):
         t = basis.detach().to("cpu", torch.float32).contiguous()
         check(self.lib.jv_load_mel_basis(self._h, t.data_ptr(), t.numel(), 0, _stream(self.device)))
 
-    def mel_spectrogram(self, wav):
-        """utils/audio.py:18-63 with extract_speech_feat's parameters: wav [B, n] -> log-mel [B, 80, 1 + (n - 480) // 480]"""
+    def mel_spectrogram(self, wav, lens=None):
+        """utils/audio.py:18-63 with extract_speech_feat's parameters: wav [B, n] -> log-mel [B, 80, 1 + (n - 480) // 480].
+        lens ([B] sample counts): recordings of different durations, recording b = wav[b, :lens[b]] with the reflect padding
+        at its own end; returns (mel, mel_lens int32 [B]) with mel[b, :, mel_lens[b]:] = 0 (jv_mel_spectrogram_ragged)"""
         w = _f32(wav, self.device)
         B, n = w.shape
         T = 1 + (n - 480) // 480
         mel = torch.empty(B, spec.N_FEATS, max(T, 0), device=self.device)
+        if lens is not None:
+            wl = lens.to(device=self.device, dtype=torch.int32).contiguous()
+            if wl.shape != (B,):
+                raise ValueError(f"mel_spectrogram: lens must have shape [{B}], got {tuple(wl.shape)}")
+            mel_lens = torch.empty(B, dtype=torch.int32, device=self.device)
+            check(self.lib.jv_mel_spectrogram_ragged(self._h, _ptr(w), _ptr(wl), B, n, _ptr(mel), _ptr(mel_lens), _stream(self.device)))
+            return mel, mel_lens
         check(self.lib.jv_mel_spectrogram(self._h, _ptr(w), B, n, _ptr(mel), _stream(self.device)))
         return mel
 
@@ -190,7 +219,9 @@ class Engine:
                                       _ptr(logw), _ptr(c), _stream(self.device)))
         return h, mu_x, logw, c
 
-    def length_regulate(self, logw, x_lengths, mu_x, length_scale=1.0):
+    def length_regulate(self, logw, x_lengths, mu_x, length_scale=1.0, host_lengths=False):
+        """host_lengths: also leave y_lengths as a list of ints in self.y_lengths_host (the voice-cloning batch sizes its
+        workspace by max(p_b + y_b) without a synchronisation of its own)"""
         B, _, Tt = logw.shape
         xl = x_lengths.to(device=self.device, dtype=torch.int64).contiguous()
         w_ceil = torch.empty(B, 1, Tt, device=self.device)
@@ -198,7 +229,11 @@ class Engine:
         st = _stream(self.device)
         check(self.lib.jv_length_regulate(self._h, _ptr(logw), _ptr(xl), _ptr(mu_x), B, Tt, float(length_scale), _ptr(w_ceil),
                                           _ptr(y_lengths), 0, None, None, st))
-        ty = int(y_lengths.max().item())       # the reference's one host sync (jyutvoice_tts.py:187)
+        if host_lengths:      # the same one host sync, all B lengths instead of their maximum
+            self.y_lengths_host = y_lengths.tolist()
+            ty = int(max(self.y_lengths_host))
+        else:
+            ty = int(y_lengths.max().item())       # the reference's one host sync (jyutvoice_tts.py:187)
         attn = torch.empty(B, Tt, ty, device=self.device)
         mu_y = torch.empty(B, spec.N_FEATS, ty, device=self.device)
         check(self.lib.jv_length_regulate(self._h, _ptr(logw), _ptr(xl), _ptr(mu_x), B, Tt, float(length_scale), _ptr(w_ceil),

@@ -5,7 +5,10 @@ return-dict keys and `ValueError` for batch != 1 as the reference; training (`fo
 scope.  All arithmetic runs in libjyutvoice_hip.so; this class only moves pointers.
 
 Extension (opt-in): `synthesise(..., batched=True)` accepts B > 1 and is defined as looping the batch-1
-reference over the utterances (padded frames of shorter utterances are returned as zeros).
+reference over the utterances (padded frames of shorter utterances are returned as zeros).  With `prompt_lengths` ([B]
+integers) every utterance brings a voice prompt of its own length: utterance b is the batch-1 reference called with
+`prompt_feat[b:b+1, :p_b]` and `prompt_h[b:b+1, :p_b]` (p_b = 0: no prompt); `utils/prompt.py::pad_prompts` builds the
+three tensors from per-utterance lists.
 """
 from __future__ import annotations
 
@@ -81,15 +84,41 @@ class JyutVoiceTTS:
         sd = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
         return self.load_state_dict(sd, strict=False)
 
+    @staticmethod
+    def _check_prompt_lengths(prompt_lengths, prompt_feat, prompt_h, B):
+        """host-side validation of the voice-cloning batch's arguments; returns the lengths as a list of ints (pass
+        prompt_lengths on the host, as pad_prompts returns it: a device tensor costs a synchronisation here)"""
+        if prompt_feat is None or prompt_h is None:
+            raise ValueError("synthesise(): prompt_lengths needs prompt_feat and prompt_h")
+        if not isinstance(prompt_lengths, torch.Tensor) or prompt_lengths.dtype not in (torch.int32, torch.int64):
+            raise ValueError("synthesise(): prompt_lengths must be an int32 / int64 tensor, got "
+                             f"{getattr(prompt_lengths, 'dtype', type(prompt_lengths).__name__)}")
+        if tuple(prompt_lengths.shape) != (B,):
+            raise ValueError(f"synthesise(): prompt_lengths must have shape [{B}], got {tuple(prompt_lengths.shape)}")
+        for name, t in (("prompt_feat", prompt_feat), ("prompt_h", prompt_h)):
+            if t.dim() != 3 or t.shape[0] != B or t.shape[2] != spec.N_FEATS:
+                raise ValueError(f"synthesise(): {name} must be [{B}, frames, {spec.N_FEATS}], got {tuple(t.shape)}")
+        limit = min(prompt_feat.shape[1], prompt_h.shape[1])
+        p_host = prompt_lengths.tolist()
+        for b, p in enumerate(p_host):
+            if p < 0 or p > limit:
+                raise ValueError(f"synthesise(): utterance {b}: prompt length {p} outside [0, {limit}] "
+                                 f"(prompt_feat holds {prompt_feat.shape[1]} frames, prompt_h {prompt_h.shape[1]})")
+        return p_host
+
     # ---- the hot path -----------------------------------------------------------------------------------------
     @torch.inference_mode()
     def synthesise(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed, prompt_feat, prompt_h=None,
-                   n_timesteps=10, temperature=1.0, length_scale=1.0, batched=False):
+                   n_timesteps=10, temperature=1.0, length_scale=1.0, batched=False, prompt_lengths=None, streaming=False):
+        if streaming:
+            raise NotImplementedError("synthesise() runs the non-streaming decoder (jyutvoice_tts.py:239 passes streaming=False)"
+                                      + ("; prompt_lengths has no streaming form" if prompt_lengths is not None else ""))
         if not self._loaded:
             raise RuntimeError(f"JyutVoiceTTS: load_state_dict() has not provided all weights yet; {len(self._missing)} tensors "
                                f"missing, e.g. {self._missing[:4]}")
         t0 = dt.datetime.now()
         B, Tt = x.shape
+        p_host = None if prompt_lengths is None else self._check_prompt_lengths(prompt_lengths, prompt_feat, prompt_h, B)
         rt = get_runtime(self.device)
         eng = rt.ensure(B, 64, Tt)
         # stage_events (a list, set by bench.py for its per-stage pass; None otherwise): events on the launch stream at the
@@ -103,11 +132,20 @@ class JyutVoiceTTS:
                 ev.append(e)
         mark()
         h, mu_x, logw, c = eng.encoder(x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed)
-        w_ceil, y_lengths, attn, mu_y = eng.length_regulate(logw, x_lengths, mu_x, length_scale)
+        w_ceil, y_lengths, attn, mu_y = eng.length_regulate(logw, x_lengths, mu_x, length_scale,
+                                                            host_lengths=prompt_lengths is not None)
         mark()
         encoder_outputs = mu_y
         if B != 1 and not batched:
             raise ValueError(f"synthesise() requires batch_size=1, got batch_size={B}. Please pass one sample at a time.")
+        if prompt_lengths is not None:
+            # voice-cloning batch, one prompt length per utterance: the glue of jyutvoice_tts.py:213-244 runs inside
+            # jv_cfm_solve_prompted, the tensors go there as they came
+            eng = rt.ensure(B, max(p + y for p, y in zip(p_host, eng.y_lengths_host)), Tt)
+            t_span = 1 - torch.cos(torch.linspace(0, 1, n_timesteps + 1) * 0.5 * torch.pi)   # flow_matching.py:387-389
+            dec = eng.cfm_solve_prompted(mu_y, y_lengths, prompt_h, prompt_feat, prompt_lengths, c, n_timesteps, temperature,
+                                         t_span=t_span)
+            return self._result(t0, B, encoder_outputs, dec, attn, y_lengths, mark)
         mel_len1 = 0
         if prompt_feat is not None and prompt_h is not None:
             # voice-cloning glue (jyutvoice_tts.py:213-225): prompt frames are prepended to mu / cond
@@ -127,6 +165,9 @@ class JyutVoiceTTS:
         t_span = 1 - torch.cos(torch.linspace(0, 1, n_timesteps + 1) * 0.5 * torch.pi)   # flow_matching.py:387-389
         dec = eng.cfm_solve(mu_y.contiguous(), lens if B > 1 else None, c, conds, n_timesteps, temperature, t_span=t_span)
         dec = dec[:, :, mel_len1:]
+        return self._result(t0, B, encoder_outputs, dec, attn, y_lengths, mark)
+
+    def _result(self, t0, B, encoder_outputs, dec, attn, y_lengths, mark):
         mark()
         torch.cuda.synchronize(self.device)      # the reference's rtf omits this and is meaningless on a GPU
         t = (dt.datetime.now() - t0).total_seconds()

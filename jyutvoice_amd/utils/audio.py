@@ -15,7 +15,6 @@ import torch
 from ..runtime import get_runtime
 
 _PARAMS = dict(n_fft=1920, num_mels=80, sampling_rate=24000, hop_size=480, win_size=1920, fmin=0, fmax=8000)
-_loaded_on = set()
 
 
 def slaney_mel_basis(sr=24000, n_fft=1920, n_mels=80, fmin=0.0, fmax=8000.0) -> np.ndarray:
@@ -62,16 +61,35 @@ def mel_spectrogram(y, n_fft=1920, num_mels=80, sampling_rate=24000, hop_size=48
     if float(y.max()) > 1.0:
         print("max value is ", float(y.max()))
     dev = y.device if y.is_cuda else torch.device(device)
-    B, n = y.shape
+    return _engine(dev).mel_spectrogram(y)
+
+
+def _engine(dev):
     eng = get_runtime(dev).ensure(1, 64, 1)
-    if id(eng) not in _loaded_on:
+    # the flag lives on the context's own object: id(eng) in a module-level set outlived the engine, and a rebuilt context that
+    # got a freed engine's id was taken for one that had the filterbank
+    if not getattr(eng, "mel_basis_loaded", False):
         eng.load_mel_basis(mel_basis())
-        _loaded_on.clear()
-        _loaded_on.add(id(eng))
-    return eng.mel_spectrogram(y)
+        eng.mel_basis_loaded = True
+    return eng
 
 
 def extract_speech_feat(speech, device="cuda:0"):
     """infer.py:166-186: speech [1, n] at 24 kHz -> (speech_feat [1, T, 80], speech_feat_len [1] int32)"""
     feat = mel_spectrogram(speech, device=device, **_PARAMS).squeeze(dim=0).transpose(0, 1).unsqueeze(dim=0)
     return feat, torch.tensor([feat.shape[1]], dtype=torch.int32, device=feat.device)
+
+
+def extract_speech_feat_batch(speeches, device="cuda:0"):
+    """`extract_speech_feat` of several recordings of different durations in one GPU pass (jv_mel_spectrogram_ragged):
+    speeches = list of [1, n_b] or [n_b] tensors at 24 kHz -> (speech_feat [B, Tmax, 80], zero behind each recording's frames,
+    speech_feat_len [B] int32).  Recording b's frames are those of `extract_speech_feat(speeches[b])`, bit for bit."""
+    wavs = [s.reshape(-1).to(torch.float32) for s in speeches]
+    if not wavs:
+        raise ValueError("extract_speech_feat_batch: no recordings")
+    lens = torch.tensor([w.numel() for w in wavs], dtype=torch.int32)
+    buf = torch.zeros(len(wavs), int(lens.max()), dtype=torch.float32)
+    for b, w in enumerate(wavs):
+        buf[b, : w.numel()] = w.cpu()
+    mel, mel_lens = _engine(torch.device(device)).mel_spectrogram(buf, lens)
+    return mel.transpose(1, 2).contiguous(), mel_lens
