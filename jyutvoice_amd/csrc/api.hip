@@ -127,8 +127,6 @@ int jv_create(jv_context** out, int device, int max_batch, int max_frames, int m
   c.exact_range = getenv("JV_EXACT_RANGE") != nullptr;
   c.dma_a = getenv("JV_DMA_A") != nullptr;
   c.no_rowgemm = getenv("JV_NO_ROWGEMM") != nullptr;
-  c.no_splitk = getenv("JV_NO_SPLITK") != nullptr;
-  c.rg_ff1 = getenv("JV_TILE_FF1") == nullptr;
   c.no_ffn_fuse = getenv("JV_NO_FFN_FUSE") != nullptr;
   c.no_block_fuse = getenv("JV_NO_BLOCK_FUSE") != nullptr;
   c.no_qkv_split = getenv("JV_NO_QKV_SPLIT") != nullptr;
@@ -138,11 +136,8 @@ int jv_create(jv_context** out, int device, int max_batch, int max_frames, int m
   c.no_res_qkv = getenv("JV_NO_RES_QKV") != nullptr;
   c.no_ln_fold = getenv("JV_NO_LN_FOLD") != nullptr;
   c.no_temb_pre = getenv("JV_NO_TEMB_PRE") != nullptr;
-  c.no_attn_planes = getenv("JV_NO_ATTN_PLANES") != nullptr;
   c.no_hiftconv = getenv("JV_NO_HIFTCONV") != nullptr;
   c.no_hift_pair = getenv("JV_NO_HIFT_PAIR") != nullptr;
-  c.attn_rows = getenv("JV_ATTN_ROWS") != nullptr;
-  c.attn_single = getenv("JV_NO_ATTN_SINGLE") == nullptr;
   c.max_frames = max_frames;
   c.max_tokens = max_tokens;
   jv::build_registry(c);
@@ -317,10 +312,7 @@ int jv_flow_contraction_info(const jv_context* ctx, int32_t* out, int n) {
   for (int i = 0; i < jv::EST_NRES; ++i)
     for (int j = 0; j < jv::EST_NBLK; ++j) {
       const jv::BtbW& b = ctx->c.est.blk[i][j];
-      const int l = (b.qkv.w2 && b.qkv.a_scale > 0.f) + (b.out.w2 && b.out.a_scale > 0.f) + (b.ff1.w2 && b.ff1.a_scale > 0.f) +
-                    (b.ff2.w2 && b.ff2.a_scale > 0.f);
-      const bool a = b.q_scale > 0.f && b.k_scale > 0.f && b.v_scale > 0.f;
-      ++blocks; lin += l; att += a; all += (l == 4 && a);
+      ++blocks; lin += b.lin_h3; att += b.attn_h3; all += b.rows_ok;
     }
   out[0] = blocks; out[1] = all; out[2] = lin; out[3] = att;
   return JV_OK;

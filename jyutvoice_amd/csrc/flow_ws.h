@@ -1,0 +1,124 @@
+// What flow.hip (workspace, entry points, solver) and estimator.hip (one estimator evaluation) share: the workspace, the row
+// geometry of a call, the route record, and the host launchers of rowgemm.hip / rowblock.hip.
+#pragma once
+#include <vector>
+#include "jv_model.h"
+#include "jv_ops.h"
+#include "rowblock_kernel.h"
+#include "rowconv_kernel.h"
+#include "rowres_kernel.h"
+
+namespace jv {
+
+// rowgemm.hip
+int rowgemm(const RowGemmArgs& a, int epi, hipStream_t st);
+int rowconv(const RowConvArgs& a, hipStream_t st);
+int rowres(const RowResArgs& a, hipStream_t st);      // a whole resnet in one launch
+bool rowres_fits(int M);
+bool rowconv_w_direct(const RowConvArgs& a);
+int rowffn(const RowFfnArgs& a, hipStream_t st);
+int rowgemm_tile(int M);
+int rowblock(const RowBlockArgs& a, bool qkv, hipStream_t st);      // rowblock.hip
+
+constexpr int FLOW_G = 4;      // leading guard rows (>= causal left context 2)
+constexpr int FLOW_GAP = 4;    // rows between utterances
+constexpr int PARTIAL_ROWS = 2048, PARTIAL_SPLITS = 8;      // split-K is for short M only (est_route)
+constexpr int TS_MAX = 64;      // steps whose timestep embeddings cfm_solve computes ahead of the loop (more: per step, as the seam does)
+
+struct FlowWs {
+  long rows_alloc = 0;      // rows every [*,C] buffer below can hold
+  float *x = nullptr, *mu = nullptr, *cond = nullptr, *spks = nullptr;   // [rows,80] x3, [maxB,80]
+  float *xin = nullptr;                                               // [rows,320]
+  float *h = nullptr, *h2 = nullptr, *res = nullptr, *cat = nullptr;  // [rows,256] x3, [rows,512]
+  float *ln = nullptr, *qkv = nullptr, *att = nullptr, *ff = nullptr; // 256, 1536, 512, 1024
+  // max |value| written to the trunk buffers during the current solve, one slot per BUFFER (h, h2, cat: a launch never
+  // reads the slot it writes) and per UTTERANCE (CFG twins count as utterances of their own: [3][2 * max_batch] floats):
+  // every kernel that writes one of them tracks it (ConvGemmArgs::amax_out, ln_epilogue_rows), and the convolutions that
+  // read them -- whose input, the residual stream, has no load-time bound -- derive their fp16x3 scale from it (amax_in).
+  // An utterance's scales therefore depend on that utterance alone: its result is the same bit for bit whatever else is
+  // in the batch and however a batch is sharded over GPUs.  Zeroed once per solve.
+  float* amax = nullptr;
+  int amax_stride = 0;      // floats per buffer = 2 * max_batch
+  float* partial = nullptr;      // [8][PARTIAL_ROWS][256] split-K partial sums (short M only)
+  unsigned long long* rb_stamps = nullptr;      // tuning builds, JV_RB_STAMPS: rowblock_kernel's phase stamps of the last launch
+  unsigned long long* rc_stamps = nullptr;      // ... and rowconv_wd_kernel's
+  float *d = nullptr;                                                 // [rows,80]
+  float *tsin = nullptr, *t1 = nullptr, *tmish = nullptr, *temb = nullptr;
+  float *t_dev = nullptr, *t_table = nullptr, *dt_table = nullptr;
+  // cfm_solve: the timestep embedding of EVERY step of a solve, computed in three launches before the loop (the steps'
+  // t are known up front and the same for all rows): [TS_MAX] rows of sinusoid / hidden / Mish / the 14 projections
+  float *ts_sin = nullptr, *ts_1 = nullptr, *ts_mish = nullptr, *ts_emb = nullptr;
+  unsigned char* rowmask = nullptr;
+  int* row_sample = nullptr;
+  int* lens2 = nullptr;     // [2*maxB]
+  // COMPACT geometry of ragged batches (cfm_solve): first row of every utterance (+ the first row past the batch), [2*maxB + 1];
+  // h_lens / h_uoff: pinned host staging (the lengths come down with the solve's one synchronisation, the offsets go up async)
+  int* uoff = nullptr;
+  int *h_lens = nullptr, *h_uoff = nullptr;
+  int* h_sum = nullptr;     // cfm_solve_prompted: p_b + y_b of every utterance and its CFG twin, [2*maxB] (pinned; goes up to lens2)
+  int max_steps = 1024;
+  // One Euler step (step scalars -> input assembly -> estimator -> CFG update) captured as a hipGraph per (B, T,
+  // attention mode): the step reads its (t, dt) through a device-side counter, so one executable graph replays for
+  // every step of every solve of that geometry.  Replayed on a private stream (the caller's may be the legacy
+  // default stream, which cannot be captured), fenced against the caller's stream with events.
+  int* step_ctr = nullptr;
+  float *t_cur = nullptr, *dt_cur = nullptr;
+  struct StepGraph { int B, T, chunk, pre; hipGraph_t graph; hipGraphExec_t exec; };      // pre: captured with the embeddings precomputed
+  std::vector<StepGraph> graphs;
+  hipStream_t gstream = nullptr;
+  hipEvent_t ev_in = nullptr, ev_out = nullptr;
+};
+
+struct Geo {
+  int B2, T, S;
+  long M;        // rows computed by every GEMM: [0, M)
+  long a_rows;   // rows that may be read
+  const float* t_ptr = nullptr;   // timestep per utterance: t_ptr[b * t_stride]
+  int t_stride = 1;
+  bool temb_pre = false;          // w.temb row 0 already holds this step's embedding, the same for every utterance (cfm_solve)
+  // COMPACT geometry (ragged batches, cfm_solve): utterance b starts at row uoff[b] and owns lens2[b] rows + the gap; M is then
+  // G + sum (len + gap), not G + B2 (T + gap), and every launch of the call is that much shorter.  null: uniform, G + b S + t
+  const int* uoff = nullptr;
+  long alg_rows = 0;              // profiler: real frames of the call (0: B2 * T)
+  long frames() const { return alg_rows ? alg_rows : (long)B2 * T; }
+};
+
+// Which of the estimator's regimes every launch of a call belongs to: decided once per call / per solve by est_route() from the
+// mode switches (Context), the row count and the load-time weight bits (BtbW / ResnetW / EstimatorW), and read -- never
+// re-derived -- by everything that launches (estimator.hip) or lays rows out (flow.hip).  DESIGN.md 5 "Estimator routes".
+// a resnet: on the tile kernels (block1, res_conv, block2; the two split K at short M) / on the row-owning convolutions wherever
+// the input has a tracked bound (block1 + res_conv, block2) / as one launch that never writes the buffer it reads (rowres_kernel.h)
+enum ResRoute : int { RES_TILES, RES_ROWS, RES_ONE };
+struct EstRoute {
+  bool exact = false;        // bf16x6 everywhere: no fp16x3 operands, no bound tracking
+  bool rows = false;         // the batch fills the chip: row-owning kernels (else the tile kernels)
+  int ksplit = 1;            // > 1: short M, K split over this many workgroups per tile
+  bool sk_blocks = false;    // every block's to_out / ff.net.2 splits K and its reduce tail writes the next LayerNorm
+  bool pre_planes = false;   // tile route: fp16x3 linears take their A operand pre-split from the producer (JV_DMA_A)
+  int qkv_split = 1, qkv_rt = 0;      // > 1: q | k | v leaves the fused block, its column chunks dealt over qkv_split workgroups per 16 * qkv_rt rows
+  bool ffn_fuse = true;      // row-owning blocks: the feed-forward pair in one launch (rowffn_kernel) ...
+  bool block_fuse = true;    // ... with to_out and the next block's q | k | v too (rowblock_kernel.h), where the weights allow
+  int attn_chunk = 0;        // > 0: streaming (chunk-causal) attention, in frames
+  bool compact = false;      // the call's rows are laid out compactly (Geo::uoff)
+  bool compact_ok = false;   // ... which a ragged batch of this many rows may be: every kernel of the route knows that geometry
+  struct Stage {
+    // all four blocks on the row-owning kernels, their attention on the k | v planes (attention_s.hip where the batch fills its
+    // rounds, else attention_pl.hip); false: tile kernels and attention.hip (a stage with one layer whose bound is unusable)
+    bool rows = false;
+    ResRoute res = RES_TILES;
+    bool res_fold = false;   // RES_ROWS: res_conv rides in block1's launch
+    bool ln_fold = false;    // the first norm1 is written by the resnet's last launch
+    bool qkv_fold = false;   // ... and the first q | k | v too (RES_ONE only)
+  } stage[EST_NRES];
+};
+
+// estimator.hip
+EstRoute est_route(const Context& c, long M, bool temb_pre, bool compact, int attn_chunk);
+int time_embedding(Context& c, const float* t, int t_stride, int n, float* sin_buf, float* h1, float* hm, float* emb, hipStream_t st);
+// the estimator body on prepared inputs: ws.xin [rows,320], ws.rowmask/row_sample/lens2, ws.t_dev [B2] -> ws.d [rows,80]
+int estimator_body(Context& c, const Geo& g, const EstRoute& rt, hipStream_t st);
+#ifdef JV_TUNING
+int est_stamps_dump(Context& c, const Geo& g, hipStream_t st);      // JV_RB_STAMPS: print the stamps the last launches left
+#endif
+
+}  // namespace jv

@@ -66,11 +66,22 @@ struct ResnetW {
   // sqrt(255) max |ln1.g| + max |ln1.b|: the range of block1's LayerNorm, hence (with Mish(v) <= max(v, 0.31) and the time
   // embedding's own maximum) of h2 -- the whole-resnet launch scales its LDS-resident h2 with it (rowres_kernel.h); 0 = n/a
   float h2_bound = 0.f;
+  // the weight half of the route (set when the model is finalized, read by est_route):
+  bool fold_ok = false;   // block1 has its planes and res_conv can ride in its fragment stream (wf4)
+  bool pair_ok = false;   // ... and block2's fragments, every column scale and a usable h2_bound: the whole resnet as one launch
 };
 struct BtbW {
   LnW n1, n3;
   GemmW qkv, out, ff1, ff2;
   float q_scale = 0.f, k_scale = 0.f, v_scale = 0.f;   // fp16x3 attention (AttnArgs), from the load-time bounds; 0 = bf16x6
+  // the weight half of the route (set when the model is finalized, read by est_route and jv_flow_contraction_info):
+  int lin_h3 = 0;         // how many of the four linears have fp16 planes and a usable input bound
+  bool attn_h3 = false;   // the attention's three scales are usable
+  bool rows_ok = false;   // lin_h3 == 4 && attn_h3: the block can run on the row-owning kernels
+  bool sk_ok = false;     // to_out and ff.net.2 have split planes at an aligned pitch (split-K tails)
+  bool qkv_wf = false;    // q | k | v in fragment order, 256 -> 1536, no bias: a preceding launch can carry it
+  bool ffn_wf = false;    // ff.net.0 / ff.net.2 in fragment order, 256 -> 1024 -> 256: the pair as one launch (rowffn_kernel)
+  bool block_wf = false;  // ... with to_out (512 -> 256) and the next block's q | k | v too: the fused block (rowblock_kernel.h)
 };
 struct EstimatorW {
   GemmW time1, time2, temb_all;
@@ -78,6 +89,9 @@ struct EstimatorW {
   BtbW blk[EST_NRES][EST_NBLK];
   GemmW down_conv, up_conv, final_conv, final_proj;
   LnW final_ln;
+  bool stage_rows_ok[EST_NRES] = {};     // all four blocks of the stage: rows_ok
+  bool rows_ok = false, sk_ok = false;   // all 56 blocks
+  bool mid_pair_ok = false;              // all 12 mid resnets: pair_ok (they ping-pong the trunk together or not at all)
 };
 
 struct EncLayerW { GemmW qkv, o, ffn1, ffn2; LnW n1, n2; };
@@ -151,16 +165,10 @@ struct Context {
   bool no_res_pair = false;      // JV_NO_RES_PAIR=1: a resnet as two row-owning launches (block1 + res_conv, block2) instead of one (rowres_kernel.h)
   bool no_res_fold = false;      // JV_NO_RES_FOLD=1: a resnet's 1 x 1 res_conv as a tile-kernel launch of its own instead of inside block1's row-owning launch
   bool no_compact = false;       // JV_NO_COMPACT=1: ragged batches keep the uniform row geometry (every utterance padded to the longest; flow.hip cfm_solve)
-  bool no_qkv_split = false;     // JV_NO_QKV_SPLIT=1: q|k|v stays inside the fused block launch at every batch size (flow.hip `qkv_split`)
+  bool no_qkv_split = false;     // JV_NO_QKV_SPLIT=1: q|k|v stays inside the fused block launch at every batch size (estimator.hip `qkv_split`)
   bool no_block_fuse = false;    // JV_NO_BLOCK_FUSE=1: to_out / feed-forward / next q|k|v as three launches (the path rowblock_kernel is checked against)
-  bool rg_ff1 = true;            // ff.net.0 on the row-owning GEMM too; JV_TILE_FF1=1: on the tile kernel (the round-2 first build, for A/B runs)
-  bool attn_single = true;       // attention_s.hip for whole-utterance attention (one wave per SIMD, software-pipelined); JV_NO_ATTN_SINGLE=1: attention_pl.hip
-  bool attn_rows = false;        // JV_ATTN_ROWS=1: the estimator's attention on attention_r.hip (one workgroup per head, 80 queries per wave; measured
-                                 // 66.6 us against attention_pl.hip's 60.0 at 32 x 300 frames: kept as a tested alternative)
   bool no_hift_pair = false;     // JV_NO_HIFT_PAIR=1: a ResBlock's two convolutions as two hiftconv launches (the path hiftpair_kernel is checked against)
   bool no_hiftconv = false;      // JV_NO_HIFTCONV=1: the vocoder's ResBlock convolutions on the tile kernels (A/B aid; the path hiftconv_kernel is checked against)
-  bool no_attn_planes = false;   // JV_NO_ATTN_PLANES=1: attention splits K / V itself (attention.hip) instead of taking planes
-  bool no_splitk = false;        // JV_NO_SPLITK=1: no split-K at short M (A/B aid)
   bool no_rowgemm = false;       // JV_NO_ROWGEMM=1: keep the transformer linears on the tile kernels at every batch size (A/B aid)
   bool exact_range = false;      // true: bf16x6 everywhere (jv_flow_set_contraction); false: fp16x3 where the range is proven
   bool step_graphs = false;      // replay the Euler step as a captured hipGraph (jv_flow_set_graph; never under the profiler)

@@ -672,7 +672,7 @@ int finalize_model(Context& c, int model, hipStream_t st) {
         if (!(w.q_scale > 0.f && w.k_scale > 0.f && w.v_scale > 0.f)) w.q_scale = w.k_scale = w.v_scale = 0.f;
         // a block whose V bound is unusable (non-finite, or beyond 1e30: h3_scale_for_bound) keeps its attention and its
         // to_out on bf16x6 and does not enter the shared scale below: one hostile layer costs that layer (and the row-owning
-        // kernels of its stage, flow.hip stage_all_rg), not the engine of the other 55 blocks
+        // kernels of its stage, EstRoute::Stage::rows), not the engine of the other 55 blocks
         w.out.a_scale = (w.v_scale > 0.f && l1_v * b1 < 1e30f) ? 1.f : 0.f;      // (1 = "usable", replaced below)
         if (w.out.a_scale > 0.f) v_bound = fmaxf(v_bound, l1_v * b1);
       }
@@ -684,6 +684,30 @@ int finalize_model(Context& c, int model, hipStream_t st) {
     for (int i = 0; i < EST_NRES; ++i)
       for (int j = 0; j < EST_NBLK; ++j)
         if (e.blk[i][j].out.a_scale > 0.f) e.blk[i][j].out.a_scale = h3_scale_for_bound(v_bound);
+    // the weight half of every route decision (est_route): nothing below changes until the next finalize
+    e.rows_ok = e.sk_ok = e.mid_pair_ok = true;
+    for (int i = 0; i < EST_NRES; ++i) {
+      ResnetW& r = e.res[i];
+      r.fold_ok = r.block1.w2 && r.wf4 && r.res.colscale && r.res.Cin == r.block1.Cin;
+      r.pair_ok = r.fold_ok && r.block2.wf && r.h2_bound > 0.f && r.block1.colscale && r.block2.colscale && !(r.block1.Cin & 63);
+      if (i >= 1 && i <= EST_NMID) e.mid_pair_ok = e.mid_pair_ok && r.pair_ok;
+      e.stage_rows_ok[i] = true;
+      for (int j = EST_NBLK - 1; j >= 0; --j) {
+        BtbW& b = e.blk[i][j];
+        auto h3 = [](const GemmW& m) { return m.w2 && m.a_scale > 0.f; };
+        auto planes = [](const GemmW& m) { return (m.w3 || m.w2) && !(m.ldw & 7); };
+        b.lin_h3 = h3(b.qkv) + h3(b.out) + h3(b.ff1) + h3(b.ff2);
+        b.attn_h3 = b.q_scale > 0.f && b.k_scale > 0.f && b.v_scale > 0.f;
+        b.rows_ok = b.lin_h3 == 4 && b.attn_h3;
+        b.sk_ok = planes(b.out) && planes(b.ff2);
+        b.qkv_wf = b.qkv.wf && b.qkv.N == 1536 && b.qkv.Cin == 256 && !b.qkv.bias;
+        b.ffn_wf = b.ff1.wf && b.ff2.wf && b.ff1.N == 1024 && b.ff1.Cin == 256 && b.ff2.N == 256 && b.ff2.Cin == 1024;
+        b.block_wf = b.ffn_wf && b.out.wf && b.out.N == 256 && b.out.Cin == 512 && (j == EST_NBLK - 1 || e.blk[i][j + 1].qkv_wf);
+        e.stage_rows_ok[i] = e.stage_rows_ok[i] && b.rows_ok;
+        e.sk_ok = e.sk_ok && b.sk_ok;
+      }
+      e.rows_ok = e.rows_ok && e.stage_rows_ok[i];
+    }
     flow_ws_forget_attention(c, st);
     e.temb_all = pk.concat(tw, tb, EST_CH, EST_TIME);
     e.down_conv = pk.conv_named(p + "down_blocks.0.2.", EST_CH, EST_CH, 3);

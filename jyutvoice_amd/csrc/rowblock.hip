@@ -1,9 +1,7 @@
 // Host side of the fused transformer-block launch (rowblock_kernel.h): argument checks, tile height, launch.
-#include "rowblock_kernel.h"
+#include "flow_ws.h"
 
 namespace jv {
-
-int rowgemm_tile(int M);      // rowgemm.hip
 
 namespace {
 template <int RT, bool QKV, bool STAG>
