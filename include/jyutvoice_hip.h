@@ -75,8 +75,15 @@ int jv_finalize(jv_context* ctx, int model, void* stream);
 /* ---- flow decoder ------------------------------------------------------------------------------------
  * jv_flow_estimator_step: CausalConditionalDecoder.forward (jyutvoice/flow/decoder.py:917-1018) through the
  * forward_estimator seam (flow_matching.py:267-297).  x, mu, cond, out: [B2,80,T]; t: [B2]; spks: [B2,80];
- * lens: [B2] int32 valid frames per row (NULL = all T), the key-padding mask of decoder.py:951-959.
- * out may alias x (the TRT seam writes its result into x). */
+ * lens: [B2] int32 valid frames per row (NULL = all T), the key-padding mask of decoder.py:951-959 (see "Lengths" below).
+ * out may alias x (the TRT seam writes its result into x).
+ *
+ * Lengths.  Every lens[b] passed to jv_flow_estimator_step, jv_cfm_solve, jv_hift_f0 and jv_hift_decode MEANS
+ * min(max(lens[b], 0), T) -- the reference's sequence_mask(lens, T): an entry above T is the full length, a negative one is 0,
+ * in the uniform row geometry and in the compact one of ragged batches alike (the result is the same bits as the call with the
+ * clamped value).  An utterance of effective length 0 comes back as zeros and changes nothing in the other utterances; none of
+ * its inputs is read.  Output frames / samples behind an utterance's length are zeros.  jv_cfm_solve_prompted and
+ * jv_mel_spectrogram_ragged do not clamp: they REJECT a length outside their stated range (JV_ERR_ARG naming the utterance). */
 int jv_flow_estimator_step(jv_context* ctx, const float* x, const int32_t* lens, const float* mu, const float* t,
                            const float* spks, const float* cond, int B2, int T, float* out, void* stream);
 /* jv_flow_estimator_masked: the same call with the six named tensors of the TensorRT seam exactly as
@@ -118,7 +125,7 @@ int jv_flow_set_contraction(jv_context* ctx, int exact_range);
 int jv_flow_contraction_info(const jv_context* ctx, int32_t* out, int n);
 /* jv_cfm_solve: CausalConditionalCFM.forward + ConditionalCFM.solve_euler (flow_matching.py:356-401, 215-265):
  * fixed noise prefix * temperature, cosine schedule, n_timesteps Euler steps with CFG rate 0.7.
- * mu, cond, mel: [B,80,T]; spks: [B,80]; lens: [B] int32 or NULL.  t_span_host: optional n_timesteps+1 host floats
+ * mu, cond, mel: [B,80,T]; spks: [B,80]; lens: [B] int32 or NULL ("Lengths" above: clamped to [0, T]).  t_span_host: optional n_timesteps+1 host floats
  * (the caller's own 1-cos(linspace*pi/2)); NULL = computed here.  B > 1 is the batched extension, defined as the
  * per-utterance loop of the batch-1-only reference. */
 int jv_cfm_solve(jv_context* ctx, const float* mu, const int32_t* lens, const float* spks, const float* cond, int B, int T,
@@ -186,7 +193,7 @@ int jv_length_regulate(jv_context* ctx, const float* logw, const int64_t* x_leng
  *                 draws supplied: phase [B,9] (harmonic 0 ignored, treated as 0), noise [B,9,480T] ~ N(0,1);
  *                 -> s [B,1,480T]
  * jv_hift_decode: HiFTGenerator.decode (generator.py:396-432): mel [B,80,T], s [B,1,480T] -> wav [B,480T]
- * lens: [B] int32 valid mel frames per utterance or NULL. */
+ * lens: [B] int32 valid mel frames per utterance or NULL ("Lengths" above: clamped to [0, T]; wav is zero behind 480 lens[b]). */
 int jv_hift_f0(jv_context* ctx, const float* mel, const int32_t* lens, int B, int T, float* f0, void* stream);
 int jv_hift_source(jv_context* ctx, const float* f0, const float* phase, const float* noise, int B, int T, float* s,
                    void* stream);

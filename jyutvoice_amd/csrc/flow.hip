@@ -131,7 +131,7 @@ int flow_estimator(Context& c, const float* x, const int* lens_dev, const float*
   JV_TRY(cf_to_rows(mu, 80L * T, T, B2, 80, T, w.mu, 80, 0, FLOW_G, g.S, 1.f, nullptr, st));
   JV_TRY(cf_to_rows(cond, 80L * T, T, B2, 80, T, w.cond, 80, 0, FLOW_G, g.S, 1.f, nullptr, st));
   if (mask_f32) hipLaunchKernelGGL(mask_to_lens_kernel, dim3(B2), dim3(64), 0, st, mask_f32, T, w.lens2);
-  else if (lens_dev) JV_HIP(hipMemcpyAsync(w.lens2, lens_dev, sizeof(int) * B2, hipMemcpyDeviceToDevice, st));
+  else if (lens_dev) JV_TRY(clamp_lens(lens_dev, B2, 1, T, w.lens2, st));
   else JV_TRY(fill_int(w.lens2, T, B2, st));
   JV_TRY(row_meta(w.rowmask, w.row_sample, w.lens2, B2, 1, FLOW_G, g.S, T, w.rows_alloc, 1, 0, st));
   JV_HIP(hipMemcpyAsync(w.t_dev, t_dev, sizeof(float) * B2, hipMemcpyDeviceToDevice, st));
@@ -294,8 +294,7 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
 
   // pack: lengths (duplicated for the CFG twin rows), masks, row-layout mu / cond / z
   if (lens_dev) {
-    JV_HIP(hipMemcpyAsync(w.lens2, lens_dev, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
-    JV_HIP(hipMemcpyAsync(w.lens2 + B, lens_dev, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
+    JV_TRY(clamp_lens(lens_dev, B, 2, T, w.lens2, st));      // (the layout above used the same clamp on the host copy)
   } else {
     JV_TRY(fill_int(w.lens2, T, B2, st));
   }
@@ -334,8 +333,8 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
   JV_HIP(hipMemcpyAsync(w.h_lens, y_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
   JV_HIP(hipMemcpyAsync(w.h_lens + B, prompt_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
   JV_HIP(hipStreamSynchronize(st));
-  // An over-long length would put one utterance's prompt rows into its neighbour's causal context (row_meta's compact
-  // branch does not clamp lens[b] > T): rejected here, on the host.
+  // A wrong length here is a wrong split point between prompt and text, which a clamp would turn into other frames silently:
+  // rejected on the host (the entries without a prompt clamp instead, jyutvoice_hip.h "Lengths").
   int T = 0;
   for (int b = 0; b < B; ++b) {
     const int y = w.h_lens[b], p = w.h_lens[B + b];

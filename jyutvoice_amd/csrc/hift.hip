@@ -163,10 +163,10 @@ void set_alg(ConvGemmArgs& a, long rows, int k) {
   a.alg_k = k;
 }
 
-// lens (device int32 [B] or null) -> ws.lens + the four row masks
+// lens (device int32 [B] or null) -> ws.lens (clamped to [0, T]: the length contract) + the four row masks
 int prepare_masks(Context& c, const HGeo& g, const int* lens, hipStream_t st) {
   HiftWs& w = *c.hws;
-  if (lens) JV_HIP(hipMemcpyAsync(w.lens, lens, sizeof(int) * g.B, hipMemcpyDeviceToDevice, st));
+  if (lens) JV_TRY(clamp_lens(lens, g.B, 1, g.T, w.lens, st));
   else JV_TRY(fill_int(w.lens, g.T, g.B, st));
   for (int l = 0; l < 4; ++l)
     JV_TRY(row_meta(w.mask[l], g.uoff[l] ? w.rsample[l] : nullptr, w.lens, g.B, 1, g.G[l], g.S[l], g.L[l], g.alloc[l], LVL_MUL[l],

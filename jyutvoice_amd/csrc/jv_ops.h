@@ -8,6 +8,8 @@ namespace jv {
 // no padding to the longest (rowops.hip); null: the uniform geometry G + b S + t
 int row_meta(unsigned char* rowmask, int* row_sample, const int* lens, int nb, int reps, int G, int S, int L, long rows,
              int mul, int add, hipStream_t st, const int* uoff = nullptr);
+// dst[i] = min(max(src[i % nb], 0), T), i < nb * reps: the entry points' length contract (jyutvoice_hip.h "Lengths")
+int clamp_lens(const int* src, int nb, int reps, int T, int* dst, hipStream_t st);
 // src[b*src_bstride + c*pitch + t] (channels-first) -> dst[(G + b*S + t)*ld + col0 + c]
 int cf_to_rows(const float* src, long src_bstride, long pitch, int B, int C, int T, float* dst, int ld, int col0, int G,
                int S, float scale, const int* lens, hipStream_t st, const int* uoff = nullptr);

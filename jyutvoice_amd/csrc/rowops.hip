@@ -315,7 +315,9 @@ __global__ void row_meta_kernel(unsigned char* rowmask, int* row_sample, const i
       if (uoff[mid] <= r) lo = mid; else hi = mid - 1;
     }
     const long t = r - uoff[lo];
-    const bool ok = t >= 0 && r < uoff[B] && t < (lens ? (long)lens[lo % nb] * mul + add : (long)L);
+    // the length contract (jyutvoice_hip.h): a caller's lens[b] means min(max(lens[b], 0), T).  The host lays the utterances out
+    // with the clamped length, so an over-long one must not claim the gap rows behind it: they are its neighbours' halo.
+    const bool ok = t >= 0 && r < uoff[B] && t < L && (!lens || t < (long)max(lens[lo % nb], 0) * mul + add);
     rowmask[r] = ok ? 1 : 0;
     if (row_sample) row_sample[r] = lo;
     return;
@@ -325,7 +327,7 @@ __global__ void row_meta_kernel(unsigned char* rowmask, int* row_sample, const i
   const int t = rel >= 0 ? (int)(rel - (long)b * S) : -1;
   bool ok = rel >= 0 && b < B && t < L;
   if (b >= B) b = B - 1;
-  if (ok && lens) ok = t < lens[b % nb] * mul + add;
+  if (ok && lens) ok = t < (long)max(lens[b % nb], 0) * mul + add;      // (t < L above: the same clamp as the compact branch)
   rowmask[r] = ok ? 1 : 0;
   if (row_sample) row_sample[r] = b;
 }
@@ -619,6 +621,20 @@ __global__ void fill_int_kernel(int* p, int v, long n) {
 int fill_int(int* p, int v, long n, hipStream_t st) {
   if (n <= 0) return JV_OK;
   hipLaunchKernelGGL(fill_int_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, st, p, v, n);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
+// the length contract of the entry points (jyutvoice_hip.h "Lengths"): dst[i] = min(max(src[i % nb], 0), T) for the nb * reps
+// utterances of a call (reps = 2: the CFG twins), so that every kernel behind the entry sees a length in [0, T]
+__global__ void clamp_lens_kernel(const int* __restrict__ src, int nb, int n, int T, int* __restrict__ dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = min(max(src[i % nb], 0), T);
+}
+int clamp_lens(const int* src, int nb, int reps, int T, int* dst, hipStream_t st) {
+  const int n = nb * reps;
+  if (n <= 0) return JV_OK;
+  hipLaunchKernelGGL(clamp_lens_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, st, src, nb, n, T, dst);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }
