@@ -261,6 +261,50 @@ int jv_op_rowconv(const float* A, int64_t rows, int M, int Cin, const float* W, 
                   const float* amax_in, float* amax_out, float* out, void* stream);
 int jv_op_layernorm(const float* x, const float* g, const float* b, float eps, int64_t rows, int C, float* out,
                     void* stream);
+/* ---- the fused row-owning launches, from fp32 operands (tests/test_gpu_fused_ops.py).  Each hook splits its operands into fp16
+ * planes, packs the weights (planes, column scales, fragment order, the registry's concatenated streams) with the library's own
+ * load-time routines and calls the production launcher.  *_bound: the caller's proven bound on a tensor; the plane scale is
+ * jv_h3_scale_for_bound(bound), so planes come back as value * that scale.
+ *
+ * jv_op_rowgemm_qkv: rowgemm's q | k | v epilogue.  A [rows, K] fp32 -- or A2, planes [2][rows][K] a producer wrote with the
+ * scale of a_bound --, W [1536, K]; q fp32 [rows, 512], kv2 planes [2][rows][1024] (k in columns 0..511, v in 512..1023);
+ * nsplit: column chunks over 1, 2, 3 or 6 workgroups per row tile; rt: tile height in 16-row units, 2 .. 5, 0 = the library's. */
+int jv_op_rowgemm_qkv(const float* A, const uint16_t* A2, int64_t rows, int M, int K, const float* W, float a_bound, float k_bound,
+                      float v_bound, int nsplit, int rt, float* q, uint16_t* kv2, void* stream);
+/* jv_op_rowres: a whole CausalResnetBlock1D (decoder.py:98-115, 767-795; rowres_kernel.h) in one launch:
+ *   h2  = Mish(LayerNorm1(conv3_causal(x * mask) + b1)) * mask + temb
+ *   out = Mish(LayerNorm2(conv3_causal(h2 * mask) + b2)) * mask + (Wr (x * mask) + br)
+ * x [rows, Cin], Cin = 256 / 512; W1 [256, 3 Cin], W2 [256, 768] tap-major (tap j reads row m - 2 + j), Wr [256, Cin]; temb [256].
+ * amax_in: per-utterance bounds of x, slot(row) = clamp((row - slot_G) / slot_S, 0, slot_nb - 1) or, slot_S < 0, row_slot[row];
+ * amax_out: max |out| over the unmasked rows is folded into the row's slot.  lnf_g / lnf_b (optional): the following block's
+ * LayerNorm1 of the stored row -> lnf_out, planes [2][rows][256]; with Wq [1536, 256] its q | k | v instead (q, kv2 as in
+ * jv_op_rowgemm_qkv).  out must not be x: the launch reads neighbouring rows as halo (JV_ERR_ARG, nothing is launched). */
+int jv_op_rowres(const float* x, int64_t rows, int M, int Cin, const uint8_t* rowmask, const float* amax_in, int slot_G, int slot_S,
+                 int slot_nb, const int32_t* row_slot, const float* W1, const float* b1, const float* ln1_g, const float* ln1_b,
+                 const float* Wr, const float* br, const float* temb, const float* W2, const float* b2, const float* ln2_g,
+                 const float* ln2_b, const float* lnf_g, const float* lnf_b, float lnf_bound, uint16_t* lnf_out, const float* Wq,
+                 float k_bound, float v_bound, float* q, uint16_t* kv2, float* amax_out, float* out, void* stream);
+/* jv_op_hiftpair: a vocoder ResBlock's convolution pair (generator.py:90-97; hiftpair_kernel.h) in one launch:
+ *   out = ((Conv1d_k(Snake_alpha2(Conv1d_k,dil(Snake_alpha1(A)) + b1)) + b2) + A + res2) * out_scale (+ out when accumulate)
+ * on a [rows, C] row buffer, C = 64 / 128, ntaps = 3 / 7 / 11, (ntaps - 1) dil <= 56, "same" padding; rows with rowmask == 0 read
+ * as zero as A and as the intermediate.  amax_in: per-utterance bounds of A (slots as in jv_op_rowres, or slot_map[row]);
+ * amax_out: max |out| over the unmasked rows per slot.  out must not be A. */
+int jv_op_hiftpair(const float* A, int64_t rows, int C, int ntaps, int dil, const float* W1, const float* b1, const float* alpha1,
+                   const float* W2, const float* b2, const float* alpha2, const uint8_t* rowmask, const float* amax_in, int slot_G,
+                   int slot_S, int slot_nb, const int32_t* slot_map, const float* res2, float out_scale, int accumulate,
+                   float* amax_out, float* out, void* stream);
+/* jv_op_rowblock: the tail of a BasicTransformerBlock and the head of the next (transformer.py:355-443; rowblock_kernel.h):
+ *   h += Wo att + bo;  out = h + W2 gelu(W1 LayerNorm3(h) + b1) + b2;  [x' = LayerNorm1_next(out);  q | k | v = Wq x']
+ * mode 0: no x'; 1: x' as planes [2][rows][256] to ln_out; 2: q | k | v (out must be h); 3: the feed-forward alone (rowffn): `att`
+ * is then x [rows, 256], the LayerNorm3 output, h the residual, ln1_g != NULL asks for x' in ln_out.  att [rows, 512],
+ * h [rows, 256] (updated in place), out [rows, ldo] (h itself, or a separate buffer).  fused 1: one launch; 0: rowgemm<res,ln> +
+ * rowffn + rowgemm<qkv> on the same plane buffers; -1: the feed-forward as rowgemm<gelu> + rowgemm<res[,ln]> as well.
+ * amax_h / amax_out: max |h| / |out| over the rows with row_mask != 0, per row_slot[row].  Row buffers hold whole tiles. */
+int jv_op_rowblock(const float* att, float* h, int64_t rows, int M, int mode, int fused, float att_bound, const float* Wo,
+                   const float* bo, const float* ln3_g, const float* ln3_b, float ln3_bound, const float* W1, const float* b1,
+                   float hid_bound, const float* W2, const float* b2, const float* ln1_g, const float* ln1_b, float ln1_bound,
+                   const float* Wq, float k_bound, float v_bound, float* out, int64_t ldo, uint16_t* ln_out, float* q, uint16_t* kv2,
+                   float* amax_h, float* amax_out, const int32_t* row_slot, const uint8_t* row_mask, void* stream);
 
 /* ---- measurement -------------------------------------------------------------------------------------------
  * HIP events on the launch stream around every conv_gemm / attention launch (replaces nothing in the reference,

@@ -76,6 +76,11 @@ SIGNATURES = {
     "jv_op_rowconv": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
     "jv_op_rowgemm": (_i, [_p, _i64, _i, _i, _p, _i, _p, _i, _p, _p, _p, _f, _f, _i, _p, _p, _p, _p]),
     "jv_op_layernorm": (_i, [_p, _p, _p, _f, _i64, _i, _p, _p]),
+    "jv_op_rowgemm_qkv": (_i, [_p, _p, _i64, _i, _i, _p, _f, _f, _f, _i, _i, _p, _p, _p]),
+    "jv_op_rowres": (_i, [_p, _i64, _i, _i, _p, _p, _i, _i, _i, _p] + [_p] * 13 + [_f, _p, _p, _f, _f, _p, _p, _p, _p, _p]),
+    "jv_op_hiftpair": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _f, _i, _p, _p, _p]),
+    "jv_op_rowblock": (_i, [_p, _p, _i64, _i, _i, _i, _f, _p, _p, _p, _p, _f, _p, _p, _f, _p, _p, _p, _p, _f, _p, _f, _f, _p, _i64,
+                            _p, _p, _p, _p, _p, _p, _p, _p]),
     "jv_profile_enable": (_i, [_i]),
     "jv_profile_report": (_i, [C.c_char_p, _i64]),
 }

@@ -8,14 +8,19 @@
 #include "../../include/jyutvoice_hip.h"
 #include "jv_model.h"
 #include "jv_ops.h"
-#include "hiftconv_kernel.h"
-#include "rowconv_kernel.h"
+#include "hiftpair_kernel.h"
+#include "rowres_kernel.h"
 
 namespace jv {
 
 int hiftconv(const HiftConvArgs& a, int C, hipStream_t st);   // hiftconv.hip
 int rowgemm(const RowGemmArgs& a, int epi, hipStream_t st);   // rowgemm.hip
 int rowconv(const RowConvArgs& a, hipStream_t st);
+int hiftpair(const HiftPairArgs& a, int C, hipStream_t st);   // hiftconv.hip
+int rowres(const RowResArgs& a, hipStream_t st);              // rowgemm.hip
+int rowffn(const RowFfnArgs& a, hipStream_t st);
+int rowblock(const RowBlockArgs& a, bool qkv, hipStream_t st);   // rowblock.hip
+int rowgemm_tile(int M);
 
 int split3_planes(const float* src, unsigned short* dst, long n, hipStream_t st);   // registry.hip
 int split2h_planes(const float* src, int rows, int ld, float* stats, unsigned short* dst, float* colscale, hipStream_t st);
@@ -81,7 +86,7 @@ static void workspaces_destroy(Context& c) {
 // looked up under a lock, so a buffer allocated on device A is never handed out after hipSetDevice(B) and two threads cannot
 // race the grow.  Calls of ONE hook on ONE device still share the buffer: the caller serialises those (stream order does).
 namespace {
-enum OpSlot { OPS_X6 = 0, OPS_H3, OPS_H3_A, OPS_CONV, OPS_RG, OPS_RG_A, OPS_RC, OPS_HIFT, OPS_ATTN, OPS_COUNT };
+enum OpSlot { OPS_X6 = 0, OPS_H3, OPS_H3_A, OPS_CONV, OPS_RG, OPS_RG_A, OPS_RC, OPS_HIFT, OPS_ATTN, OPS_QKV, OPS_QKV_A, OPS_RR, OPS_HP, OPS_RB, OPS_COUNT };
 int op_scratch(int slot, size_t need, void** out) {
   struct Buf { void* p = nullptr; size_t cap = 0; };
   static std::mutex mu;
@@ -99,6 +104,38 @@ int op_scratch(int slot, size_t need, void** out) {
   *out = b.p;
   return JV_OK;
 }
+
+// layout of one hook's scratch: the same function runs once without a base (sizes only) and once over the buffer
+struct Bump {
+  char* base;
+  size_t off = 0;
+  template <class T>
+  T* take(size_t n) {
+    T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += (n * sizeof(T) + 255) & ~(size_t)255;
+    return r;
+  }
+};
+// a weight matrix [N][K] as the registry keeps it: fp16x3 planes + column scales (+ row statistics: max |w|, L1 norm) (+ fragment order)
+struct OpW {
+  int N = 0, K = 0;
+  unsigned short* planes = nullptr;
+  float *cs = nullptr, *stats = nullptr;
+  unsigned short* wf = nullptr;
+  long n() const { return (long)N * K; }
+  void take(Bump& b, int N_, int K_, bool frag) {
+    N = N_; K = K_;
+    planes = b.take<unsigned short>(2 * (size_t)n());
+    cs = b.take<float>((size_t)N);
+    stats = b.take<float>(2 * (size_t)N);
+    wf = frag ? b.take<unsigned short>(2 * (size_t)n()) : nullptr;
+  }
+  int pack(const float* W, hipStream_t st, bool frag) const {
+    JV_TRY(jv::split2h_planes(W, N, K, stats, planes, cs, st));
+    if (frag) JV_TRY(jv::pack_wfrag(planes, n(), K, N, K, wf, n(), st));
+    return JV_OK;
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -492,6 +529,264 @@ int jv_op_rowgemm(const float* A, int64_t rows, int M, int K, const float* W, in
   a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = 1e-5f;
   a.amax_out = amax_out;
   return jv::rowgemm(a, epi, st);
+}
+
+// rowgemm's q | k | v epilogue (RG_QKV: rowgemm_wa_kernel with the column chunks dealt over nsplit workgroups per row tile, or
+// rowgemm_wd_kernel): A [rows, K] fp32 split here with the scale of a_bound -- or A2, fp16 planes [2][rows][K] a producer wrote with
+// that scale (rowres' / rowblock's LayerNorm1 planes) -- W [1536, K] (no bias); q -> fp32 [rows, 512], k | v -> planes [2][rows][1024]
+// of k * scale(k_bound), v * scale(v_bound); rt: tile height 2 .. 5 (0: rowgemm_tile)
+int jv_op_rowgemm_qkv(const float* A, const uint16_t* A2, int64_t rows, int M, int K, const float* W, float a_bound, float k_bound,
+                      float v_bound, int nsplit, int rt, float* q, uint16_t* kv2, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const float sc = jv::h3_scale_for_bound(a_bound), ks = jv::h3_scale_for_bound(k_bound), vs = jv::h3_scale_for_bound(v_bound);
+  if (!(sc > 0.f && ks > 0.f && vs > 0.f)) return jv::fail(JV_ERR_ARG, "jv_op_rowgemm_qkv: unusable bound");
+  if ((!A && !A2) || !W || !q || !kv2 || rows < M || M <= 0 || K <= 0 || (K & 63)) return jv::fail(JV_ERR_ARG, "jv_op_rowgemm_qkv: needs A or its planes, W, both outputs, rows >= M and K % 64 == 0");
+  OpW w;
+  void* scratch = nullptr;
+  { Bump b{nullptr}; w.take(b, 1536, K, true); JV_TRY(op_scratch(OPS_QKV, b.off, &scratch)); }
+  { Bump b{static_cast<char*>(scratch)}; w.take(b, 1536, K, true); }
+  JV_TRY(w.pack(W, st, true));
+  const unsigned short* ap = A2;
+  if (!ap) {
+    unsigned short* mine = nullptr;
+    JV_TRY(op_scratch(OPS_QKV_A, (size_t)rows * K * 4, reinterpret_cast<void**>(&mine)));
+    JV_TRY(jv::split2h_rows(A, K, mine, (long)rows * K, rows, K, sc, st));
+    ap = mine;
+  }
+  jv::RowGemmArgs a{};
+  a.A2 = ap; a.a2_plane = (long)rows * K; a.a_rows = rows; a.lda2 = K;
+  a.M = M; a.K = K; a.N = 1536;
+  a.W2 = w.planes; a.w2_plane = w.n(); a.ldw = K; a.colscale = w.cs; a.a_scale = sc;
+  a.Wf = w.wf; a.wf_plane = w.n();
+  a.ln_eps = 1e-5f;
+  a.nsplit = nsplit; a.rt = rt;
+  a.out = q; a.ldo = 512;
+  a.out2 = kv2; a.out2_plane = (long)rows * 1024; a.ldo2 = 1024; a.out2_scale = ks; a.out2_scale2 = vs;
+  return jv::rowgemm(a, jv::RG_QKV, st);
+}
+
+// rowres (rowres_kernel.h): a whole CausalResnetBlock1D in one launch, optionally with the following block's LayerNorm1 planes
+// (lnf_out) or its q | k | v (Wq).  x [rows, Cin]; W1 [256, 3 Cin] / W2 [256, 768] tap-major, Wr [256, Cin]; block1 | res_conv go
+// through the registry's concatenation; h2_bound as the registry computes it.  amax_in: per-utterance bounds of x, addressed by
+// (slot_G, slot_S, slot_nb) or, slot_S < 0, by row_slot [rows]; lnf_bound / k_bound / v_bound: the caller's bounds behind the
+// plane scales of the LayerNorm1 output, k and v
+int jv_op_rowres(const float* x, int64_t rows, int M, int Cin, const uint8_t* rowmask, const float* amax_in, int slot_G, int slot_S,
+                 int slot_nb, const int32_t* row_slot, const float* W1, const float* b1, const float* ln1_g, const float* ln1_b,
+                 const float* Wr, const float* br, const float* temb, const float* W2, const float* b2, const float* ln2_g,
+                 const float* ln2_b, const float* lnf_g, const float* lnf_b, float lnf_bound, uint16_t* lnf_out, const float* Wq,
+                 float k_bound, float v_bound, float* q, uint16_t* kv2, float* amax_out, float* out, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!x || !W1 || !Wr || !W2 || !ln1_g || !ln1_b || rows < M || M <= 0 || Cin < 64 || (Cin & 63))
+    return jv::fail(JV_ERR_ARG, "jv_op_rowres: needs x, the three weight matrices, LayerNorm1, rows >= M and Cin % 64 == 0");
+  OpW w1, wr, w2, wq;
+  unsigned short* wf4 = nullptr;
+  auto layout = [&](Bump& b) {
+    w1.take(b, 256, 3 * Cin, false);
+    wr.take(b, 256, Cin, false);
+    wf4 = b.take<unsigned short>(2 * 256 * 4 * (size_t)Cin);
+    w2.take(b, 256, 768, true);
+    if (Wq) wq.take(b, 1536, 256, true);
+  };
+  void* scratch = nullptr;
+  { Bump b{nullptr}; layout(b); JV_TRY(op_scratch(OPS_RR, b.off, &scratch)); }
+  { Bump b{static_cast<char*>(scratch)}; layout(b); }
+  JV_TRY(w1.pack(W1, st, false));
+  JV_TRY(wr.pack(Wr, st, false));
+  JV_TRY(jv::pack_wfrag_res4(w1.planes, w1.n(), wr.planes, wr.n(), Cin, wf4, st));
+  JV_TRY(w2.pack(W2, st, true));
+  if (Wq) JV_TRY(wq.pack(Wq, st, true));
+  float gm = 0.f, bm = 0.f;
+  JV_TRY(jv::dev_maxabs(ln1_g, 256, 1, st, &gm));
+  JV_TRY(jv::dev_maxabs(ln1_b, 256, 1, st, &bm));
+  jv::RowResArgs a{};
+  a.A = x; a.lda = Cin; a.a_rows = rows; a.M = M; a.Cin = Cin; a.rowmask = rowmask;
+  a.amax_in = amax_in; a.slot_G = slot_G; a.slot_S = slot_S; a.slot_nb = slot_nb; a.row_slot = row_slot;
+  a.Wf1 = wf4; a.wf1_plane = 256L * 4 * Cin;
+  a.cs1 = w1.cs; a.b1 = b1; a.ln1_g = ln1_g; a.ln1_b = ln1_b;
+  a.csr = wr.cs; a.br = br;
+  a.temb = temb; a.h2_bound = jv::resnet_h2_bound(gm, bm); a.ln_eps = 1e-5f;
+  a.Wf2 = w2.wf; a.wf2_plane = w2.n();
+  a.cs2 = w2.cs; a.b2 = b2; a.ln2_g = ln2_g; a.ln2_b = ln2_b;
+  a.out = out; a.ldo = 256; a.amax_out = amax_out;
+  if (lnf_g) {
+    a.lnf_g = lnf_g; a.lnf_b = lnf_b; a.lnf_scale = jv::h3_scale_for_bound(lnf_bound);
+    if (!Wq) {
+      a.lnf_out = lnf_out; a.lnf_plane = (long)rows * 256;
+    } else {
+      a.Wqf = wq.wf; a.wqf_plane = wq.n(); a.csq = wq.cs;
+      a.q = q; a.kv2 = kv2; a.kv2_plane = (long)rows * 1024;
+      a.k_scale = jv::h3_scale_for_bound(k_bound); a.v_scale = jv::h3_scale_for_bound(v_bound);
+    }
+  } else if (Wq || lnf_out) {
+    return jv::fail(JV_ERR_ARG, "jv_op_rowres: the following block's planes and q | k | v need its LayerNorm1");
+  }
+  return jv::rowres(a, st);
+}
+
+// hiftpair (hiftpair_kernel.h): a vocoder ResBlock's two convolutions in one launch, out = ((Conv1d_k(Snake2(Conv1d_k,dil(Snake1(A)) + b1))
+// + b2) + A + res2) * out_scale (+ out when accumulate); C = 64 / 128, ntaps = 3 / 7 / 11; W1, W2 [C][ntaps * C] tap-major, packed as
+// one fragment stream by the registry's concatenation; l1max, b1max, e1, e2 derived as at load time.  amax_in: per-utterance
+// bounds of A, addressed by (slot_G, slot_S, slot_nb) or by slot_map [rows]
+int jv_op_hiftpair(const float* A, int64_t rows, int C, int ntaps, int dil, const float* W1, const float* b1, const float* alpha1,
+                   const float* W2, const float* b2, const float* alpha2, const uint8_t* rowmask, const float* amax_in, int slot_G,
+                   int slot_S, int slot_nb, const int32_t* slot_map, const float* res2, float out_scale, int accumulate,
+                   float* amax_out, float* out, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!A || !W1 || !W2 || !alpha1 || !alpha2 || rows <= 0 || (C != 64 && C != 128) || ntaps < 1)
+    return jv::fail(JV_ERR_ARG, "jv_op_hiftpair: needs A, both weight matrices and Snake alphas, 64 or 128 channels");
+  const int K = ntaps * C;
+  OpW w1, w2;
+  unsigned short* wfp = nullptr;
+  auto layout = [&](Bump& b) {
+    w1.take(b, C, K, false);
+    w2.take(b, C, K, false);
+    wfp = b.take<unsigned short>(2 * (size_t)C * 2 * K);
+  };
+  void* scratch = nullptr;
+  { Bump b{nullptr}; layout(b); JV_TRY(op_scratch(OPS_HP, b.off, &scratch)); }
+  { Bump b{static_cast<char*>(scratch)}; layout(b); }
+  JV_TRY(w1.pack(W1, st, false));
+  JV_TRY(w2.pack(W2, st, false));
+  JV_TRY(jv::pack_wfrag_pair(w1.planes, w1.n(), w2.planes, w2.n(), C, K, wfp, st));
+  jv::HiftPairArgs a{};
+  JV_TRY(jv::snake_extra_of(alpha1, C, st, &a.e1));
+  JV_TRY(jv::snake_extra_of(alpha2, C, st, &a.e2));
+  JV_TRY(jv::dev_maxabs(w1.stats + C, C, 1, st, &a.l1max));      // (row L1 norms: split2h_planes' second statistic)
+  if (b1) JV_TRY(jv::dev_maxabs(b1, C, 1, st, &a.b1max));
+  if (!(a.l1max > 0.f && a.l1max < 1e30f) || !(a.b1max == a.b1max && a.b1max < 1e30f))
+    return jv::fail(JV_ERR_ARG, "jv_op_hiftpair: the first convolution's weights give no usable bound");
+  a.A = A; a.a_rows = rows; a.M = (int)rows; a.ntaps = ntaps; a.dil = dil; a.rowmask = rowmask;
+  a.alpha1 = alpha1; a.alpha2 = alpha2;
+  a.Wf = wfp; a.wf_plane = (long)C * 2 * K;
+  a.cs1 = w1.cs; a.b1 = b1; a.cs2 = w2.cs; a.b2 = b2;
+  a.amax_in = amax_in; a.slot_G = slot_G; a.slot_S = slot_S; a.slot_nb = slot_nb; a.slot_map = slot_map;
+  a.out = out; a.res2 = res2; a.out_scale = out_scale; a.accumulate = accumulate;
+  a.amax_out = amax_out;
+  return jv::hiftpair(a, C, st);
+}
+
+// The tail of a transformer block and the head of the next one (rowblock_kernel.h) from fp32 operands, as the estimator launches it:
+//   mode 0  h += to_out(att); out = h + ff.net.2(gelu(ff.net.0(LayerNorm3(h))))
+//   mode 1  ... and LayerNorm1_next(out) as planes [2][rows][256] to ln_out
+//   mode 2  ... and q | k | v = Wq LayerNorm1_next(out): q fp32 [rows, 512], kv2 planes [2][rows][1024]
+//   mode 3  the feed-forward alone (rowffn): `att` is x [rows, 256], the LayerNorm3 output, h the residual; ln1_g != NULL: planes to ln_out
+// att [rows, 512] (modes 0 - 2), h [rows, 256] (in place: h after phase A), out = h or a separate buffer with its own ldo.
+// fused = 1: one launch; 0: the separate launchers of JV_NO_BLOCK_FUSE on the same plane buffers (rowgemm<res,ln>, rowffn,
+// rowgemm<qkv>); -1: those of JV_NO_FFN_FUSE as well (rowgemm<gelu> + rowgemm<res[,ln]> for the feed-forward).  *_bound: the caller's
+// bounds behind the operand scales (att, LayerNorm3 output, hidden, LayerNorm1 output, k, v).  Row buffers must hold whole tiles.
+int jv_op_rowblock(const float* att, float* h, int64_t rows, int M, int mode, int fused, float att_bound, const float* Wo,
+                   const float* bo, const float* ln3_g, const float* ln3_b, float ln3_bound, const float* W1, const float* b1,
+                   float hid_bound, const float* W2, const float* b2, const float* ln1_g, const float* ln1_b, float ln1_bound,
+                   const float* Wq, float k_bound, float v_bound, float* out, int64_t ldo, uint16_t* ln_out, float* q, uint16_t* kv2,
+                   float* amax_h, float* amax_out, const int32_t* row_slot, const uint8_t* row_mask, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (mode < 0 || mode > 3 || fused < -1 || fused > 1) return jv::fail(JV_ERR_ARG, "jv_op_rowblock: mode 0 .. 3, fused -1 .. 1");
+  const bool ffn_only = mode == 3, qkv = mode == 2;
+  const bool follows = mode == 1 || mode == 2 || (ffn_only && ln1_g);
+  if (!att || !h || !out || !W1 || !W2 || rows < M || M <= 0 || (!ffn_only && (!Wo || !ln3_g || !ln3_b)) ||
+      (follows && (!ln1_g || !ln1_b)) || (qkv && (!Wq || !q || !kv2)) || ((mode == 1 || (ffn_only && follows)) && !ln_out))
+    return jv::fail(JV_ERR_ARG, "jv_op_rowblock: missing operand for this mode");
+  const float sc_o = ffn_only ? 1.f : jv::h3_scale_for_bound(att_bound), sc_1 = jv::h3_scale_for_bound(ln3_bound);
+  const float sc_h = jv::h3_scale_for_bound(hid_bound), sc_q = follows ? jv::h3_scale_for_bound(ln1_bound) : 1.f;
+  const float sc_k = qkv ? jv::h3_scale_for_bound(k_bound) : 1.f, sc_v = qkv ? jv::h3_scale_for_bound(v_bound) : 1.f;
+  if (!(sc_o > 0.f && sc_1 > 0.f && sc_h > 0.f && sc_q > 0.f && sc_k > 0.f && sc_v > 0.f)) return jv::fail(JV_ERR_ARG, "jv_op_rowblock: unusable bound");
+  // the plane buffers of this hook hold whole tiles of the tallest tile height (80 rows); the caller's row buffers are checked by rowblock()
+  const long R = ((long)rows + 79) / 80 * 80;
+  OpW wo, w1, w2, wq;
+  unsigned short *ap = nullptr, *lnp = nullptr, *ffp = nullptr;
+  auto layout = [&](Bump& b) {
+    if (!ffn_only) wo.take(b, 256, 512, true);
+    w1.take(b, 1024, 256, true);
+    w2.take(b, 256, 1024, true);
+    if (qkv) wq.take(b, 1536, 256, true);
+    ap = b.take<unsigned short>(2 * (size_t)R * (ffn_only ? 256 : 512));      // att planes (mode 3: the LayerNorm3 planes)
+    lnp = b.take<unsigned short>(2 * (size_t)R * 256);                          // unfused: LayerNorm planes between the launches
+    ffp = fused == -1 ? b.take<unsigned short>(2 * (size_t)R * 1024) : nullptr; // unfused feed-forward: the hidden planes
+  };
+  void* scratch = nullptr;
+  { Bump b{nullptr}; layout(b); JV_TRY(op_scratch(OPS_RB, b.off, &scratch)); }
+  { Bump b{static_cast<char*>(scratch)}; layout(b); }
+  if (!ffn_only) JV_TRY(wo.pack(Wo, st, true));
+  JV_TRY(w1.pack(W1, st, true));
+  JV_TRY(w2.pack(W2, st, true));
+  if (qkv) JV_TRY(wq.pack(Wq, st, true));
+  const int KA = ffn_only ? 256 : 512;
+  JV_HIP(hipMemsetAsync(ap, 0, 2 * (size_t)R * KA * sizeof(unsigned short), st));
+  JV_TRY(jv::split2h_rows(att, KA, ap, R * KA, rows, KA, ffn_only ? sc_1 : sc_o, st));
+
+  auto rg_args = [&](const unsigned short* planes, int K, const OpW& m, float a_scale, const float* bias) {
+    jv::RowGemmArgs a{};
+    a.A2 = planes; a.a2_plane = R * K; a.a_rows = rows; a.lda2 = K;
+    a.M = M; a.K = K; a.N = m.N;
+    a.W2 = m.planes; a.w2_plane = m.n(); a.ldw = K; a.colscale = m.cs; a.a_scale = a_scale;
+    a.Wf = m.wf; a.wf_plane = m.n();
+    a.bias = bias; a.ln_eps = 1e-5f; a.out2_scale = 1.f;
+    return a;
+  };
+  // the feed-forward (+ the next LayerNorm1) from the LayerNorm3 planes `xin`, as one launch or two (estimator.hip: block_rows)
+  auto feed_forward = [&](const unsigned short* xin, unsigned short* ln_dst) -> int {
+    if (fused >= 0) {
+      jv::RowFfnArgs f{};
+      f.A2 = xin; f.a2_plane = R * 256; f.a_rows = rows; f.lda2 = 256; f.M = M;
+      f.W1f = w1.wf; f.w1f_plane = w1.n(); f.cs1 = w1.cs; f.b1 = b1; f.a_scale1 = sc_1;
+      f.h_scale = sc_h;
+      f.W2f = w2.wf; f.w2f_plane = w2.n(); f.cs2 = w2.cs; f.b2 = b2;
+      f.out = out; f.ldo = ldo; f.res = h; f.ldr = 256;
+      f.ln_eps = 1e-5f; f.out2_scale = 1.f;
+      f.amax_out = amax_out; f.row_slot = row_slot; f.row_mask = row_mask;
+      if (follows) {
+        f.ln = 1; f.out2 = ln_dst; f.out2_plane = ln_dst == lnp ? R * 256 : (long)rows * 256; f.ldo2 = 256; f.out2_scale = sc_q;
+        f.ln_g = ln1_g; f.ln_b = ln1_b;
+      }
+      return jv::rowffn(f, st);
+    }
+    jv::RowGemmArgs a = rg_args(xin, 256, w1, sc_1, b1);
+    a.out2 = ffp; a.out2_plane = R * 1024; a.ldo2 = 1024; a.out2_scale = sc_h;
+    JV_TRY(jv::rowgemm(a, jv::RG_GELU_PL, st));
+    a = rg_args(ffp, 1024, w2, sc_h, b2);
+    a.out = out; a.ldo = ldo; a.res = h; a.ldr = 256;
+    a.amax_out = amax_out; a.row_slot = row_slot; a.row_mask = row_mask;
+    if (follows) {
+      a.out2 = ln_dst; a.out2_plane = ln_dst == lnp ? R * 256 : (long)rows * 256; a.ldo2 = 256; a.out2_scale = sc_q;
+      a.ln_g = ln1_g; a.ln_b = ln1_b;
+      return jv::rowgemm(a, jv::RG_RES_LN, st);
+    }
+    return jv::rowgemm(a, jv::RG_RES, st);
+  };
+  if (ffn_only) return feed_forward(ap, follows ? ln_out : nullptr);
+
+  if (fused == 1) {
+    jv::RowBlockArgs f{};
+    f.A2 = ap; f.a2_plane = R * 512; f.a_rows = rows; f.M = M;
+    f.Wof = wo.wf; f.wof_plane = wo.n(); f.cso = wo.cs; f.bo = bo; f.a_scale_o = sc_o;
+    f.h = h; f.ln3_g = ln3_g; f.ln3_b = ln3_b;
+    f.W1f = w1.wf; f.w1f_plane = w1.n(); f.cs1 = w1.cs; f.b1 = b1; f.a_scale1 = sc_1;
+    f.h_scale = sc_h;
+    f.W2f = w2.wf; f.w2f_plane = w2.n(); f.cs2 = w2.cs; f.b2 = b2;
+    f.out = out; f.ldo = ldo;
+    f.amax_h = amax_h; f.amax_out = amax_out; f.row_slot = row_slot; f.row_mask = row_mask;
+    if (follows) { f.ln1_g = ln1_g; f.ln1_b = ln1_b; f.a_scale_q = sc_q; }
+    if (qkv) {
+      f.Wqf = wq.wf; f.wqf_plane = wq.n(); f.csq = wq.cs;
+      f.q = q; f.kv2 = kv2; f.kv2_plane = (long)rows * 1024; f.k_scale = sc_k; f.v_scale = sc_v;
+    } else if (follows) {
+      f.ln_out = ln_out; f.ln_out_plane = (long)rows * 256;
+    }
+    return jv::rowblock(f, qkv, st);
+  }
+  // the same rows through the separate launchers (the kernels the fused launch is built from)
+  jv::RowGemmArgs a = rg_args(ap, 512, wo, sc_o, bo);      // h += to_out(att); ln = LayerNorm3(h)
+  a.out = h; a.ldo = 256; a.res = h; a.ldr = 256;
+  a.out2 = lnp; a.out2_plane = R * 256; a.ldo2 = 256; a.out2_scale = sc_1;
+  a.ln_g = ln3_g; a.ln_b = ln3_b;
+  a.amax_out = amax_h; a.row_slot = row_slot; a.row_mask = row_mask;
+  JV_TRY(jv::rowgemm(a, jv::RG_RES_LN, st));
+  JV_TRY(feed_forward(lnp, qkv ? lnp : ln_out));
+  if (!qkv) return JV_OK;
+  a = rg_args(lnp, 256, wq, sc_q, nullptr);
+  a.out = q; a.ldo = 512;
+  a.out2 = kv2; a.out2_plane = (long)rows * 1024; a.ldo2 = 1024; a.out2_scale = sc_k; a.out2_scale2 = sc_v;
+  return jv::rowgemm(a, jv::RG_QKV, st);
 }
 
 // the row-owning causal k = 3 convolution (rowconv_kernel.h) with its fused row-wise tail (test / tuning hook): one

@@ -29,7 +29,8 @@
 // impossible by construction as before; the bound is looser than a measurement (typically 5 - 20 x), which costs nothing in
 // relative precision (22 bits per element down to 2^-17 of the bound) and moves the absolute floor (2^-40 of the bound) by
 // as much.  A function of the utterance alone: results do not depend on the batch or on where a row sits.  Fused and unfused
-// agree to rounding (tests/test_gpu_ops.py, tests/test_gpu_pipeline.py).
+// agree to rounding: both sit inside the same fp64 bound (tests/test_gpu_fused_ops.py::test_hiftpair_against_two_hiftconv_launches;
+// end to end: tests/test_gpu_pipeline.py).
 #pragma once
 #include "hiftconv_kernel.h"
 

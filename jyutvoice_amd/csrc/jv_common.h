@@ -234,6 +234,15 @@ int splitk_reduce_rows(const SplitKReduceArgs& a, hipStream_t st);
 // column blocks a workgroup loads in one step are contiguous): lane l of a v_mfma_f32_16x16x32_f16 B operand holds row
 // 16 nb + (l & 15), k = 32 ks + 8 (l >> 4) ... + 8 (rowgemm.hip)
 int pack_wfrag(const unsigned short* w2, long w2_plane, int ldw, int N, int K, unsigned short* wf, long wf_plane, hipStream_t st);
+// the registry's concatenated fragment streams and load-time bounds (registry.hip), shared with the operator hooks (api.hip):
+// a vocoder ResBlock's two convolutions (hiftpair_kernel.h); a resnet's block1 | res_conv (rowconv_wd_kernel<RT, true>, rowres_kernel)
+int pack_wfrag_pair(const unsigned short* a2, long a_plane, const unsigned short* b2, long b_plane, int N, int K, unsigned short* wf,
+                    hipStream_t st);
+int pack_wfrag_res4(const unsigned short* b2, long b_plane, const unsigned short* q2, long q_plane, int Cin, unsigned short* wf,
+                    hipStream_t st);
+int dev_maxabs(const float* dev, int n, int stride, hipStream_t st, float* out);
+int snake_extra_of(const float* alpha_dev, int n, hipStream_t st, float* out);
+float resnet_h2_bound(float g_max, float b_max);
 int layernorm256_planes(const float* x, unsigned short* out2, long plane, float scale, const float* g, const float* b, float eps,
                         long rows, hipStream_t st);
 

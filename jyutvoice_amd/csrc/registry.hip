@@ -335,6 +335,62 @@ int split3_planes(const float* src, unsigned short* dst, long n, hipStream_t st)
   return JV_OK;
 }
 
+// max |x| of a small device vector, read back on `st` (load time and the operator hooks: synchronous); NaN if any element is
+int dev_maxabs(const float* dev, int n, int stride, hipStream_t st, float* out) {
+  std::vector<float> h((size_t)n * stride);
+  if (hipMemcpyAsync(h.data(), dev, h.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return fail(JV_ERR_HIP, "bound readback failed");
+  float m = 0.f;
+  for (int i = 0; i < n; ++i) {
+    const float a = fabsf(h[(size_t)i * stride]);
+    if (a != a) { *out = NAN; return JV_OK; }
+    m = fmaxf(m, a);
+  }
+  *out = m;
+  return JV_OK;
+}
+
+// x + sin^2(alpha x) / (alpha + 1e-9) <= |x| + 1 / (alpha + 1e-9): the largest such term over the channels, 0 when some
+// alpha is not positive (then the layer stays on bf16x6)
+int snake_extra_of(const float* alpha_dev, int n, hipStream_t st, float* out) {
+  std::vector<float> h((size_t)n);
+  *out = 0.f;
+  if (hipMemcpyAsync(h.data(), alpha_dev, h.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return fail(JV_ERR_HIP, "alpha readback failed");
+  float m = 0.f;
+  for (float a : h) {
+    if (!(a > 1e-6f) || !(a < 1e30f)) return JV_OK;
+    m = fmaxf(m, 1.0f / (a + 1e-9f));
+  }
+  *out = m;
+  return JV_OK;
+}
+
+// |Mish(LayerNorm_256(.))| <= sqrt(255) max |g| + max |b|: the bound rowres_kernel scales a resnet's intermediate from; 0 = unusable
+float resnet_h2_bound(float g_max, float b_max) {
+  const float hb = sqrtf(255.f) * g_max + b_max;
+  return (hb == hb && hb > 0.f && hb < 1e30f) ? hb : 0.f;
+}
+
+// a vocoder ResBlock's two convolutions (same k, N = C channels, K = k C) as ONE fragment stream (hiftpair_kernel.h): a's K / 32
+// steps, then b's; plane stride 2 N K halves
+int pack_wfrag_pair(const unsigned short* a2, long a_plane, const unsigned short* b2, long b_plane, int N, int K, unsigned short* wf,
+                    hipStream_t st) {
+  const long plane = (long)N * 2 * K;      // halves
+  const long second = (long)(K >> 5) * (N >> 4) * 512;      // k-step major: the second convolution's steps start here
+  JV_TRY(pack_wfrag(a2, a_plane, K, N, K, wf, plane, st));
+  return pack_wfrag(b2, b_plane, K, N, K, wf + second, plane, st);
+}
+
+// a resnet's block1 (k = 3, [256][3 Cin]) and its 1 x 1 res_conv ([256][Cin]), which read the same rows, as ONE fragment stream
+// (rowconv_wd_kernel<RT, true>, rowres_kernel): block1's 3 Cin / 32 steps, then res_conv's; plane stride 256 * 4 Cin halves
+int pack_wfrag_res4(const unsigned short* b2, long b_plane, const unsigned short* q2, long q_plane, int Cin, unsigned short* wf,
+                    hipStream_t st) {
+  const long plane = 256L * 4 * Cin;      // halves
+  JV_TRY(pack_wfrag(b2, b_plane, 3 * Cin, 256, 3 * Cin, wf, plane, st));
+  return pack_wfrag(q2, q_plane, Cin, 256, Cin, wf + 3L * (Cin >> 5) * 16 * 512, plane, st);
+}
+
 namespace {
 
 struct Packer {
@@ -381,35 +437,14 @@ struct Packer {
   // max |x| of a small device vector (load time only: synchronous)
   float host_maxabs(const float* dev, int n, int stride = 1) {
     if (!dev || rc != JV_OK) return NAN;
-    std::vector<float> h((size_t)n * stride);
-    if (hipMemcpyAsync(h.data(), dev, h.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      rc = fail(JV_ERR_HIP, "bound readback failed");
-      return NAN;
-    }
-    float m = 0.f;
-    for (int i = 0; i < n; ++i) {
-      const float a = fabsf(h[(size_t)i * stride]);
-      if (a != a) return NAN;
-      m = fmaxf(m, a);
-    }
+    float m = NAN;
+    if (dev_maxabs(dev, n, stride, st, &m) != JV_OK) { rc = JV_ERR_HIP; return NAN; }
     return m;
   }
-  // x + sin^2(alpha x) / (alpha + 1e-9) <= |x| + 1 / (alpha + 1e-9): the largest such term over the channels, 0 when some
-  // alpha is not positive (then the layer stays on bf16x6)
-  float snake_extra(const float* alpha_dev, int n) {
+  float snake_extra(const float* alpha_dev, int n) {      // (snake_extra_of)
     if (!alpha_dev || rc != JV_OK) return 0.f;
-    std::vector<float> h((size_t)n);
-    if (hipMemcpyAsync(h.data(), alpha_dev, h.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      rc = fail(JV_ERR_HIP, "alpha readback failed");
-      return 0.f;
-    }
     float m = 0.f;
-    for (float a : h) {
-      if (!(a > 1e-6f) || !(a < 1e30f)) return 0.f;
-      m = fmaxf(m, 1.0f / (a + 1e-9f));
-    }
+    if (snake_extra_of(alpha_dev, n, st, &m) != JV_OK) { rc = JV_ERR_HIP; return 0.f; }
     return m;
   }
   // attach the fp16x3 planes; returns the device vector of the rows' L1 norms (for the bound of what the layer produces)
@@ -453,9 +488,7 @@ struct Packer {
     float* d = alloc((size_t)plane + 8);
     if (!d) return nullptr;
     unsigned short* const wf = reinterpret_cast<unsigned short*>(d);
-    const long second = (long)(K >> 5) * (a.N >> 4) * 512;      // k-step major: the second convolution's steps start here
-    if (pack_wfrag(a.w2, (long)a.n_rows * a.ldw, a.ldw, a.N, K, wf, plane, st) != JV_OK ||
-        pack_wfrag(b.w2, (long)b.n_rows * b.ldw, b.ldw, b.N, K, wf + second, plane, st) != JV_OK) {
+    if (pack_wfrag_pair(a.w2, (long)a.n_rows * a.ldw, b.w2, (long)b.n_rows * b.ldw, a.N, K, wf, st) != JV_OK) {
       rc = JV_ERR_HIP;
       return nullptr;
     }
@@ -466,13 +499,12 @@ struct Packer {
     const GemmW &b = r.block1, &q = r.res;
     if (rc != JV_OK || !b.w2 || !q.w2 || !b.wf || b.ntaps != 3 || q.ntaps != 1 || b.Cin != q.Cin || b.N != 256 || q.N != 256 ||
         (b.Cin & 63) || b.ldw != 3 * b.Cin || q.ldw != q.Cin) return;
-    const int Cin = b.Cin, NCH = Cin >> 5;
+    const int Cin = b.Cin;
     const long plane = 256L * 4 * Cin;      // halves
     float* d = alloc((size_t)plane + 8);
     if (!d) return;
     unsigned short* const wf = reinterpret_cast<unsigned short*>(d);
-    if (pack_wfrag(b.w2, (long)b.n_rows * b.ldw, b.ldw, 256, 3 * Cin, wf, plane, st) != JV_OK ||
-        pack_wfrag(q.w2, (long)q.n_rows * q.ldw, q.ldw, 256, Cin, wf + 3L * NCH * 16 * 512, plane, st) != JV_OK) {
+    if (pack_wfrag_res4(b.w2, (long)b.n_rows * b.ldw, q.w2, (long)q.n_rows * q.ldw, Cin, wf, st) != JV_OK) {
       rc = JV_ERR_HIP;
       return;
     }
@@ -637,8 +669,7 @@ int finalize_model(Context& c, int model, hipStream_t st) {
       pk.wfrag4(e.res[i]);
       {
         const float gm = pk.host_maxabs(e.res[i].ln1.g, EST_CH), bm = pk.host_maxabs(e.res[i].ln1.b, EST_CH);
-        const float hb = sqrtf(255.f) * gm + bm;
-        e.res[i].h2_bound = (hb == hb && hb > 0.f && hb < 1e30f) ? hb : 0.f;
+        e.res[i].h2_bound = resnet_h2_bound(gm, bm);
       }
       for (int j = 0; j < EST_NBLK; ++j) {
         const std::string b = stage[i] + "1." + S(j) + ".";

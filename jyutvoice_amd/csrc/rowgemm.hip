@@ -242,6 +242,9 @@ int rowres(const RowResArgs& a, hipStream_t st) {
   if (a.M <= 0) return JV_OK;
   if (!a.A || !a.Wf1 || !a.Wf2 || !a.cs1 || !a.cs2 || !a.csr || !a.amax_in || !a.out || !a.temb || !a.ln1_g || !a.ln1_b || !a.ln2_g || !a.ln2_b)
     return fail(JV_ERR_ARG, "rowres: needs x, both fragment streams, the three column scales, the measured bound, both LayerNorms, the time embedding and an output");
+  // a workgroup reads its neighbours' rows of x as halo (block1's window of the two recomputed h2 rows): in place, a neighbour that
+  // finished first would have replaced them
+  if (static_cast<const void*>(a.out) == static_cast<const void*>(a.A)) return fail(JV_ERR_ARG, "rowres: the output must not alias the input (halo rows)");
   if ((a.Cin & 63) || a.Cin < 64 || (a.lda & 3) || (a.ldo & 3) || !(a.h2_bound > 0.f)) return fail(JV_ERR_ARG, "rowres: Cin % 64 == 0, aligned strides and the h2 bound required");
   if (a.slot_S < 0 && !a.row_slot) return fail(JV_ERR_ARG, "rowres: the compact geometry needs the row -> utterance table");
   if (a.lnf_out && (!a.lnf_g || !a.lnf_b || !(a.lnf_scale > 0.f) || a.lnf_plane <= 0 || a.ldo != 256))

@@ -33,7 +33,8 @@
 // (load time, registry.hip -- Mish(v) <= max(v, 0.31)) plus max |mlp(t)| of this step's embedding (256 values, reduced at
 // kernel start).  Overflow stays impossible by construction, the bound is a few times looser than a measurement (22
 // significant bits either way, the absolute floor 2^-40 of the bound moves with it), and it depends on the weights and on t
-// alone: batch invariance holds a fortiori.  Fused and unfused agree to the cross-regime bound (tests).
+// alone: batch invariance holds a fortiori.  Fused and unfused agree to the cross-regime bound
+// (tests/test_gpu_fused_ops.py::test_rowres_against_two_rowconv_launches).
 #pragma once
 #include "rowblock_kernel.h"
 #include "rowconv_kernel.h"

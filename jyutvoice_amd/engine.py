@@ -402,6 +402,113 @@ def op_hiftconv(A, W, bias, alpha, ntaps, dil, rowmask=None, res1=None, res2=Non
     return out
 
 
+# ---- the fused row-owning launches (tests/test_gpu_fused_ops.py).  Plane outputs come back un-scaled, as fp64 (h + l) / scale ------
+def h3_scale(bound: float) -> float:
+    """the power of two the library scales a tensor bounded by `bound` with (registry.hip h3_scale_for_bound)"""
+    return float(_lib.load().jv_h3_scale_for_bound(float(bound)))
+
+
+def _unscale(planes, scale):
+    return (planes[0].double() + planes[1].double()) / scale
+
+
+def _unscale_kv(kv2, k_bound, v_bound):
+    kv = kv2[0].double() + kv2[1].double()
+    return kv[:, :512] / h3_scale(k_bound), kv[:, 512:] / h3_scale(v_bound)
+
+
+def op_rowgemm_qkv(A, W, a_bound, k_bound, v_bound, M=None, nsplit=0, rt=0, planes=None):
+    """rowgemm's q | k | v epilogue: A [rows, K] fp32 (or planes=[2, rows, K] fp16 of A * h3_scale(a_bound), A then None),
+    W [1536, K] -> (q fp32 [rows, 512], k, v fp64 [rows, 512], kv2 the raw planes).  Rows >= M are left as allocated (NaN)."""
+    lib = _lib.load()
+    src = A if planes is None else planes
+    rows, K = src.shape[-2], src.shape[-1]
+    M = rows if M is None else M
+    q = torch.full((rows, 512), float("nan"), device=src.device)
+    kv2 = torch.full((2, rows, 1024), float("nan"), dtype=torch.float16, device=src.device)
+    check(lib.jv_op_rowgemm_qkv(_ptr(A if planes is None else None), _ptr(planes), rows, M, K, _ptr(W), float(a_bound), float(k_bound),
+                                float(v_bound), int(nsplit), int(rt), _ptr(q), _ptr(kv2), _stream(src.device)))
+    k, v = _unscale_kv(kv2, k_bound, v_bound)
+    return q, k, v, kv2
+
+
+def op_rowres(x, M, rowmask, amax_in, slots, w, lnf=None, lnf_bound=0.0, Wq=None, k_bound=0.0, v_bound=0.0, amax_out=None, out=None):
+    """rowres_kernel.h through jv_op_rowres.  x [rows, Cin]; slots = (G, S, nb) or an int32 [rows] row -> utterance table (the
+    compact addressing); w: dict W1 b1 ln1_g ln1_b Wr br temb W2 b2 ln2_g ln2_b; lnf = (g, b): the following LayerNorm1 -> planes
+    (Wq None) or q | k | v.  Returns dict(out, lnf (fp64, un-scaled), lnf_planes (raw), q, k, v)."""
+    lib = _lib.load()
+    rows, cin = x.shape
+    dev = x.device
+    if out is None:
+        out = torch.full((rows, 256), float("nan"), device=dev)
+    table = slots if torch.is_tensor(slots) else None
+    G, S, nb = (0, -1, int(amax_in.numel())) if table is not None else slots
+    g, b = lnf if lnf is not None else (None, None)
+    planes = torch.full((2, rows, 256), float("nan"), dtype=torch.float16, device=dev) if (lnf is not None and Wq is None) else None
+    q = torch.full((rows, 512), float("nan"), device=dev) if Wq is not None else None
+    kv2 = torch.full((2, rows, 1024), float("nan"), dtype=torch.float16, device=dev) if Wq is not None else None
+    check(lib.jv_op_rowres(_ptr(x), rows, int(M), cin, _ptr(rowmask), _ptr(amax_in), int(G), int(S), int(nb), _ptr(table),
+                           _ptr(w["W1"]), _ptr(w["b1"]), _ptr(w["ln1_g"]), _ptr(w["ln1_b"]), _ptr(w["Wr"]), _ptr(w["br"]),
+                           _ptr(w["temb"]), _ptr(w["W2"]), _ptr(w["b2"]), _ptr(w["ln2_g"]), _ptr(w["ln2_b"]), _ptr(g), _ptr(b),
+                           float(lnf_bound), _ptr(planes), _ptr(Wq), float(k_bound), float(v_bound), _ptr(q), _ptr(kv2),
+                           _ptr(amax_out), _ptr(out), _stream(dev)))
+    res = {"out": out, "lnf_planes": planes, "q": q}
+    if planes is not None:
+        res["lnf"] = _unscale(planes, h3_scale(lnf_bound))
+    if Wq is not None:
+        res["k"], res["v"] = _unscale_kv(kv2, k_bound, v_bound)
+        res["kv2"] = kv2
+    return res
+
+
+def op_hiftpair(A, W1, b1, alpha1, W2, b2, alpha2, ntaps, dil, amax_in, slots, rowmask=None, res2=None, out_scale=1.0, prev=None,
+                amax_out=None, out=None):
+    """hiftpair_kernel.h through jv_op_hiftpair: A [rows, C]; W1, W2 [C, ntaps * C] tap-major; slots = (G, S, nb) or an int32
+    [rows] row -> utterance table; prev: accumulate onto a copy of this tensor"""
+    lib = _lib.load()
+    rows, C = A.shape
+    if out is None:
+        out = prev.clone() if prev is not None else torch.full((rows, C), float("nan"), device=A.device)
+    table = slots if torch.is_tensor(slots) else None
+    G, S, nb = (0, 0, int(amax_in.numel())) if table is not None else slots
+    check(lib.jv_op_hiftpair(_ptr(A), rows, C, int(ntaps), int(dil), _ptr(W1), _ptr(b1), _ptr(alpha1), _ptr(W2), _ptr(b2), _ptr(alpha2),
+                             _ptr(rowmask), _ptr(amax_in), int(G), int(S), int(nb), _ptr(table), _ptr(res2), float(out_scale),
+                             1 if prev is not None else 0, _ptr(amax_out), _ptr(out), _stream(A.device)))
+    return out
+
+
+def op_rowblock(att, h, M, w, bounds, mode="plain", fused=1, out_ld=None, row_slot=None, row_mask=None, nslots=0):
+    """rowblock_kernel.h / rowffn through jv_op_rowblock.  att [rows, 512] (mode "ffn": x [rows, 256], the LayerNorm3 output),
+    h [rows, 256] (copied: the caller's tensor is left alone); w: dict Wo bo ln3_g ln3_b W1 b1 W2 b2 (+ ln1_g ln1_b, Wq);
+    bounds: dict att ln3 hid ln1 k v; mode "plain" / "ln" / "qkv" / "ffn"; out_ld = 512: out is a separate [rows, 512] buffer
+    (columns 0..255 written) instead of h.  Returns dict(h, out, ln, ln_planes, q, k, v, kv2, amax_h, amax_out)."""
+    lib = _lib.load()
+    dev = att.device
+    rows = h.shape[0]
+    code = {"plain": 0, "ln": 1, "qkv": 2, "ffn": 3}[mode]
+    h = h.clone()
+    out = h if out_ld is None else torch.full((rows, out_ld), float("nan"), device=dev)
+    follows = code in (1, 2) or (code == 3 and w.get("ln1_g") is not None)
+    ln_planes = torch.full((2, rows, 256), float("nan"), dtype=torch.float16, device=dev) if (follows and code != 2) else None
+    q = torch.full((rows, 512), float("nan"), device=dev) if code == 2 else None
+    kv2 = torch.full((2, rows, 1024), float("nan"), dtype=torch.float16, device=dev) if code == 2 else None
+    amax_h = torch.zeros(nslots, device=dev) if nslots else None
+    amax_out = torch.zeros(nslots, device=dev) if nslots else None
+    B = lambda k: float(bounds.get(k, 0.0))
+    P = lambda k: _ptr(w.get(k))
+    check(lib.jv_op_rowblock(_ptr(att), _ptr(h), rows, int(M), code, int(fused), B("att"), P("Wo"), P("bo"), P("ln3_g"), P("ln3_b"),
+                             B("ln3"), P("W1"), P("b1"), B("hid"), P("W2"), P("b2"), P("ln1_g") if follows else None,
+                             P("ln1_b") if follows else None, B("ln1"), P("Wq") if code == 2 else None, B("k"), B("v"), _ptr(out),
+                             256 if out_ld is None else int(out_ld), _ptr(ln_planes), _ptr(q), _ptr(kv2), _ptr(amax_h), _ptr(amax_out),
+                             _ptr(row_slot), _ptr(row_mask), _stream(dev)))
+    res = {"h": h, "out": out, "ln_planes": ln_planes, "q": q, "kv2": kv2, "amax_h": amax_h, "amax_out": amax_out}
+    if ln_planes is not None:
+        res["ln"] = _unscale(ln_planes, h3_scale(B("ln1")))
+    if code == 2:
+        res["k"], res["v"] = _unscale_kv(kv2, B("k"), B("v"))
+    return res
+
+
 def op_layernorm(x, g, b, eps=1e-5):
     lib = _lib.load()
     out = torch.empty_like(x)
