@@ -171,6 +171,38 @@ int jv_mel_spectrogram(jv_context* ctx, const float* wav, int B, int n_samples, 
 int jv_mel_spectrogram_ragged(jv_context* ctx, const float* wav, const int32_t* wav_lens, int B, int n_samples, float* mel,
                               int32_t* mel_lens, void* stream);
 
+/* ---- sample-rate conversion ----------------------------------------------------------------------------------
+ * The two `torchaudio.transforms.Resample(orig, new)` of infer.py:368-382 (the --ref_audio recording to 16 kHz and to 24 kHz), i.e.
+ * torchaudio.functional.resample with its defaults: sinc_interp_hann, lowpass_filter_width = 6, rolloff = 0.99.  Restated (unpinned:
+ * torchaudio is not part of this build) with g = gcd(orig, new), o = orig / g, n = new / g:
+ *   orig == new: a copy.  Otherwise base = 0.99 min(o, n), width = ceil(6 o / base), K = 2 width + o,
+ *   h(tau) = (base / o) sinc(base tau) cos^2(pi base tau / 12) for |base tau| <= 6, else 0  (sinc(u) = sin(pi u) / (pi u)),
+ *   tab[p][k] = h((k - width) / o - p / n), p in [0, n), k in [0, K): evaluated in fp64, rounded once to fp32,
+ *   y[i n + p] = sum_{k < K} tab[p][k] x[i o + k - width], x = 0 outside [0, L), for the first ceil(n L / o) output samples;
+ *   products and sum in fp32, k ascending, the same order for every sample wherever it lies in a batch.
+ *
+ * jv_resample_length: infer.py:368-382's output length, ceil(new n / orig) in reduced integers; n for equal rates; -1 for n < 0,
+ *   a rate <= 0 or a result beyond int64.  Host only, no context.
+ * jv_resample_table: the table above for a rate pair (host only, no context, no device, like jv_h3_scale_for_bound).  Writes
+ *   *o, *n, *width (each optional); with tab != NULL and cap >= n K also tab[p * K + k], with tab != NULL and a smaller cap
+ *   JV_ERR_SHAPE; tab == NULL queries the sizes.  Equal rates give o = n = 1 and the filter of that pair, which jv_resample does
+ *   not use.  JV_ERR_ARG for a rate <= 0 or a table of more than 2^20 entries (n K; the message names o, n and the cap).
+ * jv_resample: infer.py:368-382 for a ragged batch in one launch.  wav: [B, n_in]; lens: [B] int32 on the device or NULL (all n_in),
+ *   clamped as under "Lengths" above: it MEANS len_b = min(max(lens[b], 0), n_in), and what lies behind it is not read (it may be
+ *   NaN).  out: [B, n_out], n_out >= jv_resample_length(n_in, orig_freq, new_freq) else JV_ERR_SHAPE; recording b fills
+ *   out[b, :ceil(n len_b / o)], zeros behind.  out_lens: optional [B] int32 on the device, receives ceil(n len_b / o).
+ *   Rates <= 0 and reduced pairs whose table exceeds 2^20 entries: JV_ERR_ARG, before anything is launched; the context stays
+ *   usable.  The table is built on the host and uploaded once per (o, n) (a small cache in the context, untouched by jv_reserve);
+ *   with the table cached the call only enqueues on `stream` and never synchronises.  A miss allocates, copies synchronously and,
+ *   once the cache holds 8 tables, waits for the device and frees the least recently used one.  So under stream capture: make the
+ *   first call for a reduced pair (o, n) OUTSIDE the capture (a miss while capturing fails), and a context that has served more
+ *   than 8 distinct reduced pairs since may have freed the table a captured launch points to -- capture again after that.
+ *   One launch holds fewer than 2^24 workgroups (B ceil(n_out / tile), tile <= 1024): beyond that JV_ERR_SHAPE. */
+int64_t jv_resample_length(int64_t n, int orig_freq, int new_freq);
+int jv_resample_table(int orig_freq, int new_freq, float* tab, int64_t cap, int32_t* o, int32_t* n, int32_t* width);
+int jv_resample(jv_context* ctx, const float* wav, const int32_t* lens, int B, int n_in, int orig_freq, int new_freq, float* out,
+                int64_t n_out, int32_t* out_lens, void* stream);
+
 /* ---- text encoder + duration predictor + length regulation ---------------------------------------------
  * jv_encoder_fwd: spk_embed_affine_layer(normalize(spk)) + TextEncoder.forward + DurationPredictor.forward
  * (jyutvoice/models/jyutvoice_tts.py:175-182, text_encoder.py:406-451, duration_predictor.py:48-60).

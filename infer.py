@@ -17,12 +17,15 @@ mel extractor.  Instead this CLI takes their outputs directly:
                              "spk_embed": [192 floats], and for voice cloning
                              "prompt_token": [speech-token ids] + either "prompt_feat": [[80 floats] per frame] or
                              "prompt_wav_24k": "ref_24k.wav" (16-bit mono; its mel is extracted on the GPU as
-                             infer.py:386 does) -- what infer.py:386-392 gets from --ref_audio; the prompt encoder
+                             infer.py:386 does) or "prompt_wav": "ref.wav" (any rate, PCM or float, any number of channels:
+                             read by jyutvoice_amd.utils.audio.load_wav and resampled to 24 kHz on the GPU as infer.py:368-382
+                             does) -- what infer.py:386-392 gets from --ref_audio; the prompt encoder
                              (--flow_encoder) then runs on the GPU exactly as infer.py:390-392 runs it
                              A JSON *list* of such objects is synthesised as ONE batch, every utterance with its own
                              prompt of its own length (or none); the results go to OUTPUT with _000, _001, ... before the
                              extension.  Each utterance's prompt_h (2 frames per prompt token) and prompt mel are trimmed
                              to the shorter of the two first: the batch takes one prompt length per utterance
+    --sample_rate R          write the audio at R Hz instead of 24000 (resampled on the GPU, the whole batch in one call)
     --synthetic N            no checkpoint / no tokens: N synthetic tokens, key-hashed weights (smoke / demo)
     --synthetic-prompt K     with --synthetic: also a synthetic K-token voice prompt through the prompt encoder
 
@@ -70,6 +73,20 @@ def read_wav_24k(path: str):
     return (torch.frombuffer(bytearray(pcm), dtype=torch.int16).float() / 32768.0).unsqueeze(0)
 
 
+PROMPT_SOURCES = ("prompt_feat", "prompt_wav_24k", "prompt_wav")
+
+
+def read_prompt_wav(tok):
+    """the recording of a request, from `prompt_wav` (any format load_wav reads) or `prompt_wav_24k`: ([1, n] float, sample rate)"""
+    if "prompt_wav" in tok:
+        from jyutvoice_amd.utils.audio import load_wav
+        try:
+            return load_wav(tok["prompt_wav"])
+        except (OSError, ValueError) as e:
+            raise SystemExit(str(e))
+    return read_wav_24k(tok["prompt_wav_24k"]), 24000
+
+
 def synthesise_list(toks, args, tts, hift, device):
     """--tokens with a JSON list: all utterances in one batch through synthesise(batched=True, prompt_lengths=...)"""
     import torch
@@ -94,7 +111,7 @@ def synthesise_list(toks, args, tts, hift, device):
     # prompts: the prompt encoder on the ragged token batch, the prompt mels of all recordings in one ragged pass
     empty = torch.zeros(0, 80)
     feats, hs = [empty] * B, [empty] * B
-    with_prompt = [b for b, t in enumerate(toks) if "prompt_token" in t and ("prompt_feat" in t or "prompt_wav_24k" in t)]
+    with_prompt = [b for b, t in enumerate(toks) if "prompt_token" in t and any(k in t for k in PROMPT_SOURCES)]
     if with_prompt:
         from jyutvoice_amd.flow.encoder import load_flow_encoder
         from jyutvoice_amd.utils.audio import extract_speech_feat_batch
@@ -105,8 +122,11 @@ def synthesise_list(toks, args, tts, hift, device):
         for i, b in enumerate(with_prompt):
             ptok[i, : plens[i]] = torch.tensor(toks[b]["prompt_token"], dtype=torch.int64)
         h, h_len = flow_encoder(ptok, plens)
-        from_wav = [b for b in with_prompt if "prompt_wav_24k" in toks[b]]
-        if from_wav:
+        from_wav = [b for b in with_prompt if "prompt_wav_24k" in toks[b] or "prompt_wav" in toks[b]]
+        if any("prompt_wav" in toks[b] for b in from_wav):      # recordings at rates of their own: grouped by rate, resampled on the GPU
+            recs = [read_prompt_wav(toks[b]) for b in from_wav]
+            mel, mel_len = extract_speech_feat_batch([w for w, _ in recs], device, sample_rates=[r for _, r in recs])
+        elif from_wav:
             mel, mel_len = extract_speech_feat_batch([read_wav_24k(toks[b]["prompt_wav_24k"]) for b in from_wav], device)
         for i, b in enumerate(with_prompt):
             if b in from_wav:
@@ -130,11 +150,15 @@ def synthesise_list(toks, args, tts, hift, device):
     wav, _ = hift.inference(result["mel"], lengths=result["mel_lengths"])
     torch.cuda.synchronize()
     print(f"Synthesis time: {time.time() - start:.2f} s (rtf of synthesise(): {result['rtf']:.4f})")
+    samples = result["mel_lengths"] * 480
+    if args.sample_rate != 24000:      # the whole batch in one ragged call, each utterance at its own length
+        from jyutvoice_amd.utils.audio import resample
+        wav, samples = resample(wav, 24000, args.sample_rate, lengths=samples)
     stem, ext = os.path.splitext(args.output)
-    for b, frames in enumerate(result["mel_lengths"].tolist()):
+    for b, n in enumerate(samples.tolist()):
         path = f"{stem}_{b:03d}{ext}"
-        write_wav(path, wav[b, : frames * 480])
-        print(f"Generated audio saved to: {path} ({frames * 480 / 24000:.2f} seconds)")
+        write_wav(path, wav[b, :n], args.sample_rate)
+        print(f"Generated audio saved to: {path} ({n / args.sample_rate:.2f} seconds)")
 
 
 def main(argv=None):
@@ -156,7 +180,14 @@ def main(argv=None):
     p.add_argument("--synthetic", type=int, default=0, help="use N synthetic tokens and synthetic weights")
     p.add_argument("--synthetic-prompt", type=int, default=0, help="with --synthetic: K synthetic prompt tokens (voice-cloning path)")
     p.add_argument("--seed", type=int, default=0, help="seed of the vocoder's source-noise draws")
+    p.add_argument("--sample_rate", type=int, default=24000, help="sample rate of the written audio (resampled on the GPU)")
     args = p.parse_args(argv)
+    if args.sample_rate <= 0:
+        raise SystemExit("--sample_rate must be positive")
+    if args.sample_rate != 24000:      # a rate whose filter table the library refuses: say so before anything is loaded
+        from jyutvoice_amd import _lib
+        if _lib.load().jv_resample_table(24000, args.sample_rate, None, 0, None, None, None) != 0:
+            raise SystemExit("--sample_rate: " + _lib.load().jv_last_error().decode("utf-8", "replace"))
 
     import torch
 
@@ -202,13 +233,17 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit(str(e))
         spk = torch.tensor(tok["spk_embed"], dtype=torch.float32).view(1, 192) if "spk_embed" in tok else torch.randn(1, 192)
-        if "prompt_token" in tok and ("prompt_feat" in tok or "prompt_wav_24k" in tok):   # infer.py:386-392
+        if "prompt_token" in tok and any(k in tok for k in PROMPT_SOURCES):   # infer.py:386-392
             from jyutvoice_amd.flow.encoder import load_flow_encoder
             print(f"Loading flow encoder from {args.flow_encoder}...")
             flow_encoder = load_flow_encoder(args.flow_encoder, device)
             ptok = torch.tensor(tok["prompt_token"], dtype=torch.int64).view(1, -1)
             prompt_h, _ = flow_encoder(ptok, torch.tensor([ptok.shape[1]], dtype=torch.int64))
-            if "prompt_wav_24k" in tok:
+            if "prompt_wav" in tok:      # infer.py:368-382: the recording at its own rate -> 24 kHz on the GPU
+                from jyutvoice_amd.utils.audio import extract_speech_feat, resample
+                speech, rate = read_prompt_wav(tok)
+                prompt_feat, _ = extract_speech_feat(resample(speech, rate, 24000, device=device), device)
+            elif "prompt_wav_24k" in tok:
                 from jyutvoice_amd.utils.audio import extract_speech_feat
                 prompt_feat, _ = extract_speech_feat(read_wav_24k(tok["prompt_wav_24k"]), device)
             else:
@@ -226,10 +261,13 @@ def main(argv=None):
     wav, _ = hift.inference(result["mel"])
     torch.cuda.synchronize()
     print(f"Synthesis time: {time.time() - start:.2f} s (rtf of synthesise(): {result['rtf']:.4f})")
+    if args.sample_rate != 24000:
+        from jyutvoice_amd.utils.audio import resample
+        wav = resample(wav, 24000, args.sample_rate)
     print(f"Saving audio to {args.output}...")
-    write_wav(args.output, wav[0])
+    write_wav(args.output, wav[0], args.sample_rate)
     print(f"Generated audio saved to: {args.output}")
-    print(f"Audio duration: {wav.shape[1] / 24000:.2f} seconds")
+    print(f"Audio duration: {wav.shape[1] / args.sample_rate:.2f} seconds")
 
 
 if __name__ == "__main__":

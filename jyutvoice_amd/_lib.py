@@ -59,6 +59,9 @@ SIGNATURES = {
     "jv_load_mel_basis": (_i, [_p, _p, _i64, _i, _p]),
     "jv_mel_spectrogram": (_i, [_p, _p, _i, _i, _p, _p]),
     "jv_mel_spectrogram_ragged": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
+    "jv_resample_length": (_i64, [_i64, _i, _i]),
+    "jv_resample_table": (_i, [_i, _i, _p, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "jv_resample": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i64, _p, _p]),
     "jv_prompt_encoder_fwd": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "jv_length_regulate": (_i, [_p, _p, _p, _p, _i, _i, _f, _p, _p, _i, _p, _p, _p]),
     "jv_hift_f0": (_i, [_p, _p, _p, _i, _i, _p, _p]),

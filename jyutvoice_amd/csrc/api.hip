@@ -232,6 +232,7 @@ void jv_destroy(jv_context* ctx) {
   c.raw_arena.release();
   c.packed.release();
   jv::audio_ws_destroy(c);
+  jv::resample_ws_destroy(c);
   delete ctx;
 }
 

@@ -180,6 +180,7 @@ struct Context {
   struct EncWs* ews = nullptr;
   struct PromptWs* pws = nullptr;
   struct AudioWs* aws = nullptr;
+  struct ResampleWs* rws = nullptr;   // resampling tables per reduced rate pair (resample.hip): not workspace, survives jv_reserve
   std::string last_error;
 };
 
@@ -209,6 +210,9 @@ void prompt_ws_destroy(Context& c);
 
 // audio.hip
 void audio_ws_destroy(Context& c);
+
+// resample.hip
+void resample_ws_destroy(Context& c);
 
 }  // namespace jv
 

@@ -195,6 +195,27 @@ class Engine:
         check(self.lib.jv_mel_spectrogram(self._h, _ptr(w), B, n, _ptr(mel), _stream(self.device)))
         return mel
 
+    # ---- sample-rate conversion ------------------------------------------------------------------------
+    def resample(self, wav, orig_freq, new_freq, lens=None):
+        """torchaudio.functional.resample(wav, orig_freq, new_freq) with its defaults (infer.py:368-382; jv_resample):
+        wav [B, n] -> out [B, resample_length(n)].  lens ([B] sample counts, clamped to [0, n]): recording b = wav[b, :lens[b]],
+        what lies behind is not read; returns (out, out_lens int32 [B]) with out[b, out_lens[b]:] = 0"""
+        w = _f32(wav, self.device)
+        if w.dim() != 2:
+            raise ValueError(f"resample: wav must be [B, n], got {tuple(w.shape)}")
+        B, n = w.shape
+        n_out = int(self.lib.jv_resample_length(n, int(orig_freq), int(new_freq)))
+        out = torch.empty(B, max(n_out, 0), device=self.device)
+        wl = out_lens = None
+        if lens is not None:
+            wl = lens.to(device=self.device, dtype=torch.int32).contiguous()
+            if wl.shape != (B,):
+                raise ValueError(f"resample: lens must have shape [{B}], got {tuple(wl.shape)}")
+            out_lens = torch.empty(B, dtype=torch.int32, device=self.device)
+        check(self.lib.jv_resample(self._h, _ptr(w), _ptr(wl), B, n, int(orig_freq), int(new_freq), _ptr(out), out.shape[1],
+                                   _ptr(out_lens), _stream(self.device)))
+        return out if lens is None else (out, out_lens)
+
     # ---- prompt branch --------------------------------------------------------------------------------
     def prompt_encoder(self, token, token_len):
         """FlowEncoder.forward (infer.py:66-83): token [B,Tk] int64, token_len [B] -> prompt_h [B, 2*Tk, 80]"""

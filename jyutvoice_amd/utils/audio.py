@@ -1,6 +1,7 @@
 """`mel_spectrogram` / `extract_speech_feat` drop-ins (jyutvoice/utils/audio.py:18-63, infer.py:166-186): the prompt mel of
 the voice-cloning branch, computed on the GPU by libjyutvoice_hip.so (jv_mel_spectrogram: STFT as a GEMM against a windowed
-DFT basis, magnitude, mel projection, log).
+DFT basis, magnitude, mel projection, log) -- and what infer.py:368-382 does before it: `load_wav` reads the recording at whatever
+rate the file has, `resample` converts it on the GPU (jv_resample: torchaudio.functional.resample with its defaults).
 
 The mel filterbank is data handed to the library.  The reference takes it from `librosa.filters.mel`; when librosa is
 importable it is used here too, otherwise `slaney_mel_basis` evaluates the same published construction (Slaney mel scale,
@@ -8,6 +9,7 @@ triangular filters on the FFT bin centres, area normalisation) so that the modul
 from __future__ import annotations
 
 import math
+import struct
 
 import numpy as np
 import torch
@@ -80,16 +82,132 @@ def extract_speech_feat(speech, device="cuda:0"):
     return feat, torch.tensor([feat.shape[1]], dtype=torch.int32, device=feat.device)
 
 
-def extract_speech_feat_batch(speeches, device="cuda:0"):
+def extract_speech_feat_batch(speeches, device="cuda:0", sample_rates=None):
     """`extract_speech_feat` of several recordings of different durations in one GPU pass (jv_mel_spectrogram_ragged):
     speeches = list of [1, n_b] or [n_b] tensors at 24 kHz -> (speech_feat [B, Tmax, 80], zero behind each recording's frames,
-    speech_feat_len [B] int32).  Recording b's frames are those of `extract_speech_feat(speeches[b])`, bit for bit."""
+    speech_feat_len [B] int32).  Recording b's frames are those of `extract_speech_feat(speeches[b])`, bit for bit.
+
+    sample_rates (one int per recording): the recordings come at rates of their own (infer.py:368-382).  They are grouped by
+    rate, each group goes through one ragged `jv_resample` call to 24 kHz, and the lengths it leaves on the device feed the
+    ragged mel pass: recording b's frames are those of `extract_speech_feat(resample(speeches[b], sample_rates[b], 24000))`,
+    bit for bit.  None is the 24 kHz path above, untouched."""
     wavs = [s.reshape(-1).to(torch.float32) for s in speeches]
     if not wavs:
         raise ValueError("extract_speech_feat_batch: no recordings")
+    if sample_rates is not None:
+        return _extract_resampled(wavs, [int(r) for r in sample_rates], torch.device(device))
+    buf, lens = _pad_rows(wavs)
+    mel, mel_lens = _engine(torch.device(device)).mel_spectrogram(buf, lens)
+    return mel.transpose(1, 2).contiguous(), mel_lens
+
+
+def _pad_rows(wavs):
     lens = torch.tensor([w.numel() for w in wavs], dtype=torch.int32)
     buf = torch.zeros(len(wavs), int(lens.max()), dtype=torch.float32)
     for b, w in enumerate(wavs):
         buf[b, : w.numel()] = w.cpu()
-    mel, mel_lens = _engine(torch.device(device)).mel_spectrogram(buf, lens)
+    return buf, lens
+
+
+def _extract_resampled(wavs, rates, dev):
+    if len(rates) != len(wavs):
+        raise ValueError(f"extract_speech_feat_batch: {len(wavs)} recordings, {len(rates)} sample rates")
+    eng = _engine(dev)
+    groups = {}
+    for b, r in enumerate(rates):
+        groups.setdefault(r, []).append(b)
+    done = []
+    for r, members in groups.items():      # one ragged launch per rate; nothing comes back to the host
+        buf, lens = _pad_rows([wavs[b] for b in members])
+        out, out_lens = eng.resample(buf, r, _PARAMS["sampling_rate"], lens)
+        done.append((torch.tensor(members, device=out.device), out, out_lens))
+    wav24 = torch.zeros(len(wavs), max(out.shape[1] for _, out, _ in done), device=done[0][1].device)
+    lens24 = torch.zeros(len(wavs), dtype=torch.int32, device=wav24.device)
+    for idx, out, out_lens in done:
+        wav24[idx, : out.shape[1]] = out
+        lens24[idx] = out_lens
+    mel, mel_lens = eng.mel_spectrogram(wav24, lens24)
     return mel.transpose(1, 2).contiguous(), mel_lens
+
+
+# ---- infer.py:368-382: the recording at its own rate, and its 16 / 24 kHz copies ----------------------------------------------
+def resample_length(n, orig_freq, new_freq):
+    """samples that n samples at orig_freq become at new_freq: ceil(new n / orig) in reduced integers (jv_resample_length)"""
+    from .. import _lib
+    got = int(_lib.load().jv_resample_length(int(n), int(orig_freq), int(new_freq)))
+    if got < 0:
+        raise ValueError(f"resample_length: need n >= 0 and positive rates, got n = {n}, {orig_freq} -> {new_freq}")
+    return got
+
+
+def resample(waveform, orig_freq, new_freq, lengths=None, device="cuda:0"):
+    """`torchaudio.functional.resample(waveform, orig_freq, new_freq)` with its defaults -- what the two
+    `torchaudio.transforms.Resample` of infer.py:368-382 compute -- on the GPU (jv_resample).  waveform [n] or [B, n] -> the same
+    rank, resample_length(n) samples.  lengths ([B] sample counts): recordings of different durations in one call, recording b
+    = waveform[b, :lengths[b]]; returns (out, out_lengths int32 [B]) with zeros behind each recording's samples."""
+    if waveform.dim() not in (1, 2):
+        raise ValueError(f"resample: waveform must be [n] or [B, n], got {tuple(waveform.shape)}")
+    dev = waveform.device if waveform.is_cuda else torch.device(device)
+    eng = get_runtime(dev).ensure(1, 64, 1)
+    res = eng.resample(waveform if waveform.dim() == 2 else waveform.unsqueeze(0), orig_freq, new_freq, lengths)
+    if lengths is not None:
+        return res
+    return res if waveform.dim() == 2 else res.squeeze(0)
+
+
+_PCM, _FLOAT, _EXTENSIBLE = 1, 3, 0xFFFE
+
+
+def load_wav(path):
+    """RIFF/WAVE file -> (wav [1, n] float32 in [-1, 1), sample_rate): the `torchaudio.load` of infer.py:368.  Format tags 1 (PCM:
+    8-bit unsigned, 16 / 24 / 32-bit signed, scaled by 2^-(bits - 1)), 3 (float32 / float64) and 0xFFFE (extensible: the sub-format
+    is the first two bytes of its GUID); chunks other than `fmt ` and `data` are skipped, pad byte included; a data size of 0 or
+    0xFFFFFFFF (a streamed file) reads to the end of the file.
+
+    Several channels are AVERAGED to one.  `torchaudio.load` keeps them as [channels, n], which the reference then passes on as
+    if the channels were a batch (infer.py:371-392 index row 0 in some places and all rows in others); a mono prompt is what that
+    path means."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise ValueError(f"{path}: not a RIFF/WAVE file")
+    pos, fmt, pcm = 12, None, None
+    while pos + 8 <= len(data) and pcm is None:
+        tag, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
+        body = pos + 8
+        if tag == b"fmt ":
+            if size < 16 or body + 16 > len(data):
+                raise ValueError(f"{path}: truncated fmt chunk")
+            code, channels, rate, _, align, bits = struct.unpack("<HHIIHH", data[body:body + 16])
+            if code == _EXTENSIBLE:
+                if size < 40 or body + 26 > len(data):
+                    raise ValueError(f"{path}: extensible format without its sub-format")
+                code = struct.unpack("<H", data[body + 24:body + 26])[0]
+            fmt = (code, channels, rate, bits)
+        elif tag == b"data":
+            if fmt is None:
+                raise ValueError(f"{path}: data chunk before the fmt chunk")
+            pcm = data[body:] if size in (0, 0xFFFFFFFF) else data[body:body + size]
+        pos = body + size + (size & 1)
+    if fmt is None or pcm is None:
+        raise ValueError(f"{path}: no {'fmt' if fmt is None else 'data'} chunk")
+    code, channels, rate, bits = fmt
+    if channels < 1 or rate < 1:
+        raise ValueError(f"{path}: {channels} channels at {rate} Hz")
+    if code == _PCM and bits in (8, 16, 24, 32):
+        width = bits // 8
+        raw = np.frombuffer(pcm, dtype=np.uint8, count=len(pcm) // width * width)
+        if bits == 8:
+            x = (raw.astype(np.float64) - 128.0) / 128.0
+        elif bits == 24:
+            b3 = raw.reshape(-1, 3).astype(np.int32)
+            x = (((b3[:, 0] | (b3[:, 1] << 8) | (b3[:, 2] << 16)) ^ 0x800000) - 0x800000).astype(np.float64) / float(1 << 23)
+        else:
+            x = raw.view("<i2" if bits == 16 else "<i4").astype(np.float64) / float(1 << (bits - 1))
+    elif code == _FLOAT and bits in (32, 64):
+        width = bits // 8
+        x = np.frombuffer(pcm, dtype="<f4" if bits == 32 else "<f8", count=len(pcm) // width).astype(np.float64)
+    else:
+        raise ValueError(f"{path}: format tag {code} with {bits} bits per sample is not supported (PCM 8/16/24/32, float 32/64)")
+    x = x[: x.size // channels * channels].reshape(-1, channels).mean(axis=1)
+    return torch.from_numpy(x.astype(np.float32)).unsqueeze(0), int(rate)
