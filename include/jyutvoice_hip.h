@@ -203,6 +203,51 @@ int jv_resample_table(int orig_freq, int new_freq, float* tab, int64_t cap, int3
 int jv_resample(jv_context* ctx, const float* wav, const int32_t* lens, int B, int n_in, int orig_freq, int new_freq, float* out,
                 int64_t n_out, int32_t* out_lens, void* stream);
 
+/* ---- reference-audio features at 16 kHz ---------------------------------------------------------------------
+ * What infer.py:98-163 computes from the 16 kHz copy of the reference recording: the input of campplus.onnx
+ * (`kaldi.fbank(speech, num_mel_bins=80, dither=0, sample_frequency=16000)` minus its mean over frames, infer.py:148-163) and the
+ * input of speech_tokenizer_v2.onnx (`whisper.log_mel_spectrogram(audio, n_mels=128)`, infer.py:98-145).  Both are restated here
+ * (unpinned: torchaudio and whisper are not part of this build).
+ *
+ * fbank.  x: len samples in [-1, 1], NOT rescaled to int16 range.  len < 400: 0 frames.  Otherwise T = 1 + (len - 400) / 160 frames,
+ *   frame f = x[160 f : 160 f + 400]; per frame: subtract the frame's mean; pre-emphasis a[i] -= 0.97 a[i-1] with a[-1] := a[0];
+ *   times the Povey window (0.5 - 0.5 cos(2 pi i / 399))^0.85; zero-pad to 512, |rfft|^2; 80 triangular banks equally spaced on
+ *   mel(f) = 1127 ln(1 + f / 700) between mel(20) and mel(8000): bank b rises from lo + b d to lo + (b + 1) d and falls to
+ *   lo + (b + 2) d, d = (hi - lo) / 81, the weight of bin k < 256 is max(0, min(up, down)) at mel(31.25 k), bin 256 has weight 0;
+ *   log(max(E, 2^-23)), natural.  [T, 80]; with subtract_mean the mean over the recording's own T frames is subtracted per bin.
+ * Whisper log-mel.  Reflect-pad 200 samples per side (needs len > 200); frames of 400 every 160, periodic Hann
+ *   0.5 - 0.5 cos(2 pi i / 400), 400-point |rfft|^2 (201 bins); the last frame is dropped: T = len / 160 frames; the 128 x 201
+ *   filterbank is data (whisper ships librosa.filters.mel(sr=16000, n_fft=400, n_mels=128); jv_load_whisper_filters);
+ *   L = log10(max(E, 1e-10)); L = max(L, max(L) - 8), the maximum over that recording's whole [128, T]; (L + 4) / 4.  [128, T].
+ * Arithmetic: conditioning, both products (k in a fixed order that does not depend on the frame's place in a tile or a batch),
+ *   the power and the logs in fp32; windows and DFT bases evaluated in fp64 and rounded once; a recording's mean / maximum is
+ *   reduced over its tiles of 32 frames in ascending order.  A recording gives the same bits alone and in any batch.
+ *
+ * jv_fbank_frames / jv_whisper_frames: the frame counts above for n samples (0 when too short).  Host only, no context.
+ * jv_kaldi_mel_banks: the 80 x 257 bank weights above, evaluated in fp64 and rounded once.  Host only, no context.
+ * jv_load_whisper_filters: the [128, 201] filterbank (host or device memory); numel != 128 * 201: JV_ERR_SHAPE.  Synchronises.
+ * jv_fbank: wav [B, n]; lens: [B] int32 on the device or NULL (all n), clamped as under "Lengths" above: it MEANS
+ *   len_b = min(max(lens[b], 0), n), and what lies behind it is not read (it may be NaN).  out: [B, Tmax, 80],
+ *   Tmax = jv_fbank_frames(n); recording b fills out[b, :T_b], exact zeros behind.  out_lens: optional [B] int32 on the device,
+ *   receives T_b.  A recording too short for a frame has T_b = 0, a zero row and no error (nothing comes down to the host, so the
+ *   library cannot reject it); with lens == NULL the host knows n and returns JV_ERR_ARG for n < 400.
+ * jv_whisper_log_mel: the same contract; out: [B, 128, Tmax], Tmax = jv_whisper_frames(n); too short is len <= 200.
+ *   JV_ERR_STATE before jv_load_whisper_filters.
+ * Every error is returned before anything is launched and leaves the context usable.  Each call is two launches on `stream`
+ * (one with subtract_mean == 0) and never synchronises -- except that the first call of a feature in a context allocates its
+ * window, basis and bank tables (fbank: uploads the banks synchronously), and a call with more tiles (B ceil(Tmax / 32)) than any
+ * before waits for the device and re-allocates the partials buffer: under stream capture make a call of the largest shape
+ * outside the capture first.  These buffers are not workspace: jv_reserve leaves them alone, jv_destroy frees them.
+ * One launch holds fewer than 2^24 workgroups: beyond that JV_ERR_SHAPE. */
+int64_t jv_fbank_frames(int64_t n);
+int64_t jv_whisper_frames(int64_t n);
+int jv_kaldi_mel_banks(float* out /* 80 * 257 */);
+int jv_load_whisper_filters(jv_context* ctx, const float* data, int64_t numel, int on_device, void* stream);
+int jv_fbank(jv_context* ctx, const float* wav, const int32_t* lens, int B, int n, int subtract_mean, float* out, int32_t* out_lens,
+             void* stream);
+int jv_whisper_log_mel(jv_context* ctx, const float* wav, const int32_t* lens, int B, int n, float* out, int32_t* out_lens,
+                       void* stream);
+
 /* ---- text encoder + duration predictor + length regulation ---------------------------------------------
  * jv_encoder_fwd: spk_embed_affine_layer(normalize(spk)) + TextEncoder.forward + DurationPredictor.forward
  * (jyutvoice/models/jyutvoice_tts.py:175-182, text_encoder.py:406-451, duration_predictor.py:48-60).

@@ -26,6 +26,10 @@ mel extractor.  Instead this CLI takes their outputs directly:
                              extension.  Each utterance's prompt_h (2 frames per prompt token) and prompt mel are trimmed
                              to the shorter of the two first: the batch takes one prompt length per utterance
     --sample_rate R          write the audio at R Hz instead of 24000 (resampled on the GPU, the whole batch in one call)
+    --dump-ref-features DIR  every request with a "prompt_wav" (or "prompt_wav_24k") also gets what infer.py:98-163 feeds the two ONNX
+                             front-ends from the recording's 16 kHz copy: DIR/ref_NNN_fbank.npy (kaldi fbank minus its mean over
+                             frames, [T, 80]) and DIR/ref_NNN_logmel.npy (whisper log-mel, [128, T]), NNN the request's number; all
+                             requests of a list in one GPU batch per feature (the ONNX sessions themselves are not loaded here)
     --synthetic N            no checkpoint / no tokens: N synthetic tokens, key-hashed weights (smoke / demo)
     --synthetic-prompt K     with --synthetic: also a synthetic K-token voice prompt through the prompt encoder
 
@@ -87,6 +91,29 @@ def read_prompt_wav(tok):
     return read_wav_24k(tok["prompt_wav_24k"]), 24000
 
 
+def dump_ref_features(toks, args, device):
+    """--dump-ref-features: the speaker fbank and the tokenizer log-mel of every request's recording, one ragged batch per feature"""
+    import numpy as np
+
+    from jyutvoice_amd.utils.audio import extract_spk_feat_batch, extract_token_feat_batch
+    idx = [b for b, t in enumerate(toks) if "prompt_wav" in t or "prompt_wav_24k" in t]
+    if not idx:
+        return
+    recs = [read_prompt_wav(toks[b]) for b in idx]
+    wavs, rates = [w for w, _ in recs], [r for _, r in recs]
+    try:
+        fb, fb_len = extract_spk_feat_batch(wavs, rates, device)
+        lm, lm_len = extract_token_feat_batch(wavs, rates, device)
+    except ValueError as e:
+        raise SystemExit(f"--dump-ref-features: {e}")
+    os.makedirs(args.dump_ref_features, exist_ok=True)
+    for i, b in enumerate(idx):
+        stem = os.path.join(args.dump_ref_features, f"ref_{b:03d}")
+        np.save(stem + "_fbank.npy", fb[i, : int(fb_len[i])].cpu().numpy())
+        np.save(stem + "_logmel.npy", lm[i, :, : int(lm_len[i])].cpu().numpy())
+    print(f"Reference features of {len(idx)} recordings saved to: {args.dump_ref_features}")
+
+
 def synthesise_list(toks, args, tts, hift, device):
     """--tokens with a JSON list: all utterances in one batch through synthesise(batched=True, prompt_lengths=...)"""
     import torch
@@ -96,6 +123,8 @@ def synthesise_list(toks, args, tts, hift, device):
     B = len(toks)
     if B == 0:
         raise SystemExit(f"{args.tokens}: empty list")
+    if args.dump_ref_features:
+        dump_ref_features(toks, args, device)
     try:
         ids = [load_tokens_json(t) for t in toks]
     except ValueError as e:
@@ -181,6 +210,8 @@ def main(argv=None):
     p.add_argument("--synthetic-prompt", type=int, default=0, help="with --synthetic: K synthetic prompt tokens (voice-cloning path)")
     p.add_argument("--seed", type=int, default=0, help="seed of the vocoder's source-noise draws")
     p.add_argument("--sample_rate", type=int, default=24000, help="sample rate of the written audio (resampled on the GPU)")
+    p.add_argument("--dump-ref-features", default=None, metavar="DIR",
+                   help="also write each request's reference-recording features (fbank, whisper log-mel) as .npy files into DIR")
     args = p.parse_args(argv)
     if args.sample_rate <= 0:
         raise SystemExit("--sample_rate must be positive")
@@ -233,6 +264,8 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit(str(e))
         spk = torch.tensor(tok["spk_embed"], dtype=torch.float32).view(1, 192) if "spk_embed" in tok else torch.randn(1, 192)
+        if args.dump_ref_features:
+            dump_ref_features([tok], args, device)
         if "prompt_token" in tok and any(k in tok for k in PROMPT_SOURCES):   # infer.py:386-392
             from jyutvoice_amd.flow.encoder import load_flow_encoder
             print(f"Loading flow encoder from {args.flow_encoder}...")

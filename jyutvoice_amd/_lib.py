@@ -62,6 +62,12 @@ SIGNATURES = {
     "jv_resample_length": (_i64, [_i64, _i, _i]),
     "jv_resample_table": (_i, [_i, _i, _p, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "jv_resample": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i64, _p, _p]),
+    "jv_fbank_frames": (_i64, [_i64]),
+    "jv_whisper_frames": (_i64, [_i64]),
+    "jv_kaldi_mel_banks": (_i, [_p]),
+    "jv_load_whisper_filters": (_i, [_p, _p, _i64, _i, _p]),
+    "jv_fbank": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
+    "jv_whisper_log_mel": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
     "jv_prompt_encoder_fwd": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "jv_length_regulate": (_i, [_p, _p, _p, _p, _i, _i, _f, _p, _p, _i, _p, _p, _p]),
     "jv_hift_f0": (_i, [_p, _p, _p, _i, _i, _p, _p]),

@@ -233,6 +233,7 @@ void jv_destroy(jv_context* ctx) {
   c.packed.release();
   jv::audio_ws_destroy(c);
   jv::resample_ws_destroy(c);
+  jv::feat16k_ws_destroy(c);
   delete ctx;
 }
 

@@ -181,6 +181,7 @@ struct Context {
   struct PromptWs* pws = nullptr;
   struct AudioWs* aws = nullptr;
   struct ResampleWs* rws = nullptr;   // resampling tables per reduced rate pair (resample.hip): not workspace, survives jv_reserve
+  struct FeatWs* fws = nullptr;       // windows, DFT bases, mel weights and per-tile partials of the 16 kHz features (feat16k.hip): not workspace, survives jv_reserve
   std::string last_error;
 };
 
@@ -213,6 +214,9 @@ void audio_ws_destroy(Context& c);
 
 // resample.hip
 void resample_ws_destroy(Context& c);
+
+// feat16k.hip
+void feat16k_ws_destroy(Context& c);
 
 }  // namespace jv
 

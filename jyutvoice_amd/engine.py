@@ -216,6 +216,45 @@ class Engine:
                                    _ptr(out_lens), _stream(self.device)))
         return out if lens is None else (out, out_lens)
 
+    # ---- reference-audio features at 16 kHz -----------------------------------------------------------
+    def load_whisper_filters(self, filters: torch.Tensor):
+        """the [128, 201] filterbank whisper ships (librosa.filters.mel(sr=16000, n_fft=400, n_mels=128)); jv_load_whisper_filters"""
+        t = filters.detach().to("cpu", torch.float32).contiguous()
+        check(self.lib.jv_load_whisper_filters(self._h, t.data_ptr(), t.numel(), 0, _stream(self.device)))
+
+    def _feat16k(self, who, wav, lens):
+        w = _f32(wav, self.device)
+        if w.dim() != 2:
+            raise ValueError(f"{who}: wav must be [B, n], got {tuple(w.shape)}")
+        wl = out_lens = None
+        if lens is not None:
+            wl = lens.to(device=self.device, dtype=torch.int32).contiguous()
+            if wl.shape != (w.shape[0],):
+                raise ValueError(f"{who}: lens must have shape [{w.shape[0]}], got {tuple(wl.shape)}")
+            out_lens = torch.empty(w.shape[0], dtype=torch.int32, device=self.device)
+        return w, wl, out_lens
+
+    def fbank(self, wav, lens=None, subtract_mean=True):
+        """kaldi.fbank(wav, num_mel_bins=80, dither=0, sample_frequency=16000) [minus its mean over frames] (infer.py:148-163;
+        jv_fbank): wav [B, n] at 16 kHz -> [B, Tmax, 80], Tmax = 1 + (n - 400) // 160.  lens ([B] sample counts, clamped to
+        [0, n]): recording b = wav[b, :lens[b]], what lies behind is not read; returns (out, out_lens int32 [B]) with exact
+        zeros behind each recording's frames.  Nothing comes back to the host."""
+        w, wl, out_lens = self._feat16k("fbank", wav, lens)
+        B, n = w.shape
+        out = torch.empty(B, int(self.lib.jv_fbank_frames(n)), 80, device=self.device)
+        check(self.lib.jv_fbank(self._h, _ptr(w), _ptr(wl), B, n, 1 if subtract_mean else 0, _ptr(out), _ptr(out_lens),
+                                _stream(self.device)))
+        return out if lens is None else (out, out_lens)
+
+    def whisper_log_mel(self, wav, lens=None):
+        """whisper.log_mel_spectrogram(wav, n_mels=128) (infer.py:98-145; jv_whisper_log_mel): wav [B, n] at 16 kHz ->
+        [B, 128, n // 160]; the max - 8 clamp is taken per recording.  lens as in `fbank`."""
+        w, wl, out_lens = self._feat16k("whisper_log_mel", wav, lens)
+        B, n = w.shape
+        out = torch.empty(B, 128, int(self.lib.jv_whisper_frames(n)), device=self.device)
+        check(self.lib.jv_whisper_log_mel(self._h, _ptr(w), _ptr(wl), B, n, _ptr(out), _ptr(out_lens), _stream(self.device)))
+        return out if lens is None else (out, out_lens)
+
     # ---- prompt branch --------------------------------------------------------------------------------
     def prompt_encoder(self, token, token_len):
         """FlowEncoder.forward (infer.py:66-83): token [B,Tk] int64, token_len [B] -> prompt_h [B, 2*Tk, 80]"""

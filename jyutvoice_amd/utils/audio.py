@@ -211,3 +211,147 @@ def load_wav(path):
         raise ValueError(f"{path}: format tag {code} with {bits} bits per sample is not supported (PCM 8/16/24/32, float 32/64)")
     x = x[: x.size // channels * channels].reshape(-1, channels).mean(axis=1)
     return torch.from_numpy(x.astype(np.float32)).unsqueeze(0), int(rate)
+
+
+# ---- infer.py:98-163: what the two ONNX sessions consume, from the 16 kHz copy ---------------------------------------------------
+_FBANK = dict(num_mel_bins=80, dither=0, sample_frequency=16000)
+_LOGMEL = dict(n_mels=128, padding=0)
+
+
+def whisper_filters() -> torch.Tensor:
+    """the [128, 201] filterbank of whisper.log_mel_spectrogram(n_mels=128): whisper ships it as data computed by
+    librosa.filters.mel(sr=16000, n_fft=400, n_mels=128); taken from whisper when importable, else the same construction"""
+    try:
+        from whisper.audio import mel_filters
+        return mel_filters("cpu", 128).to(torch.float32).contiguous()
+    except ImportError:
+        return torch.from_numpy(np.ascontiguousarray(slaney_mel_basis(16000, 400, 128, 0.0, 8000.0), dtype=np.float32))
+
+
+def _engine16k(dev):
+    eng = get_runtime(dev).ensure(1, 64, 1)
+    if not getattr(eng, "whisper_filters_loaded", False):      # (on the context's own object, as in `_engine`)
+        eng.load_whisper_filters(whisper_filters())
+        eng.whisper_filters_loaded = True
+    return eng
+
+
+def _rows16k(who, x):
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(np.asarray(x))
+    if x.dim() not in (1, 2):
+        raise ValueError(f"{who}: expected [n] or [B, n], got {tuple(x.shape)}")
+    return x.to(torch.float32), x.dim() == 1
+
+
+def fbank(waveform, num_mel_bins=80, dither=0, sample_frequency=16000, device="cuda:0", **kw):
+    """`torchaudio.compliance.kaldi.fbank(waveform, num_mel_bins=80, dither=0, sample_frequency=16000)` on the GPU (jv_fbank):
+    waveform [1, n] (or [B, n]: every row a recording of n samples) in [-1, 1] -> [T, 80] (or [B, T, 80]), T = 1 + (n - 400) // 160,
+    no mean subtracted.  n < 400 gives [0, 80], as the reference does.  Only this parameter set is built."""
+    got = dict(num_mel_bins=num_mel_bins, dither=dither, sample_frequency=sample_frequency)
+    if got != _FBANK or kw:
+        raise NotImplementedError(f"libjyutvoice_hip computes the fbank of infer.py:148-163 only ({_FBANK}, every other parameter at "
+                                  f"its default); got {dict(got, **kw)}")
+    w, single = _rows16k("fbank", waveform)
+    if single:
+        w = w.unsqueeze(0)
+    dev = w.device if w.is_cuda else torch.device(device)
+    if w.shape[1] < 400:
+        out = torch.zeros(w.shape[0], 0, 80, device=dev)
+    else:
+        out = _engine16k(dev).fbank(w, subtract_mean=False)
+    return out[0] if out.shape[0] == 1 else out
+
+
+def log_mel_spectrogram(audio, n_mels=128, padding=0, device="cuda:0", **kw):
+    """`whisper.log_mel_spectrogram(audio, n_mels=128)` on the GPU (jv_whisper_log_mel): audio [n] -> [128, n // 160], [B, n] ->
+    [B, 128, n // 160] with the max - 8 clamp per row.  ValueError for n <= 200, where the reference's reflect pad raises.  Only
+    this parameter set is built."""
+    got = dict(n_mels=n_mels, padding=padding)
+    if got != _LOGMEL or kw:
+        raise NotImplementedError(f"libjyutvoice_hip computes the log-mel of infer.py:98-145 only ({_LOGMEL}); got {dict(got, **kw)}")
+    w, single = _rows16k("log_mel_spectrogram", audio)
+    if w.shape[-1] <= 200:
+        raise ValueError(f"log_mel_spectrogram: {w.shape[-1]} samples; the reflect padding needs more than 200")
+    dev = w.device if w.is_cuda else torch.device(device)
+    out = _engine16k(dev).whisper_log_mel(w.unsqueeze(0) if single else w)
+    return out[0] if single else out
+
+
+def extract_spk_feat(speech, device="cuda:0"):
+    """infer.py:150-151: speech [1, n] at 16 kHz -> fbank minus its mean over frames, [T, 80]"""
+    w, single = _rows16k("extract_spk_feat", speech)
+    w = w.reshape(1, -1)
+    dev = w.device if w.is_cuda else torch.device(device)
+    if w.shape[1] < 400:      # no frame: the reference returns an empty feature here too
+        return torch.zeros(0, 80, device=dev)
+    return _engine16k(dev).fbank(w, subtract_mean=True)[0]
+
+
+def _to16k_batch(who, speeches, sample_rates, dev, min_len):
+    """recordings at rates of their own -> ([B, n] at 16 kHz on the device, lens int32 [B] on the device); grouped by rate, one
+    ragged `jv_resample` per rate, nothing comes back to the host (as `_extract_resampled` does for 24 kHz)"""
+    wavs = [torch.as_tensor(s).reshape(-1).to(torch.float32) for s in speeches]
+    if not wavs:
+        raise ValueError(f"{who}: no recordings")
+    rates = [16000] * len(wavs) if sample_rates is None else [int(r) for r in sample_rates]
+    if len(rates) != len(wavs):
+        raise ValueError(f"{who}: {len(wavs)} recordings, {len(rates)} sample rates")
+    for b, (w, r) in enumerate(zip(wavs, rates)):      # the lengths are on the host here: refuse what the reference would
+        if min_len and resample_length(w.numel(), r, 16000) < min_len:
+            raise ValueError(f"{who}: recording {b}: {w.numel()} samples at {r} Hz are fewer than {min_len} at 16 kHz")
+    eng = _engine16k(dev)
+    if all(r == 16000 for r in rates):
+        buf, lens = _pad_rows(wavs)
+        return eng, buf.to(dev), lens.to(dev)
+    groups = {}
+    for b, r in enumerate(rates):
+        groups.setdefault(r, []).append(b)
+    done = []
+    for r, members in groups.items():
+        buf, lens = _pad_rows([wavs[b] for b in members])
+        out, out_lens = eng.resample(buf, r, 16000, lens)
+        done.append((torch.tensor(members, device=out.device), out, out_lens))
+    wav16 = torch.zeros(len(wavs), max(out.shape[1] for _, out, _ in done), device=done[0][1].device)
+    lens16 = torch.zeros(len(wavs), dtype=torch.int32, device=wav16.device)
+    for idx, out, out_lens in done:
+        wav16[idx, : out.shape[1]] = out
+        lens16[idx] = out_lens
+    return eng, wav16, lens16
+
+
+def extract_spk_feat_batch(speeches, sample_rates=None, device="cuda:0"):
+    """`extract_spk_feat` of several recordings in one GPU pass: -> (spk_feat [B, Tmax, 80], exact zeros behind each recording's
+    frames, lens int32 [B]).  sample_rates (one int per recording; None: all 16 kHz): grouped by rate and resampled to 16 kHz
+    on the GPU; recording b's rows are those of `extract_spk_feat(resample(speeches[b], sample_rates[b], 16000))`, bit for bit.
+    A recording of fewer than 400 samples at 16 kHz has no frame: a zero row and length 0, as the reference's empty feature."""
+    eng, wav16, lens16 = _to16k_batch("extract_spk_feat_batch", speeches, sample_rates, torch.device(device), 0)
+    return eng.fbank(wav16, lens16, subtract_mean=True)
+
+
+def extract_token_feat_batch(speeches, sample_rates=None, device="cuda:0"):
+    """`log_mel_spectrogram` of several recordings in one GPU pass: -> (feat [B, 128, Tmax], zeros behind, lens int32 [B]); the
+    max - 8 clamp is each recording's own.  sample_rates as in `extract_spk_feat_batch`."""
+    eng, wav16, lens16 = _to16k_batch("extract_token_feat_batch", speeches, sample_rates, torch.device(device), 201)
+    return eng.whisper_log_mel(wav16, lens16)
+
+
+def extract_spk_embedding(spk_model, speech, device="cuda:0"):
+    """infer.py:148-163 with the feature on the GPU.  spk_model: anything with .run() and .get_inputs() (an onnxruntime session of
+    campplus.onnx in the reference; onnxruntime is not imported here) -> embedding [1, D]"""
+    spk_feat = extract_spk_feat(speech, device)
+    embedding = spk_model.run(None, {spk_model.get_inputs()[0].name: spk_feat.unsqueeze(dim=0).cpu().numpy()})[0].flatten().tolist()
+    return torch.tensor([embedding])
+
+
+def extract_speech_token(audio, speech_tokenizer_session, device="cuda:0"):
+    """infer.py:98-145 with the feature on the GPU.  audio: [n] at 16 kHz (tensor or ndarray); the session is anything with .run()
+    and .get_inputs() -> (speech_token int32 [1, K], speech_token_len int32 [1])"""
+    if not isinstance(audio, (torch.Tensor, np.ndarray)):
+        raise ValueError("Audio must be torch.Tensor or numpy.ndarray")
+    feat = log_mel_spectrogram(torch.as_tensor(audio).float().reshape(1, -1), n_mels=128, device=device)
+    inputs = speech_tokenizer_session.get_inputs()
+    token = speech_tokenizer_session.run(None, {inputs[0].name: feat.detach().cpu().numpy(),
+                                                inputs[1].name: np.array([feat.shape[2]], dtype=np.int32)})[0].flatten().tolist()
+    speech_token = torch.tensor([token], dtype=torch.int32)
+    return speech_token, torch.tensor([len(speech_token[0])], dtype=torch.int32)
