@@ -1,57 +1,34 @@
 // Host side of the vocoder's row-owning ResBlock convolution (hiftconv_kernel.h): argument checks and launch.
 #include "hiftconv_kernel.h"
 #include "hiftpair_kernel.h"
+#include "jv_launch.h"
 
 namespace jv {
 
 namespace {
 template <int C, int NG>
 int hc_launch(const HiftConvArgs& a, hipStream_t st) {
-  static int raised[64] = {};      // per device: the LDS size the attribute was last raised to
-  int dev = 0;
-  JV_HIP(hipGetDevice(&dev));
   const int lds = hc_lds_bytes<C, NG>(a.ntaps, a.dil);
   if (lds > 160 * 1024) return fail(JV_ERR_ARG, "hiftconv: the window does not fit LDS");
-  if (raised[dev & 63] < lds) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hiftconv_kernel<C, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    raised[dev & 63] = lds;
-  }
-  const bool prof = prof_on();
-  if (prof) prof_begin(st);
-  hipLaunchKernelGGL((hiftconv_kernel<C, NG>), dim3(cdiv(a.M, hc_rows<NG>())), dim3(hc_threads<C, NG>()), lds, st, a);
-  if (prof) {
+  return launch_lds<hiftconv_kernel<C, NG>>(dim3(cdiv(a.M, hc_rows<NG>())), dim3(hc_threads<C, NG>()), lds, st, a, [&]() {
     static const std::string name = std::string("hiftconv_h3<") + std::to_string(hc_rows<NG>()) + "x" + std::to_string(C) + ",snake>";
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     const double k = (double)a.ntaps * C;
     prof_end(st, name.c_str(), 2.0 * rows * C * k, 4.0 * (rows * C * (2 + (a.res1 ? 1 : 0) + (a.res2 ? 1 : 0) + (a.accumulate ? 1 : 0)) + C * k));
-  }
-  JV_HIP(hipGetLastError());
-  return JV_OK;
+  });
 }
 template <int C, int NG, int KT>
 int hp_launch(const HiftPairArgs& a, hipStream_t st) {
-  static int raised[64] = {};      // per device: the LDS size the attribute was last raised to
-  int dev = 0;
-  JV_HIP(hipGetDevice(&dev));
   const int lds = hp_lds_bytes<C, NG>(a.ntaps, a.dil);
   if (lds > 160 * 1024) return fail(JV_ERR_ARG, "hiftpair: the window does not fit LDS");
-  if (raised[dev & 63] < lds) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hiftpair_kernel<C, NG, KT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    raised[dev & 63] = lds;
-  }
-  const bool prof = prof_on();
-  if (prof) prof_begin(st);
   const int ro = hp_rows<NG>() - (a.ntaps - 1);      // output rows per workgroup
-  hipLaunchKernelGGL((hiftpair_kernel<C, NG, KT>), dim3(cdiv(a.M, ro)), dim3(hc_threads<C, NG>()), lds, st, a);
-  if (prof) {
+  return launch_lds<hiftpair_kernel<C, NG, KT>>(dim3(cdiv(a.M, ro)), dim3(hc_threads<C, NG>()), lds, st, a, [&]() {
     static const std::string name = std::string("hiftpair_h3<") + std::to_string(hp_rows<NG>()) + "x" + std::to_string(C) + ",snake>";
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     const double k = (double)a.ntaps * C;
     // algorithmic: both convolutions; bytes: x in (once as the operand, once as the residual), the result out (+ res2, + previous out)
     prof_end(st, name.c_str(), 2.0 * 2.0 * rows * C * k, 4.0 * (rows * C * (3 + (a.res2 ? 1 : 0) + (a.accumulate ? 1 : 0)) + 2 * C * k));
-  }
-  JV_HIP(hipGetLastError());
-  return JV_OK;
+  });
 }
 }  // namespace
 

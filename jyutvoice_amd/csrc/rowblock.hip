@@ -1,23 +1,13 @@
 // Host side of the fused transformer-block launch (rowblock_kernel.h): argument checks, tile height, launch.
 #include "flow_ws.h"
+#include "jv_launch.h"
 
 namespace jv {
 
 namespace {
 template <int RT, bool QKV, bool STAG>
 int rb_launch(const RowBlockArgs& a, hipStream_t st) {
-  static bool raised[64] = {};
-  int dev = 0;
-  JV_HIP(hipGetDevice(&dev));
-  if (!raised[dev & 63]) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rowblock_kernel<RT, QKV, STAG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               rb_lds_bytes<RT>()));
-    raised[dev & 63] = true;
-  }
-  const bool prof = prof_on();
-  if (prof) prof_begin(st);
-  hipLaunchKernelGGL((rowblock_kernel<RT, QKV, STAG>), dim3(cdiv(a.M, 16 * RT)), dim3(512), rb_lds_bytes<RT>(), st, a);
-  if (prof) {
+  return launch_lds<rowblock_kernel<RT, QKV, STAG>>(dim3(cdiv(a.M, 16 * RT)), dim3(512), rb_lds_bytes<RT>(), st, a, [&]() {
     static const std::string name_plain = std::string("rowblock_h3<") + std::to_string(16 * RT) + "x256" + (QKV ? ",qkv>" : ">");
     static const std::string name_ln = std::string("rowblock_h3<") + std::to_string(16 * RT) + "x256,ln>";
     const std::string& name = (!QKV && a.ln_out) ? name_ln : name_plain;
@@ -27,9 +17,7 @@ int rb_launch(const RowBlockArgs& a, hipStream_t st) {
     const double macs = 256.0 * 512 + 2.0 * 256 * 1024 + (QKV ? 256.0 * 1536 : 0.0);
     const double bytes = 4.0 * (rows * (512 + 256 + 256 + (QKV ? 1536 : 0)) + macs);
     prof_end(st, name.c_str(), 2.0 * rows * macs, bytes);
-  }
-  JV_HIP(hipGetLastError());
-  return JV_OK;
+  });
 }
 
 // JV_FF_STAGGER=1: the feed-forward with waves 0..3 half a hidden chunk ahead of waves 4..7 (rowblock_kernel.h, STAG; the same
@@ -72,13 +60,7 @@ int rowblock(const RowBlockArgs& a, bool qkv, hipStream_t st) {
   b.inv_a_scale_o = 1.0f / a.a_scale_o; b.inv_a_scale1 = 1.0f / a.a_scale1; b.inv_h_scale = 1.0f / a.h_scale;
   b.inv_a_scale_q = qkv ? 1.0f / a.a_scale_q : 0.f;
   if (const char* ab = tuning_env("JV_RB_ABLATE")) b.ablate = atoi(ab);
-  switch (rt) {
-    case 2: return rb_launch1<2>(b, qkv, st);
-    case 3: return rb_launch1<3>(b, qkv, st);
-    case 4: return rb_launch1<4>(b, qkv, st);
-    case 5: return rb_launch1<5>(b, qkv, st);
-    default: return fail(JV_ERR_ARG, "rowblock: bad tile height");
-  }
+  return dispatch_rt(rt, "rowblock: bad tile height", [&](auto t) { return rb_launch1<decltype(t)::value>(b, qkv, st); });
 }
 
 }  // namespace jv

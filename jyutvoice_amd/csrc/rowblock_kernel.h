@@ -403,50 +403,35 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
       if (amax) {
 #pragma unroll
         for (int j = 0; j < RT; ++j) {
-          unsigned u = 0u;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) u = max(u, __float_as_uint(v[j][e]) & 0x7fffffffu);
+          unsigned u = absmax4(v[j]);
           const int trk = __builtin_amdgcn_readlane(facts.trk, ps * RT + j);
           const unsigned seen = (unsigned)__builtin_amdgcn_readlane((int)facts.seen, ps * RT + j);
-          if (trk && __builtin_amdgcn_ballot_w64(u > seen) != 0) {      // wave-uniform: nothing to do once the slot holds a larger value
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o));
+          if (absmax_exceeds(trk, u, seen)) {
+            u = wave_umax(u);
             if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(amax + __builtin_amdgcn_readlane(facts.slot, ps * RT + j)), u);
           }
         }
       }
       if (ln) {
         float sum[RT], sq[RT];
-#pragma unroll
-        for (int j = 0; j < RT; ++j) sum[j] = wave_sum((v[j][0] + v[j][1]) + (v[j][2] + v[j][3]));
-#pragma unroll
-        for (int j = 0; j < RT; ++j) {
-          const rg_f32x4 d = v[j] - sum[j] * (1.f / 256.f);
-          sq[j] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-        }
-        // 1 / sqrt(var + eps) of the RT rows in ONE evaluation: lane j computes row j's (the correctly rounded division and
-        // square root are ~30 instructions; per row, on wave-uniform values, that was a third of this pass), then broadcast
-        float var_l = sq[0];
+        ln256_moments(v, sum, sq);
+        float var_l = sq[0];      // (1 / sqrt(var + eps) of the RT rows in ONE evaluation, lane j computing row j's: row_tail.h)
 #pragma unroll
         for (int j = 1; j < RT; ++j) var_l = lane == j ? sq[j] : var_l;
-        const float rstd_l = 1.0f / sqrtf(var_l * (1.f / 256.f) + LN_EPS);
+        const float rstd_l = ln256_rstd(var_l, LN_EPS);
 #pragma unroll
         for (int j = 0; j < RT; ++j) {
           const int trow = wave * NRW + ps * RT + j;
-          const float mean = sum[j] * (1.f / 256.f);
-          const float rstd = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rstd_l), j));
-          const rg_f32x4 y = (v[j] - mean) * rstd * gg + bb;
-          const Split2 s0 = split2h_pair(y[0] * sc, y[1] * sc);
-          const Split2 s1 = split2h_pair(y[2] * sc, y[3] * sc);
+          const Planes4 y = split2h_x4(ln256_apply(v[j], sum[j], lane_bcast(rstd_l, j), gg, bb), sc);
           // columns 4 lane .. + 3 = k-step lane >> 3, 16-byte slot (lane & 7) >> 1 (swizzled), its half lane & 1
           unsigned char* d = rg_lds + (lane >> 3) * STAGE + trow * 64 + (((((lane & 7) >> 1) ^ rg_key(trow))) << 4) + (lane & 1) * 8;
-          *reinterpret_cast<rg_u32x2*>(d) = rg_u32x2{s0.h, s1.h};
-          *reinterpret_cast<rg_u32x2*>(d + A_PLANE) = rg_u32x2{s0.l, s1.l};
+          *reinterpret_cast<rg_u32x2*>(d) = y.h;
+          *reinterpret_cast<rg_u32x2*>(d + A_PLANE) = y.l;
           if constexpr (!QKV) {
             if (gplanes && ok[j]) {
               unsigned short* const o2 = gplanes + (long)(drow0 + j) * 256 + lane4;
-              *(__attribute__((address_space(1))) rg_u32x2*)(o2) = rg_u32x2{s0.h, s1.h};
-              *(__attribute__((address_space(1))) rg_u32x2*)(o2 + p.ln_out_plane) = rg_u32x2{s0.l, s1.l};
+              *(__attribute__((address_space(1))) rg_u32x2*)(o2) = y.h;
+              *(__attribute__((address_space(1))) rg_u32x2*)(o2 + p.ln_out_plane) = y.l;
             }
           }
         }

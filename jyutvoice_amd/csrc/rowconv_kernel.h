@@ -321,19 +321,9 @@ __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
     }
     if (p.ln) {
       float sum[RPW], sq[RPW];
+      ln256_moments(v, sum, sq);
 #pragma unroll
-      for (int jj = 0; jj < RPW; ++jj) sum[jj] = wave_sum((v[jj][0] + v[jj][1]) + (v[jj][2] + v[jj][3]));
-#pragma unroll
-      for (int jj = 0; jj < RPW; ++jj) {
-        const rg_f32x4 d = v[jj] - sum[jj] * (1.f / 256.f);
-        sq[jj] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-      }
-#pragma unroll
-      for (int jj = 0; jj < RPW; ++jj) {
-        const float mean = sum[jj] * (1.f / 256.f);
-        const float rstd = 1.0f / sqrtf(sq[jj] * (1.f / 256.f) + p.ln_eps);
-        v[jj] = (v[jj] - mean) * rstd * gg + bb;
-      }
+      for (int jj = 0; jj < RPW; ++jj) v[jj] = ln256_apply(v[jj], sum[jj], ln256_rstd(sq[jj], p.ln_eps), gg, bb);
     }
 #pragma unroll
     for (int jj = 0; jj < RPW; ++jj) {
@@ -345,12 +335,9 @@ __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
     if (p.amax_out) {
 #pragma unroll
       for (int jj = 0; jj < RPW; ++jj) {
-        unsigned u = 0u;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u = max(u, __float_as_uint(v[jj][e]) & 0x7fffffffu);
-        if (tracked[jj] && __builtin_amdgcn_ballot_w64(u > seen[jj]) != 0) {
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o));
+        unsigned u = absmax4(v[jj]);
+        if (absmax_exceeds(tracked[jj], u, seen[jj])) {
+          u = wave_umax(u);
           if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(p.amax_out + slot[jj]), u);
         }
       }
@@ -700,24 +687,13 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
     }
     if (p.ln) {
       float sum[RPW], sq[RPW];
-#pragma unroll
-      for (int jj = 0; jj < RPW; ++jj) sum[jj] = wave_sum((v[jj][0] + v[jj][1]) + (v[jj][2] + v[jj][3]));
-#pragma unroll
-      for (int jj = 0; jj < RPW; ++jj) {
-        const rg_f32x4 d = v[jj] - sum[jj] * (1.f / 256.f);
-        sq[jj] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-      }
-      // 1 / sqrt(var + eps) of the group's rows in ONE evaluation, lane jj computing row jj's (rowblock_kernel.h)
+      ln256_moments(v, sum, sq);
       float var_l = sq[0];
 #pragma unroll
       for (int jj = 1; jj < RPW; ++jj) var_l = lane == jj ? sq[jj] : var_l;
-      const float rstd_l = 1.0f / sqrtf(var_l * (1.f / 256.f) + p.ln_eps);
+      const float rstd_l = ln256_rstd(var_l, p.ln_eps);
 #pragma unroll
-      for (int jj = 0; jj < RPW; ++jj) {
-        const float mean = sum[jj] * (1.f / 256.f);
-        const float rstd = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rstd_l), jj));
-        v[jj] = (v[jj] - mean) * rstd * gg + bb;
-      }
+      for (int jj = 0; jj < RPW; ++jj) v[jj] = ln256_apply(v[jj], sum[jj], lane_bcast(rstd_l, jj), gg, bb);
     }
 #pragma unroll
     for (int jj = 0; jj < RPW; ++jj) {
@@ -727,43 +703,30 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
       v[jj] = (v[jj] + in.rv[jj]) + in.r[jj];
       if (in.ok[jj]) *reinterpret_cast<rg_f32x4*>(p.out + mrow * p.ldo + 4 * lane) = v[jj];
     }
-    if (p.ln2_out) {      // (uniform) the following block's norm1 of the stored rows -> operand planes (rowblock_kernel.h's row pass)
+    if (p.ln2_out) {      // (uniform) the following block's norm1 of the stored rows -> operand planes (row_tail.h)
       float sum[RPW], sq[RPW];
-#pragma unroll
-      for (int jj = 0; jj < RPW; ++jj) sum[jj] = wave_sum((v[jj][0] + v[jj][1]) + (v[jj][2] + v[jj][3]));
-#pragma unroll
-      for (int jj = 0; jj < RPW; ++jj) {
-        const rg_f32x4 d = v[jj] - sum[jj] * (1.f / 256.f);
-        sq[jj] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-      }
+      ln256_moments(v, sum, sq);
       float var_l = sq[0];
 #pragma unroll
       for (int jj = 1; jj < RPW; ++jj) var_l = lane == jj ? sq[jj] : var_l;
-      const float rstd_l = 1.0f / sqrtf(var_l * (1.f / 256.f) + p.ln_eps);
+      const float rstd_l = ln256_rstd(var_l, p.ln_eps);
 #pragma unroll
       for (int jj = 0; jj < RPW; ++jj) {
         const long mrow = (long)m0 + wave * 2 * RT + ps * RT + jj;
-        const float mean = sum[jj] * (1.f / 256.f);
-        const float rstd = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rstd_l), jj));
-        const rg_f32x4 y = (v[jj] - mean) * rstd * g2 + b2;
-        const Split2 s0 = split2h_pair(y[0] * p.ln2_scale, y[1] * p.ln2_scale);
-        const Split2 s1 = split2h_pair(y[2] * p.ln2_scale, y[3] * p.ln2_scale);
+        const Planes4 y = split2h_x4(ln256_apply(v[jj], sum[jj], lane_bcast(rstd_l, jj), g2, b2), p.ln2_scale);
         if (in.ok[jj]) {
           unsigned short* const o2 = p.ln2_out + mrow * 256 + 4 * lane;
-          *reinterpret_cast<rg_u32x2*>(o2) = rg_u32x2{s0.h, s1.h};
-          *reinterpret_cast<rg_u32x2*>(o2 + p.ln2_plane) = rg_u32x2{s0.l, s1.l};
+          *reinterpret_cast<rg_u32x2*>(o2) = y.h;
+          *reinterpret_cast<rg_u32x2*>(o2 + p.ln2_plane) = y.l;
         }
       }
     }
     if (p.amax_out) {
 #pragma unroll
       for (int jj = 0; jj < RPW; ++jj) {
-        unsigned u = 0u;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u = max(u, __float_as_uint(v[jj][e]) & 0x7fffffffu);
-        if (in.tracked[jj] && __builtin_amdgcn_ballot_w64(u > in.seen[jj]) != 0) {
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o));
+        unsigned u = absmax4(v[jj]);
+        if (absmax_exceeds(in.tracked[jj], u, in.seen[jj])) {
+          u = wave_umax(u);
           if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(p.amax_out + in.slot[jj]), u);
         }
       }

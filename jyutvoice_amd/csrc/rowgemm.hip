@@ -1,4 +1,5 @@
 // Host side of the row-owning fp16x3 GEMM (rowgemm_kernel.h): tile height choice and launch.
+#include "jv_launch.h"
 #include "rowconv_kernel.h"
 #include "rowres_kernel.h"
 
@@ -21,64 +22,29 @@ __global__ void pack_wfrag_kernel(const unsigned short* __restrict__ w2, long w2
 }
 
 template <int RT, int EPI>
-int rg_launch_wd(const RowGemmArgs& a, hipStream_t st) {
-  static bool raised[64] = {};
-  int dev = 0;
-  JV_HIP(hipGetDevice(&dev));
-  if (!raised[dev & 63]) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_wd_kernel<RT, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               rgw_lds_bytes<RT>()));
-    raised[dev & 63] = true;
-  }
-  hipLaunchKernelGGL((rowgemm_wd_kernel<RT, EPI>), dim3(cdiv(a.M, 16 * RT)), dim3(512), rgw_lds_bytes<RT>(), st, a);
-  return JV_OK;
-}
-
-// A-resident form (rowgemm_wa_kernel): the multi-chunk epilogues when the whole A tile fits beside the slab
-template <int RT, int EPI>
-int rg_launch_wa(const RowGemmArgs& a, hipStream_t st) {
-  static int raised[64] = {};      // per device: the LDS size the attribute was last raised to
-  int dev = 0;
-  JV_HIP(hipGetDevice(&dev));
-  const int lds = rgwa_lds_bytes<RT>(a.K >> 5);
-  if (raised[dev & 63] < lds) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_wa_kernel<RT, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    raised[dev & 63] = lds;
-  }
-  const int nc = a.N >> 8;
-  const int ns = a.nsplit > 1 ? (a.nsplit < nc ? a.nsplit : nc) : 1;      // column chunks dealt over grid.y (RowGemmArgs::nsplit)
-  hipLaunchKernelGGL((rowgemm_wa_kernel<RT, EPI>), dim3(cdiv(a.M, 16 * RT), ns), dim3(512), lds, st, a);
-  return JV_OK;
-}
-
-template <int RT, int EPI>
 int rg_launch2(const RowGemmArgs& a, hipStream_t st) {
-  static bool raised[64] = {};      // per device: the attribute belongs to the kernel's image on the current device
-  int dev = 0;
-  JV_HIP(hipGetDevice(&dev));
-  if (!raised[dev & 63]) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_kernel<RT, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               rg_lds_bytes<RT>()));
-    raised[dev & 63] = true;
-  }
-  const bool prof = prof_on();
-  if (prof) prof_begin(st);
-  constexpr bool MULTI = EPI == RG_PLAIN || EPI == RG_GELU_PL || EPI == RG_QKV;
-  const bool wdir = a.Wf && !(a.K & 63) && !dyn_env("JV_RG_WLDS");
-  if (MULTI && wdir && a.N > 256 && rgwa_lds_bytes<RT>(a.K >> 5) <= 160 * 1024 && !dyn_env("JV_RG_NO_ARES")) {
-    if constexpr (MULTI) JV_TRY((rg_launch_wa<RT, EPI>(a, st)));
-  } else if (wdir) JV_TRY((rg_launch_wd<RT, EPI>(a, st)));
-  else hipLaunchKernelGGL((rowgemm_kernel<RT, EPI>), dim3(cdiv(a.M, 16 * RT)), dim3(512), rg_lds_bytes<RT>(), st, a);
-  if (prof) {
+  auto prof_done = [&]() {
     static const std::string name = std::string("rowgemm_h3<") + std::to_string(16 * RT) + "x256" +
                                     (EPI == RG_GELU_PL ? ",gelu" : EPI == RG_RES ? ",res" : EPI == RG_RES_LN ? ",res,ln" : EPI == RG_QKV ? ",qkv" : "") + ">";
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     const double bytes = 4.0 * (rows * a.K + (double)a.N * a.K + rows * a.N * ((EPI == RG_RES || EPI == RG_RES_LN) ? 2 : 1) +
                                 (EPI == RG_RES_LN ? rows * 256 : 0));
     prof_end(st, name.c_str(), 2.0 * rows * a.N * a.K, bytes);
+  };
+  constexpr bool MULTI = EPI == RG_PLAIN || EPI == RG_GELU_PL || EPI == RG_QKV;
+  const bool wdir = a.Wf && !(a.K & 63) && !dyn_env("JV_RG_WLDS");
+  const unsigned tiles = cdiv(a.M, 16 * RT);
+  if constexpr (MULTI) {
+    // A-resident form (rowgemm_wa_kernel): the multi-chunk epilogues when the whole A tile fits beside the slab
+    const int lds = rgwa_lds_bytes<RT>(a.K >> 5);
+    if (wdir && a.N > 256 && lds <= 160 * 1024 && !dyn_env("JV_RG_NO_ARES")) {
+      const int nc = a.N >> 8;
+      const int ns = a.nsplit > 1 ? (a.nsplit < nc ? a.nsplit : nc) : 1;      // column chunks dealt over grid.y (RowGemmArgs::nsplit)
+      return launch_lds<rowgemm_wa_kernel<RT, EPI>>(dim3(tiles, ns), dim3(512), lds, st, a, prof_done);
+    }
   }
-  JV_HIP(hipGetLastError());
-  return JV_OK;
+  if (wdir) return launch_lds<rowgemm_wd_kernel<RT, EPI>>(dim3(tiles), dim3(512), rgw_lds_bytes<RT>(), st, a, prof_done);
+  return launch_lds<rowgemm_kernel<RT, EPI>>(dim3(tiles), dim3(512), rg_lds_bytes<RT>(), st, a, prof_done);
 }
 
 template <int RT>
@@ -141,40 +107,21 @@ bool rowconv_w_direct(const RowConvArgs& a) { return a.Wf && !((a.Cin >> 5) & 1)
 namespace {
 template <int RT>
 int rc_launch(const RowConvArgs& a, hipStream_t st) {
-  static bool raised[64] = {};
-  int dev = 0;
-  JV_HIP(hipGetDevice(&dev));
-  if (!raised[dev & 63]) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rowconv_kernel<RT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               rc_lds_bytes<RT>()));
-    raised[dev & 63] = true;
-  }
-  static bool raised_wd[64] = {};
   const bool wdir = rowconv_w_direct(a);
   if (a.ln2_out && !wdir) return fail(JV_ERR_ARG, "rowconv: the following LayerNorm exists on the W-direct kernel only");
   if (a.res_out && !wdir) return fail(JV_ERR_ARG, "rowconv: the folded res_conv exists on the W-direct kernel only");
-  if (wdir && !raised_wd[dev & 63]) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rowconv_wd_kernel<RT, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               rcw_lds_bytes<RT>()));
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rowconv_wd_kernel<RT, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               rcw_lds_bytes<RT>()));
-    raised_wd[dev & 63] = true;
-  }
-  const bool prof = prof_on();
-  if (prof) prof_begin(st);
-  if (wdir && a.res_out) hipLaunchKernelGGL((rowconv_wd_kernel<RT, true>), dim3(cdiv(a.M, 16 * RT)), dim3(512), rcw_lds_bytes<RT>(), st, a);
-  else if (wdir) hipLaunchKernelGGL((rowconv_wd_kernel<RT, false>), dim3(cdiv(a.M, 16 * RT)), dim3(512), rcw_lds_bytes<RT>(), st, a);
-  else hipLaunchKernelGGL((rowconv_kernel<RT>), dim3(cdiv(a.M, 16 * RT)), dim3(512), rc_lds_bytes<RT>(), st, a);
-  if (prof) {
+  auto prof_done = [&]() {
     static const std::string name = std::string("rowconv_h3<") + std::to_string(16 * RT) + "x256,k3>";
     static const std::string name_res = std::string("rowconv_h3<") + std::to_string(16 * RT) + "x256,k3+res>";
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     const int taps = a.res_out ? 4 : 3;      // (the folded 1 x 1 res_conv is a fourth tap's worth of work and one more output)
     const double bytes = 4.0 * (rows * a.Cin + 256.0 * taps * a.Cin + rows * 256 * ((a.res ? 2 : 1) + (a.res_out ? 1 : 0)));
     prof_end(st, (a.res_out ? name_res : name).c_str(), 2.0 * rows * 256.0 * taps * a.Cin, bytes);
-  }
-  JV_HIP(hipGetLastError());
-  return JV_OK;
+  };
+  const dim3 grid(cdiv(a.M, 16 * RT)), block(512);
+  if (wdir && a.res_out) return launch_lds<rowconv_wd_kernel<RT, true>>(grid, block, rcw_lds_bytes<RT>(), st, a, prof_done);
+  if (wdir) return launch_lds<rowconv_wd_kernel<RT, false>>(grid, block, rcw_lds_bytes<RT>(), st, a, prof_done);
+  return launch_lds<rowconv_kernel<RT>>(grid, block, rc_lds_bytes<RT>(), st, a, prof_done);
 }
 }  // namespace
 
@@ -191,31 +138,14 @@ int rowconv(const RowConvArgs& a, hipStream_t st) {
   if (a.ln2_out && (!a.ln2_g || !a.ln2_b || !(a.ln2_scale > 0.f) || a.ln2_plane <= 0 || a.ldo != 256))
     return fail(JV_ERR_ARG, "rowconv: the following LayerNorm needs gain, offset, a scale, a plane stride and 256-wide output rows");
   int rt = rowgemm_tile(a.M);
-  if (rt == 0) rt = 2;
-  switch (rt) {
-    case 1:
-    case 2: return rc_launch<2>(a, st);
-    case 3: return rc_launch<3>(a, st);
-    case 4: return rc_launch<4>(a, st);
-    case 5: return rc_launch<5>(a, st);
-    default: return fail(JV_ERR_ARG, "rowconv: bad tile height");
-  }
+  if (rt == 0 || rt == 1) rt = 2;
+  return dispatch_rt(rt, "rowconv: bad tile height", [&](auto t) { return rc_launch<decltype(t)::value>(a, st); });
 }
 
 namespace {
 template <int RT, bool QKV>
 int rr_launch(const RowResArgs& a, hipStream_t st) {
-  static bool raised[64] = {};
-  int dev = 0;
-  JV_HIP(hipGetDevice(&dev));
-  if (!raised[dev & 63]) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rowres_kernel<RT, QKV>), hipFuncAttributeMaxDynamicSharedMemorySize, rr_lds_bytes<RT>()));
-    raised[dev & 63] = true;
-  }
-  const bool prof = prof_on();
-  if (prof) prof_begin(st);
-  hipLaunchKernelGGL((rowres_kernel<RT, QKV>), dim3(cdiv(a.M, 16 * RT - 2)), dim3(512), rr_lds_bytes<RT>(), st, a);
-  if (prof) {
+  return launch_lds<rowres_kernel<RT, QKV>>(dim3(cdiv(a.M, 16 * RT - 2)), dim3(512), rr_lds_bytes<RT>(), st, a, [&]() {
     static const std::string name = std::string("rowres_h3<") + std::to_string(16 * RT) + "x256" + (QKV ? ",qkv>" : ">");
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     // block1's three taps + res_conv, block2's three taps (+ the following block's to_q | to_k | to_v)
@@ -223,9 +153,7 @@ int rr_launch(const RowResArgs& a, hipStream_t st) {
     // x in, out rows, the weights (h2 and res never leave the chip) (+ q rows and the k / v planes out)
     const double bytes = 4.0 * (rows * (a.Cin + 256 + (QKV ? 1536 : 0)) + macs);
     prof_end(st, name.c_str(), 2.0 * rows * macs, bytes);
-  }
-  JV_HIP(hipGetLastError());
-  return JV_OK;
+  });
 }
 }  // namespace
 
@@ -255,36 +183,21 @@ int rowres(const RowResArgs& a, hipStream_t st) {
     return fail(JV_ERR_ARG, "rowres: q | k | v needs its fragments, column scales, outputs, the attention scales and the following LayerNorm");
   const int rt = rowgemm_tile(a.M);
   // the kernel reads whole window rows up to the last tile's end: they must exist in the input buffer or read as masked (a_rows clamps)
-  switch (rt) {
-    case 2: return qkv ? rr_launch<2, true>(a, st) : rr_launch<2, false>(a, st);
-    case 3: return qkv ? rr_launch<3, true>(a, st) : rr_launch<3, false>(a, st);
-    case 4: return qkv ? rr_launch<4, true>(a, st) : rr_launch<4, false>(a, st);
-    case 5: return qkv ? rr_launch<5, true>(a, st) : rr_launch<5, false>(a, st);
-    default: return fail(JV_ERR_ARG, "rowres: no row-owning tile height for this row count");
-  }
+  return dispatch_rt(rt, "rowres: no row-owning tile height for this row count", [&](auto t) {
+    constexpr int RT = decltype(t)::value;
+    return qkv ? rr_launch<RT, true>(a, st) : rr_launch<RT, false>(a, st);
+  });
 }
 
 namespace {
 template <int RT>
 int rf_launch(const RowFfnArgs& a, hipStream_t st) {
-  static bool raised[64] = {};
-  int dev = 0;
-  JV_HIP(hipGetDevice(&dev));
-  if (!raised[dev & 63]) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rowffn_kernel<RT>), hipFuncAttributeMaxDynamicSharedMemorySize, rgf_lds_bytes<RT>()));
-    raised[dev & 63] = true;
-  }
-  const bool prof = prof_on();
-  if (prof) prof_begin(st);
-  hipLaunchKernelGGL((rowffn_kernel<RT>), dim3(cdiv(a.M, 16 * RT)), dim3(512), rgf_lds_bytes<RT>(), st, a);
-  if (prof) {
+  return launch_lds<rowffn_kernel<RT>>(dim3(cdiv(a.M, 16 * RT)), dim3(512), rgf_lds_bytes<RT>(), st, a, [&]() {
     static const std::string name = std::string("rowffn_h3<") + std::to_string(16 * RT) + "x256" + ">";
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     // algorithmic bytes: LayerNorm planes in (rows x 256 x 4 B), both weight matrices, residual in, rows out (+ planes out)
     prof_end(st, name.c_str(), 2.0 * rows * 2.0 * 256.0 * 1024.0, 4.0 * (rows * 256 * (a.ln ? 4 : 3) + 2.0 * 256 * 1024));
-  }
-  JV_HIP(hipGetLastError());
-  return JV_OK;
+  });
 }
 }  // namespace
 
@@ -296,15 +209,8 @@ int rowffn(const RowFfnArgs& a, hipStream_t st) {
   if ((a.lda2 & 7) || (a.ldo & 3) || (a.ldr & 3) || (a.ln && (!a.out2 || (a.ldo2 & 3) || !a.ln_g || !a.ln_b)))
     return fail(JV_ERR_ARG, "rowffn: aligned strides (and gain / offset / plane buffer for the LayerNorm epilogue) required");
   int rt = rowgemm_tile(a.M);
-  if (rt == 0) rt = 2;
-  switch (rt) {
-    case 1:
-    case 2: return rf_launch<2>(a, st);
-    case 3: return rf_launch<3>(a, st);
-    case 4: return rf_launch<4>(a, st);
-    case 5: return rf_launch<5>(a, st);
-    default: return fail(JV_ERR_ARG, "rowffn: bad tile height");
-  }
+  if (rt == 0 || rt == 1) rt = 2;
+  return dispatch_rt(rt, "rowffn: bad tile height", [&](auto t) { return rf_launch<decltype(t)::value>(a, st); });
 }
 
 int rowgemm(const RowGemmArgs& a, int epi, hipStream_t st) {
@@ -321,15 +227,8 @@ int rowgemm(const RowGemmArgs& a, int epi, hipStream_t st) {
   if ((epi == RG_GELU_PL || epi == RG_RES_LN) && (!a.out2 || (a.ldo2 & 3))) return fail(JV_ERR_ARG, "rowgemm: bad plane output");
   if (epi == RG_RES_LN && (!a.ln_g || !a.ln_b)) return fail(JV_ERR_ARG, "rowgemm: LayerNorm epilogue needs gain and offset");
   int rt = (a.rt >= 2 && a.rt <= 5) ? a.rt : rowgemm_tile(a.M);
-  if (rt == 0) rt = 2;      // callers ask rowgemm_tile() first; a direct call still works
-  switch (rt) {
-    case 1:
-    case 2: return rg_launch1<2>(a, epi, st);
-    case 3: return rg_launch1<3>(a, epi, st);
-    case 4: return rg_launch1<4>(a, epi, st);
-    case 5: return rg_launch1<5>(a, epi, st);
-    default: return fail(JV_ERR_ARG, "rowgemm: bad tile height");
-  }
+  if (rt == 0 || rt == 1) rt = 2;      // callers ask rowgemm_tile() first; a direct call still works
+  return dispatch_rt(rt, "rowgemm: bad tile height", [&](auto t) { return rg_launch1<decltype(t)::value>(a, epi, st); });
 }
 
 }  // namespace jv

@@ -26,13 +26,9 @@
 
 #include "jv_common.h"
 #include "jv_device.h"
+#include "row_tail.h"
 
 namespace jv {
-
-typedef _Float16 rg_f16x8 __attribute__((ext_vector_type(8)));
-typedef float rg_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int rg_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int rg_u32x2 __attribute__((ext_vector_type(2)));
 
 enum RowGemmEpi : int {
   RG_PLAIN = 0,      // out = acc * colscale / a_scale (+ bias): fp32 rows
@@ -302,11 +298,10 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
 #pragma unroll
           for (int j = 0; j < RPW; ++j) {
             if (!ok[j]) continue;
-            const Split2 s0 = split2h_pair(v[j][0] * sc, v[j][1] * sc);
-            const Split2 s1 = split2h_pair(v[j][2] * sc, v[j][3] * sc);
+            const Planes4 y = split2h_x4(v[j], sc);
             unsigned short* o2 = p.out2 + mrow[j] * p.ldo2 + (n0 - 512);
-            *reinterpret_cast<rg_u32x2*>(o2) = rg_u32x2{s0.h, s1.h};
-            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = rg_u32x2{s0.l, s1.l};
+            *reinterpret_cast<rg_u32x2*>(o2) = y.h;
+            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = y.l;
           }
         }
       } else if constexpr (EPI == RG_GELU_PL) {
@@ -316,11 +311,10 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
           rg_f32x4 t = v[j];
 #pragma unroll
           for (int e = 0; e < 4; ++e) t[e] = gelu_erf(t[e]);
-          const Split2 s0 = split2h_pair(t[0] * p.out2_scale, t[1] * p.out2_scale);
-          const Split2 s1 = split2h_pair(t[2] * p.out2_scale, t[3] * p.out2_scale);
+          const Planes4 y = split2h_x4(t, p.out2_scale);
           unsigned short* o2 = p.out2 + mrow[j] * p.ldo2 + n0;
-          *reinterpret_cast<rg_u32x2*>(o2) = rg_u32x2{s0.h, s1.h};
-          *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = rg_u32x2{s0.l, s1.l};
+          *reinterpret_cast<rg_u32x2*>(o2) = y.h;
+          *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = y.l;
         }
       } else {
         // + residual -> fp32 rows (+ tracking) (-> LayerNorm -> planes)
@@ -346,41 +340,26 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
         if (p.amax_out) {
 #pragma unroll
           for (int j = 0; j < RPW; ++j) {
-            unsigned u = 0u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u = max(u, __float_as_uint(v[j][e]) & 0x7fffffffu);
-            // wave-uniform branch (a wave holds whole rows): nothing to do once the slot holds a larger value
-            if (tracked[j] && __builtin_amdgcn_ballot_w64(u > seen[j]) != 0) {
-#pragma unroll
-              for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o));
+            unsigned u = absmax4(v[j]);
+            if (absmax_exceeds(tracked[j], u, seen[j])) {
+              u = wave_umax(u);
               if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(p.amax_out + (p.row_slot ? p.row_slot[mrow[j]] : 0)), u);
             }
           }
         }
         if constexpr (EPI == RG_RES_LN) {
-          // LayerNorm over the row's 256 channels (two-pass, as rowops.hip's layernorm256_kernel), written as the next
-          // GEMM's pre-split operand
+          // LayerNorm of the stored row, written as the next GEMM's pre-split operand
           const rg_f32x4 gg = *reinterpret_cast<const rg_f32x4*>(p.ln_g + 4 * lane);
           const rg_f32x4 bb = *reinterpret_cast<const rg_f32x4*>(p.ln_b + 4 * lane);
           float sum[RPW], sq[RPW];
-#pragma unroll
-          for (int j = 0; j < RPW; ++j) sum[j] = wave_sum((v[j][0] + v[j][1]) + (v[j][2] + v[j][3]));
-#pragma unroll
-          for (int j = 0; j < RPW; ++j) {
-            const rg_f32x4 d = v[j] - sum[j] * (1.f / 256.f);
-            sq[j] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-          }
+          ln256_moments(v, sum, sq);
 #pragma unroll
           for (int j = 0; j < RPW; ++j) {
             if (!ok[j]) continue;
-            const float mean = sum[j] * (1.f / 256.f);
-            const float rstd = 1.0f / sqrtf(sq[j] * (1.f / 256.f) + p.ln_eps);
-            const rg_f32x4 y = (v[j] - mean) * rstd * gg + bb;
-            const Split2 s0 = split2h_pair(y[0] * p.out2_scale, y[1] * p.out2_scale);
-            const Split2 s1 = split2h_pair(y[2] * p.out2_scale, y[3] * p.out2_scale);
+            const Planes4 y = split2h_x4(ln256_apply(v[j], sum[j], ln256_rstd(sq[j], p.ln_eps), gg, bb), p.out2_scale);
             unsigned short* o2 = p.out2 + mrow[j] * p.ldo2 + 4 * lane;
-            *reinterpret_cast<rg_u32x2*>(o2) = rg_u32x2{s0.h, s1.h};
-            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = rg_u32x2{s0.l, s1.l};
+            *reinterpret_cast<rg_u32x2*>(o2) = y.h;
+            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = y.l;
           }
         }
       }
@@ -737,11 +716,10 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
 #pragma unroll
           for (int j = 0; j < RPW; ++j) {
             if (!ok[j]) continue;
-            const Split2 s0 = split2h_pair(v[j][0] * sc, v[j][1] * sc);
-            const Split2 s1 = split2h_pair(v[j][2] * sc, v[j][3] * sc);
+            const Planes4 y = split2h_x4(v[j], sc);
             unsigned short* o2 = p.out2 + mrow[j] * p.ldo2 + (n0 - 512);
-            *reinterpret_cast<rg_u32x2*>(o2) = rg_u32x2{s0.h, s1.h};
-            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = rg_u32x2{s0.l, s1.l};
+            *reinterpret_cast<rg_u32x2*>(o2) = y.h;
+            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = y.l;
           }
         }
       } else if constexpr (EPI == RG_GELU_PL) {
@@ -751,11 +729,10 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
           rg_f32x4 t = v[j];
 #pragma unroll
           for (int e = 0; e < 4; ++e) t[e] = gelu_erf(t[e]);
-          const Split2 s0 = split2h_pair(t[0] * p.out2_scale, t[1] * p.out2_scale);
-          const Split2 s1 = split2h_pair(t[2] * p.out2_scale, t[3] * p.out2_scale);
+          const Planes4 y = split2h_x4(t, p.out2_scale);
           unsigned short* o2 = p.out2 + mrow[j] * p.ldo2 + n0;
-          *reinterpret_cast<rg_u32x2*>(o2) = rg_u32x2{s0.h, s1.h};
-          *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = rg_u32x2{s0.l, s1.l};
+          *reinterpret_cast<rg_u32x2*>(o2) = y.h;
+          *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = y.l;
         }
       } else {
         // + residual -> fp32 rows (+ tracking) (-> LayerNorm -> planes)
@@ -776,41 +753,26 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
         if (p.amax_out) {
 #pragma unroll
           for (int j = 0; j < RPW; ++j) {
-            unsigned u = 0u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u = max(u, __float_as_uint(v[j][e]) & 0x7fffffffu);
-            // wave-uniform branch (a wave holds whole rows): nothing to do once the slot holds a larger value
-            if (tracked[j] && __builtin_amdgcn_ballot_w64(u > seen[j]) != 0) {
-#pragma unroll
-              for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o));
+            unsigned u = absmax4(v[j]);
+            if (absmax_exceeds(tracked[j], u, seen[j])) {
+              u = wave_umax(u);
               if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(p.amax_out + (p.row_slot ? p.row_slot[mrow[j]] : 0)), u);
             }
           }
         }
         if constexpr (EPI == RG_RES_LN) {
-          // LayerNorm over the row's 256 channels (two-pass, as rowops.hip's layernorm256_kernel), written as the next
-          // GEMM's pre-split operand
+          // LayerNorm of the stored row, written as the next GEMM's pre-split operand
           const rg_f32x4 gg = *reinterpret_cast<const rg_f32x4*>(p.ln_g + 4 * lane);
           const rg_f32x4 bb = *reinterpret_cast<const rg_f32x4*>(p.ln_b + 4 * lane);
           float sum[RPW], sq[RPW];
-#pragma unroll
-          for (int j = 0; j < RPW; ++j) sum[j] = wave_sum((v[j][0] + v[j][1]) + (v[j][2] + v[j][3]));
-#pragma unroll
-          for (int j = 0; j < RPW; ++j) {
-            const rg_f32x4 d = v[j] - sum[j] * (1.f / 256.f);
-            sq[j] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-          }
+          ln256_moments(v, sum, sq);
 #pragma unroll
           for (int j = 0; j < RPW; ++j) {
             if (!ok[j]) continue;
-            const float mean = sum[j] * (1.f / 256.f);
-            const float rstd = 1.0f / sqrtf(sq[j] * (1.f / 256.f) + p.ln_eps);
-            const rg_f32x4 y = (v[j] - mean) * rstd * gg + bb;
-            const Split2 s0 = split2h_pair(y[0] * p.out2_scale, y[1] * p.out2_scale);
-            const Split2 s1 = split2h_pair(y[2] * p.out2_scale, y[3] * p.out2_scale);
+            const Planes4 y = split2h_x4(ln256_apply(v[j], sum[j], ln256_rstd(sq[j], p.ln_eps), gg, bb), p.out2_scale);
             unsigned short* o2 = p.out2 + mrow[j] * p.ldo2 + 4 * lane;
-            *reinterpret_cast<rg_u32x2*>(o2) = rg_u32x2{s0.h, s1.h};
-            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = rg_u32x2{s0.l, s1.l};
+            *reinterpret_cast<rg_u32x2*>(o2) = y.h;
+            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = y.l;
           }
         }
       }
@@ -1047,11 +1009,10 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
             }
-            const Split2 s0 = split2h_pair(v[0] * sc, v[1] * sc);
-            const Split2 s1 = split2h_pair(v[2] * sc, v[3] * sc);
+            const Planes4 y = split2h_x4(v, sc);
             unsigned short* o2 = p.out2 + mrow * p.ldo2 + (EPI == RG_GELU_PL ? nw : nw - 512);
-            *reinterpret_cast<rg_u32x2*>(o2) = rg_u32x2{s0.h, s1.h};
-            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = rg_u32x2{s0.l, s1.l};
+            *reinterpret_cast<rg_u32x2*>(o2) = y.h;
+            *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = y.l;
           }
         }
       }
@@ -1313,7 +1274,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
     }
   }
 
-  // ---- ff.net.2's epilogue: + bias + residual -> rows (+ tracking) (-> LayerNorm -> planes); rowgemm_wd_kernel's ----
+  // ---- ff.net.2's epilogue: + bias + residual -> rows (+ tracking) (-> LayerNorm -> planes): the row tail (row_tail.h) ----
   constexpr int NRW = 2 * RT;
   rg_f32x4 rpre[NRW];
   unsigned seenpre[NRW];
@@ -1373,36 +1334,23 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
     if (p.amax_out) {
 #pragma unroll
       for (int j = 0; j < RT; ++j) {
-        unsigned u = 0u;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u = max(u, __float_as_uint(v[j][e]) & 0x7fffffffu);
-        if (trkpre[ps * RT + j] && __builtin_amdgcn_ballot_w64(u > seenpre[ps * RT + j]) != 0) {
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o));
+        unsigned u = absmax4(v[j]);
+        if (absmax_exceeds(trkpre[ps * RT + j], u, seenpre[ps * RT + j])) {
+          u = wave_umax(u);
           if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(p.amax_out + (p.row_slot ? p.row_slot[mrow[j]] : 0)), u);
         }
       }
     }
     if (p.ln) {
       float sum[RT], sq[RT];
-#pragma unroll
-      for (int j = 0; j < RT; ++j) sum[j] = wave_sum((v[j][0] + v[j][1]) + (v[j][2] + v[j][3]));
-#pragma unroll
-      for (int j = 0; j < RT; ++j) {
-        const rg_f32x4 d = v[j] - sum[j] * (1.f / 256.f);
-        sq[j] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-      }
+      ln256_moments(v, sum, sq);
 #pragma unroll
       for (int j = 0; j < RT; ++j) {
         if (!ok[j]) continue;
-        const float mean = sum[j] * (1.f / 256.f);
-        const float rstd = 1.0f / sqrtf(sq[j] * (1.f / 256.f) + p.ln_eps);
-        const rg_f32x4 y = (v[j] - mean) * rstd * gg + bb;
-        const Split2 s0 = split2h_pair(y[0] * p.out2_scale, y[1] * p.out2_scale);
-        const Split2 s1 = split2h_pair(y[2] * p.out2_scale, y[3] * p.out2_scale);
+        const Planes4 y = split2h_x4(ln256_apply(v[j], sum[j], ln256_rstd(sq[j], p.ln_eps), gg, bb), p.out2_scale);
         unsigned short* o2 = p.out2 + mrow[j] * p.ldo2 + 4 * lane;
-        *reinterpret_cast<rg_u32x2*>(o2) = rg_u32x2{s0.h, s1.h};
-        *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = rg_u32x2{s0.l, s1.l};
+        *reinterpret_cast<rg_u32x2*>(o2) = y.h;
+        *reinterpret_cast<rg_u32x2*>(o2 + p.out2_plane) = y.l;
       }
     }
   }

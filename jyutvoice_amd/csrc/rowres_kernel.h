@@ -349,6 +349,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
   load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
   advance_w();
 
+
   auto acc_to_slab = [&](const rg_f32x4 (&a)[RT][2]) {
 #pragma unroll
     for (int mt = 0; mt < RT; ++mt)
@@ -357,7 +358,6 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) slab[rb_slab(mt * 16 + kq * 4 + e, wave * 32 + nt * 16 + r16)] = a[mt][nt][e];
   };
-  auto bcast_f = [&](const float v, const int j) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j)); };
 
   // ================================ epilogue 1: h2 -> the operand image; res_conv's rows -> registers ================================
   acc_to_slab(acc);      // (the slab is the upper half: nothing of product 1 lives there)
@@ -368,35 +368,26 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
 #pragma unroll
     for (int j = 0; j < RT; ++j) {
       const int trow = wave * NRW + ps * RT + j;
-      v[j] = *reinterpret_cast<const rg_f32x4*>(slab + rb_slab(trow, 4 * lane)) * (cs1 * bcast_f(f_inv1, ps * RT + j)) + b1;
+      v[j] = *reinterpret_cast<const rg_f32x4*>(slab + rb_slab(trow, 4 * lane)) * (cs1 * lane_bcast(f_inv1, ps * RT + j)) + b1;
     }
     float sum[RT], sq[RT];
-#pragma unroll
-    for (int j = 0; j < RT; ++j) sum[j] = wave_sum((v[j][0] + v[j][1]) + (v[j][2] + v[j][3]));
-#pragma unroll
-    for (int j = 0; j < RT; ++j) {
-      const rg_f32x4 d = v[j] - sum[j] * (1.f / 256.f);
-      sq[j] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-    }
+    ln256_moments(v, sum, sq);
     float var_l = sq[0];
 #pragma unroll
     for (int j = 1; j < RT; ++j) var_l = lane == j ? sq[j] : var_l;
-    const float rstd_l = 1.0f / sqrtf(var_l * (1.f / 256.f) + p.ln_eps);
+    const float rstd_l = ln256_rstd(var_l, p.ln_eps);
 #pragma unroll
     for (int j = 0; j < RT; ++j) {
       const int trow = wave * NRW + ps * RT + j;
-      const float mean = sum[j] * (1.f / 256.f);
-      const float rstd = bcast_f(rstd_l, j);
-      rg_f32x4 y = (v[j] - mean) * rstd * g1 + o1;
+      rg_f32x4 y = ln256_apply(v[j], sum[j], lane_bcast(rstd_l, j), g1, o1);
       const bool live = __builtin_amdgcn_readlane(f_live, ps * RT + j) != 0;
 #pragma unroll
       for (int e = 0; e < 4; ++e) y[e] = live ? (mish_fast(y[e]) + te4[e]) * scale2 : 0.f;      // (a padding row reads as zero in block2)
-      const Split2 s0 = split2h_pair(y[0], y[1]);
-      const Split2 s1 = split2h_pair(y[2], y[3]);
+      const Planes4 y2 = split2h_x4(y);
       // columns 4 lane .. + 3 = k-step lane >> 3, 16-byte slot (lane & 7) >> 1 (swizzled), its half lane & 1 (rowblock_kernel's X)
       unsigned char* d = rr_lds + (lane >> 3) * STAGE + trow * 64 + (((((lane & 7) >> 1) ^ rg_key(trow))) << 4) + (lane & 1) * 8;
-      *reinterpret_cast<rg_u32x2*>(d) = rg_u32x2{s0.h, s1.h};
-      *reinterpret_cast<rg_u32x2*>(d + XP) = rg_u32x2{s0.l, s1.l};
+      *reinterpret_cast<rg_u32x2*>(d) = y2.h;
+      *reinterpret_cast<rg_u32x2*>(d + XP) = y2.l;
     }
   }
   rg_lds_barrier();      // every wave has read its slab rows: res_conv's product goes through the slab next
@@ -407,7 +398,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
   for (int j = 0; j < NRW; ++j) {
     const int t = wave * NRW + j;
     const int srow = t + 2 < R ? t + 2 : R - 1;      // (t >= RO: no output row)
-    res[j] = *reinterpret_cast<const rg_f32x4*>(slab + rb_slab(srow, 4 * lane)) * (csr * bcast_f(f_invo, j)) + br;
+    res[j] = *reinterpret_cast<const rg_f32x4*>(slab + rb_slab(srow, 4 * lane)) * (csr * lane_bcast(f_invo, j)) + br;
   }
   rg_wait_vmcnt<0>();      // block2's first fragments
   asm volatile("" ::"v"(warm3));      // (issued an epilogue ago)
@@ -469,7 +460,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
     }
   }
 
-  // ================================ epilogue 2 (rowconv_wd_kernel's row pass) ================================
+  // ================================ epilogue 2 (rowconv_wd_kernel's row pass in steps; the arithmetic is row_tail.h's) ================================
   // per-column constants of epilogue 2 (requested here, behind product 2 -- its loop has no registers to carry them; the slab write and its barrier cover most of their latency)
   const rg_f32x4 cs2 = *reinterpret_cast<const rg_f32x4*>(p.cs2 + 4 * lane);
   rg_f32x4 b2 = {0.f, 0.f, 0.f, 0.f};
@@ -501,22 +492,13 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
     }
     {
       float sum[RT], sq[RT];
-#pragma unroll
-      for (int j = 0; j < RT; ++j) sum[j] = wave_sum((v[j][0] + v[j][1]) + (v[j][2] + v[j][3]));
-#pragma unroll
-      for (int j = 0; j < RT; ++j) {
-        const rg_f32x4 d = v[j] - sum[j] * (1.f / 256.f);
-        sq[j] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-      }
+      ln256_moments(v, sum, sq);
       float var_l = sq[0];
 #pragma unroll
       for (int j = 1; j < RT; ++j) var_l = lane == j ? sq[j] : var_l;
-      const float rstd_l = 1.0f / sqrtf(var_l * (1.f / 256.f) + p.ln_eps);
+      const float rstd_l = ln256_rstd(var_l, p.ln_eps);
 #pragma unroll
-      for (int j = 0; j < RT; ++j) {
-        const float mean = sum[j] * (1.f / 256.f);
-        v[j] = (v[j] - mean) * bcast_f(rstd_l, j) * g2 + o2;
-      }
+      for (int j = 0; j < RT; ++j) v[j] = ln256_apply(v[j], sum[j], lane_bcast(rstd_l, j), g2, o2);
     }
     bool ok[RT];
 #pragma unroll
@@ -529,34 +511,25 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
       v[j] = v[j] + res[jj];
       if (ok[j]) *(__attribute__((address_space(1))) rg_f32x4*)(p.out + (long)(drow0 + j) * p.ldo + 4 * lane) = v[j];
     }
-    if (QKV || p.lnf_out) {      // (uniform) the following block's norm1 of the stored rows -> operand planes (rowconv_wd_kernel)
+    if (QKV || p.lnf_out) {      // (uniform) the following block's norm1 of the stored rows -> operand planes (row_tail.h)
       float sum[RT], sq[RT];
-#pragma unroll
-      for (int j = 0; j < RT; ++j) sum[j] = wave_sum((v[j][0] + v[j][1]) + (v[j][2] + v[j][3]));
-#pragma unroll
-      for (int j = 0; j < RT; ++j) {
-        const rg_f32x4 d = v[j] - sum[j] * (1.f / 256.f);
-        sq[j] = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
-      }
+      ln256_moments(v, sum, sq);
       float var_l = sq[0];
 #pragma unroll
       for (int j = 1; j < RT; ++j) var_l = lane == j ? sq[j] : var_l;
-      const float rstd_l = 1.0f / sqrtf(var_l * (1.f / 256.f) + p.ln_eps);
+      const float rstd_l = ln256_rstd(var_l, p.ln_eps);
 #pragma unroll
       for (int j = 0; j < RT; ++j) {
-        const float mean = sum[j] * (1.f / 256.f);
-        const rg_f32x4 y = (v[j] - mean) * bcast_f(rstd_l, j) * gf + of;
-        const Split2 s0 = split2h_pair(y[0] * p.lnf_scale, y[1] * p.lnf_scale);
-        const Split2 s1 = split2h_pair(y[2] * p.lnf_scale, y[3] * p.lnf_scale);
+        const Planes4 y = split2h_x4(ln256_apply(v[j], sum[j], lane_bcast(rstd_l, j), gf, of), p.lnf_scale);
         if constexpr (QKV) {      // the operand image of product 3 (rows >= RO / past the end: never stored, and a row's product reads its own row only)
           const int trow = wave * NRW + ps * RT + j;
           unsigned char* d = rr_lds + (lane >> 3) * STAGE + trow * 64 + (((((lane & 7) >> 1) ^ rg_key(trow))) << 4) + (lane & 1) * 8;
-          *reinterpret_cast<rg_u32x2*>(d) = rg_u32x2{s0.h, s1.h};
-          *reinterpret_cast<rg_u32x2*>(d + XP) = rg_u32x2{s0.l, s1.l};
+          *reinterpret_cast<rg_u32x2*>(d) = y.h;
+          *reinterpret_cast<rg_u32x2*>(d + XP) = y.l;
         } else if (ok[j]) {
           unsigned short* const o2p = p.lnf_out + (long)(drow0 + j) * 256 + 4 * lane;
-          *(__attribute__((address_space(1))) rg_u32x2*)(o2p) = rg_u32x2{s0.h, s1.h};
-          *(__attribute__((address_space(1))) rg_u32x2*)(o2p + p.lnf_plane) = rg_u32x2{s0.l, s1.l};
+          *(__attribute__((address_space(1))) rg_u32x2*)(o2p) = y.h;
+          *(__attribute__((address_space(1))) rg_u32x2*)(o2p + p.lnf_plane) = y.l;
         }
       }
     }
@@ -564,14 +537,11 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
 #pragma unroll
       for (int j = 0; j < RT; ++j) {
         const int jj = ps * RT + j;
-        unsigned u = 0u;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u = max(u, __float_as_uint(v[j][e]) & 0x7fffffffu);
+        unsigned u = absmax4(v[j]);
         const bool trk = __builtin_amdgcn_readlane(f_keep, jj) != 0;
         const unsigned seen = (unsigned)__builtin_amdgcn_readlane((int)f_seen, jj);
-        if (trk && __builtin_amdgcn_ballot_w64(u > seen) != 0) {      // wave-uniform: nothing to do once the slot holds a larger value
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o));
+        if (absmax_exceeds(trk, u, seen)) {
+          u = wave_umax(u);
           if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(p.amax_out + __builtin_amdgcn_readlane(f_slot, jj)), u);
         }
       }

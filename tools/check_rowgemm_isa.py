@@ -13,7 +13,12 @@ Second check, attention_s.hip (attn64_s_kernel): that kernel keeps its O accumul
 itself inside inline asm (a32 and up), without telling the compiler.  Sound only if the compiler-generated code of the kernel
 touches no AGPR from a32 up and spills nothing (a scratch reload would not be a hazard, but the kernel is written to fit): asserted here.
 
-usage: python tools/check_rowgemm_isa.py   (exit code 0 = clean)"""
+Footprints: --resources prints, for every kernel of rowgemm.hip, rowblock.hip and hiftconv.hip, its name, next free VGPR, accum
+offset (where the AGPRs begin), next free SGPR, private segment (scratch) and group segment (static LDS) size, from the same
+compile; --resources=PATH also writes the table as JSON (profiles/row_kernels_resources.json is one such file).
+
+usage: python tools/check_rowgemm_isa.py [--resources[=PATH]]   (exit code 0 = clean)"""
+import json
 import os
 import re
 import subprocess
@@ -129,8 +134,23 @@ def check_agpr_owner(name, body):
     return n_asm, bad
 
 
+RES_KEYS = {"vgpr": "next_free_vgpr", "accum_offset": "accum_offset", "sgpr": "next_free_sgpr",
+            "scratch": "private_segment_fixed_size", "lds": "group_segment_fixed_size"}
+
+
+def kernel_resources(asm):
+    """{kernel name: {vgpr, accum_offset, sgpr, scratch, lds}} from the .amdhsa_kernel blocks of an assembly text"""
+    out = {}
+    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S+)\n(.*?)\.end_amdhsa_kernel", asm, re.S | re.M):
+        d = dict(re.findall(r"\.amdhsa_(\w+)\s+(\d+)", m.group(2)))
+        out[m.group(1)] = {k: int(d[v]) for k, v in RES_KEYS.items()}
+    return out
+
+
 def main():
+    res_arg = next((a for a in sys.argv[1:] if a == "--resources" or a.startswith("--resources=")), None)
     s = ""
+    s_row = ""      # the three row-owning translation units alone: what the footprint table covers
     with tempfile.TemporaryDirectory() as d:
         for src, extra in [(f, []) for f in SRCS + [ATTN_S]] + [(ATTN_S, ["-DJV_TUNING"])]:      # (the tuning build's variants too)
             out = os.path.join(d, os.path.basename(src) + (".tune" if extra else "") + ".s")
@@ -140,12 +160,24 @@ def main():
                 print(r.stderr[-3000:])
                 return 2
             s += open(out).read()
+            if src in SRCS:
+                s_row += open(out).read()
             # -S does not run the assembler over the inline asm: an operand the assembler rejects only shows with -c
             r = subprocess.run([CLANG] + [f for f in FLAGS if f != "-S"] + ["-c", "-o", os.path.join(d, os.path.basename(src) + ".o"), src],
                                capture_output=True, text=True)
             if r.returncode != 0:
                 print(r.stderr[-3000:])
                 return 2
+    if res_arg:
+        table = kernel_resources(s_row)
+        print(f"{'vgpr':>5} {'accum':>5} {'sgpr':>5} {'scratch':>7} {'lds':>6}  kernel")
+        for name in sorted(table):
+            r = table[name]
+            print(f"{r['vgpr']:5d} {r['accum_offset']:5d} {r['sgpr']:5d} {r['scratch']:7d} {r['lds']:6d}  {name}")
+        if "=" in res_arg:
+            with open(res_arg.split("=", 1)[1], "w") as f:
+                json.dump(table, f, indent=0, sort_keys=True)
+                f.write("\n")
     n_k = n_bad = 0
     for m in re.finditer(r"^(_ZN2jv\d+(rowgemm_wd_kernel|rowgemm_wa_kernel|rowffn_kernel|rowconv_wd_kernel|rowblock_kernel|rowres_kernel|hiftconv_kernel|hiftpair_kernel)\w+):\s*;.*?\n(.*?)\.end_amdhsa_kernel", s, re.S | re.M):
         name, body = m.group(1), m.group(3)
