@@ -248,6 +248,57 @@ int jv_fbank(jv_context* ctx, const float* wav, const int32_t* lens, int B, int 
 int jv_whisper_log_mel(jv_context* ctx, const float* wav, const int32_t* lens, int B, int n, float* out, int32_t* out_lens,
                        void* stream);
 
+/* ---- evaluation forward(): alignment search and the three losses (no gradients) --------------------------------
+ * What JyutVoiceTTS.forward (jyutvoice_tts.py:255-364) computes between the encoder and its return, around one call of
+ * jv_flow_estimator_step.  Tensors are device pointers: mu_x [B,80,Tx], h = decoder_h [B,Ty,80] (batch, time, channel), x_lens and
+ * y_lens [B] int32, attn / log_prior [B,Tx,Ty] (the reference's layout), frame_index [B,Ty] int32, durations [B,Tx] int32.
+ *
+ * Lengths of jv_log_prior, jv_maximum_path and jv_align: 1 <= x_lens[b] <= Tx and x_lens[b] <= y_lens[b] <= Ty, else JV_ERR_ARG
+ * naming the utterance, before anything is launched (the reference reads out of bounds when t_y < t_x: that case is rejected, not
+ * clamped).  Both vectors come down with the call's one synchronisation.  Tx <= max_tokens, Ty <= max_frames of the context and
+ * Tx <= 2048, else JV_ERR_SHAPE.  Nothing behind a length is read (it may be NaN).  jv_align_losses, jv_cfm_loss_inputs and
+ * jv_masked_mse never synchronise; their lengths MEAN min(max(len, 0), T) as under "Lengths" above.
+ *
+ * jv_log_prior: jyutvoice_tts.py:306-314.  log_prior[b,x,y] = -0.5 sum_c (h[b,y,c] - mu_x[b,c,x])^2 - 0.5 log(2 pi) 80 for
+ *   x < x_lens[b], y < y_lens[b], zeros elsewhere.  The reference expands the square into three matmuls with factor = -0.5; this is
+ *   the difference form, fp32: one fused multiply-add per channel into four interleaved partial sums (c mod 4), (s0 + s1) + (s2 + s3).
+ * jv_maximum_path: monotonic_align.maximum_path (utils/monotonic_align/__init__.py:7-22, core.pyx:11-37) on the device.  value:
+ *   [B,Tx,Ty] scores.  The recurrence of core.pyx:19-32 in fp32 (max_neg_val = -1e9, one add per cell) and the backtrack of
+ *   core.pyx:34-37 with its tie rule (`<`, strict: equal scores stay on the same token).  attn (optional): fp32 one-hot path, zeros
+ *   outside the utterance; frame_index: the token of every frame, -1 behind y_lens[b]; durations (optional): frames per token, 0
+ *   behind x_lens[b].  One workgroup per utterance; no workgroup waits for another.
+ * jv_align: jv_log_prior + jv_maximum_path from mu_x and h without the [B,Tx,Ty] round trip; log_prior is optional.
+ * jv_align_losses: logw [B,1,Tx] ->
+ *   dur_loss   = sum((logw - log(1e-8 + durations) * x_mask)^2) / sum(x_lens)          (utils/model.py:49-51, jyutvoice_tts.py:321-322)
+ *                summed over x < x_lens[b]: the reference's logw is masked by the duration predictor, so its terms behind the
+ *                length are zeros; logw, durations, mu_x, h and frame_index are not read behind their lengths
+ *   mu_y[b,:,y] = mu_x[b,:,frame_index[b,y]], zeros behind y_lens[b]: [B,80,Ty]         (jyutvoice_tts.py:334-335, the one-hot matmul)
+ *   prior_loss = sum(0.5 ((h - mu_y)^2 + log(2 pi)) * y_mask) / (sum(y_lens) * 80)     (jyutvoice_tts.py:349-362)
+ *   dur_loss, prior_loss: one device float each.
+ * jv_cfm_loss_inputs: the estimator inputs of ConditionalCFM.compute_loss (flow_matching.py:319-334) and the condition prefix of
+ *   jyutvoice_tts.py:325-330.  x1 = y, z, mu_y: [B,80,T]; t: [B], already cosine-warped; cfg_mask: [B] floats 0 / 1; cond_index: [B]
+ *   int32 k_b; spks: [B,80].  y_t = (1 - (1 - 1e-6) t) z + t x1; u = x1 - (1 - 1e-6) z; mu_masked = mu_y m; spks_masked = spks m;
+ *   cond[b,:,:k_b] = x1[b,:,:k_b] m, zeros behind k_b.  Each product and sum rounded on its own, as the reference's tensor ops are.
+ * jv_masked_mse: F.mse_loss(a * mask, b * mask, reduction="sum") / (sum(mask) * C) of flow_matching.py:337-339; a, b: [B,C,T], mask
+ *   from lens; out: one device float.
+ * Reductions are per-workgroup partials added in a fixed order by one finishing launch: no float atomics, the same bits every run.
+ * The search's score buffer ([B,Ty,Tx]), its decision bits, the partials and a pinned length vector belong to the context and grow
+ * on demand (a call larger than any before waits for the device and re-allocates: under stream capture make the largest call
+ * outside the capture first).  They are not workspace: jv_reserve leaves them alone, jv_destroy frees them. */
+int jv_log_prior(jv_context* ctx, const float* mu_x, const float* h, const int32_t* x_lens, const int32_t* y_lens, int B, int Tx, int Ty,
+                 float* log_prior, void* stream);
+int jv_maximum_path(jv_context* ctx, const float* value, const int32_t* x_lens, const int32_t* y_lens, int B, int Tx, int Ty, float* attn,
+                    int32_t* frame_index, int32_t* durations, void* stream);
+int jv_align(jv_context* ctx, const float* mu_x, const float* h, const int32_t* x_lens, const int32_t* y_lens, int B, int Tx, int Ty,
+             float* log_prior, float* attn, int32_t* frame_index, int32_t* durations, void* stream);
+int jv_align_losses(jv_context* ctx, const float* logw, const int32_t* durations, const int32_t* x_lens, const float* mu_x, const float* h,
+                    const int32_t* frame_index, const int32_t* y_lens, int B, int Tx, int Ty, float* mu_y, float* dur_loss,
+                    float* prior_loss, void* stream);
+int jv_cfm_loss_inputs(jv_context* ctx, const float* x1, const float* z, const float* t, const float* cfg_mask, const int32_t* cond_index,
+                       const float* mu_y, const float* spks, int B, int T, float* y_t, float* u, float* mu_masked, float* spks_masked,
+                       float* cond, void* stream);
+int jv_masked_mse(jv_context* ctx, const float* a, const float* b, const int32_t* lens, int B, int C, int T, float* out, void* stream);
+
 /* ---- text encoder + duration predictor + length regulation ---------------------------------------------
  * jv_encoder_fwd: spk_embed_affine_layer(normalize(spk)) + TextEncoder.forward + DurationPredictor.forward
  * (jyutvoice/models/jyutvoice_tts.py:175-182, text_encoder.py:406-451, duration_predictor.py:48-60).

@@ -68,6 +68,12 @@ SIGNATURES = {
     "jv_load_whisper_filters": (_i, [_p, _p, _i64, _i, _p]),
     "jv_fbank": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "jv_whisper_log_mel": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
+    "jv_log_prior": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "jv_maximum_path": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "jv_align": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "jv_align_losses": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "jv_cfm_loss_inputs": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "jv_masked_mse": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "jv_prompt_encoder_fwd": (_i, [_p, _p, _p, _i, _i, _p, _p]),
     "jv_length_regulate": (_i, [_p, _p, _p, _p, _i, _i, _f, _p, _p, _i, _p, _p, _p]),
     "jv_hift_f0": (_i, [_p, _p, _p, _i, _i, _p, _p]),

@@ -234,6 +234,7 @@ void jv_destroy(jv_context* ctx) {
   jv::audio_ws_destroy(c);
   jv::resample_ws_destroy(c);
   jv::feat16k_ws_destroy(c);
+  jv::align_ws_destroy(c);
   delete ctx;
 }
 

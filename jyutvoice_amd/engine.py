@@ -300,6 +300,84 @@ class Engine:
                                           _ptr(y_lengths), ty, _ptr(attn), _ptr(mu_y), st))
         return w_ceil, y_lengths, attn, mu_y
 
+    # ---- evaluation forward(): alignment search and losses ------------------------------------------------
+    def _lens32(self, who, lens, B):
+        v = lens.to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(v.shape) != (B,):
+            raise ValueError(f"{who}: lengths must have shape [{B}], got {tuple(v.shape)}")
+        return v
+
+    def log_prior(self, mu_x, h, x_lens, y_lens):
+        """jv_log_prior (jyutvoice_tts.py:306-314): mu_x [B,80,Tx], h [B,Ty,80] -> log_prior [B,Tx,Ty], zeros outside the utterance"""
+        mu_x, h = _f32(mu_x, self.device), _f32(h, self.device)
+        B, _, Tx = mu_x.shape
+        Ty = h.shape[1]
+        xl, yl = self._lens32("log_prior", x_lens, B), self._lens32("log_prior", y_lens, B)
+        out = torch.empty(B, Tx, Ty, device=self.device)
+        check(self.lib.jv_log_prior(self._h, _ptr(mu_x), _ptr(h), _ptr(xl), _ptr(yl), B, Tx, Ty, _ptr(out), _stream(self.device)))
+        return out
+
+    def maximum_path(self, value, x_lens, y_lens):
+        """jv_maximum_path (monotonic_align/core.pyx): value [B,Tx,Ty] scores -> (attn fp32 [B,Tx,Ty] one-hot, frame_index int32
+        [B,Ty], -1 behind y_lens; durations int32 [B,Tx]).  What lies behind the lengths is not read."""
+        value = _f32(value, self.device)
+        B, Tx, Ty = value.shape
+        xl, yl = self._lens32("maximum_path", x_lens, B), self._lens32("maximum_path", y_lens, B)
+        attn = torch.empty(B, Tx, Ty, device=self.device)
+        fi = torch.empty(B, Ty, dtype=torch.int32, device=self.device)
+        dur = torch.empty(B, Tx, dtype=torch.int32, device=self.device)
+        check(self.lib.jv_maximum_path(self._h, _ptr(value), _ptr(xl), _ptr(yl), B, Tx, Ty, _ptr(attn), _ptr(fi), _ptr(dur),
+                                       _stream(self.device)))
+        return attn, fi, dur
+
+    def align(self, mu_x, h, x_lens, y_lens, want_log_prior=False, want_attn=True):
+        """jv_align: prior + search from mu_x [B,80,Tx] and h [B,Ty,80] -> (attn, frame_index, durations, log_prior or None)"""
+        mu_x, h = _f32(mu_x, self.device), _f32(h, self.device)
+        B, _, Tx = mu_x.shape
+        Ty = h.shape[1]
+        xl, yl = self._lens32("align", x_lens, B), self._lens32("align", y_lens, B)
+        lp = torch.empty(B, Tx, Ty, device=self.device) if want_log_prior else None
+        attn = torch.empty(B, Tx, Ty, device=self.device) if want_attn else None
+        fi = torch.empty(B, Ty, dtype=torch.int32, device=self.device)
+        dur = torch.empty(B, Tx, dtype=torch.int32, device=self.device)
+        check(self.lib.jv_align(self._h, _ptr(mu_x), _ptr(h), _ptr(xl), _ptr(yl), B, Tx, Ty, _ptr(lp), _ptr(attn), _ptr(fi), _ptr(dur),
+                                _stream(self.device)))
+        return attn, fi, dur, lp
+
+    def align_losses(self, logw, durations, x_lens, mu_x, h, frame_index, y_lens):
+        """jv_align_losses -> (dur_loss, prior_loss: 0-d device tensors; mu_y [B,80,Ty])"""
+        logw, mu_x, h = _f32(logw, self.device), _f32(mu_x, self.device), _f32(h, self.device)
+        B, _, Tx = mu_x.shape
+        Ty = h.shape[1]
+        xl, yl = self._lens32("align_losses", x_lens, B), self._lens32("align_losses", y_lens, B)
+        mu_y = torch.empty(B, spec.N_FEATS, Ty, device=self.device)
+        losses = torch.empty(2, device=self.device)
+        check(self.lib.jv_align_losses(self._h, _ptr(logw), _ptr(durations), _ptr(xl), _ptr(mu_x), _ptr(h), _ptr(frame_index), _ptr(yl),
+                                       B, Tx, Ty, _ptr(mu_y), C.c_void_p(losses.data_ptr()), C.c_void_p(losses.data_ptr() + 4),
+                                       _stream(self.device)))
+        return losses[0], losses[1], mu_y
+
+    def cfm_loss_inputs(self, x1, z, t, cfg_mask, cond_index, mu_y, spks):
+        """jv_cfm_loss_inputs: t [B] already warped, cfg_mask [B] (0 / 1), cond_index [B] -> (y_t, u, mu_masked, spks_masked, cond)"""
+        x1, z, mu_y, spks = (_f32(v, self.device) for v in (x1, z, mu_y, spks))
+        t, m = _f32(t, self.device), _f32(cfg_mask, self.device)
+        B, _, T = x1.shape
+        k = self._lens32("cfm_loss_inputs", cond_index, B)
+        y_t, u, mu_m, cond = (torch.empty_like(x1) for _ in range(4))
+        spks_m = torch.empty_like(spks)
+        check(self.lib.jv_cfm_loss_inputs(self._h, _ptr(x1), _ptr(z), _ptr(t), _ptr(m), _ptr(k), _ptr(mu_y), _ptr(spks), B, T, _ptr(y_t),
+                                          _ptr(u), _ptr(mu_m), _ptr(spks_m), _ptr(cond), _stream(self.device)))
+        return y_t, u, mu_m, spks_m, cond
+
+    def masked_mse(self, a, b, lens):
+        """jv_masked_mse: sum(((a - b) * mask)^2) / (sum(mask) * C) over [B,C,T] -> a 0-d device tensor"""
+        a, b = _f32(a, self.device), _f32(b, self.device)
+        B, Cc, T = a.shape
+        ln = self._lens32("masked_mse", lens, B)
+        out = torch.empty(1, device=self.device)
+        check(self.lib.jv_masked_mse(self._h, _ptr(a), _ptr(b), _ptr(ln), B, Cc, T, _ptr(out), _stream(self.device)))
+        return out[0]
+
     # ---- HiFT -----------------------------------------------------------------------------------------
     def hift_f0(self, mel, lens=None):
         B, _, T = mel.shape

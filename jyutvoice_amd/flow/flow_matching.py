@@ -18,6 +18,10 @@ class CausalConditionalCFM:
         if self.t_scheduler != "cosine" or abs(self.inference_cfg_rate - spec.CFG_RATE) > 1e-12 or spk_emb_dim != spec.N_FEATS:
             raise NotImplementedError("libjyutvoice_hip is built for t_scheduler='cosine', inference_cfg_rate=0.7, "
                                       "spk_emb_dim=80 (configs/base.yaml:76-87)")
+        try:      # used by JyutVoiceTTS.forward only (flow_matching.py:330-334); base.yaml: 0.2
+            self.training_cfg_rate = float(_get(cfm_params, "training_cfg_rate"))
+        except (KeyError, AttributeError):
+            self.training_cfg_rate = 0.2
         self.estimator = estimator
         self.device = torch.device("cuda:0")      # JyutVoiceTTS sets it to its own device
 

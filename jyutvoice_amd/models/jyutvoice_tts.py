@@ -1,8 +1,10 @@
-"""`JyutVoiceTTS` drop-in for the synthesis path (jyutvoice/models/jyutvoice_tts.py:23-253).
+"""`JyutVoiceTTS` drop-in for the synthesis path and the evaluation `forward()` (jyutvoice/models/jyutvoice_tts.py:23-364).
 
 Same constructor keywords, `load_state_dict` / `load_pretrain` key names, `synthesise()` signature, defaults,
-return-dict keys and `ValueError` for batch != 1 as the reference; training (`forward`, Lightning hooks) is out of
-scope.  All arithmetic runs in libjyutvoice_hip.so; this class only moves pointers.
+return-dict keys and `ValueError` for batch != 1 as the reference.  `forward()` has the reference's positional signature and
+returns its `(dur_loss, prior_loss, diff_loss, attn)` without gradients: validation losses, forced alignment, durations.
+Backward passes, optimisers and the Lightning hooks are out of scope.  All arithmetic runs in libjyutvoice_hip.so; this class
+only moves pointers.
 
 Extension (opt-in): `synthesise(..., batched=True)` accepts B > 1 and is defined as looping the batch-1
 reference over the utterances (padded frames of shorter utterances are returned as zeros).  With `prompt_lengths` ([B]
@@ -14,6 +16,7 @@ from __future__ import annotations
 
 import datetime as dt
 import os
+import random
 from typing import Dict
 
 import torch
@@ -166,6 +169,84 @@ class JyutVoiceTTS:
         dec = eng.cfm_solve(mu_y.contiguous(), lens if B > 1 else None, c, conds, n_timesteps, temperature, t_span=t_span)
         dec = dec[:, :, mel_len1:]
         return self._result(t0, B, encoder_outputs, dec, attn, y_lengths, mark)
+
+    # ---- evaluation: alignment and the three losses (jyutvoice_tts.py:255-364), no gradients ------------------------------
+    @torch.inference_mode()
+    def forward(self, x, x_lengths, y, y_lengths, lang, tone, word_pos, syllable_pos, spk_embed, decoder_h, *, t=None, z=None,
+                cfg_mask=None, cond_index=None, generator=None, return_parts=False):
+        """-> (dur_loss, prior_loss, diff_loss, attn): three 0-d device tensors and the alignment [B, T_text, T_mel].
+
+        x .. decoder_h as in the reference: y [B, 80, T_mel] target mels, decoder_h [B, T_mel, 80] hidden states of the flow
+        encoder.  Every utterance needs 1 <= x_lengths[b] <= y_lengths[b] <= T_mel (an alignment gives each token a frame;
+        the reference reads out of bounds otherwise): ValueError naming the utterance, before anything is launched.
+
+        The reference draws four random things; each may be supplied instead (keyword-only):
+          t           [B] in [0, 1): the uniform draw of flow_matching.py:320, BEFORE the cosine warp (applied here as there)
+          z           like y: the noise of flow_matching.py:324
+          cfg_mask    [B] bool / 0-1: False drops mu, spks and cond of that utterance (flow_matching.py:331-334)
+          cond_index  [B] ints k_b: cond[b, :, :k_b] = y[b, :, :k_b]; 0 = no condition (jyutvoice_tts.py:325-330)
+          generator   a torch.Generator of this model's device for what is NOT supplied of t, z, cfg_mask (drawn on the device;
+                      same seed, same losses); cond_index is drawn with Python's `random` as the reference draws it.
+        return_parts=True appends a dict: log_prior [B, T_text, T_mel], frame_index [B, T_mel] int32 (-1 behind the length),
+        durations [B, T_text] int32, mu_y, y_t, u, pred [B, 80, T_mel], logw, mu_x, t (warped), spks (the projected speaker
+        vector [B, 80]) and the masked estimator inputs mu_masked, spks_masked, cond."""
+        if not self._loaded:
+            raise RuntimeError(f"JyutVoiceTTS: load_state_dict() has not provided all weights yet; {len(self._missing)} tensors "
+                               f"missing, e.g. {self._missing[:4]}")
+        B, Tt = x.shape
+        if y.dim() != 3 or y.shape[0] != B or y.shape[1] != self.n_feats:
+            raise ValueError(f"forward(): y must be [{B}, {self.n_feats}, T_mel], got {tuple(y.shape)}")
+        Ty = y.shape[-1]
+        if decoder_h.dim() != 3 or decoder_h.shape[0] != B or decoder_h.shape[2] != self.n_feats or decoder_h.shape[1] != Ty:
+            raise ValueError(f"forward(): decoder_h must be [{B}, {Ty}, {self.n_feats}] (as many frames as y), "
+                             f"got {tuple(decoder_h.shape)}")
+        xl_host, yl_host = [int(v) for v in x_lengths.tolist()], [int(v) for v in y_lengths.tolist()]
+        if len(xl_host) != B or len(yl_host) != B:
+            raise ValueError(f"forward(): x_lengths and y_lengths must have shape [{B}]")
+        for b, (nx, ny) in enumerate(zip(xl_host, yl_host)):
+            if nx < 1 or nx > Tt:
+                raise ValueError(f"forward(): utterance {b}: {nx} tokens outside [1, {Tt}]")
+            if ny < nx or ny > Ty:
+                raise ValueError(f"forward(): utterance {b}: {ny} frames outside [tokens = {nx}, {Ty}]: an alignment needs a "
+                                 "frame for every token")
+        dev = self.device
+        if cond_index is None:      # jyutvoice_tts.py:326-330
+            cond_index = [0 if random.random() < 0.5 else random.randint(0, int(0.3 * ny)) for ny in yl_host]
+        k_host = [int(v) for v in (cond_index.tolist() if torch.is_tensor(cond_index) else cond_index)]
+        if len(k_host) != B:
+            raise ValueError(f"forward(): cond_index must hold {B} entries")
+        for b, k in enumerate(k_host):
+            if k < 0 or k > Ty:
+                raise ValueError(f"forward(): utterance {b}: cond_index {k} outside [0, {Ty}]")
+        t = torch.rand(B, device=dev, generator=generator) if t is None else t.to(dev, torch.float32).reshape(B)
+        t = 1 - torch.cos(t * 0.5 * torch.pi)      # flow_matching.py:321-322 (t_scheduler == "cosine")
+        y = y.to(dev, torch.float32).contiguous()
+        decoder_h = decoder_h.to(dev, torch.float32).contiguous()
+        if z is None:
+            z = torch.randn(y.shape, device=dev, generator=generator)
+        elif tuple(z.shape) != tuple(y.shape):
+            raise ValueError(f"forward(): z must have y's shape {tuple(y.shape)}, got {tuple(z.shape)}")
+        if cfg_mask is None:
+            rate = getattr(self.decoder, "training_cfg_rate", 0.2)
+            cfg_mask = torch.rand(B, device=dev, generator=generator) > rate if rate > 0 else torch.ones(B, device=dev)
+        cfg_mask = cfg_mask.to(dev).reshape(B).ne(0).to(torch.float32)
+
+        eng = get_runtime(dev).ensure(B, Ty, Tt)
+        xl = torch.tensor(xl_host, dtype=torch.int32, device=dev)
+        yl = torch.tensor(yl_host, dtype=torch.int32, device=dev)
+        _, mu_x, logw, c = eng.encoder(x, xl, lang, tone, word_pos, syllable_pos, spk_embed)
+        attn, frame_index, durations, log_prior = eng.align(mu_x, decoder_h, xl, yl, want_log_prior=return_parts)
+        dur_loss, prior_loss, mu_y = eng.align_losses(logw, durations, xl, mu_x, decoder_h, frame_index, yl)
+        y_t, u, mu_m, spks_m, cond = eng.cfm_loss_inputs(y, z, t, cfg_mask, torch.tensor(k_host, dtype=torch.int32), mu_y, c)
+        pred = eng.flow_estimator(y_t, yl, mu_m, t, spks_m, cond)
+        diff_loss = eng.masked_mse(pred, u, yl)
+        if not return_parts:
+            return dur_loss, prior_loss, diff_loss, attn
+        parts = {"log_prior": log_prior, "frame_index": frame_index, "durations": durations, "mu_y": mu_y, "y_t": y_t, "u": u,
+                 "pred": pred, "logw": logw, "mu_x": mu_x, "t": t, "spks": c, "mu_masked": mu_m, "spks_masked": spks_m, "cond": cond}
+        return dur_loss, prior_loss, diff_loss, attn, parts
+
+    __call__ = forward
 
     def _result(self, t0, B, encoder_outputs, dec, attn, y_lengths, mark):
         mark()
