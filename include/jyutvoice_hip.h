@@ -33,6 +33,9 @@ extern "C" {
 #define JV_MODEL_HIFT 1 /* HiFTGenerator state-dict                                                                */
 #define JV_MODEL_PROMPT 2 /* FlowEncoder state-dict (infer.py:35-83: input_embedding.*, encoder.*, encoder_proj.*) plus the
                              host-computed "pos_enc.div_term" [256] (jyutvoice/transformer/embedding.py:239-242)     */
+#define JV_MODEL_FLOW 3 /* the flow decoder alone: the `decoder.*` and `spk_embed_affine_layer.*` tensors of JV_MODEL_TTS -- what a
+                           CosyVoice2 flow.pt holds besides its encoder.  Not a registry of its own (jv_tensor_model never returns
+                           it): only an argument of jv_finalize                                                     */
 
 typedef struct jv_context jv_context;
 
@@ -69,7 +72,11 @@ int jv_load_tensor(jv_context* ctx, const char* name, const float* data, const i
 /* the CFM's fixed noise tensor [1,80,15000] (CausalConditionalCFM.rand_noise, flow_matching.py:353-354: a plain
  * attribute, not a state-dict entry; the host regenerates it from torch seed 0) */
 int jv_load_noise(jv_context* ctx, const float* data, int64_t numel, int on_device, void* stream);
-/* all tensors of `model` present -> fold weight-norm, pack GEMM operands.  Errors name the missing key. */
+/* all tensors of `model` present -> fold weight-norm, pack GEMM operands.  Errors name the missing key.
+ * JV_MODEL_FLOW asks only for the `decoder.*` and `spk_embed_affine_layer.*` tensors of JV_MODEL_TTS (same slots, same packing)
+ * and makes the estimator, the solver and the speaker projection usable: jv_flow_estimator_*, jv_cfm_solve*, jv_flow_token2mel.
+ * JV_MODEL_TTS keeps asking for all of its tensors and implies JV_MODEL_FLOW; after JV_MODEL_FLOW it packs the rest.  The text-side
+ * entries (jv_encoder_fwd) on a flow-only context return JV_ERR_STATE naming what is missing. */
 int jv_finalize(jv_context* ctx, int model, void* stream);
 
 /* ---- flow decoder ------------------------------------------------------------------------------------
@@ -152,6 +159,30 @@ int jv_cfm_solve_prompted(jv_context* ctx, const float* mu_y, const int32_t* y_l
  * zero beyond 2*token_len[b].  B > 1 is the per-utterance loop of the B = 1 reference usage.  2*Tk <= max_frames. */
 int jv_prompt_encoder_fwd(jv_context* ctx, const int64_t* tokens, const int64_t* token_len, int B, int Tk, float* prompt_h,
                           void* stream);
+
+/* ---- token-to-mel: CausalMaskedDiffWithXvec.inference (jyutvoice/flow/flow.py:300-358), finalize=True ------------------------
+ * jv_flow_encoder_fwd: flow.py:319-328, 338 -- utterance b's token sequence is [prompt_tokens[b, :p_b] | tokens[b, :n_b]]
+ * (concatenated inside the embedding kernel; what lies behind either length is not read), Embedding(clamp(token, 0)) * mask ->
+ * UpsampleConformerEncoder(streaming) -> Linear(512, 80).  prompt_tokens: int64 [B,P] (P = 0: none, the pointers may be NULL),
+ * tokens: int64 [B,N]; prompt_lens, token_lens: int64 [B], clamped to [0, P] / [0, N]; h: [B, 2*(P+N), 80] (batch, time, channel),
+ * zeros behind 2*(p_b + n_b); h_lens: optional [B] int32, receives 2*(p_b + n_b).  streaming != 0: the chunk masks of
+ * upsample_encoder.py:338-367 (static_chunk_size 25 tokens, 50 after the up-sampling, all left chunks; the look-ahead convolution
+ * reaches across chunk edges as in the reference).  The relative-position attention is ONE launch per block (relattn.hip, online
+ * softmax): this route's workspace holds no [T, T] buffer.  Needs JV_MODEL_PROMPT; 2*(P+N) <= max_frames, P+N <= 2048.
+ * jv_flow_token2mel: the rest of flow.py:314-358 for a batch -- F.normalize + spk_embed_affine_layer, mu = h, cond = [prompt_feat_b
+ * [:f_b] | 0], the solver of jv_cfm_solve over T_b = 2*(p_b + n_b) frames (with the estimator's streaming mask when streaming != 0,
+ * restored afterwards), and frames f_b .. T_b - 1 left-aligned in mel[b] with zeros behind y_b = T_b - f_b.  Noise column j belongs
+ * to frame j of the utterance's own sequence.  B > 1 is the B = 1 reference looped over the utterances.
+ * prompt_feat: [B,F,80] (batch, time, channel; 16-byte aligned; F = 0: none); feat_lens: [B] int32 f_b; embedding: [B,192] raw;
+ * mel: [B,80,Tm], Tm = 2*(P+N); mel_lens: optional [B] int32, receives y_b.  0 <= f_b <= min(F, T_b), else JV_ERR_ARG naming the
+ * utterance, before the solve is launched (a wrong f_b is a wrong split point, which a clamp would turn into other frames silently:
+ * the rule of jv_cfm_solve_prompted).  Needs JV_MODEL_PROMPT and JV_MODEL_FLOW (or JV_MODEL_TTS) and the noise tensor. */
+int jv_flow_encoder_fwd(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                        const int64_t* token_lens, int B, int P, int N, int streaming, float* h, int32_t* h_lens, void* stream);
+int jv_flow_token2mel(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                      const int64_t* token_lens, const float* prompt_feat, const int32_t* feat_lens, const float* embedding, int B,
+                      int P, int N, int F, int streaming, int n_timesteps, float temperature, const float* t_span_host, float* mel,
+                      int32_t* mel_lens, void* stream);
 
 /* jv_load_mel_basis / jv_mel_spectrogram: the prompt-mel front-end, `extract_speech_feat` of infer.py:166-186 ->
  * `mel_spectrogram` of jyutvoice/utils/audio.py:18-63 (24 kHz, n_fft = win = 1920 periodic Hann, hop 480, reflect pad 720,
@@ -352,6 +383,15 @@ int jv_op_conv_gemm(const float* A, int64_t a_rows, int M, int Cin, int ntaps, i
                     const float* bias, int act, int prologue, const float* alpha, float slope, const float* ln_g,
                     const float* ln_b, float ln_eps, const uint8_t* rowmask, const float* res, float* out, void* stream);
 int jv_op_attention(const float* qkv, const int32_t* lens, int B, int G, int S, int L, float* out, void* stream);
+/* jv_op_rel_attention: the conformer block's relative-position attention (attention.py:204-334) on caller-supplied buffers.
+ * qkv [rows,1536] rows G + b*S + t; p = linear_pos(pos_emb) [2T-1,512]; u, v: pos_bias_u / pos_bias_v [8,64]; lens: int64 [B],
+ * utterance b has min(lens[b] * len_mul, T) rows.  For head h, query i, key j:
+ *   s = ((q_i + u_h) . k_j + (q_i + v_h) . p_h[T-1-i+j]) / 8  over keys j < min(L_b, (i / chunk + 1) * chunk)  (chunk = 0: j < L_b),
+ * out[row(b,i), h*64 ..] = softmax_j(s) V; rows L_b <= i < T are written as zeros.  fused = 1: relattn.hip, one launch, online
+ * softmax, nothing quadratic in memory; fused = 0: the three-GEMM sequence jv_prompt_encoder_fwd runs (temporaries allocated and
+ * freed inside the call, which then synchronises). */
+int jv_op_rel_attention(const float* qkv, const float* p, const float* u, const float* v, const int64_t* lens, int B, int T, int G,
+                        int S, int len_mul, int chunk, int fused, float* out, void* stream);
 float jv_h3_scale_for_bound(float bound);   /* host only: the power of two chosen for a proven bound (0 = unusable) */
 int jv_op_conv_h3_measured(const float* A, int64_t a_rows, int M, int Cin, int ntaps, int tap_row0, int dil, const float* W,
                            int N, const float* bias, int act, int prologue, const float* alpha, float slope,

@@ -30,6 +30,14 @@ mel extractor.  Instead this CLI takes their outputs directly:
                              front-ends from the recording's 16 kHz copy: DIR/ref_NNN_fbank.npy (kaldi fbank minus its mean over
                              frames, [T, 80]) and DIR/ref_NNN_logmel.npy (whisper log-mel, [128, T]), NNN the request's number; all
                              requests of a list in one GPU batch per feature (the ONNX sessions themselves are not loaded here)
+    --token2wav list.json    speech tokens -> audio without the text side: CosyVoice2's token-to-mel flow (--flow flow.pt, the
+                             1121-key CausalMaskedDiffWithXvec state-dict) and the vocoder.  A JSON list of requests, each
+                             {"speech_token": [ids], "embedding": [192 floats]} plus optionally "prompt_token": [ids] and either
+                             "prompt_feat": [[80 floats] per frame] or "prompt_wav": "ref.wav" (any rate) / "prompt_wav_24k"; the
+                             list runs as ONE batch through inference(batched=True) and HiFTGenerator.inference and is written
+                             to OUTPUT with _000, _001, ... before the extension.  A prompt mel longer than the request's
+                             2 * tokens frames is trimmed to them.  --streaming: the chunk-causal masks of the encoder and the
+                             estimator (streaming=True of flow.py:300-358).  With --synthetic 1: key-hashed weights.
     --synthetic N            no checkpoint / no tokens: N synthetic tokens, key-hashed weights (smoke / demo)
     --synthetic-prompt K     with --synthetic: also a synthetic K-token voice prompt through the prompt encoder
 
@@ -190,6 +198,91 @@ def synthesise_list(toks, args, tts, hift, device):
         print(f"Generated audio saved to: {path} ({n / args.sample_rate:.2f} seconds)")
 
 
+def token2wav_list(reqs, args, device):
+    """--token2wav: speech tokens (+ voice prompt) -> mel -> wav for a JSON list of requests, as one batch"""
+    import torch
+
+    import jyutvoice_amd
+    from jyutvoice_amd import synth
+    from jyutvoice_amd.flow.flow import CausalMaskedDiffWithXvec, load_flow
+    if not isinstance(reqs, list) or not reqs:
+        raise SystemExit(f"{args.token2wav}: need a non-empty JSON list of requests")
+    B = len(reqs)
+    for b, r in enumerate(reqs):
+        if "speech_token" not in r or "embedding" not in r or len(r["embedding"]) != 192:
+            raise SystemExit(f"{args.token2wav}: request {b}: needs \"speech_token\" and an \"embedding\" of 192 floats")
+    _, hift = jyutvoice_amd.build_default(device)
+    # the flow's decoder takes the slots a JyutVoiceTTS would: a process that already holds one on this device (a caller of main())
+    # gives the flow a runtime of its own
+    from jyutvoice_amd.engine import JV_MODEL_TTS
+    from jyutvoice_amd.runtime import Runtime, get_runtime
+    rt = Runtime(str(device)) if JV_MODEL_TTS in get_runtime(device).sds else None
+    if args.synthetic:
+        flow = CausalMaskedDiffWithXvec(vocab_size=6561, input_frame_rate=25, device=device, runtime=rt)
+        sd = synth.prompt_state_dict()
+        sd.update({k: v for k, v in synth.tts_state_dict().items() if k.startswith(("decoder.", "spk_embed_affine_layer."))})
+        flow.load_state_dict(sd)
+        hift.load_state_dict(synth.hift_state_dict())
+    else:
+        print(f"Loading flow from {args.flow}...")
+        flow = load_flow(args.flow, device, runtime=rt)
+        print(f"Loading HiFT vocoder from {args.hift}...")
+        hift.load_state_dict(torch.load(args.hift, map_location="cpu"))
+    hift = hift.eval().to(device)
+    hift.manual_seed(args.seed)
+
+    def pad_ids(key):
+        lens = torch.tensor([len(r.get(key, [])) for r in reqs], dtype=torch.int64)
+        out = torch.zeros(B, int(lens.max()), dtype=torch.int64)
+        for b, r in enumerate(reqs):
+            out[b, : lens[b]] = torch.tensor(r.get(key, []), dtype=torch.int64)
+        return out, lens
+
+    token, token_len = pad_ids("speech_token")
+    prompt_token, prompt_token_len = pad_ids("prompt_token")
+    embedding = torch.tensor([r["embedding"] for r in reqs], dtype=torch.float32)
+    # prompt mels: given, or extracted from the recordings in one ragged GPU pass (at their own rates)
+    feats = [torch.zeros(0, 80)] * B
+    from_wav = [b for b, r in enumerate(reqs) if "prompt_wav" in r or "prompt_wav_24k" in r]
+    if from_wav:
+        from jyutvoice_amd.utils.audio import extract_speech_feat_batch
+        recs = [read_prompt_wav(reqs[b]) for b in from_wav]
+        mel, mel_len = extract_speech_feat_batch([w for w, _ in recs], device, sample_rates=[r for _, r in recs])
+        for j, b in enumerate(from_wav):
+            feats[b] = mel[j, : int(mel_len[j])].cpu()
+    for b, r in enumerate(reqs):
+        if b not in from_wav and "prompt_feat" in r:
+            feats[b] = torch.tensor(r["prompt_feat"], dtype=torch.float32).view(-1, 80)
+        limit = 2 * int(prompt_token_len[b] + token_len[b])
+        if feats[b].shape[0] > limit:
+            print(f"request {b}: the prompt mel has {feats[b].shape[0]} frames, the utterance {limit}: trimmed")
+            feats[b] = feats[b][:limit]
+    feat_len = torch.tensor([f.shape[0] for f in feats], dtype=torch.int32)
+    prompt_feat = torch.zeros(B, int(feat_len.max()), 80)
+    for b, f in enumerate(feats):
+        prompt_feat[b, : f.shape[0]] = f
+
+    print(f"Running token-to-mel of {B} requests as one batch" + (" (streaming masks)" if args.streaming else "") + "...")
+    start = time.time()
+    try:
+        mel, _ = flow.inference(token, token_len, prompt_token, prompt_token_len, prompt_feat, feat_len, embedding, args.streaming,
+                                True, batched=True, n_timesteps=args.n_timesteps)
+    except ValueError as e:
+        raise SystemExit(f"{args.token2wav}: {e}")
+    wav, _ = hift.inference(mel, lengths=flow.mel_lengths)
+    torch.cuda.synchronize()
+    print(f"Synthesis time: {time.time() - start:.2f} s")
+    samples = flow.mel_lengths.to(torch.int64) * 480
+    if args.sample_rate != 24000:
+        from jyutvoice_amd.utils.audio import resample
+        wav, samples = resample(wav, 24000, args.sample_rate, lengths=samples)
+    stem, ext = os.path.splitext(args.output)
+    for b, n in enumerate(samples.tolist()):
+        path = f"{stem}_{b:03d}{ext}"
+        write_wav(path, wav[b, :n], args.sample_rate)
+        print(f"Generated audio saved to: {path} ({n / args.sample_rate:.2f} seconds)")
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="JyutVoice TTS inference on MI355X (jyutvoice_amd)")
     p.add_argument("--text", default=None, help="Text to synthesize (needs the reference's G2P front-end; see --tokens)")
@@ -206,6 +299,10 @@ def main(argv=None):
     p.add_argument("--n_timesteps", type=int, default=10, help="Number of diffusion timesteps")
     p.add_argument("--length_scale", type=float, default=0.9, help="Length scale for speech duration control")
     p.add_argument("--tokens", default=None, help="JSON with the five id lists (and optionally spk_embed)")
+    p.add_argument("--token2wav", default=None, metavar="LIST.json",
+                   help="JSON list of {speech_token, embedding[, prompt_token, prompt_feat | prompt_wav]}: token-to-mel flow + vocoder")
+    p.add_argument("--flow", default="pretrained_models/flow.pt", help="Path to the CosyVoice2 flow weights (--token2wav)")
+    p.add_argument("--streaming", action="store_true", help="--token2wav: chunk-causal masks in the flow encoder and the estimator")
     p.add_argument("--synthetic", type=int, default=0, help="use N synthetic tokens and synthetic weights")
     p.add_argument("--synthetic-prompt", type=int, default=0, help="with --synthetic: K synthetic prompt tokens (voice-cloning path)")
     p.add_argument("--seed", type=int, default=0, help="seed of the vocoder's source-noise draws")
@@ -229,6 +326,8 @@ def main(argv=None):
         raise SystemExit("no AMD GPU visible: jyutvoice_amd has no CPU path")
     device = torch.device("cuda:0")
     print(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
+    if args.token2wav:
+        return token2wav_list(json.load(open(args.token2wav)), args, device)
     tts, hift = jyutvoice_amd.build_default(device)
 
     prompt_feat = prompt_h = None

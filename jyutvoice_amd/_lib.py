@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("JYUTVOICE_HIP_LIB") or os.path.join(HERE, "libjyutvoi
 JV_MODEL_TTS = 0
 JV_MODEL_HIFT = 1
 JV_MODEL_PROMPT = 2
+JV_MODEL_FLOW = 3      # the decoder.* / spk_embed_affine_layer.* part of JV_MODEL_TTS (jv_finalize only)
 
 ACT = {"none": 0, "relu": 1, "gelu": 2, "mish": 3, "elu": 4, "silu": 5}
 PRO = {"none": 0, "snake": 1, "lrelu": 2}
@@ -55,6 +56,8 @@ SIGNATURES = {
     "jv_flow_contraction_info": (_i, [_p, _p, _i]),
     "jv_cfm_solve": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p]),
     "jv_cfm_solve_prompted": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p]),
+    "jv_flow_encoder_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "jv_flow_token2mel": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "jv_encoder_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "jv_load_mel_basis": (_i, [_p, _p, _i64, _i, _p]),
     "jv_mel_spectrogram": (_i, [_p, _p, _i, _i, _p, _p]),
@@ -82,6 +85,7 @@ SIGNATURES = {
     "jv_hift_decode": (_i, [_p, _p, _p, _p, _i, _i, _p, _p]),
     "jv_op_conv_gemm": (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _p, _p, _f, _p, _p, _p, _p]),
     "jv_op_attention": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
+    "jv_op_rel_attention": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "jv_h3_scale_for_bound": (_f, [_f]),
     "jv_op_conv_h3_measured": (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _p, _p, _p, _f, _p, _p, _p]),
     "jv_op_attention_h3": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _f, _p, _p]),

@@ -138,6 +138,10 @@ struct OpW {
 };
 }  // namespace
 
+namespace jv {
+int zero_rows_behind(float* att, const long* len, int len_mul, int B, int T, int G, int S, hipStream_t st);   // promptops.hip
+}
+
 extern "C" {
 
 const char* jv_last_error(void) { return jv::g_last_error.c_str(); }
@@ -270,7 +274,8 @@ int jv_load_tensor(jv_context* ctx, const char* name, const float* data, const i
     for (int d = 0; d < ndim; ++d) got += std::to_string(shape[d]) + ",";
     return jv::fail(JV_ERR_SHAPE, std::string("size mismatch for ") + name + ": expected [" + want + "] got [" + got + "]");
   }
-  if (c.ready[t.model]) return jv::fail(JV_ERR_STATE, "model already finalized; create a new context to reload");
+  if (c.ready[t.model] || (t.model == jv::MODEL_TTS && c.ready[jv::MODEL_FLOW] && jv::flow_part(t.name)))
+    return jv::fail(JV_ERR_STATE, "model already finalized; create a new context to reload");
   if (!t.dev) JV_TRY(c.raw_arena.alloc((size_t)t.numel, &t.dev));
   hipStream_t st = static_cast<hipStream_t>(stream);
   JV_HIP(hipMemcpyAsync(t.dev, data, sizeof(float) * t.numel, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
@@ -293,10 +298,10 @@ int jv_load_noise(jv_context* ctx, const float* data, int64_t numel, int on_devi
 
 int jv_finalize(jv_context* ctx, int model, void* stream) {
   CTX_GUARD(ctx);
-  if (model != JV_MODEL_TTS && model != JV_MODEL_HIFT && model != JV_MODEL_PROMPT)
+  if (model != JV_MODEL_TTS && model != JV_MODEL_HIFT && model != JV_MODEL_PROMPT && model != JV_MODEL_FLOW)
     return jv::fail(JV_ERR_ARG, "jv_finalize: unknown model id");
   if (ctx->c.ready[model]) return JV_OK;
-  if (model == JV_MODEL_TTS) jv::flow_graphs_drop(ctx->c);
+  if (model == JV_MODEL_TTS || model == JV_MODEL_FLOW) jv::flow_graphs_drop(ctx->c);
   return jv::finalize_model(ctx->c, model, static_cast<hipStream_t>(stream));
 }
 
@@ -347,7 +352,7 @@ int jv_flow_set_contraction(jv_context* ctx, int exact_range) {
 
 int jv_flow_contraction_info(const jv_context* ctx, int32_t* out, int n) {
   if (!ctx || !out || n < 4) return jv::fail(JV_ERR_ARG, "jv_flow_contraction_info: null argument or fewer than 4 slots");
-  if (!ctx->c.ready[jv::MODEL_TTS]) return jv::fail(JV_ERR_STATE, "tts weights not finalized");
+  if (!ctx->c.ready[jv::MODEL_FLOW]) return jv::fail(JV_ERR_STATE, "tts weights not finalized");
   int blocks = 0, all = 0, lin = 0, att = 0;
   for (int i = 0; i < jv::EST_NRES; ++i)
     for (int j = 0; j < jv::EST_NBLK; ++j) {
@@ -447,6 +452,52 @@ int jv_op_attention(const float* qkv, const int32_t* lens, int B, int G, int S, 
   at.qkv = qkv; at.ld = 1536; at.k_off = 512; at.v_off = 1024; at.out = out; at.ldo = 512;
   at.B = B; at.H = 8; at.G = G; at.S = S; at.L = L; at.lens = lens; at.chunk = 0;
   return jv::attention64(at, static_cast<hipStream_t>(stream));
+}
+
+// The conformer block's relative-position attention on caller-supplied buffers: relattn.hip's one launch (fused) or the block's
+// three-GEMM sequence (prompt.hip rel_attention_gemm) with temporaries of this call (test hook)
+int jv_op_rel_attention(const float* qkv, const float* p, const float* u, const float* v, const int64_t* lens, int B, int T, int G,
+                        int S, int len_mul, int chunk, int fused, float* out, void* stream) {
+  if (!qkv || !p || !u || !v || !lens || !out) return jv::fail(JV_ERR_ARG, "jv_op_rel_attention: null argument");
+  if (B < 1 || T < 1 || G < 0 || S < T || len_mul < 1 || chunk < 0) return jv::fail(JV_ERR_ARG, "jv_op_rel_attention: bad geometry");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long* len = reinterpret_cast<const long*>(lens);
+  if (fused) return jv::rel_attention(qkv, p, 2L * T - 1, u, v, len, len_mul, B, T, G, S, chunk, out, st);
+  static bool inited = false;
+  if (!inited) {
+    JV_TRY(jv::conv_gemm_init());
+    inited = true;
+  }
+  const size_t rows = (size_t)G + (size_t)B * S, ld = (size_t)jv::round_up(T, 32), ldb = (size_t)jv::round_up(2 * T - 1, 32);
+  const size_t n_q = rows * 512, n_ac = (size_t)B * 8 * T * ld, n_bd = (size_t)B * 8 * T * ldb, n_vt = (size_t)B * 8 * 64 * ld,
+               n_p = (ldb + 128) * 512;      // (p with the zero rows behind 2T - 1 that the encoder's workspace has)
+  float* tmp = nullptr;
+  JV_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(float) * (2 * n_q + n_ac + n_bd + n_vt + n_p)));
+  float *qu = tmp, *qv = qu + n_q, *ac = qv + n_q, *bd = ac + n_ac, *vt = bd + n_bd, *pp = vt + n_vt;
+  int rc = JV_OK;
+  if (hipMemsetAsync(tmp, 0, sizeof(float) * (2 * n_q + n_ac + n_bd + n_vt + n_p), st) != hipSuccess ||
+      hipMemcpyAsync(pp, p, sizeof(float) * (2 * (size_t)T - 1) * 512, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    rc = jv::fail(JV_ERR_HIP, "jv_op_rel_attention: staging failed");
+  if (rc == JV_OK) rc = jv::rel_attention_gemm(qkv, pp, u, v, qu, qv, ac, bd, vt, out, len, len_mul, B, T, G, S, chunk, st);
+  if (rc == JV_OK) rc = jv::zero_rows_behind(out, len, len_mul, B, T, G, S, st);
+  const hipError_t se = hipStreamSynchronize(st);
+  (void)hipFree(tmp);
+  if (rc == JV_OK && se != hipSuccess) rc = jv::fail(JV_ERR_HIP, std::string("jv_op_rel_attention: ") + hipGetErrorString(se));
+  return rc;
+}
+
+int jv_flow_token2mel(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                      const int64_t* token_lens, const float* prompt_feat, const int32_t* feat_lens, const float* embedding, int B,
+                      int P, int N, int F, int streaming, int n_timesteps, float temperature, const float* t_span_host, float* mel,
+                      int32_t* mel_lens, void* stream) {
+  CTX_GUARD(ctx);
+  if (!token_lens || !feat_lens || !embedding || !mel || (N > 0 && !tokens) || (P > 0 && (!prompt_tokens || !prompt_lens)) ||
+      (F > 0 && !prompt_feat))
+    return jv::fail(JV_ERR_ARG, "jv_flow_token2mel: null tensor");
+  return jv::flow_token2mel(ctx->c, reinterpret_cast<const long*>(prompt_tokens), reinterpret_cast<const long*>(prompt_lens),
+                            reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_lens), prompt_feat, feat_lens,
+                            embedding, B, P, N, F, streaming, n_timesteps, temperature, t_span_host, mel, mel_lens,
+                            static_cast<hipStream_t>(stream));
 }
 
 // conv_gemm through the fp16x3 main loop with a MEASURED bound: amax_in = device float >= max |A| (e.g. the amax_out of

@@ -98,10 +98,23 @@ ConvGemmArgs gemm_args(const float* A, int lda, long a_rows, long M, const GemmW
 
 }  // namespace
 
+// Linear(192 -> 80)(F.normalize(spk)): the speaker vector of the flow decoder (jyutvoice_tts.py:175-176, flow/flow.py:315-316)
+int speaker_projection(Context& c, const float* spk, int B, float* spks_out, hipStream_t st) {
+  if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "flow decoder weights not finalized (spk_embed_affine_layer)");
+  if (B < 1 || B > c.max_batch) return fail(JV_ERR_SHAPE, "batch exceeds the capacity given to jv_create");
+  EncWs& w = *c.ews;
+  JV_TRY(l2_normalize(spk, w.spkn, B, 192, st));
+  ConvGemmArgs a = gemm_args(w.spkn, 192, B, B, c.enc.spk_affine, spks_out, 80);
+  return conv_gemm(a, 1, st);
+}
+
 int encoder_fwd(Context& c, const long* phone, const long* lang, const long* tone, const long* wpos, const long* spos,
                 const long* xlen, const float* spk, int B, int Tt, float* x_out, float* mu_out, float* logw_out,
                 float* spks_out, hipStream_t st) {
-  if (!c.ready[MODEL_TTS]) return fail(JV_ERR_STATE, "tts weights not finalized");
+  if (!c.ready[MODEL_TTS])
+    return fail(JV_ERR_STATE, c.ready[MODEL_FLOW] ? "tts weights not finalized: this context holds the flow decoder only (JV_MODEL_FLOW); "
+                                                    "the text encoder (encoder.*) and the duration predictor (dp.*) are missing"
+                                                  : "tts weights not finalized");
   if (B < 1 || Tt < 1) return fail(JV_ERR_ARG, "batch and token count must be positive");
   if (B > c.max_batch || Tt > c.max_tokens || Tt > 512)
     return fail(JV_ERR_SHAPE, "batch/tokens exceed the capacity given to jv_create (and the 512-token attention limit)");
@@ -115,11 +128,7 @@ int encoder_fwd(Context& c, const long* phone, const long* lang, const long* ton
   JV_TRY(row_meta(w.mask, nullptr, w.lens, B, 1, E_G, S, Tt, AR, 1, 0, st));
 
   // speaker projection for the flow decoder: Linear(192->80)(normalize(spk))  (jyutvoice_tts.py:175-176)
-  JV_TRY(l2_normalize(spk, w.spkn, B, 192, st));
-  {
-    ConvGemmArgs a = gemm_args(w.spkn, 192, B, B, e.spk_affine, spks_out, 80);
-    JV_TRY(conv_gemm(a, 1, st));
-  }
+  JV_TRY(speaker_projection(c, spk, B, spks_out, st));
 
   // embeddings -> prenet (3 x conv k5 + channel-LN(eps 1e-4) + ReLU, 1x1 proj, residual, mask)
   JV_TRY(embed_sum(phone, tone, wpos, spos, e.emb, e.tone_emb, e.wpos_emb, e.spos_emb, w.e0, B, Tt, E_G, S, st));

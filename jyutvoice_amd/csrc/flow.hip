@@ -55,6 +55,8 @@ int flow_ws_create(Context& c) {
   JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->h_lens), (size_t)B2 * sizeof(int), hipHostMallocDefault));
   JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->h_uoff), (size_t)(B2 + 1) * sizeof(int), hipHostMallocDefault));
   JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->h_sum), (size_t)B2 * sizeof(int), hipHostMallocDefault));
+  JV_TRY(ws_alloc(c, (size_t)B2 * sizeof(int), reinterpret_cast<void**>(&w->t2m_lens)));
+  JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->h_y), (size_t)B2 * sizeof(int), hipHostMallocDefault));
   JV_TRY(ws_alloc(c, sizeof(int), reinterpret_cast<void**>(&w->step_ctr)));
   JV_TRY(F(&w->t_cur, 1));
   JV_TRY(F(&w->dt_cur, 1));
@@ -102,7 +104,7 @@ __global__ void step_advance_kernel(const float* __restrict__ t_table, const flo
 bool flow_compact_ok(const Context& c, long M) { return est_route(c, M, false, true, c.attn_chunk).compact_ok; }
 
 int check_shape(Context& c, int B2, int T) {
-  if (!c.ready[MODEL_TTS]) return fail(JV_ERR_STATE, "tts weights not finalized");
+  if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "tts weights not finalized");
   if (B2 < 1 || T < 1) return fail(JV_ERR_ARG, "batch and frame count must be positive");
   if (B2 > 2 * c.max_batch || T > c.max_frames || flow_rows(B2, T) + 128 > c.flow->rows_alloc)
     return fail(JV_ERR_SHAPE, "batch/frames exceed the capacity given to jv_create");
@@ -317,7 +319,7 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
 int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const float* prompt_h, const float* prompt_feat,
                        const int* prompt_lens, const float* spks, int B, int Ty, int Ph, int Pf, int n_timesteps,
                        float temperature, const float* t_span_host, float* mel, hipStream_t st) {
-  if (!c.ready[MODEL_TTS]) return fail(JV_ERR_STATE, "tts weights not finalized");
+  if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "tts weights not finalized");
   if (B < 1 || Ty < 1 || Ph < 0 || Pf < 0) return fail(JV_ERR_ARG, "jv_cfm_solve_prompted: B, Ty must be positive, Ph, Pf non-negative");
   if (B > c.max_batch) return fail(JV_ERR_SHAPE, "batch/frames exceed the capacity given to jv_create");
   if (!c.noise_loaded) return fail(JV_ERR_STATE, "CFM noise tensor not loaded (jv_load_noise)");
@@ -368,6 +370,77 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
   return rows_to_cf_from(w.x, 80, FLOW_G, g.S, prompt_lens, y_lens, mel, 80L * Ty, B, 80, Ty, st, g.uoff);
 }
 
+constexpr int T2M_EST_CHUNK = 50;      // the estimator's static_chunk_size in frames (configs/base.yaml:98; decoder.py:951-954)
+
+// Token-to-mel (flow/flow.py:314-358 looped over the utterances): the flow encoder's h over [prompt tokens | tokens] is mu for the
+// whole sequence of T_b = 2 (p_b + n_b) frames, cond = [prompt_feat_b[:f_b] | 0], and frames f_b .. T_b - 1 come back.  The same
+// schedule, geometry rule, Euler loop, pack and unpack kernels as cfm_solve_prompted: in its terms every frame is a "prompt" frame
+// of mu (Ty = 0) and the condition prefix has a length of its own.
+int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const float* prompt_feat,
+                   const int* feat_lens, const float* embedding, int B, int P, int N, int F, int streaming, int n_timesteps,
+                   float temperature, const float* t_span_host, float* mel, int* mel_lens, hipStream_t st) {
+  if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "flow decoder weights not finalized (JV_MODEL_FLOW or JV_MODEL_TTS)");
+  if (!c.ready[MODEL_PROMPT]) return fail(JV_ERR_STATE, "prompt encoder weights not finalized");
+  if (B < 1 || P < 0 || N < 0 || P + N < 1 || F < 0) return fail(JV_ERR_ARG, "jv_flow_token2mel: B, P + N must be positive, P, N, F non-negative");
+  if (B > c.max_batch) return fail(JV_ERR_SHAPE, "batch/frames exceed the capacity given to jv_create");
+  if (!c.noise_loaded) return fail(JV_ERR_STATE, "CFM noise tensor not loaded (jv_load_noise)");
+  FlowWs& w = *c.flow;
+  if (n_timesteps < 1 || n_timesteps > w.max_steps) return fail(JV_ERR_ARG, "n_timesteps out of range");
+  if (reinterpret_cast<uintptr_t>(prompt_feat) & 15) return fail(JV_ERR_ARG, "jv_flow_token2mel: prompt_feat must be 16-byte aligned");
+  const int B2 = 2 * B, Tm = 2 * (P + N);
+  JV_TRY(check_shape(c, B2, Tm));
+  if (Tm > NOISE_FRAMES) return fail(JV_ERR_SHAPE, "more frames than the fixed noise tensor holds (15000)");
+
+  // h [B, Tm, 80] and the projected speaker vectors wait in buffers the estimator writes only once the loop runs: w.d (its
+  // output, rows_alloc * 80 floats >= B * Tm * 80) and w.tsin ([2B, 320]); solve_loop copies the vectors to w.spks first
+  float* const h = w.d;
+  float* const spks = w.tsin;
+  int* const hl = w.t2m_lens;
+  int* const yl = w.t2m_lens + c.max_batch;
+  JV_TRY(flow_encoder_fwd(c, ptok, plen, tok, len, B, P, N, streaming, h, hl, st));
+  JV_TRY(speaker_projection(c, embedding, B, spks, st));
+
+  std::vector<float> tt, dts;
+  JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
+  JV_HIP(hipMemcpyAsync(w.h_lens, hl, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  JV_HIP(hipMemcpyAsync(w.h_lens + B, feat_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  JV_HIP(hipStreamSynchronize(st));
+  int T = 0;
+  for (int b = 0; b < B; ++b) {
+    const int tb = w.h_lens[b], f = w.h_lens[B + b];
+    if (f < 0 || f > std::min(F, tb)) {
+      char msg[200];
+      snprintf(msg, sizeof msg, "jv_flow_token2mel: utterance %d: prompt_feat length %d outside [0, min(F = %d, 2 * tokens = %d)]", b, f, F, tb);
+      return fail(JV_ERR_ARG, msg);
+    }
+    w.h_sum[b] = w.h_sum[B + b] = tb;
+    w.h_y[b] = tb - f;
+    T = std::max(T, tb);
+  }
+  if (T < 1) {      // every utterance empty: nothing to solve
+    JV_HIP(hipMemsetAsync(mel, 0, sizeof(float) * 80 * (size_t)B * Tm, st));
+    if (mel_lens) JV_HIP(hipMemsetAsync(mel_lens, 0, sizeof(int) * B, st));
+    return JV_OK;
+  }
+  Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, nullptr, 0};
+  if (B > 1 && flow_compact_ok(c, g.M)) JV_TRY(solve_compact(c, g, w.h_sum, B, T, st));
+
+  JV_HIP(hipMemcpyAsync(w.lens2, w.h_sum, sizeof(int) * B2, hipMemcpyHostToDevice, st));      // (pinned: stays valid)
+  JV_HIP(hipMemcpyAsync(yl, w.h_y, sizeof(int) * B, hipMemcpyHostToDevice, st));
+  const int* const clens = g.uoff ? w.lens2 : nullptr;
+  JV_TRY(row_meta(w.rowmask, w.row_sample, w.lens2, B2, 1, FLOW_G, g.S, T, w.rows_alloc, 1, 0, st, g.uoff));
+  JV_TRY(pack_prompted(nullptr, 0, h, Tm, prompt_feat, F, hl, w.lens2, B, T, w.mu, w.cond, FLOW_G, g.S, st, g.uoff, feat_lens));
+  JV_TRY(cf_to_rows(c.noise, 0, NOISE_FRAMES, B, 80, T, w.x, 80, 0, FLOW_G, g.S, temperature, clens, st, g.uoff));
+
+  const int chunk_was = c.attn_chunk;
+  c.attn_chunk = streaming ? T2M_EST_CHUNK : 0;
+  const int rc = solve_loop(c, g, spks, B, T, n_timesteps, st);
+  c.attn_chunk = chunk_was;
+  JV_TRY(rc);
+  if (mel_lens) JV_HIP(hipMemcpyAsync(mel_lens, yl, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
+  return rows_to_cf_from(w.x, 80, FLOW_G, g.S, feat_lens, yl, mel, 80L * Tm, B, 80, Tm, st, g.uoff);
+}
+
 void flow_ws_destroy(Context& c) {
   if (c.flow) {
     flow_graphs_drop(c);
@@ -377,6 +450,7 @@ void flow_ws_destroy(Context& c) {
     if (c.flow->h_lens) (void)hipHostFree(c.flow->h_lens);
     if (c.flow->h_uoff) (void)hipHostFree(c.flow->h_uoff);
     if (c.flow->h_sum) (void)hipHostFree(c.flow->h_sum);
+    if (c.flow->h_y) (void)hipHostFree(c.flow->h_y);
   }
   delete c.flow;
   c.flow = nullptr;

@@ -21,7 +21,9 @@ constexpr int HIFT_CH = 512, HIFT_F0_CH = 512, HIFT_NFFT = 16, HIFT_HOP = 4, HIF
 
 constexpr int PR_DIM = 512, PR_HEADS = 8, PR_FFN = 2048, PR_BLOCKS = 6, PR_UP_BLOCKS = 4, PR_VOCAB = 6561;
 
-enum Model : int { MODEL_TTS = 0, MODEL_HIFT = 1, MODEL_PROMPT = 2 };
+enum Model : int { MODEL_TTS = 0, MODEL_HIFT = 1, MODEL_PROMPT = 2, MODEL_FLOW = 3 };   // MODEL_FLOW: the decoder.* / spk_embed_affine_layer.* part of MODEL_TTS
+// is a tensor of MODEL_TTS part of MODEL_FLOW (what a flow.pt holds besides its encoder)?
+inline bool flow_part(const std::string& name) { return name.rfind("decoder.", 0) == 0 || name.rfind("spk_embed_affine_layer.", 0) == 0; }
 
 struct RawTensor {
   std::string name;
@@ -148,7 +150,7 @@ struct Context {
   std::vector<RawTensor> raw;
   std::unordered_map<std::string, int> index;
   Arena raw_arena, packed;
-  bool ready[3] = {false, false, false};
+  bool ready[4] = {false, false, false, false};
   bool broken = false;           // jv_reserve failed and could not restore the old workspace: every entry point returns JV_ERR_STATE
   EstimatorW est;
   EncoderW enc;
@@ -206,8 +208,23 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
                        const int* prompt_lens, const float* spks, int B, int Ty, int Ph, int Pf, int n_timesteps,
                        float temperature, const float* t_span_host, float* mel, hipStream_t st);
 
+int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const float* prompt_feat,
+                   const int* feat_lens, const float* embedding, int B, int P, int N, int F, int streaming, int n_timesteps,
+                   float temperature, const float* t_span_host, float* mel, int* mel_lens, hipStream_t st);
+
+// encoder.hip: Linear(192 -> 80)(F.normalize(spk)) (jyutvoice_tts.py:175-176, flow.py:315-316)
+int speaker_projection(Context& c, const float* spk, int B, float* spks_out, hipStream_t st);
+
 // prompt.hip
 int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int Tk, float* h_out, hipStream_t st);
+int flow_encoder_fwd(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, int B, int P, int N,
+                     int streaming, float* h_out, int* h_lens, hipStream_t st);
+// the three-GEMM relative-position attention of a conformer block on explicit buffers (prompt.hip); chunk as rel_attention
+int rel_attention_gemm(const float* qkv, const float* p, const float* u, const float* v, float* qu, float* qv, float* ac, float* bd,
+                       float* vt, float* att, const long* len, int len_mul, int B, int T, int G, int S, int chunk, hipStream_t st);
+// relattn.hip: the same attention in one launch (online softmax, no [T, T] buffer); p_rows = rows of p that may be read
+int rel_attention(const float* qkv, const float* p, long p_rows, const float* u, const float* v, const long* len, int len_mul, int B,
+                  int T, int G, int S, int chunk, float* att, hipStream_t st);
 void prompt_ws_destroy(Context& c);
 
 // audio.hip

@@ -16,9 +16,12 @@ int cf_to_rows(const float* src, long src_bstride, long pitch, int B, int C, int
 int rows_to_cf(const float* src, int ld, int col0, int G, int S, float* dst, long dst_bstride, int B, int C, int T,
                const int* lens, hipStream_t st, const int* uoff = nullptr);
 // cfm_solve_prompted's pack and unpack (rowops.hip): row-layout mu / cond of [prompt_b | text_b] sequences in one launch; the
-// generated frames first[b] .. first[b] + lens[b] - 1 back to channels-first, zero-filled to T
+// generated frames first[b] .. first[b] + lens[b] - 1 back to channels-first, zero-filled to T.  clens (optional): the condition
+// prefix has a length of its own, cond = [prompt_feat_b[:clens[b]] | 0] while mu = [prompt_h[b, :plens[b]] | mu_y] (token-to-mel:
+// all of mu comes from the flow encoder, plens = sums, Ty = 0); null: clens = plens
 int pack_prompted(const float* mu_y, int Ty, const float* prompt_h, int Ph, const float* prompt_feat, int Pf, const int* plens,
-                  const int* sums, int B, int T, float* mu, float* cond, int G, int S, hipStream_t st, const int* uoff = nullptr);
+                  const int* sums, int B, int T, float* mu, float* cond, int G, int S, hipStream_t st, const int* uoff = nullptr,
+                  const int* clens = nullptr);
 int rows_to_cf_from(const float* src, int ld, int G, int S, const int* first, const int* lens, float* dst, long dst_bstride,
                     int B, int C, int T, hipStream_t st, const int* uoff = nullptr);
 int assemble_xin(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int G, int S,

@@ -9,6 +9,10 @@
 // synthesis, so no dedicated attention kernel is tuned for it (same choice as the text encoder, encoder.hip).
 // Batches are per-utterance loops of the B = 1 reference: rows at and beyond an utterance's length are zero for the
 // look-ahead / upsampling convolutions (select-zero row mask) and masked as attention keys.
+//
+// The same two stages serve CausalMaskedDiffWithXvec.inference (flow/flow.py:300-358, flow_encoder_fwd below), where the encoder
+// runs over the WHOLE utterance [prompt tokens | tokens] in the text encoder's place: there the attention is relattn.hip's single
+// launch (no [T, T] buffer in that route's workspace) and `streaming` sets the chunk masks of upsample_encoder.py:338-367.
 #include <math.h>
 
 #include "../../include/jyutvoice_hip.h"
@@ -17,22 +21,27 @@
 
 namespace jv {
 
-int prompt_embed(const long* tok, const long* len, const float* emb, float* rows, int B, int T, int G, int S, int vocab,
-                 hipStream_t st);
+int prompt_embed(const long* ptok, const long* plen, int P, const long* tok, const long* len, int N, const float* emb, float* rows,
+                 int B, int G, int S, int vocab, hipStream_t st);
+int sum_lens(const long* plen, int P, const long* len, int N, int B, long* sum, int* out32, int mul, hipStream_t st);
 int rel_pos_table(float* pe, const float* div, int T, hipStream_t st);
 int add_pos_bias(const float* qkv, const float* u, const float* v, float* qu, float* qv, long rows, hipStream_t st);
-int rel_softmax(float* ac, const float* bd, const long* len, int len_mul, int B, int H, int T, int ld, int ldb, hipStream_t st);
+int rel_softmax(float* ac, const float* bd, const long* len, int len_mul, int B, int H, int T, int ld, int ldb, int chunk,
+                hipStream_t st);
 int prompt_transpose_v(const float* qkv, float* vt, int B, int T, int ld, int G, int S, hipStream_t st);
 int repeat_rows2(const float* src, float* dst, int B, int T, int G, int S, int G2, int S2, hipStream_t st);
 int rows_to_btc(const float* rows, const long* len, int len_mul, float* out, int B, int T, int C, int G, int S, hipStream_t st);
 int lens_to_i32(const long* a, int* o, int n, int cap, hipStream_t st);   // encops.hip
 
 constexpr int P_G = 8, P_GAP = 8;   // guard rows >= the widest context (look-ahead 3, causal 2, upsampling conv 4)
+constexpr int PR_CHUNK = 25;        // static_chunk_size of the encoder in tokens (configs: 25; x up-sampling stride 2 in stage 2)
 
 // Sized on first use for the (B, Tk) asked for and regrown when a larger call arrives: prompts are short and rare next to
 // synthesis, so this memory is not reserved at jv_create.
 struct PromptWs {
   int B = 0, Tk = 0;
+  bool quad = false;      // holds the three-GEMM attention's buffers (qu, qv, ac, bd, vt); the fused route needs none of them
+  long* lens64 = nullptr;   // [B] p_b + n_b of the token-to-mel route
   long rows = 0;
   std::vector<void*> allocs;
   float *x = nullptr, *y = nullptr, *ln = nullptr, *qu = nullptr, *qv = nullptr, *att = nullptr;   // [rows,512]
@@ -54,15 +63,16 @@ void prompt_ws_destroy(Context& c) {
 
 namespace {
 
-int ensure_ws(Context& c, int B, int Tk) {
-  if (c.pws && c.pws->B >= B && c.pws->Tk >= Tk) return JV_OK;
+int ensure_ws(Context& c, int B, int Tk, bool quad) {
+  if (c.pws && c.pws->B >= B && c.pws->Tk >= Tk && (c.pws->quad || !quad)) return JV_OK;
+  quad = quad || (c.pws && c.pws->quad);
   const int nb = c.pws ? (B > c.pws->B ? B : c.pws->B) : B;
   const int nt = c.pws ? (Tk > c.pws->Tk ? Tk : c.pws->Tk) : Tk;
   JV_HIP(hipDeviceSynchronize());     // nothing may still be using the buffers about to be freed
   prompt_ws_destroy(c);
   PromptWs* w = new PromptWs();
   c.pws = w;
-  w->B = nb; w->Tk = nt;
+  w->B = nb; w->Tk = nt; w->quad = quad;
   const int T2 = 2 * nt;
   w->rows = round_up(P_G + nb * (T2 + P_GAP), 128) + 256;
   const size_t R = (size_t)w->rows;
@@ -77,17 +87,18 @@ int ensure_ws(Context& c, int B, int Tk) {
   JV_TRY(F(&w->x, R * 512));
   JV_TRY(F(&w->y, R * 512));
   JV_TRY(F(&w->ln, R * 512));
-  JV_TRY(F(&w->qu, R * 512));
-  JV_TRY(F(&w->qv, R * 512));
+  if (quad) JV_TRY(F(&w->qu, R * 512));
+  if (quad) JV_TRY(F(&w->qv, R * 512));
   JV_TRY(F(&w->att, R * 512));
   JV_TRY(F(&w->qkv, R * 1536));
   JV_TRY(F(&w->ffn, R * 2048));
   JV_TRY(F(&w->o80, R * 80));
   JV_TRY(F(&w->pe, (size_t)ldb * 512));
   JV_TRY(F(&w->p, (size_t)(ldb + 128) * 512));
-  JV_TRY(F(&w->ac, (size_t)nb * 8 * T2 * ld));
-  JV_TRY(F(&w->bd, (size_t)nb * 8 * T2 * ldb));
-  JV_TRY(F(&w->vt, (size_t)nb * 8 * 64 * ld));
+  if (quad) JV_TRY(F(&w->ac, (size_t)nb * 8 * T2 * ld));
+  if (quad) JV_TRY(F(&w->bd, (size_t)nb * 8 * T2 * ldb));
+  if (quad) JV_TRY(F(&w->vt, (size_t)nb * 8 * 64 * ld));
+  JV_TRY(A(reinterpret_cast<void**>(&w->lens64), sizeof(long) * nb));
   JV_TRY(A(reinterpret_cast<void**>(&w->mask1), R));
   JV_TRY(A(reinterpret_cast<void**>(&w->mask2), R));
   JV_TRY(A(reinterpret_cast<void**>(&w->lens_i), sizeof(int) * nb));
@@ -105,44 +116,61 @@ ConvGemmArgs lin_args(const float* A, int lda, long a_rows, long M, const GemmW&
   return a;
 }
 
-// one pre-LN block on T rows per utterance (geometry G, S): x += MHA_rel(LN(x)); x += W2 silu(W1 LN(x))
-int conformer_block(Context& c, const ConfBlockW& k, int B, int T, int G, int S, long M, const long* len, int len_mul,
-                    hipStream_t st) {
-  PromptWs& w = *c.pws;
-  const long AR = w.rows;
+}  // namespace
+
+// The block's attention as three batched GEMMs around the rel-shift softmax, on explicit buffers (the conformer block's own
+// workspace, or jv_op_rel_attention's): qu, qv [rows, 512]; ac [B,8,T,ld], bd [B,8,T,ldb], vt [B,8,64,ld], ld = round_up(T, 32),
+// ldb = round_up(2T - 1, 32); p must be readable for round_up(2T - 1, 64) rows (the GEMM's weight-tile loads).
+int rel_attention_gemm(const float* qkv, const float* p, const float* u, const float* v, float* qu, float* qv, float* ac, float* bd,
+                       float* vt, float* att, const long* len, int len_mul, int B, int T, int G, int S, int chunk, hipStream_t st) {
   const int ld = round_up(T, 32), npos = 2 * T - 1, ldb = round_up(npos, 32);
-  JV_TRY(layernorm_rows(w.x, nullptr, w.ln, k.n_mha.g, k.n_mha.b, 1e-5f, M, 512, nullptr, st));
-  ConvGemmArgs a = lin_args(w.ln, 512, AR, M, k.qkv, w.qkv, 1536);
-  JV_TRY(conv_gemm(a, 1, st));
-  a = lin_args(w.pe, 512, npos, npos, k.pos, w.p, 512);                       // p = linear_pos(pos_emb), shared by the batch
-  JV_TRY(conv_gemm(a, 1, st));
-  JV_TRY(add_pos_bias(w.qkv, k.u, k.v, w.qu, w.qv, M, st));
+  const long M = (long)G + (long)B * S;
+  ConvGemmArgs a;
+  JV_TRY(add_pos_bias(qkv, u, v, qu, qv, M, st));
   // ac[b,h] = (q + u) K^T : the K rows are the K-contiguous "weight" operand
   conv_gemm_defaults(a);
-  a.A = w.qu + (long)G * 512; a.lda = 512; a.a_rows = T; a.M = T; a.Cin = 64; a.ntaps = 1;
-  a.W = w.qkv + (long)G * 1536 + 512; a.ldw = 1536; a.n_rows_w = T; a.N = T;
-  a.out = w.ac; a.ldo = ld;
+  a.A = qu + (long)G * 512; a.lda = 512; a.a_rows = T; a.M = T; a.Cin = 64; a.ntaps = 1;
+  a.W = qkv + (long)G * 1536 + 512; a.ldw = 1536; a.n_rows_w = T; a.N = T;
+  a.out = ac; a.ldo = ld;
   a.nb2 = 8;
   a.sA1 = (long)S * 512; a.sA2 = 64; a.sW1 = (long)S * 1536; a.sW2 = 64; a.sO1 = 8L * T * ld; a.sO2 = (long)T * ld;
   JV_TRY(conv_gemm(a, B * 8, st));
   // bd[b,h] = (q + v) P_h^T over all 2T-1 relative positions (rel_shift happens inside the softmax's indexing)
   conv_gemm_defaults(a);
-  a.A = w.qv + (long)G * 512; a.lda = 512; a.a_rows = T; a.M = T; a.Cin = 64; a.ntaps = 1;
-  a.W = w.p; a.ldw = 512; a.n_rows_w = npos; a.N = npos;
-  a.out = w.bd; a.ldo = ldb;
+  a.A = qv + (long)G * 512; a.lda = 512; a.a_rows = T; a.M = T; a.Cin = 64; a.ntaps = 1;
+  a.W = p; a.ldw = 512; a.n_rows_w = npos; a.N = npos;
+  a.out = bd; a.ldo = ldb;
   a.nb2 = 8;
   a.sA1 = (long)S * 512; a.sA2 = 64; a.sW1 = 0; a.sW2 = 64; a.sO1 = 8L * T * ldb; a.sO2 = (long)T * ldb;
   JV_TRY(conv_gemm(a, B * 8, st));
-  JV_TRY(rel_softmax(w.ac, w.bd, len, len_mul, B, 8, T, ld, ldb, st));
-  JV_TRY(prompt_transpose_v(w.qkv, w.vt, B, T, ld, G, S, st));
+  JV_TRY(rel_softmax(ac, bd, len, len_mul, B, 8, T, ld, ldb, chunk, st));
+  JV_TRY(prompt_transpose_v(qkv, vt, B, T, ld, G, S, st));
   // att[b, :, h*64:(h+1)*64] = P_bh V_bh
   conv_gemm_defaults(a);
-  a.A = w.ac; a.lda = ld; a.a_rows = T; a.M = T; a.Cin = ld; a.ntaps = 1;
-  a.W = w.vt; a.ldw = ld; a.n_rows_w = 64; a.N = 64;
-  a.out = w.att + (long)G * 512; a.ldo = 512;
+  a.A = ac; a.lda = ld; a.a_rows = T; a.M = T; a.Cin = ld; a.ntaps = 1;
+  a.W = vt; a.ldw = ld; a.n_rows_w = 64; a.N = 64;
+  a.out = att + (long)G * 512; a.ldo = 512;
   a.nb2 = 8;
   a.sA1 = 8L * T * ld; a.sA2 = (long)T * ld; a.sW1 = 8L * 64 * ld; a.sW2 = 64L * ld; a.sO1 = (long)S * 512; a.sO2 = 64;
-  JV_TRY(conv_gemm(a, B * 8, st));
+  return conv_gemm(a, B * 8, st);
+}
+
+namespace {
+
+// one pre-LN block on T rows per utterance (geometry G, S): x += MHA_rel(LN(x)); x += W2 silu(W1 LN(x)).  fused: the attention
+// as relattn.hip's one launch instead of the three GEMMs; chunk > 0: the streaming mask (keys j < (i / chunk + 1) * chunk)
+int conformer_block(Context& c, const ConfBlockW& k, int B, int T, int G, int S, long M, const long* len, int len_mul, bool fused,
+                    int chunk, hipStream_t st) {
+  PromptWs& w = *c.pws;
+  const long AR = w.rows;
+  const int npos = 2 * T - 1;
+  JV_TRY(layernorm_rows(w.x, nullptr, w.ln, k.n_mha.g, k.n_mha.b, 1e-5f, M, 512, nullptr, st));
+  ConvGemmArgs a = lin_args(w.ln, 512, AR, M, k.qkv, w.qkv, 1536);
+  JV_TRY(conv_gemm(a, 1, st));
+  a = lin_args(w.pe, 512, npos, npos, k.pos, w.p, 512);                       // p = linear_pos(pos_emb), shared by the batch
+  JV_TRY(conv_gemm(a, 1, st));
+  if (fused) JV_TRY(rel_attention(w.qkv, w.p, npos, k.u, k.v, len, len_mul, B, T, G, S, chunk, w.att, st));
+  else JV_TRY(rel_attention_gemm(w.qkv, w.p, k.u, k.v, w.qu, w.qv, w.ac, w.bd, w.vt, w.att, len, len_mul, B, T, G, S, chunk, st));
   a = lin_args(w.att, 512, AR, M, k.out, w.x, 512);
   a.res1 = w.x; a.ldr1 = 512;
   JV_TRY(conv_gemm(a, 1, st));
@@ -155,19 +183,17 @@ int conformer_block(Context& c, const ConfBlockW& k, int B, int T, int G, int S,
   return conv_gemm(a, 1, st);
 }
 
-}  // namespace
-
-int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int Tk, float* h_out, hipStream_t st) {
-  if (!c.ready[MODEL_PROMPT]) return fail(JV_ERR_STATE, "prompt encoder weights not finalized");
-  if (B < 1 || Tk < 1) return fail(JV_ERR_ARG, "batch and token count must be positive");
-  if (B > c.max_batch || 2 * Tk > c.max_frames || Tk > 2048)
-    return fail(JV_ERR_SHAPE, "prompt batch/tokens exceed the capacity given to jv_create (2*tokens <= max_frames, tokens <= 2048)");
-  JV_TRY(ensure_ws(c, B, Tk));
+// Both stages for utterance b's ids [ptok[b, :p_b] | tok[b, :n_b]] (P = 0: one source), T1 = P + N token rows.  `len`: the int64
+// lengths p_b + n_b on the device.  fused / streaming: the attention route and the chunk masks of conformer_block.
+int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const long* tok, const long* tlen, int N, const long* len,
+                   int B, bool fused, bool streaming, float* h_out, hipStream_t st) {
   PromptWs& w = *c.pws;
   const PromptW& e = c.prompt;
   const long AR = w.rows;
+  const int Tk = P + N;
   const int T1 = Tk, S1 = T1 + P_GAP, T2 = 2 * Tk, S2 = T2 + P_GAP;
   const long M1 = P_G + (long)B * S1, M2 = P_G + (long)B * S2;
+  const int chunk1 = streaming ? PR_CHUNK : 0, chunk2 = 2 * chunk1;
 
   JV_TRY(lens_to_i32(len, w.lens_i, B, Tk, st));
   JV_TRY(row_meta(w.mask1, nullptr, w.lens_i, B, 1, P_G, S1, T1, AR, 1, 0, st));
@@ -175,7 +201,7 @@ int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int 
 
   // ---- stage 1: embedding -> Linear + LayerNorm (* sqrt 512) -> look-ahead convs -> 6 blocks ---------------------------
   JV_TRY(fill(w.y, 0.f, M1 * 512, st));                     // gap rows of the embedding buffer must read as zero tokens
-  JV_TRY(prompt_embed(tok, len, e.emb, w.y, B, T1, P_G, S1, PR_VOCAB, st));
+  JV_TRY(prompt_embed(ptok, plen, P, tok, tlen, N, e.emb, w.y, B, P_G, S1, PR_VOCAB, st));
   ConvGemmArgs a = lin_args(w.y, 512, AR, M1, e.emb_lin, w.ln, 512);
   JV_TRY(conv_gemm(a, 1, st));
   JV_TRY(layernorm_rows(w.ln, nullptr, w.x, e.emb_ln.g, e.emb_ln.b, 1e-5f, M1, 512, nullptr, st));
@@ -193,7 +219,7 @@ int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int 
   a.res1 = w.x; a.ldr1 = 512;
   JV_TRY(conv_gemm(a, 1, st));
   JV_HIP(hipMemcpyAsync(w.x, w.ln, sizeof(float) * M1 * 512, hipMemcpyDeviceToDevice, st));
-  for (int i = 0; i < PR_BLOCKS; ++i) JV_TRY(conformer_block(c, e.blk[i], B, T1, P_G, S1, M1, len, 1, st));
+  for (int i = 0; i < PR_BLOCKS; ++i) JV_TRY(conformer_block(c, e.blk[i], B, T1, P_G, S1, M1, len, 1, fused, chunk1, st));
 
   // ---- stage 2: nearest x2 -> conv k5 over rows u-4 .. u -> Linear + LayerNorm (* sqrt 512) -> 4 blocks -> LN -> proj ----
   JV_TRY(fill(w.y, 0.f, M2 * 512, st));
@@ -206,11 +232,39 @@ int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int 
   JV_TRY(conv_gemm(a, 1, st));
   JV_TRY(layernorm_rows(w.y, nullptr, w.x, e.up_emb_ln.g, e.up_emb_ln.b, 1e-5f, M2, 512, nullptr, st));
   JV_TRY(rel_pos_table(w.pe, e.div, T2, st));
-  for (int i = 0; i < PR_UP_BLOCKS; ++i) JV_TRY(conformer_block(c, e.up[i], B, T2, P_G, S2, M2, len, 2, st));
+  for (int i = 0; i < PR_UP_BLOCKS; ++i) JV_TRY(conformer_block(c, e.up[i], B, T2, P_G, S2, M2, len, 2, fused, chunk2, st));
   JV_TRY(layernorm_rows(w.x, nullptr, w.ln, e.after.g, e.after.b, 1e-5f, M2, 512, nullptr, st));
   a = lin_args(w.ln, 512, AR, M2, e.proj, w.o80, 80);
   JV_TRY(conv_gemm(a, 1, st));
   return rows_to_btc(w.o80, len, 2, h_out, B, T2, 80, P_G, S2, st);
+}
+
+int check_encoder_call(Context& c, int B, int Tk) {
+  if (!c.ready[MODEL_PROMPT]) return fail(JV_ERR_STATE, "prompt encoder weights not finalized");
+  if (B < 1 || Tk < 1) return fail(JV_ERR_ARG, "batch and token count must be positive");
+  if (B > c.max_batch || 2 * Tk > c.max_frames || Tk > 2048)
+    return fail(JV_ERR_SHAPE, "prompt batch/tokens exceed the capacity given to jv_create (2*tokens <= max_frames, tokens <= 2048)");
+  return JV_OK;
+}
+
+}  // namespace
+
+int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int Tk, float* h_out, hipStream_t st) {
+  JV_TRY(check_encoder_call(c, B, Tk));
+  JV_TRY(ensure_ws(c, B, Tk, true));
+  // the three-GEMM attention, full context: this entry's launches and bits are what they were before relattn.hip existed
+  return encoder_stages(c, nullptr, nullptr, 0, tok, len, Tk, len, B, false, false, h_out, st);
+}
+
+// flow.py:319-328, 338: [prompt tokens | tokens] -> h, on the fused attention (no ac / bd / vt in this route's workspace)
+int flow_encoder_fwd(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, int B, int P, int N,
+                     int streaming, float* h_out, int* h_lens, hipStream_t st) {
+  if (P < 0 || N < 0) return fail(JV_ERR_ARG, "jv_flow_encoder_fwd: P and N must be non-negative");
+  JV_TRY(check_encoder_call(c, B, P + N));
+  JV_TRY(ensure_ws(c, B, P + N, false));
+  PromptWs& w = *c.pws;
+  JV_TRY(sum_lens(plen, P, len, N, B, w.lens64, h_lens, 2, st));
+  return encoder_stages(c, ptok, plen, P, tok, len, N, w.lens64, B, true, streaming != 0, h_out, st);
 }
 
 }  // namespace jv
@@ -223,6 +277,16 @@ int jv_prompt_encoder_fwd(jv_context* ctx, const int64_t* tokens, const int64_t*
   JV_HIP(hipSetDevice(ctx->c.device));
   return jv::prompt_encoder_fwd(ctx->c, reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_len), B, Tk,
                                 prompt_h, static_cast<hipStream_t>(stream));
+}
+
+int jv_flow_encoder_fwd(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                        const int64_t* token_lens, int B, int P, int N, int streaming, float* h, int32_t* h_lens, void* stream) {
+  if (!ctx || !h || !token_lens || (N > 0 && !tokens) || (P > 0 && (!prompt_tokens || !prompt_lens)))
+    return jv::fail(JV_ERR_ARG, "jv_flow_encoder_fwd: null argument");
+  JV_HIP(hipSetDevice(ctx->c.device));
+  return jv::flow_encoder_fwd(ctx->c, reinterpret_cast<const long*>(prompt_tokens), reinterpret_cast<const long*>(prompt_lens),
+                              reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_lens), B, P, N, streaming, h,
+                              h_lens, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

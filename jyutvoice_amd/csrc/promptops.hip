@@ -9,28 +9,50 @@ namespace jv {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// rows[G + b*S + t][0:512] = emb[clamp(tok[b][t], 0)] for t < len[b], zero for len[b] <= t < T
-__global__ __launch_bounds__(256) void prompt_embed_kernel(const long* __restrict__ tok, const long* __restrict__ len,
+// rows[G + b*S + t][0:512] = emb[clamp(id(b, t), 0)] for t < p_b + n_b, zero for p_b + n_b <= t < T, where utterance b's ids are
+// [ptok[b, :p_b] | tok[b, :n_b]] (flow.py:319-324: the concatenation happens here, from two sources), p_b = clamp(plen[b], 0, P),
+// n_b = clamp(len[b], 0, N), T = P + N.  P = 0 (ptok, plen unused): one source, the prompt encoder's call.
+__global__ __launch_bounds__(256) void prompt_embed_kernel(const long* __restrict__ ptok, const long* __restrict__ plen, int P,
+                                                           const long* __restrict__ tok, const long* __restrict__ len, int N,
                                                            const float* __restrict__ emb, float* __restrict__ rows, int B,
-                                                           int T, int G, int S, int vocab) {
+                                                           int G, int S, int vocab) {
+  const int T = P + N;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;   // f32x4 index over B*T*128
   if (idx >= (long)B * T * 128) return;
   const int c4 = (int)(idx & 127);
   const long bt = idx >> 7;
   const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
+  const int pb = P > 0 ? (int)min(max(plen[b], 0L), (long)P) : 0;
+  const int nb = (int)min(max(len[b], 0L), (long)N);
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (t < (int)len[b]) {
-    long id = tok[(long)b * T + t];
+  if (t < pb + nb) {
+    long id = t < pb ? ptok[(long)b * P + t] : tok[(long)b * N + (t - pb)];
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     v = *reinterpret_cast<const f32x4*>(emb + id * 512 + 4 * c4);
   }
   *reinterpret_cast<f32x4*>(rows + ((long)G + (long)b * S + t) * 512 + 4 * c4) = v;
 }
 
-int prompt_embed(const long* tok, const long* len, const float* emb, float* rows, int B, int T, int G, int S, int vocab,
-                 hipStream_t st) {
-  hipLaunchKernelGGL(prompt_embed_kernel, dim3((unsigned)cdivl((long)B * T * 128, 256)), dim3(256), 0, st, tok, len, emb, rows,
-                     B, T, G, S, vocab);
+int prompt_embed(const long* ptok, const long* plen, int P, const long* tok, const long* len, int N, const float* emb, float* rows,
+                 int B, int G, int S, int vocab, hipStream_t st) {
+  hipLaunchKernelGGL(prompt_embed_kernel, dim3((unsigned)cdivl((long)B * (P + N) * 128, 256)), dim3(256), 0, st, ptok, plen, P, tok,
+                     len, N, emb, rows, B, G, S, vocab);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
+// sum[b] = clamp(plen[b], 0, P) + clamp(len[b], 0, N) as int64 (the encoder's length vector) and, optionally, mul * sum[b] as int32
+__global__ void sum_lens_kernel(const long* __restrict__ plen, int P, const long* __restrict__ len, int N, int B,
+                                long* __restrict__ sum, int* __restrict__ out32, int mul) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const long s = (P > 0 ? min(max(plen[b], 0L), (long)P) : 0L) + min(max(len[b], 0L), (long)N);
+  sum[b] = s;
+  if (out32) out32[b] = (int)s * mul;
+}
+
+int sum_lens(const long* plen, int P, const long* len, int N, int B, long* sum, int* out32, int mul, hipStream_t st) {
+  hipLaunchKernelGGL(sum_lens_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, plen, P, len, N, B, sum, out32, mul);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }
@@ -72,17 +94,19 @@ int add_pos_bias(const float* qkv, const float* u, const float* v, float* qu, fl
   return JV_OK;
 }
 
-// P[b,h,i,j] = softmax_j((ac[b,h,i,j] + bd[b,h,i, j - i + T - 1]) / 8) over keys j < len[b]; masked keys and the padding
+// P[b,h,i,j] = softmax_j((ac[b,h,i,j] + bd[b,h,i, j - i + T - 1]) / 8) over keys j < len[b] -- with chunk > 0 (streaming,
+// utils/mask.py:91-126: all left chunks) over j < min(len[b], (i / chunk + 1) * chunk); masked keys and the padding
 // columns T <= j < ld are written as 0 (they are the K operand's zero padding of the P V product).  One wave per row.
 __global__ __launch_bounds__(256) void rel_softmax_kernel(float* __restrict__ ac, const float* __restrict__ bd,
                                                           const long* __restrict__ len, int len_mul, int B, int H, int T,
-                                                          int ld, int ldb) {
+                                                          int ld, int ldb, int chunk) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (long)B * H * T) return;
   const int i = (int)(row % T);
   const int b = (int)(row / ((long)H * T));
-  const int L = min((int)len[b] * len_mul, T);
+  int L = min((int)len[b] * len_mul, T);
+  if (chunk > 0) L = min(L, (i / chunk + 1) * chunk);
   float* p = ac + row * ld;
   const float* q = bd + row * ldb + (T - 1 - i);
   float m = -INFINITY;
@@ -105,10 +129,30 @@ __global__ __launch_bounds__(256) void rel_softmax_kernel(float* __restrict__ ac
   for (int j = lane; j < ld; j += 64) p[j] = j < L ? p[j] * r : 0.f;
 }
 
-int rel_softmax(float* ac, const float* bd, const long* len, int len_mul, int B, int H, int T, int ld, int ldb,
+int rel_softmax(float* ac, const float* bd, const long* len, int len_mul, int B, int H, int T, int ld, int ldb, int chunk,
                 hipStream_t st) {
   hipLaunchKernelGGL(rel_softmax_kernel, dim3((unsigned)cdivl((long)B * H * T, 4)), dim3(256), 0, st, ac, bd, len, len_mul, B,
-                     H, T, ld, ldb);
+                     H, T, ld, ldb, chunk);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
+// att[G + b*S + i][0:512] = 0 for min(len[b] * len_mul, T) <= i < T: the three-GEMM route leaves the softmax of padding queries there
+// (harmless inside the encoder, whose padding rows never reach a real frame); jv_op_rel_attention's contract is zeros
+__global__ __launch_bounds__(256) void zero_rows_behind_kernel(float* __restrict__ att, const long* __restrict__ len, int len_mul,
+                                                               int B, int T, int G, int S) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)B * T * 128) return;
+  const int c4 = (int)(idx & 127);
+  const long bt = idx >> 7;
+  const int b = (int)(bt / T), i = (int)(bt - (long)b * T);
+  const long L = min(max(len[b] * (long)len_mul, 0L), (long)T);
+  if (i >= L) *reinterpret_cast<f32x4*>(att + ((long)G + (long)b * S + i) * 512 + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+int zero_rows_behind(float* att, const long* len, int len_mul, int B, int T, int G, int S, hipStream_t st) {
+  hipLaunchKernelGGL(zero_rows_behind_kernel, dim3((unsigned)cdivl((long)B * T * 128, 256)), dim3(256), 0, st, att, len, len_mul, B, T,
+                     G, S);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

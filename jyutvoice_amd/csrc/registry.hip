@@ -586,8 +586,11 @@ struct Packer {
 int scale_copy(const float* x, float* y, float s, int n, hipStream_t st);   // promptops.hip
 
 int finalize_model(Context& c, int model, hipStream_t st) {
-  for (const RawTensor& t : c.raw)
-    if (t.model == model && !t.loaded) return fail(JV_ERR_STATE, "missing tensor: " + t.name);
+  // MODEL_FLOW is the decoder.* / spk_embed_affine_layer.* part of MODEL_TTS's tensors: the same slots, the same packing
+  for (const RawTensor& t : c.raw) {
+    const bool wanted = model == MODEL_FLOW ? (t.model == MODEL_TTS && flow_part(t.name)) : t.model == model;
+    if (wanted && !t.loaded) return fail(JV_ERR_STATE, "missing tensor: " + t.name);
+  }
   Packer pk{c, st};
 
   if (model == MODEL_PROMPT) {
@@ -639,8 +642,8 @@ int finalize_model(Context& c, int model, hipStream_t st) {
     return JV_OK;
   }
 
-  if (model == MODEL_TTS) {
-    // ---------------- estimator ----------------
+  if ((model == MODEL_TTS || model == MODEL_FLOW) && !c.ready[MODEL_FLOW]) {
+    // ---------------- estimator + speaker projection (MODEL_FLOW; part of MODEL_TTS) ----------------
     const std::string p = "decoder.estimator.";
     EstimatorW& e = c.est;
     e.time1 = pk.linear(p + "time_mlp.linear_1.weight", p + "time_mlp.linear_1.bias", EST_TIME, EST_IN);
@@ -751,7 +754,11 @@ int finalize_model(Context& c, int model, hipStream_t st) {
     (void)pk.half3(e.final_conv);
     (void)pk.half3(e.final_proj);
     pk.wfrag(e.down_conv); pk.wfrag(e.up_conv); pk.wfrag(e.final_conv);
-
+    c.enc.spk_affine = pk.linear("spk_embed_affine_layer.weight", "spk_embed_affine_layer.bias", N_FEATS, SPK_DIM);
+  }
+  if (model == MODEL_FLOW) {
+    // (nothing else)
+  } else if (model == MODEL_TTS) {
     // ---------------- text encoder + duration predictor ----------------
     EncoderW& n = c.enc;
     const std::string q = "encoder.";
@@ -783,7 +790,6 @@ int finalize_model(Context& c, int model, hipStream_t st) {
     n.dp_conv2 = pk.conv_named("dp.conv_2.", DP_FILTER, DP_FILTER, 3);
     n.dp_ln2 = pk.ln("dp.norm_2.", "gamma", "beta");
     n.dp_proj = pk.linear("dp.proj.weight", "dp.proj.bias", 1, DP_FILTER);
-    n.spk_affine = pk.linear("spk_embed_affine_layer.weight", "spk_embed_affine_layer.bias", N_FEATS, SPK_DIM);
   } else if (model == MODEL_HIFT) {
     HiftW& h = c.hift;
     for (int i = 0; i < 5; ++i) {
@@ -844,6 +850,7 @@ int finalize_model(Context& c, int model, hipStream_t st) {
   JV_HIP(hipGetLastError());
   JV_HIP(hipStreamSynchronize(st));
   c.ready[model] = true;
+  if (model == MODEL_TTS) c.ready[MODEL_FLOW] = true;
   return JV_OK;
 }
 

@@ -411,15 +411,17 @@ int rows_to_cf(const float* src, int ld, int col0, int G, int S, float* dst, lon
 // prompt_feat[b, t, :] (frame-major already: 16-byte row copies); frame p_b <= t < sums[b] takes mu_y[b, :, t - p_b] through an
 // LDS tile (read along t, written along c) and zeros in cond; frames behind sums[b] are zero (uniform geometry only: in the
 // compact one they are the next utterance's).  Every index is clamped by the extents given as arguments, whatever the
-// length vectors hold.
+// length vectors hold.  clens (optional): the condition prefix ends at its own frame pc_b = clens[b] instead of at p_b
+// (token-to-mel, flow/flow.py:341-345: mu is the flow encoder's h over the whole sequence, cond only the prompt's mel).
 __global__ __launch_bounds__(256) void pack_prompted_kernel(const float* __restrict__ mu_y, int Ty, const float* __restrict__ prompt_h,
                                                             int Ph, const float* __restrict__ prompt_feat, int Pf,
                                                             const int* __restrict__ plens, const int* __restrict__ sums, int T,
                                                             float* __restrict__ mu, float* __restrict__ cond, int G, int S,
-                                                            const int* __restrict__ uoff) {
+                                                            const int* __restrict__ uoff, const int* __restrict__ clens) {
   __shared__ float tile[32][81];
   const int b = blockIdx.y, t0 = blockIdx.x * 32;
-  const int p = min(max(plens[b], 0), min(min(Ph, Pf), T));
+  const int p = min(max(plens[b], 0), min(clens ? Ph : min(Ph, Pf), T));
+  const int pc = clens ? min(max(clens[b], 0), min(Pf, T)) : p;
   const int len = min(max(sums[b], p), min(T, p + Ty));      // p <= len <= T, len - p <= Ty
   const long row0 = uoff ? (long)uoff[b] : (long)G + (long)b * S;
   const int twr = uoff ? len : T;
@@ -435,9 +437,9 @@ __global__ __launch_bounds__(256) void pack_prompted_kernel(const float* __restr
     const int r = idx / 20, q = idx - r * 20, t = t0 + r;
     if (t >= twr) continue;
     float4 m = make_float4(0.f, 0.f, 0.f, 0.f), cd = m;
+    if (t < pc) cd = *reinterpret_cast<const float4*>(prompt_feat + ((long)b * Pf + t) * 80 + 4 * q);
     if (t < p) {
       m = *reinterpret_cast<const float4*>(prompt_h + ((long)b * Ph + t) * 80 + 4 * q);
-      cd = *reinterpret_cast<const float4*>(prompt_feat + ((long)b * Pf + t) * 80 + 4 * q);
     } else if (t < len) {
       m = make_float4(tile[r][4 * q], tile[r][4 * q + 1], tile[r][4 * q + 2], tile[r][4 * q + 3]);
     }
@@ -447,10 +449,11 @@ __global__ __launch_bounds__(256) void pack_prompted_kernel(const float* __restr
 }
 
 int pack_prompted(const float* mu_y, int Ty, const float* prompt_h, int Ph, const float* prompt_feat, int Pf, const int* plens,
-                  const int* sums, int B, int T, float* mu, float* cond, int G, int S, hipStream_t st, const int* uoff) {
+                  const int* sums, int B, int T, float* mu, float* cond, int G, int S, hipStream_t st, const int* uoff,
+                  const int* clens) {
   if (B <= 0 || T <= 0) return JV_OK;
   hipLaunchKernelGGL(pack_prompted_kernel, dim3(cdiv(T, 32), B), dim3(256), 0, st, mu_y, Ty, prompt_h, Ph, prompt_feat, Pf, plens,
-                     sums, T, mu, cond, G, S, uoff);
+                     sums, T, mu, cond, G, S, uoff, clens);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

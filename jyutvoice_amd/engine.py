@@ -11,7 +11,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib, spec
-from ._lib import JV_MODEL_HIFT, JV_MODEL_PROMPT, JV_MODEL_TTS, JvError, check
+from ._lib import JV_MODEL_FLOW, JV_MODEL_HIFT, JV_MODEL_PROMPT, JV_MODEL_TTS, JvError, check
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -43,7 +43,7 @@ class Engine:
         self.device = torch.device("cuda", idx)
         check(self.lib.jv_create(C.byref(h), idx, max_batch, max_frames, max_tokens))
         self._h = h
-        self._loaded = {JV_MODEL_TTS: False, JV_MODEL_HIFT: False, JV_MODEL_PROMPT: False}
+        self._loaded = {JV_MODEL_TTS: False, JV_MODEL_HIFT: False, JV_MODEL_PROMPT: False, JV_MODEL_FLOW: False}
 
     def reserve(self, max_batch, max_frames, max_tokens):
         """grow (or shrink) the workspace of the live context; weights stay loaded (jv_reserve)"""
@@ -67,9 +67,13 @@ class Engine:
 
     # ---- registry ---------------------------------------------------------------------------------
     def registry(self, model: int) -> Dict[str, tuple]:
+        """name -> shape of a model's tensors; JV_MODEL_FLOW: the decoder.* / spk_embed_affine_layer.* slots of JV_MODEL_TTS"""
         out = {}
+        owner = JV_MODEL_TTS if model == JV_MODEL_FLOW else model
         for i in range(self.lib.jv_num_tensors(self._h)):
-            if self.lib.jv_tensor_model(self._h, i) != model:
+            if self.lib.jv_tensor_model(self._h, i) != owner:
+                continue
+            if model == JV_MODEL_FLOW and not self.lib.jv_tensor_name(self._h, i).decode().startswith(spec.FLOW_DECODER_PREFIXES):
                 continue
             nd = self.lib.jv_tensor_ndim(self._h, i)
             out[self.lib.jv_tensor_name(self._h, i).decode()] = tuple(
@@ -100,6 +104,8 @@ class Engine:
         if not missing:
             check(self.lib.jv_finalize(self._h, model, st))
             self._loaded[model] = True
+            if model == JV_MODEL_TTS:
+                self._loaded[JV_MODEL_FLOW] = True
         return missing, unexpected
 
     def load_noise(self, noise: torch.Tensor):
@@ -264,6 +270,46 @@ class Engine:
         h = torch.empty(B, 2 * Tk, spec.N_FEATS, device=self.device)
         check(self.lib.jv_prompt_encoder_fwd(self._h, _ptr(tok), _ptr(tl), B, Tk, _ptr(h), _stream(self.device)))
         return h
+
+    # ---- token-to-mel (flow/flow.py:300-358) -------------------------------------------------------------
+    def _tok(self, t):
+        return None if t is None else t.to(device=self.device, dtype=torch.int64).contiguous()
+
+    def flow_encoder(self, prompt_token, prompt_len, token, token_len, streaming=False):
+        """jv_flow_encoder_fwd: utterance b = [prompt_token[b, :p_b] | token[b, :n_b]] (prompt_token None or [B, 0]: no prompt)
+        -> (h [B, 2*(P+N), 80], h_lens int32 [B]); zeros behind 2*(p_b + n_b)"""
+        B, N = token.shape
+        P = 0 if prompt_token is None else prompt_token.shape[1]
+        tok, tl = self._tok(token), self._tok(token_len)
+        ptok, pl = (self._tok(prompt_token), self._tok(prompt_len)) if P > 0 else (None, None)
+        h = torch.empty(B, 2 * (P + N), spec.N_FEATS, device=self.device)
+        hl = torch.empty(B, dtype=torch.int32, device=self.device)
+        check(self.lib.jv_flow_encoder_fwd(self._h, _ptr(ptok), _ptr(pl), _ptr(tok), _ptr(tl), B, P, N, 1 if streaming else 0, _ptr(h),
+                                           _ptr(hl), _stream(self.device)))
+        return h, hl
+
+    def flow_token2mel(self, prompt_token, prompt_len, token, token_len, prompt_feat, feat_len, embedding, streaming=False,
+                       n_timesteps=10, temperature=1.0, t_span=None):
+        """jv_flow_token2mel: tokens -> (mel [B, 80, 2*(P+N)], mel_lens int32 [B]): frames f_b .. T_b - 1 of each utterance,
+        left-aligned, zeros behind.  prompt_feat [B, F, 80] (None: F = 0), feat_len [B] = f_b, embedding [B, 192] raw."""
+        B, N = token.shape
+        P = 0 if prompt_token is None else prompt_token.shape[1]
+        F = 0 if prompt_feat is None else prompt_feat.shape[1]
+        tok, tl = self._tok(token), self._tok(token_len)
+        ptok, pl = (self._tok(prompt_token), self._tok(prompt_len)) if P > 0 else (None, None)
+        pf = _f32(prompt_feat, self.device) if F > 0 else None
+        fl = feat_len.to(device=self.device, dtype=torch.int32).contiguous()
+        emb = _f32(embedding, self.device)
+        mel = torch.empty(B, spec.N_FEATS, 2 * (P + N), device=self.device)
+        ml = torch.empty(B, dtype=torch.int32, device=self.device)
+        ts = None
+        if t_span is not None:
+            ts_host = t_span.detach().to("cpu", torch.float32).contiguous()
+            ts = (C.c_float * ts_host.numel())(*ts_host.tolist())
+        check(self.lib.jv_flow_token2mel(self._h, _ptr(ptok), _ptr(pl), _ptr(tok), _ptr(tl), _ptr(pf), _ptr(fl), _ptr(emb), B, P, N, F,
+                                         1 if streaming else 0, int(n_timesteps), float(temperature), ts, _ptr(mel), _ptr(ml),
+                                         _stream(self.device)))
+        return mel, ml
 
     # ---- encoder --------------------------------------------------------------------------------------
     def encoder(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed):
@@ -445,6 +491,18 @@ def op_attention(qkv, lens, B, G, S, L):
     lib = _lib.load()
     out = torch.zeros(qkv.shape[0], 512, device=qkv.device)
     check(lib.jv_op_attention(_ptr(qkv), _ptr(lens), B, G, S, L, _ptr(out), _stream(qkv.device)))
+    return out
+
+
+def op_rel_attention(qkv, p, u, v, lens, B, T, G, S, len_mul=1, chunk=0, fused=True):
+    """the conformer block's relative-position attention (jv_op_rel_attention): qkv [rows, 1536] (rows G + b*S + t), p [2T-1, 512],
+    u, v [8, 64], lens int64 [B] -> out [rows, 512]; fused: relattn.hip's one launch, else the three-GEMM sequence.  Rows the
+    call does not own come back NaN."""
+    lib = _lib.load()
+    out = torch.full((qkv.shape[0], 512), float("nan"), device=qkv.device)
+    lens = lens.to(device=qkv.device, dtype=torch.int64).contiguous()
+    check(lib.jv_op_rel_attention(_ptr(qkv), _ptr(p), _ptr(u), _ptr(v), _ptr(lens), int(B), int(T), int(G), int(S), int(len_mul),
+                                  int(chunk), 1 if fused else 0, _ptr(out), _stream(qkv.device)))
     return out
 
 

@@ -9,7 +9,7 @@ from typing import Dict, Optional
 import torch
 
 from . import synth
-from .engine import JV_MODEL_HIFT, JV_MODEL_TTS, Engine
+from .engine import JV_MODEL_FLOW, JV_MODEL_HIFT, JV_MODEL_TTS, Engine
 
 
 def _round_up(v: int, m: int) -> int:
@@ -26,7 +26,12 @@ class Runtime:
 
     def set_weights(self, model: int, sd: Dict[str, torch.Tensor]):
         """validate + upload a state-dict (raises like nn.Module.load_state_dict)"""
+        if model == JV_MODEL_FLOW and JV_MODEL_TTS in self.sds:
+            raise RuntimeError("this runtime already holds a JyutVoiceTTS, whose decoder occupies the flow decoder's slots: load the "
+                               "flow with decoder=\"shared\" to reuse it, or use another Runtime")
         fresh = model not in self.sds
+        if model == JV_MODEL_TTS and self.sds.pop(JV_MODEL_FLOW, None) is not None:
+            fresh = False      # the full model replaces a flow-only decoder: new context
         self.sds[model] = {k: v.detach() for k, v in sd.items()}
         if self.engine is None:
             self.ensure(1, 512, 256)

@@ -300,11 +300,16 @@ def _prompt_inventory() -> "OrderedDict[str, tuple]":
 TTS_INVENTORY = _tts_inventory()
 HIFT_INVENTORY = _hift_inventory()
 PROMPT_INVENTORY = _prompt_inventory()
+# CausalMaskedDiffWithXvec (flow/flow.py:187-252), i.e. a CosyVoice2 flow.pt: the flow encoder plus the decoder part of the TTS model
+FLOW_DECODER_PREFIXES = ("decoder.", "spk_embed_affine_layer.")
+FLOW_DECODER_INVENTORY = OrderedDict((k, v) for k, v in TTS_INVENTORY.items() if k.startswith(FLOW_DECODER_PREFIXES))
+FLOW_INVENTORY = OrderedDict(list(PROMPT_INVENTORY.items()) + list(FLOW_DECODER_INVENTORY.items()))
 
 # known-answer structural checks (README.md:171,233 of the reference)
 assert len(TTS_INVENTORY) == 117 + 12 + 910 + 2, len(TTS_INVENTORY)
 assert len(HIFT_INVENTORY) == 328, len(HIFT_INVENTORY)
 assert len(PROMPT_INVENTORY) == 1 + 206 + 2, len(PROMPT_INVENTORY)   # the instantiated reference encoder has 206 tensors
+assert len(FLOW_INVENTORY) == 206 + 910 + 5, len(FLOW_INVENTORY)      # the instantiated reference flow has 1121 tensors
 
 
 def numel(shape: tuple) -> int:
