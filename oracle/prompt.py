@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 HEADS = 8
+STATIC_CHUNK = 25      # the encoder's static_chunk_size in tokens (configs/base.yaml:9); times the up-layer's stride of 2 behind it
 
 
 def rel_pos_emb(T, d=512):
@@ -37,8 +38,15 @@ def rel_shift(x):
     return xp[:, :, 1:].view_as(x)[:, :, :, : n // 2 + 1]
 
 
+def chunk_mask(T, chunk):
+    """[T, T] bool: query i sees keys j < (i // chunk + 1) * chunk -- static chunks with every chunk to the left
+    (utils/mask.py:91-126 as add_optional_chunk_mask calls it with static_chunk_size = chunk, num_left_chunks = -1)"""
+    i = torch.arange(T)
+    return i[None, :] < ((i // chunk + 1) * chunk)[:, None]
+
+
 def rel_attention(sd, pre, x, pos_emb, key_mask):
-    """x [B,T,512], pos_emb [1,2T-1,512], key_mask [B,1,T] bool -> [B,T,512]"""
+    """x [B,T,512], pos_emb [1,2T-1,512], key_mask [B,1,T] (keys) or [B,T,T] (query, key) bool -> [B,T,512]"""
     B, T, D = x.shape
     dk = D // HEADS
     lin = lambda n, z: F.linear(z, sd[pre + f"linear_{n}.weight"], sd.get(pre + f"linear_{n}.bias"))
@@ -51,7 +59,7 @@ def rel_attention(sd, pre, x, pos_emb, key_mask):
     ac = qu @ k.transpose(-2, -1)
     bd = rel_shift(qv @ p.transpose(-2, -1))
     scores = (ac + bd) / math.sqrt(dk)
-    dead = ~key_mask.unsqueeze(1)                                   # [B,1,1,T]
+    dead = ~key_mask.unsqueeze(1)                                   # [B,1,1,T] or [B,1,T,T]
     attn = torch.softmax(scores.masked_fill(dead, -float("inf")), dim=-1).masked_fill(dead, 0.0)
     o = (attn @ v).transpose(1, 2).reshape(B, T, D)
     return lin("out", o)
@@ -68,7 +76,7 @@ def embed(sd, pre, x):
     """Linear -> LayerNorm -> x * sqrt(512), and the relative positional table"""
     x = F.linear(x, sd[pre + "out.0.weight"], sd[pre + "out.0.bias"])
     x = F.layer_norm(x, (x.shape[-1],), sd[pre + "out.1.weight"], sd[pre + "out.1.bias"], 1e-5)
-    return x * math.sqrt(x.shape[-1]), rel_pos_emb(x.shape[1], x.shape[-1])
+    return x * math.sqrt(x.shape[-1]), rel_pos_emb(x.shape[1], x.shape[-1]).to(x.dtype)   # the table is fp32 arithmetic in any dtype
 
 
 def pre_lookahead(sd, pre, x):
@@ -85,12 +93,15 @@ def upsample(sd, pre, x):
     return F.conv1d(F.pad(h, (4, 0)), sd[pre + "conv.weight"], sd[pre + "conv.bias"]).transpose(1, 2)
 
 
-def _encode_one(sd, token, taps=None):
-    """token [1,Tk] -> [1, 2Tk, 80]  (one utterance, full key mask)"""
+def _encode_one(sd, token, taps=None, streaming=False):
+    """token [1,Tk] -> [1, 2Tk, 80]  (one utterance, every key alive).  streaming: static chunks of 25 tokens in the six
+    token-rate blocks and of 25 * 2 frames in the four mel-rate blocks, ANDed with the key mask (upsample_encoder.py:338-367)"""
     x = F.embedding(torch.clamp(token, min=0), sd["input_embedding.weight"])
     pre = "encoder."
     T = x.shape[1]
     ones = torch.ones(1, 1, T, dtype=torch.bool)
+    if streaming:
+        ones = ones & chunk_mask(T, STATIC_CHUNK)[None]
     x, pos = embed(sd, pre + "embed.", x)
     x = pre_lookahead(sd, pre + "pre_lookahead_layer.", x)
     if taps is not None:
@@ -103,6 +114,8 @@ def _encode_one(sd, token, taps=None):
     if taps is not None:
         taps["up"] = x
     ones2 = torch.ones(1, 1, 2 * T, dtype=torch.bool)
+    if streaming:
+        ones2 = ones2 & chunk_mask(2 * T, STATIC_CHUNK * 2)[None]
     x, pos = embed(sd, pre + "up_embed.", x)
     for i in range(4):
         x = conformer_block(sd, pre + f"up_encoders.{i}.", x, pos, ones2)
@@ -110,12 +123,16 @@ def _encode_one(sd, token, taps=None):
     return F.linear(x, sd["encoder_proj.weight"], sd["encoder_proj.bias"])
 
 
-def flow_encoder(sd, token, token_len, taps=None):
-    """token [B,Tk] int64 (padded), token_len [B] -> h [B, 2*Tk, 80] (zero beyond 2*len), h_lengths [B]"""
+def flow_encoder(sd, token, token_len, taps=None, streaming=False, dtype=torch.float32):
+    """token [B,Tk] int64 (padded), token_len [B] -> h [B, 2*Tk, 80] (zero beyond 2*len), h_lengths [B].
+    streaming: the chunk masks of `_encode_one`.  dtype=torch.float64: weights and activations are cast up (the positional
+    table stays the reference's fp32 expression, cast afterwards: it is an input the device is meant to reproduce)"""
     B, Tk = token.shape
-    h = torch.zeros(B, 2 * Tk, sd["encoder_proj.weight"].shape[0])
+    if dtype != torch.float32:
+        sd = {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}
+    h = torch.zeros(B, 2 * Tk, sd["encoder_proj.weight"].shape[0], dtype=dtype)
     for b in range(B):
         L = int(token_len[b])
         if L > 0:
-            h[b, : 2 * L] = _encode_one(sd, token[b : b + 1, :L], taps if b == 0 else None)[0]
+            h[b, : 2 * L] = _encode_one(sd, token[b : b + 1, :L], taps if b == 0 else None, streaming)[0]
     return h, token_len * 2

@@ -45,7 +45,7 @@ def run_pair(qkv, p, u, v, lens, B, T, S, len_mul, chunk):
 
 
 @pytest.mark.parametrize("chunk", [0, 25, 50])
-@pytest.mark.parametrize("T", [1, 25, 26, 64, 65, 186])
+@pytest.mark.parametrize("T", [1, 25, 26, 64, 65, 186, 257, 600])
 def test_fused_against_fp64_and_three_gemm(T, chunk):
     qkv, p, u, v, S = make_inputs(1, T, 1000 + T)
     _, _, err = run_pair(qkv, p, u, v, [T], 1, T, S, 1, chunk)
@@ -74,6 +74,29 @@ def test_ragged_batch_zero_rows(chunk):
     for b, n in enumerate(lens):
         hostile[G + b * S + min(2 * n, T):G + b * S + T] = float("nan")
     again = op_rel_attention(hostile.cuda(), p.cuda(), u.cuda(), v.cuda(), torch.tensor(lens), 3, T, G, S, 2, chunk, fused=True)
+    assert torch.equal(again.cpu().double().nan_to_num(nan=-7.0), got[1].nan_to_num(nan=-7.0))
+
+
+@pytest.mark.parametrize("chunk", [0, 50])
+def test_ragged_batch_long_rows(chunk):
+    """T = 300 at len_mul = 1: three workgroups per (utterance, head), ten key tiles.  The full utterance ends 44 queries into
+    the workgroup at I0 = 256; the one of 129 rows has one query in its second workgroup and nothing but padding in its third;
+    the one of a single row has one query and one key.  Same assertions as test_ragged_batch_zero_rows"""
+    from jyutvoice_amd.engine import op_rel_attention
+    T = 300
+    lens = [300, 129, 1]
+    qkv, p, u, v, S = make_inputs(3, T, 78)
+    got, want, err = run_pair(qkv, p, u, v, lens, 3, T, S, 1, chunk)
+    print(f"rel_attention ragged T=300 chunk={chunk}: fused {err[1]:.3e}  three-GEMM {err[0]:.3e}")
+    assert err[1] <= max(2 * err[0], 1e-6)
+    for b, L in enumerate(lens):
+        r0 = G + b * S
+        for f in (1, 0):
+            assert float(got[f][r0 + L:r0 + T].abs().max()) == 0.0 if L < T else True, (b, f)
+    hostile = qkv.clone()
+    for b, L in enumerate(lens):
+        hostile[G + b * S + L:G + b * S + T] = float("nan")
+    again = op_rel_attention(hostile.cuda(), p.cuda(), u.cuda(), v.cuda(), torch.tensor(lens), 3, T, G, S, 1, chunk, fused=True)
     assert torch.equal(again.cpu().double().nan_to_num(nan=-7.0), got[1].nan_to_num(nan=-7.0))
 
 
