@@ -183,6 +183,21 @@ int jv_flow_token2mel(jv_context* ctx, const int64_t* prompt_tokens, const int64
                       const int64_t* token_lens, const float* prompt_feat, const int32_t* feat_lens, const float* embedding, int B,
                       int P, int N, int F, int streaming, int n_timesteps, float temperature, const float* t_span_host, float* mel,
                       int32_t* mel_lens, void* stream);
+/* Partial sequences, B = 1 -- what flow.py:327-336 (`finalize=False`) intends: of the m = P + N tokens the last
+ * pre_lookahead_len = 3 are look-ahead context only (`token[:, -3:]`, flow.py:330-333).  They are embedded row-wise like the
+ * others (upsample_encoder.py:446-453, forward_chunk) and read by PreLookaheadLayer.conv1 alone, in place of its zero padding
+ * (upsample_encoder.py:110-121); the encoder, every length and mask, the solve and the unpack run on L = m - 3 tokens.  A caller
+ * that feeds tokens as they arrive gets, with streaming != 0 and L a multiple of 25, frames that no later token changes.
+ * jv_flow_encoder_fwd_partial: h [1, 2 L, 80], h_lens receives 2 (p + n - 3).
+ * jv_flow_token2mel_partial: mel [1, 80, 2 L], frames f .. 2 L - 1 left-aligned, mel_lens receives 2 L - f; 0 <= f <= min(F, 2 L).
+ * Arguments as in the whole-sequence entries with B = 1; P + N >= 4, else JV_ERR_ARG.  The whole-sequence entries run the same code
+ * with a context of 0 tokens: their launches and bits are unchanged. */
+int jv_flow_encoder_fwd_partial(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                                const int64_t* token_lens, int P, int N, int streaming, float* h, int32_t* h_lens, void* stream);
+int jv_flow_token2mel_partial(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                              const int64_t* token_lens, const float* prompt_feat, const int32_t* feat_lens, const float* embedding,
+                              int P, int N, int F, int streaming, int n_timesteps, float temperature, const float* t_span_host,
+                              float* mel, int32_t* mel_lens, void* stream);
 
 /* jv_load_mel_basis / jv_mel_spectrogram: the prompt-mel front-end, `extract_speech_feat` of infer.py:166-186 ->
  * `mel_spectrogram` of jyutvoice/utils/audio.py:18-63 (24 kHz, n_fft = win = 1920 periodic Hann, hop 480, reflect pad 720,
@@ -363,6 +378,14 @@ int jv_hift_source(jv_context* ctx, const float* f0, const float* phase, const f
  * oracle's noise through jv_hift_source instead. */
 int jv_hift_source_seeded(jv_context* ctx, const float* f0, const float* phase, uint64_t seed, uint32_t call, int B, int T, float* s,
                           void* stream);
+/* jv_hift_source_cont: jv_hift_source_seeded for a signal that arrives in pieces.  This call writes samples sample0 ..
+ * sample0 + 480 T - 1 from the f0 of the next T frames; `cum` [B,9] doubles (device, 8-byte aligned) carries the sine generator's
+ * running phase sums from call to call -- all zeros before the first piece, read and updated on the stream, no host round trip --
+ * and the noise counters use the absolute sample index.  Over any split of an f0 array into consecutive pieces the concatenated
+ * output equals jv_hift_source_seeded on the whole array with the same (phase, seed, call) bit for bit: the frame scan is a
+ * sequential fp64 recurrence that simply resumes, and a sample is a pure function of (its frame's start sum, f0, index). */
+int jv_hift_source_cont(jv_context* ctx, const float* f0, const float* phase, uint64_t seed, uint32_t call, int64_t sample0, double* cum,
+                        int B, int T, float* s, void* stream);
 int jv_hift_decode(jv_context* ctx, const float* mel, const float* s, const int32_t* lens, int B, int T, float* wav,
                    void* stream);
 

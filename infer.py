@@ -38,6 +38,9 @@ mel extractor.  Instead this CLI takes their outputs directly:
                              to OUTPUT with _000, _001, ... before the extension.  A prompt mel longer than the request's
                              2 * tokens frames is trimmed to them.  --streaming: the chunk-causal masks of the encoder and the
                              estimator (streaming=True of flow.py:300-358).  With --synthetic 1: key-hashed weights.
+    --stream-hop K           with --token2wav: every request runs through a streaming session of its own
+                             (jyutvoice_amd.stream.Token2WavStream, always on the streaming masks), its tokens pushed K at a time;
+                             the same files are written, and the time to the first audio is printed per request
     --synthetic N            no checkpoint / no tokens: N synthetic tokens, key-hashed weights (smoke / demo)
     --synthetic-prompt K     with --synthetic: also a synthetic K-token voice prompt through the prompt encoder
 
@@ -262,17 +265,21 @@ def token2wav_list(reqs, args, device):
     for b, f in enumerate(feats):
         prompt_feat[b, : f.shape[0]] = f
 
-    print(f"Running token-to-mel of {B} requests as one batch" + (" (streaming masks)" if args.streaming else "") + "...")
-    start = time.time()
-    try:
-        mel, _ = flow.inference(token, token_len, prompt_token, prompt_token_len, prompt_feat, feat_len, embedding, args.streaming,
-                                True, batched=True, n_timesteps=args.n_timesteps)
-    except ValueError as e:
-        raise SystemExit(f"{args.token2wav}: {e}")
-    wav, _ = hift.inference(mel, lengths=flow.mel_lengths)
-    torch.cuda.synchronize()
-    print(f"Synthesis time: {time.time() - start:.2f} s")
-    samples = flow.mel_lengths.to(torch.int64) * 480
+    if args.stream_hop:
+        wav, samples = token2wav_sessions(args, flow, hift, token, token_len, prompt_token, prompt_token_len, prompt_feat, feat_len,
+                                          embedding)
+    else:
+        print(f"Running token-to-mel of {B} requests as one batch" + (" (streaming masks)" if args.streaming else "") + "...")
+        start = time.time()
+        try:
+            mel, _ = flow.inference(token, token_len, prompt_token, prompt_token_len, prompt_feat, feat_len, embedding, args.streaming,
+                                    True, batched=True, n_timesteps=args.n_timesteps)
+        except ValueError as e:
+            raise SystemExit(f"{args.token2wav}: {e}")
+        wav, _ = hift.inference(mel, lengths=flow.mel_lengths)
+        torch.cuda.synchronize()
+        print(f"Synthesis time: {time.time() - start:.2f} s")
+        samples = flow.mel_lengths.to(torch.int64) * 480
     if args.sample_rate != 24000:
         from jyutvoice_amd.utils.audio import resample
         wav, samples = resample(wav, 24000, args.sample_rate, lengths=samples)
@@ -281,6 +288,44 @@ def token2wav_list(reqs, args, device):
         path = f"{stem}_{b:03d}{ext}"
         write_wav(path, wav[b, :n], args.sample_rate)
         print(f"Generated audio saved to: {path} ({n / args.sample_rate:.2f} seconds)")
+
+
+def token2wav_sessions(args, flow, hift, token, token_len, prompt_token, prompt_token_len, prompt_feat, feat_len, embedding):
+    """--stream-hop K: one Token2WavStream per request, its tokens pushed K at a time -> (wav [B, longest], samples [B])"""
+    import torch
+
+    from jyutvoice_amd.stream import Token2WavStream
+    if args.stream_hop < 1:
+        raise SystemExit("--stream-hop must be positive")
+    if not args.streaming:
+        print("--stream-hop: a session always runs on the streaming masks (--streaming is implied)")
+    pieces_all = []
+    for b in range(token.shape[0]):
+        n, p, f = int(token_len[b]), int(prompt_token_len[b]), int(feat_len[b])
+        start = time.time()
+        first = None
+        try:
+            session = Token2WavStream(flow, hift, prompt_token[b:b + 1, :p], prompt_feat[b:b + 1, :f], embedding[b:b + 1], max(n, 1),
+                                      n_timesteps=args.n_timesteps)
+            pieces = []
+            for i in range(0, n, args.stream_hop):
+                pieces.append(session.push(token[b, i:min(i + args.stream_hop, n)]))
+                if first is None and pieces[-1].shape[1] > 0:
+                    torch.cuda.synchronize()
+                    first = time.time() - start
+            pieces.append(session.finish())
+        except ValueError as e:
+            raise SystemExit(f"{args.token2wav}: request {b}: {e}")
+        torch.cuda.synchronize()
+        total = time.time() - start
+        first = total if first is None else first
+        print(f"request {b}: {n} tokens in hops of {args.stream_hop}: first audio after {first:.3f} s, all of it after {total:.3f} s")
+        pieces_all.append(torch.cat(pieces, dim=1)[0])
+    samples = torch.tensor([w.shape[0] for w in pieces_all], dtype=torch.int64)
+    wav = torch.zeros(len(pieces_all), int(samples.max()), device=pieces_all[0].device)
+    for b, w in enumerate(pieces_all):
+        wav[b, : w.shape[0]] = w
+    return wav, samples
 
 
 def main(argv=None):
@@ -303,6 +348,8 @@ def main(argv=None):
                    help="JSON list of {speech_token, embedding[, prompt_token, prompt_feat | prompt_wav]}: token-to-mel flow + vocoder")
     p.add_argument("--flow", default="pretrained_models/flow.pt", help="Path to the CosyVoice2 flow weights (--token2wav)")
     p.add_argument("--streaming", action="store_true", help="--token2wav: chunk-causal masks in the flow encoder and the estimator")
+    p.add_argument("--stream-hop", type=int, default=0, metavar="K",
+                   help="--token2wav: a streaming session per request, its tokens pushed K at a time")
     p.add_argument("--synthetic", type=int, default=0, help="use N synthetic tokens and synthetic weights")
     p.add_argument("--synthetic-prompt", type=int, default=0, help="with --synthetic: K synthetic prompt tokens (voice-cloning path)")
     p.add_argument("--seed", type=int, default=0, help="seed of the vocoder's source-noise draws")

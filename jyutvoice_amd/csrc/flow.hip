@@ -376,9 +376,11 @@ constexpr int T2M_EST_CHUNK = 50;      // the estimator's static_chunk_size in f
 // whole sequence of T_b = 2 (p_b + n_b) frames, cond = [prompt_feat_b[:f_b] | 0], and frames f_b .. T_b - 1 come back.  The same
 // schedule, geometry rule, Euler loop, pack and unpack kernels as cfm_solve_prompted: in its terms every frame is a "prompt" frame
 // of mu (Ty = 0) and the condition prefix has a length of its own.
+// ctx = 3 (jv_flow_token2mel_partial; flow.py:327-336): the last three tokens are look-ahead context of the encoder only, so the
+// sequence is L = P + N - 3 tokens and everything from h onwards -- lengths, masks, the solve, the unpack -- runs on 2 L frames.
 int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const float* prompt_feat,
                    const int* feat_lens, const float* embedding, int B, int P, int N, int F, int streaming, int n_timesteps,
-                   float temperature, const float* t_span_host, float* mel, int* mel_lens, hipStream_t st) {
+                   float temperature, const float* t_span_host, float* mel, int* mel_lens, hipStream_t st, int ctx) {
   if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "flow decoder weights not finalized (JV_MODEL_FLOW or JV_MODEL_TTS)");
   if (!c.ready[MODEL_PROMPT]) return fail(JV_ERR_STATE, "prompt encoder weights not finalized");
   if (B < 1 || P < 0 || N < 0 || P + N < 1 || F < 0) return fail(JV_ERR_ARG, "jv_flow_token2mel: B, P + N must be positive, P, N, F non-negative");
@@ -387,7 +389,8 @@ int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* t
   FlowWs& w = *c.flow;
   if (n_timesteps < 1 || n_timesteps > w.max_steps) return fail(JV_ERR_ARG, "n_timesteps out of range");
   if (reinterpret_cast<uintptr_t>(prompt_feat) & 15) return fail(JV_ERR_ARG, "jv_flow_token2mel: prompt_feat must be 16-byte aligned");
-  const int B2 = 2 * B, Tm = 2 * (P + N);
+  if (ctx < 0 || P + N - ctx < 1) return fail(JV_ERR_ARG, "jv_flow_token2mel_partial: P + N must be at least 4 (one encoded token + 3 of context)");
+  const int B2 = 2 * B, Tm = 2 * (P + N - ctx);
   JV_TRY(check_shape(c, B2, Tm));
   if (Tm > NOISE_FRAMES) return fail(JV_ERR_SHAPE, "more frames than the fixed noise tensor holds (15000)");
 
@@ -397,7 +400,7 @@ int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* t
   float* const spks = w.tsin;
   int* const hl = w.t2m_lens;
   int* const yl = w.t2m_lens + c.max_batch;
-  JV_TRY(flow_encoder_fwd(c, ptok, plen, tok, len, B, P, N, streaming, h, hl, st));
+  JV_TRY(flow_encoder_fwd(c, ptok, plen, tok, len, B, P, N, streaming, h, hl, st, ctx));
   JV_TRY(speaker_projection(c, embedding, B, spks, st));
 
   std::vector<float> tt, dts;

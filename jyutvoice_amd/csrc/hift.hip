@@ -24,7 +24,7 @@ int hiftpair(const HiftPairArgs& a, int C, hipStream_t st);
 
 int f0_head(const float* h, const float* w, const float* bias, float* f0, int B, int T, int G, int S, hipStream_t st);
 int sine_source(const float* f0, const float* phase, const float* noise, const float* lin_w, const float* lin_b, float* frac,
-                float* s, int B, int T, hipStream_t st, unsigned long long seed, unsigned call);
+                float* s, int B, int T, hipStream_t st, unsigned long long seed, unsigned call, long sample0 = 0, double* cum_io = nullptr);
 // (uoff3: optional first rows of the utterances at level 3 -- the compact geometry of ragged batches, below)
 int stft_rows(const float* s, float* out, const int* lens, int B, int T, int G3, int S3, long rows, hipStream_t st, const int* uoff3 = nullptr);
 int reflect_fix(float* x, int B, int G3, int S3, int C, hipStream_t st, const int* uoff3 = nullptr);
@@ -295,9 +295,9 @@ int hift_f0(Context& c, const float* mel, const int* lens, int B, int T, float* 
 
 // noise == nullptr: the N(0,1) draws are generated inside source_mix from (seed, call) -- hiftops.hip
 int hift_source(Context& c, const float* f0, const float* phase, const float* noise, int B, int T, float* s, hipStream_t st,
-                unsigned long long seed = 0, unsigned call = 0) {
+                unsigned long long seed = 0, unsigned call = 0, long sample0 = 0, double* cum = nullptr) {
   JV_TRY(check(c, B, T));
-  return sine_source(f0, phase, noise, c.hift.src_lin_w, c.hift.src_lin_b, c.hws->frac, s, B, T, st, seed, call);
+  return sine_source(f0, phase, noise, c.hift.src_lin_w, c.hift.src_lin_b, c.hws->frac, s, B, T, st, seed, call, sample0, cum);
 }
 
 int hift_decode(Context& c, const float* mel, const float* s, const int* lens, int B, int T, float* wav, hipStream_t st) {
@@ -413,6 +413,15 @@ int jv_hift_source_seeded(jv_context* ctx, const float* f0, const float* phase, 
   if (!ctx || !f0 || !phase || !s) return jv::fail(JV_ERR_ARG, "jv_hift_source_seeded: null argument");
   JV_HIP(hipSetDevice(ctx->c.device));
   return jv::hift_source(ctx->c, f0, phase, nullptr, B, T, s, static_cast<hipStream_t>(stream), seed, call);
+}
+
+int jv_hift_source_cont(jv_context* ctx, const float* f0, const float* phase, uint64_t seed, uint32_t call, int64_t sample0, double* cum,
+                        int B, int T, float* s, void* stream) {
+  if (!ctx || !f0 || !phase || !cum || !s) return jv::fail(JV_ERR_ARG, "jv_hift_source_cont: null argument");
+  if (sample0 < 0) return jv::fail(JV_ERR_ARG, "jv_hift_source_cont: sample0 must be non-negative");
+  if (reinterpret_cast<uintptr_t>(cum) & 7) return jv::fail(JV_ERR_ARG, "jv_hift_source_cont: cum must be 8-byte aligned");
+  JV_HIP(hipSetDevice(ctx->c.device));
+  return jv::hift_source(ctx->c, f0, phase, nullptr, B, T, s, static_cast<hipStream_t>(stream), seed, call, (long)sample0, cum);
 }
 
 int jv_hift_decode(jv_context* ctx, const float* mel, const float* s, const int32_t* lens, int B, int T, float* wav,

@@ -78,12 +78,16 @@ __device__ __forceinline__ bool frame_adds_exact(const double start, const float
   return q == trunc(q);
 }
 
-__global__ void sine_frame_scan_kernel(const float* __restrict__ f0, double* __restrict__ start, int B, int T) {
+// cum_io (jv_hift_source_cont, else null): the running sums [B, 9] of the frames that came before this call, read here and
+// replaced by the sums after its last frame -- the recurrence below simply resumes, so a signal produced piece by piece walks
+// through the same fp64 values as the one-shot scan
+__global__ void sine_frame_scan_kernel(const float* __restrict__ f0, double* __restrict__ start, int B, int T,
+                                       double* __restrict__ cum_io) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * 9) return;
   const int b = idx / 9, h = idx - b * 9;
   const float mult = (float)(h + 1);
-  double cum = 0.0;
+  double cum = cum_io ? cum_io[idx] : 0.0;
   for (int t = 0; t < T; ++t) {
     start[(long)idx * T + t] = cum;
     const float F = f0[b * T + t] * mult / 24000.0f;
@@ -93,6 +97,7 @@ __global__ void sine_frame_scan_kernel(const float* __restrict__ f0, double* __r
       for (int k = 0; k < 480; ++k) cum = cum + (double)F;
     }
   }
+  if (cum_io) cum_io[idx] = cum;
 }
 
 // Philox4x32-10 (Salmon et al., SC'11): the counter-based generator behind the seeded source noise -- a sample's nine draws
@@ -121,12 +126,13 @@ __device__ __forceinline__ void box_muller(unsigned a, unsigned b, float& z0, fl
 
 // s[b,n] = tanh( lin_b + sum_h lin_w[h] * ( 0.1 sin(2 pi frac + phi_h) * uv + namp * noise ) )
 // noise == nullptr: the nine N(0,1) draws of a sample come from Philox keyed by (seed_lo, seed_hi), counter (utterance,
-// sample, call, 3 blocks) -- generator.py:171 draws them with torch.randn_like, whose values no caller can depend on
+// sample, call, 3 blocks) -- generator.py:171 draws them with torch.randn_like, whose values no caller can depend on.
+// sample0: the index of this call's first sample in the signal it continues (0 unless jv_hift_source_cont); only the counter sees it
 __global__ __launch_bounds__(256) void source_mix_kernel(const float* __restrict__ f0, const double* __restrict__ start,
                                                          const float* __restrict__ phase, const float* __restrict__ noise,
                                                          const float* __restrict__ lin_w, const float* __restrict__ lin_b,
                                                          float* __restrict__ s, int B, int T, unsigned seed_lo, unsigned seed_hi,
-                                                         unsigned call) {
+                                                         unsigned call, long sample0) {
   const long n_per = (long)T * 480;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= n_per * B) return;
@@ -141,7 +147,7 @@ __global__ __launch_bounds__(256) void source_mix_kernel(const float* __restrict
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       unsigned r[4];
-      philox4x32_10((unsigned)n, (unsigned)b, call, (unsigned)j, seed_lo, seed_hi, r);
+      philox4x32_10((unsigned)(n + sample0), (unsigned)b, call, (unsigned)j, seed_lo, seed_hi, r);
       box_muller(r[0], r[1], z[4 * j], z[4 * j + 1]);
       box_muller(r[2], r[3], z[4 * j + 2], z[4 * j + 3]);
     }
@@ -169,12 +175,12 @@ __global__ __launch_bounds__(256) void source_mix_kernel(const float* __restrict
 }
 
 int sine_source(const float* f0, const float* phase, const float* noise, const float* lin_w, const float* lin_b, float* frac,
-                float* s, int B, int T, hipStream_t st, unsigned long long seed, unsigned call) {
+                float* s, int B, int T, hipStream_t st, unsigned long long seed, unsigned call, long sample0, double* cum_io) {
   // `frac` (sized [B, 9, 480 T] floats by hift_ws_create) now only holds the [B, 9, T] frame-start sums, as doubles
   double* start = reinterpret_cast<double*>(frac);
-  hipLaunchKernelGGL(sine_frame_scan_kernel, dim3(cdiv(B * 9, 64)), dim3(64), 0, st, f0, start, B, T);
+  hipLaunchKernelGGL(sine_frame_scan_kernel, dim3(cdiv(B * 9, 64)), dim3(64), 0, st, f0, start, B, T, cum_io);
   hipLaunchKernelGGL(source_mix_kernel, dim3((unsigned)cdivl((long)B * T * 480, 256)), dim3(256), 0, st, f0, start, phase, noise,
-                     lin_w, lin_b, s, B, T, (unsigned)seed, (unsigned)(seed >> 32), call);
+                     lin_w, lin_b, s, B, T, (unsigned)seed, (unsigned)(seed >> 32), call, sample0);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

@@ -13,6 +13,11 @@
 // The same two stages serve CausalMaskedDiffWithXvec.inference (flow/flow.py:300-358, flow_encoder_fwd below), where the encoder
 // runs over the WHOLE utterance [prompt tokens | tokens] in the text encoder's place: there the attention is relattn.hip's single
 // launch (no [T, T] buffer in that route's workspace) and `streaming` sets the chunk masks of upsample_encoder.py:338-367.
+//
+// Partial sequences (flow.py:327-336, what `finalize=False` intends; jv_flow_token2mel_partial): the last ctx = 3 tokens are embedded
+// like the others (upsample_encoder.py:446-453) but are only the look-ahead convolution's right context, in place of its zero padding
+// (upsample_encoder.py:110-121).  They sit in the first rows of the gap behind the L = P + N - ctx encoded ones; a second row mask
+// (mask1c) lets conv1, and nothing else, read them.  ctx = 0 is the whole-sequence path, launch for launch.
 #include <math.h>
 
 #include "../../include/jyutvoice_hip.h"
@@ -23,7 +28,7 @@ namespace jv {
 
 int prompt_embed(const long* ptok, const long* plen, int P, const long* tok, const long* len, int N, const float* emb, float* rows,
                  int B, int G, int S, int vocab, hipStream_t st);
-int sum_lens(const long* plen, int P, const long* len, int N, int B, long* sum, int* out32, int mul, hipStream_t st);
+int sum_lens(const long* plen, int P, const long* len, int N, int B, long* sum, int* out32, int mul, int ctx, hipStream_t st);
 int rel_pos_table(float* pe, const float* div, int T, hipStream_t st);
 int add_pos_bias(const float* qkv, const float* u, const float* v, float* qu, float* qv, long rows, hipStream_t st);
 int rel_softmax(float* ac, const float* bd, const long* len, int len_mul, int B, int H, int T, int ld, int ldb, int chunk,
@@ -34,6 +39,7 @@ int rows_to_btc(const float* rows, const long* len, int len_mul, float* out, int
 int lens_to_i32(const long* a, int* o, int n, int cap, hipStream_t st);   // encops.hip
 
 constexpr int P_G = 8, P_GAP = 8;   // guard rows >= the widest context (look-ahead 3, causal 2, upsampling conv 4)
+constexpr int PR_LOOKAHEAD = 3;     // pre_lookahead_len: conv1 reads rows t .. t + 3
 constexpr int PR_CHUNK = 25;        // static_chunk_size of the encoder in tokens (configs: 25; x up-sampling stride 2 in stage 2)
 
 // Sized on first use for the (B, Tk) asked for and regrown when a larger call arrives: prompts are short and rare next to
@@ -50,7 +56,7 @@ struct PromptWs {
   float* o80 = nullptr;                                                                         // [rows,80]
   float *pe = nullptr, *p = nullptr;                                                            // [2*T2,512]
   float *ac = nullptr, *bd = nullptr, *vt = nullptr;
-  unsigned char *mask1 = nullptr, *mask2 = nullptr;
+  unsigned char *mask1 = nullptr, *mask2 = nullptr, *mask1c = nullptr;      // mask1c: mask1 + the look-ahead context rows
   int* lens_i = nullptr;
 };
 
@@ -101,6 +107,7 @@ int ensure_ws(Context& c, int B, int Tk, bool quad) {
   JV_TRY(A(reinterpret_cast<void**>(&w->lens64), sizeof(long) * nb));
   JV_TRY(A(reinterpret_cast<void**>(&w->mask1), R));
   JV_TRY(A(reinterpret_cast<void**>(&w->mask2), R));
+  JV_TRY(A(reinterpret_cast<void**>(&w->mask1c), R));
   JV_TRY(A(reinterpret_cast<void**>(&w->lens_i), sizeof(int) * nb));
   return JV_OK;
 }
@@ -184,13 +191,15 @@ int conformer_block(Context& c, const ConfBlockW& k, int B, int T, int G, int S,
 }
 
 // Both stages for utterance b's ids [ptok[b, :p_b] | tok[b, :n_b]] (P = 0: one source), T1 = P + N token rows.  `len`: the int64
-// lengths p_b + n_b on the device.  fused / streaming: the attention route and the chunk masks of conformer_block.
+// lengths p_b + n_b - ctx on the device.  fused / streaming: the attention route and the chunk masks of conformer_block.
+// ctx > 0 (< P_GAP): the last ctx tokens of the P + N are context of the look-ahead convolution only; every length below is the
+// encoded one, T1 = P + N - ctx
 int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const long* tok, const long* tlen, int N, const long* len,
-                   int B, bool fused, bool streaming, float* h_out, hipStream_t st) {
+                   int B, bool fused, bool streaming, int ctx, float* h_out, hipStream_t st) {
   PromptWs& w = *c.pws;
   const PromptW& e = c.prompt;
   const long AR = w.rows;
-  const int Tk = P + N;
+  const int Tk = P + N - ctx;
   const int T1 = Tk, S1 = T1 + P_GAP, T2 = 2 * Tk, S2 = T2 + P_GAP;
   const long M1 = P_G + (long)B * S1, M2 = P_G + (long)B * S2;
   const int chunk1 = streaming ? PR_CHUNK : 0, chunk2 = 2 * chunk1;
@@ -198,6 +207,7 @@ int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const 
   JV_TRY(lens_to_i32(len, w.lens_i, B, Tk, st));
   JV_TRY(row_meta(w.mask1, nullptr, w.lens_i, B, 1, P_G, S1, T1, AR, 1, 0, st));
   JV_TRY(row_meta(w.mask2, nullptr, w.lens_i, B, 1, P_G, S2, T2, AR, 2, 0, st));
+  if (ctx > 0) JV_TRY(row_meta(w.mask1c, nullptr, w.lens_i, B, 1, P_G, S1, T1 + ctx, AR, 1, ctx, st));      // rows [0, len + ctx)
 
   // ---- stage 1: embedding -> Linear + LayerNorm (* sqrt 512) -> look-ahead convs -> 6 blocks ---------------------------
   JV_TRY(fill(w.y, 0.f, M1 * 512, st));                     // gap rows of the embedding buffer must read as zero tokens
@@ -206,10 +216,11 @@ int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const 
   JV_TRY(conv_gemm(a, 1, st));
   JV_TRY(layernorm_rows(w.ln, nullptr, w.x, e.emb_ln.g, e.emb_ln.b, 1e-5f, M1, 512, nullptr, st));
   JV_TRY(rel_pos_table(w.pe, e.div, T1, st));
-  // conv1: rows t .. t+3 of the valid frames (zeros beyond the end), bias; LeakyReLU(0.01) is conv2's prologue
+  // conv1: rows t .. t+3 of the valid frames (zeros beyond the end -- or, behind the last encoded frame of a partial sequence, the
+  // embedded context rows), bias; LeakyReLU(0.01) is conv2's prologue
   a = lin_args(w.x, 512, AR, M1, e.look1, w.y, 512);
   a.tap_row0 = 0;
-  a.rowmask_in = w.mask1;
+  a.rowmask_in = ctx > 0 ? w.mask1c : w.mask1;
   JV_TRY(conv_gemm(a, 1, st));
   // conv2: rows t-2 .. t of leaky(conv1) over the valid frames (zeros before the start), + bias + x
   a = lin_args(w.y, 512, AR, M1, e.look2, w.ln, 512);
@@ -253,18 +264,21 @@ int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int 
   JV_TRY(check_encoder_call(c, B, Tk));
   JV_TRY(ensure_ws(c, B, Tk, true));
   // the three-GEMM attention, full context: this entry's launches and bits are what they were before relattn.hip existed
-  return encoder_stages(c, nullptr, nullptr, 0, tok, len, Tk, len, B, false, false, h_out, st);
+  return encoder_stages(c, nullptr, nullptr, 0, tok, len, Tk, len, B, false, false, 0, h_out, st);
 }
 
 // flow.py:319-328, 338: [prompt tokens | tokens] -> h, on the fused attention (no ac / bd / vt in this route's workspace)
+// ctx = 3: flow.py:330-336, h over the first P + N - 3 tokens with the last three as look-ahead context ([B, 2 (P + N - 3), 80])
 int flow_encoder_fwd(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, int B, int P, int N,
-                     int streaming, float* h_out, int* h_lens, hipStream_t st) {
+                     int streaming, float* h_out, int* h_lens, hipStream_t st, int ctx) {
   if (P < 0 || N < 0) return fail(JV_ERR_ARG, "jv_flow_encoder_fwd: P and N must be non-negative");
+  if (ctx != 0 && ctx != PR_LOOKAHEAD) return fail(JV_ERR_ARG, "flow encoder: the context is the look-ahead length (3 tokens) or nothing");
+  if (ctx > 0 && (B != 1 || P + N <= ctx)) return fail(JV_ERR_ARG, "partial flow encoder: B must be 1 and P + N at least 4 (one encoded token + 3 of context)");
   JV_TRY(check_encoder_call(c, B, P + N));
   JV_TRY(ensure_ws(c, B, P + N, false));
   PromptWs& w = *c.pws;
-  JV_TRY(sum_lens(plen, P, len, N, B, w.lens64, h_lens, 2, st));
-  return encoder_stages(c, ptok, plen, P, tok, len, N, w.lens64, B, true, streaming != 0, h_out, st);
+  JV_TRY(sum_lens(plen, P, len, N, B, w.lens64, h_lens, 2, ctx, st));
+  return encoder_stages(c, ptok, plen, P, tok, len, N, w.lens64, B, true, streaming != 0, ctx, h_out, st);
 }
 
 }  // namespace jv
@@ -287,6 +301,16 @@ int jv_flow_encoder_fwd(jv_context* ctx, const int64_t* prompt_tokens, const int
   return jv::flow_encoder_fwd(ctx->c, reinterpret_cast<const long*>(prompt_tokens), reinterpret_cast<const long*>(prompt_lens),
                               reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_lens), B, P, N, streaming, h,
                               h_lens, static_cast<hipStream_t>(stream));
+}
+
+int jv_flow_encoder_fwd_partial(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                                const int64_t* token_lens, int P, int N, int streaming, float* h, int32_t* h_lens, void* stream) {
+  if (!ctx || !h || !token_lens || (N > 0 && !tokens) || (P > 0 && (!prompt_tokens || !prompt_lens)))
+    return jv::fail(JV_ERR_ARG, "jv_flow_encoder_fwd_partial: null argument");
+  JV_HIP(hipSetDevice(ctx->c.device));
+  return jv::flow_encoder_fwd(ctx->c, reinterpret_cast<const long*>(prompt_tokens), reinterpret_cast<const long*>(prompt_lens),
+                              reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_lens), 1, P, N, streaming, h,
+                              h_lens, static_cast<hipStream_t>(stream), jv::PR_LOOKAHEAD);
 }
 
 }  // extern "C"

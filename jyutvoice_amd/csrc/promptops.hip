@@ -41,18 +41,20 @@ int prompt_embed(const long* ptok, const long* plen, int P, const long* tok, con
   return JV_OK;
 }
 
-// sum[b] = clamp(plen[b], 0, P) + clamp(len[b], 0, N) as int64 (the encoder's length vector) and, optionally, mul * sum[b] as int32
+// sum[b] = clamp(plen[b], 0, P) + clamp(len[b], 0, N) - ctx as int64 (the encoder's length vector) and, optionally, mul * sum[b] as
+// int32.  ctx: the tokens at the end of the sequence that are look-ahead context only (flow.py:330-333: `token[:, :-pre_lookahead_len]`
+// is what the encoder runs on); 0 is the whole sequence, and a sequence shorter than ctx has length 0
 __global__ void sum_lens_kernel(const long* __restrict__ plen, int P, const long* __restrict__ len, int N, int B,
-                                long* __restrict__ sum, int* __restrict__ out32, int mul) {
+                                long* __restrict__ sum, int* __restrict__ out32, int mul, int ctx) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
-  const long s = (P > 0 ? min(max(plen[b], 0L), (long)P) : 0L) + min(max(len[b], 0L), (long)N);
+  const long s = max((P > 0 ? min(max(plen[b], 0L), (long)P) : 0L) + min(max(len[b], 0L), (long)N) - ctx, 0L);
   sum[b] = s;
   if (out32) out32[b] = (int)s * mul;
 }
 
-int sum_lens(const long* plen, int P, const long* len, int N, int B, long* sum, int* out32, int mul, hipStream_t st) {
-  hipLaunchKernelGGL(sum_lens_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, plen, P, len, N, B, sum, out32, mul);
+int sum_lens(const long* plen, int P, const long* len, int N, int B, long* sum, int* out32, int mul, int ctx, hipStream_t st) {
+  hipLaunchKernelGGL(sum_lens_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, plen, P, len, N, B, sum, out32, mul, ctx);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

@@ -311,6 +311,46 @@ class Engine:
                                          _stream(self.device)))
         return mel, ml
 
+    def flow_encoder_partial(self, prompt_token, prompt_len, token, token_len, streaming=False):
+        """jv_flow_encoder_fwd_partial (B = 1): the last 3 of the P + N tokens are look-ahead context only -> (h [1, 2*(P+N-3), 80],
+        h_lens int32 [1])"""
+        B, N = token.shape
+        P = 0 if prompt_token is None else prompt_token.shape[1]
+        if B != 1 or P + N < 4:
+            raise ValueError(f"flow_encoder_partial(): B must be 1 and P + N at least 4, got B = {B}, P + N = {P + N}")
+        tok, tl = self._tok(token), self._tok(token_len)
+        ptok, pl = (self._tok(prompt_token), self._tok(prompt_len)) if P > 0 else (None, None)
+        h = torch.empty(1, 2 * (P + N - 3), spec.N_FEATS, device=self.device)
+        hl = torch.empty(1, dtype=torch.int32, device=self.device)
+        check(self.lib.jv_flow_encoder_fwd_partial(self._h, _ptr(ptok), _ptr(pl), _ptr(tok), _ptr(tl), P, N, 1 if streaming else 0,
+                                                   _ptr(h), _ptr(hl), _stream(self.device)))
+        return h, hl
+
+    def flow_token2mel_partial(self, prompt_token, prompt_len, token, token_len, prompt_feat, feat_len, embedding, streaming=False,
+                               n_timesteps=10, temperature=1.0, t_span=None):
+        """jv_flow_token2mel_partial (B = 1): as flow_token2mel on the first L = P + N - 3 tokens, the last three being the look-ahead
+        convolution's context -> (mel [1, 80, 2 L], mel_lens int32 [1] = 2 L - f)"""
+        B, N = token.shape
+        P = 0 if prompt_token is None else prompt_token.shape[1]
+        F = 0 if prompt_feat is None else prompt_feat.shape[1]
+        if B != 1 or P + N < 4:
+            raise ValueError(f"flow_token2mel_partial(): B must be 1 and P + N at least 4, got B = {B}, P + N = {P + N}")
+        tok, tl = self._tok(token), self._tok(token_len)
+        ptok, pl = (self._tok(prompt_token), self._tok(prompt_len)) if P > 0 else (None, None)
+        pf = _f32(prompt_feat, self.device) if F > 0 else None
+        fl = feat_len.to(device=self.device, dtype=torch.int32).contiguous()
+        emb = _f32(embedding, self.device)
+        mel = torch.empty(1, spec.N_FEATS, 2 * (P + N - 3), device=self.device)
+        ml = torch.empty(1, dtype=torch.int32, device=self.device)
+        ts = None
+        if t_span is not None:
+            ts_host = t_span.detach().to("cpu", torch.float32).contiguous()
+            ts = (C.c_float * ts_host.numel())(*ts_host.tolist())
+        check(self.lib.jv_flow_token2mel_partial(self._h, _ptr(ptok), _ptr(pl), _ptr(tok), _ptr(tl), _ptr(pf), _ptr(fl), _ptr(emb), P, N,
+                                                 F, 1 if streaming else 0, int(n_timesteps), float(temperature), ts, _ptr(mel),
+                                                 _ptr(ml), _stream(self.device)))
+        return mel, ml
+
     # ---- encoder --------------------------------------------------------------------------------------
     def encoder(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed):
         B, Tt = x.shape
@@ -447,6 +487,21 @@ class Engine:
         s = torch.empty(B, 1, T * spec.HIFT_UPSAMPLE_TOTAL, device=self.device)
         check(self.lib.jv_hift_source_seeded(self._h, _ptr(f0), _ptr(phase), C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint32(call & 0xFFFFFFFF),
                                              B, T, _ptr(s), _stream(self.device)))
+        return s
+
+    def hift_source_cont(self, f0, phase, seed: int, call: int, sample0: int, cum):
+        """jv_hift_source_cont: the next 480 T samples of a source signal whose first `sample0` samples came from earlier calls.
+        cum: float64 [B, 9] on the device, zeros before the first piece; updated in place on the stream."""
+        B, T = f0.shape
+        if cum.dtype != torch.float64 or tuple(cum.shape) != (B, 9) or cum.device != self.device or not cum.is_contiguous():
+            raise ValueError(f"hift_source_cont(): cum must be a contiguous float64 [{B}, 9] tensor on {self.device}, got "
+                             f"{cum.dtype} {tuple(cum.shape)} on {cum.device}")
+        if sample0 < 0:
+            raise ValueError(f"hift_source_cont(): sample0 must be non-negative, got {sample0}")
+        f0, phase = _f32(f0, self.device), _f32(phase, self.device)
+        s = torch.empty(B, 1, T * spec.HIFT_UPSAMPLE_TOTAL, device=self.device)
+        check(self.lib.jv_hift_source_cont(self._h, _ptr(f0), _ptr(phase), C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint32(call & 0xFFFFFFFF),
+                                           C.c_int64(sample0), _ptr(cum), B, T, _ptr(s), _stream(self.device)))
         return s
 
     def hift_decode(self, mel, s, lens=None):

@@ -10,6 +10,11 @@ speaker projection, the Euler / CFG solver); this class validates and moves poin
 `finalize=False` is not implemented: the reference itself raises TypeError there (flow.py:330-336 passes `context=` to
 UpsampleConformerEncoder.forward, which has no such parameter).  Training `forward()` is out of scope.
 
+Extension: `inference_partial(...)` is what that branch intends -- the last `pre_lookahead_len` = 3 tokens are the look-ahead
+convolution's right context and nothing else (jv_flow_token2mel_partial) -- under a name of its own, so `finalize=False` keeps raising
+as the reference does.  With `streaming=True` and an encoded length that is a multiple of 25 tokens its frames are final: they are the
+first frames of `inference` on any longer sequence (jyutvoice_amd/stream.py builds the session on that).
+
 Extension (opt-in): `inference(..., batched=True)` accepts B > 1 and is defined as the B = 1 reference looped over the utterances
 with every tensor cut to the utterance's own length: tokens `token[b, :token_len[b]]`, prompt `prompt_token[b, :prompt_token_len[b]]`,
 `prompt_feat[b, :prompt_feat_len[b]]`.  Nothing behind a length is read.  The mel comes back [B, 80, max_b y_b] with utterance b in
@@ -173,6 +178,50 @@ class CausalMaskedDiffWithXvec:
         y_host = [spec.PROMPT_UP_STRIDE * (p + n) - f for p, n, f in zip(p_host, n_host, f_host)]
         width = max(y_host) if batched else spec.PROMPT_UP_STRIDE * (P + N) - F      # flow.py:337,356
         return mel[:, :, :width].float(), None
+
+
+    @torch.inference_mode()
+    def inference_partial(self, token, token_len, prompt_token, prompt_token_len, prompt_feat, prompt_feat_len, embedding, streaming,
+                          n_timesteps: int = 10, temperature: float = 1.0):
+        """flow.py:327-336 as intended, B = 1 -> (mel [1, 80, 2 L - F] float32, None).  Of the m = P + N tokens the encoder runs on
+        the first L = m - 3 (every length and mask uses L); the last three are embedded like the others (upsample_encoder.py:446-453)
+        and read by PreLookaheadLayer.conv1 alone, in place of its zero padding (upsample_encoder.py:110-121).  F = prompt_feat.shape[1]
+        (prompt_feat_len is not consulted, as in `inference`)."""
+        if token.dim() != 2 or token.shape[0] != 1:
+            raise ValueError(f"inference_partial(): token must be [1, N], got {tuple(token.shape)}")
+        if prompt_token is None:
+            prompt_token = torch.zeros(1, 0, dtype=torch.int64)
+        if prompt_token.dim() != 2 or prompt_token.shape[0] != 1:
+            raise ValueError(f"inference_partial(): prompt_token must be [1, P], got {tuple(prompt_token.shape)}")
+        N, P = token.shape[1], prompt_token.shape[1]
+        if prompt_feat is None:
+            prompt_feat = torch.zeros(1, 0, spec.N_FEATS)
+        if prompt_feat.dim() != 3 or prompt_feat.shape[0] != 1 or prompt_feat.shape[2] != spec.N_FEATS:
+            raise ValueError(f"inference_partial(): prompt_feat must be [1, frames, {spec.N_FEATS}], got {tuple(prompt_feat.shape)}")
+        if embedding.dim() != 2 or tuple(embedding.shape) != (1, spec.SPK_EMBED_DIM):
+            raise ValueError(f"inference_partial(): embedding must be [1, {spec.SPK_EMBED_DIM}], got {tuple(embedding.shape)}")
+        F = prompt_feat.shape[1]
+        m = _host_ints(token_len, "token_len", 1)[0] + (_host_ints(prompt_token_len, "prompt_token_len", 1)[0] if P > 0 else 0)
+        if not P <= m <= P + N:
+            raise ValueError(f"inference_partial(): prompt_token_len + token_len = {m} outside [{P}, {P + N}]: the reference's "
+                             f"sequence is the {P} prompt columns followed by the tokens")
+        if m < spec.PROMPT_LOOKAHEAD + 1:
+            raise ValueError(f"inference_partial(): {m} tokens: at least {spec.PROMPT_LOOKAHEAD + 1} are needed (the last "
+                             f"{spec.PROMPT_LOOKAHEAD} are look-ahead context only)")
+        L = m - spec.PROMPT_LOOKAHEAD
+        if F > spec.PROMPT_UP_STRIDE * L:
+            raise ValueError(f"inference_partial(): prompt_feat has {F} frames but the {L} encoded tokens give only "
+                             f"{spec.PROMPT_UP_STRIDE * L}")
+        if not self._loaded:
+            raise RuntimeError(f"{_NAME}: load_state_dict() has not been called")
+        eng = self._rt().ensure(1, spec.PROMPT_UP_STRIDE * (P + N), 1)
+        t_span = 1 - torch.cos(torch.linspace(0, 1, n_timesteps + 1) * 0.5 * torch.pi)      # flow_matching.py:387-389
+        mel, lens = eng.flow_token2mel_partial(prompt_token if P > 0 else None, torch.tensor([P]), token, torch.tensor([m - P]),
+                                               prompt_feat if F > 0 else None, torch.tensor([F], dtype=torch.int32), embedding,
+                                               streaming=bool(streaming), n_timesteps=n_timesteps, temperature=temperature,
+                                               t_span=t_span)
+        self.mel_lengths = lens
+        return mel[:, :, :spec.PROMPT_UP_STRIDE * L - F].float(), None
 
 
 def load_flow(flow_path, device="cuda:0", decoder: str = "own", runtime=None):

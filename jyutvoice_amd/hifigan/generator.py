@@ -7,7 +7,10 @@ The reference's sine generator draws Uniform(-pi, pi) phases and N(0,1) noise pe
 the per-sample N(0,1) noise from a counter-based generator INSIDE the source kernel (jv_hift_source_seeded: Philox keyed by
 the seed, counted per call -- `manual_seed` makes both repeatable), so the 9 x 480 T noise tensor is never materialised.
 The library owns no RNG state: (seed, call) are arguments.  `Engine.hift_source(f0, phase, noise)` (jv_hift_source) injects a
-caller's draws instead -- what the parity tests do with the oracle's."""
+caller's draws instead -- what the parity tests do with the oracle's.
+
+Extension: `stream()` opens a `HiFTStream`, which takes the mel in pieces and returns the samples that are final -- the same
+waveform `inference` gives on the whole mel (module-level docstring of HiFTStream)."""
 from __future__ import annotations
 
 import math
@@ -81,6 +84,22 @@ class HiFTGenerator:
         rt = get_runtime(self.device)
         return rt.ensure(B, T, 1)
 
+    def _source_draws(self, B):
+        """the random draws of one source signal: (phase [B, 9] on the device, seed, call) -- one `inference`, or one stream"""
+        phase = (torch.rand(B, 9, device=self.device, generator=self._gen) * 2 - 1) * math.pi
+        if self._seed is None:      # (a host draw: no device synchronisation)
+            self._seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        call = self._calls
+        self._calls += 1
+        return phase, self._seed, call
+
+    def stream(self) -> "HiFTStream":
+        """a chunked session (B = 1): `push(mel piece)` returns the samples that are now final, `finish()` the rest; the pieces
+        concatenate to what `inference` returns for the whole mel after the same `manual_seed`"""
+        if not self._loaded:
+            raise RuntimeError("HiFTGenerator: load_state_dict() has not been called")
+        return HiFTStream(self)
+
     @torch.inference_mode()
     def decode(self, x: torch.Tensor, s: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """generator.py:396-432: mel [B,80,T] + source [B,1,480T] -> waveform [B,480T]"""
@@ -94,11 +113,96 @@ class HiFTGenerator:
         B, _, T = speech_feat.shape
         eng = self._engine(B, T)
         f0 = eng.hift_f0(speech_feat, lengths)
-        phase = (torch.rand(B, 9, device=self.device, generator=self._gen) * 2 - 1) * math.pi
-        if self._seed is None:      # (a host draw: no device synchronisation)
-            self._seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        s = eng.hift_source_seeded(f0, phase, self._seed, self._calls)
-        self._calls += 1
+        phase, seed, call = self._source_draws(B)
+        s = eng.hift_source_seeded(f0, phase, seed, call)
         if cache_source.shape[2] != 0:
             s[:, :, : cache_source.shape[2]] = cache_source.to(self.device)
         return eng.hift_decode(speech_feat, s, lengths), s
+
+
+class HiFTStream:
+    """One utterance through the vocoder in pieces, B = 1.  `push(mel [1, 80, t]) -> (wav [1, 480 k], s [1, 1, 480 k])` with the k
+    frames that became final (k may be 0); `finish()` returns the rest.  Nothing is cross-faded: every emitted sample is the centre
+    of a window wide enough that the one-shot decode of the whole mel computes the same value.
+
+    With A frames received:
+      f0      is final for frames < A - HIFT_F0_HALO (five k = 3 convolutions): jv_hift_f0 on a window with that halo on its left,
+              cropped;
+      source  appended for exactly those frames by jv_hift_source_cont -- the running phase sums live in `cum` on the device, the
+              noise counters are absolute, so the assembled signal is bit for bit jv_hift_source_seeded on the f0 record;
+      decode  jv_hift_decode on [E - HIFT_DECODE_HALO, A_src), E frames emitted so far, A_src frames of source; frames
+              [E, A_src - HIFT_DECODE_HALO) are kept.  A window edge that is the utterance's true start (or, in finish(), end) needs
+              no halo.
+    The newest emitted frame trails the newest received one by 21 frames.  State: the mel and source of frames not yet retired, the
+    f0 record (`f0`, [1, frames with a final f0]), `cum`, the counts.  Phases and (seed, call) are drawn once, when the stream is
+    opened, the way `inference` draws them."""
+
+    def __init__(self, hift):
+        self._hift = hift
+        self._phase, self._seed, self._call = hift._source_draws(1)
+        dev = self._phase.device
+        self.cum = torch.zeros(1, 9, dtype=torch.float64, device=dev)
+        self.f0 = torch.zeros(1, 0, device=dev)
+        self._mel = torch.zeros(1, spec.N_FEATS, 0, device=dev)      # frames [self._base, self.received)
+        self._s = torch.zeros(1, 1, 0, device=dev)                  # samples of frames [self._base, self.sourced)
+        self._base = 0
+        self.received = self.sourced = self.emitted = 0
+        self.finished = False
+
+    def _check(self, mel):
+        if self.finished:
+            raise RuntimeError("HiFTStream: finish() has been called")
+        if not isinstance(mel, torch.Tensor) or mel.dim() != 3 or mel.shape[0] != 1 or mel.shape[1] != spec.N_FEATS:
+            raise ValueError(f"HiFTStream.push(): mel must be [1, {spec.N_FEATS}, frames], got "
+                             f"{tuple(mel.shape) if isinstance(mel, torch.Tensor) else type(mel).__name__}")
+
+    @torch.inference_mode()
+    def push(self, mel: torch.Tensor):
+        self._check(mel)
+        return self._advance(mel, final=False)
+
+    @torch.inference_mode()
+    def finish(self, mel: Optional[torch.Tensor] = None):
+        if mel is not None:
+            self._check(mel)
+        elif self.finished:
+            raise RuntimeError("HiFTStream: finish() has been called")
+        out = self._advance(mel, final=True)
+        self.finished = True
+        return out
+
+    def _advance(self, mel, final):
+        up, dev = spec.HIFT_UPSAMPLE_TOTAL, self._mel.device
+        if mel is not None and mel.shape[2] > 0:
+            self._mel = torch.cat([self._mel, mel.to(device=dev, dtype=torch.float32)], dim=2)
+            self.received += mel.shape[2]
+        A, base = self.received, self._base
+        # f0 and source of the frames whose f0 no later frame can change
+        f_hi = A if final else max(A - spec.HIFT_F0_HALO, self.sourced)
+        if f_hi > self.sourced:
+            lo = max(self.sourced - spec.HIFT_F0_HALO, 0)
+            eng = self._hift._engine(1, A - lo)
+            f0 = eng.hift_f0(self._mel[:, :, lo - base:])[:, self.sourced - lo: f_hi - lo]
+            piece = eng.hift_source_cont(f0, self._phase, self._seed, self._call, up * self.sourced, self.cum)
+            self.f0 = torch.cat([self.f0, f0], dim=1)
+            self._s = torch.cat([self._s, piece], dim=2)
+            self.sourced = f_hi
+        # decode the frames that have a full halo of mel and source on their right
+        E = self.emitted
+        k_hi = self.sourced if final else max(self.sourced - spec.HIFT_DECODE_HALO, E)
+        if k_hi > E:
+            lo = max(E - spec.HIFT_DECODE_HALO, 0)
+            eng = self._hift._engine(1, self.sourced - lo)
+            s_win = self._s[:, :, up * (lo - base):]
+            wav = eng.hift_decode(self._mel[:, :, lo - base: self.sourced - base], s_win)
+            out = wav[:, up * (E - lo): up * (k_hi - lo)], s_win[:, :, up * (E - lo): up * (k_hi - lo)]
+            self.emitted = k_hi
+        else:
+            out = torch.zeros(1, 0, device=dev), torch.zeros(1, 1, 0, device=dev)
+        # retire what neither the next f0 window nor the next decode window reads
+        keep = max(min(self.emitted - spec.HIFT_DECODE_HALO, self.sourced - spec.HIFT_F0_HALO), base)
+        if keep > base:
+            self._mel = self._mel[:, :, keep - base:]
+            self._s = self._s[:, :, up * (keep - base):]
+            self._base = keep
+        return out

@@ -77,6 +77,13 @@ HIFT_F0_CH = 512
 # source_downs: (kernel, stride, padding) for the three fusion points (generator.py:308-332)
 HIFT_SRC_DOWNS = ((30, 15, 7), (6, 3, 1), (1, 1, 0))
 HIFT_UPSAMPLE_TOTAL = 480  # 8*5*3*4
+# Streaming (HiFTStream): mel frames of context a window needs on a side that is not the utterance's true edge, so that its centre
+# equals the one-shot result.  Derived from the architecture in DESIGN.md section 5 ("Streaming token-to-wav"): the F0 predictor is five k = 3 convolutions
+# (5 frames); the decoder's longest path, source -> STFT -> source_downs.0 -> source_resblocks.0 -> the k = 11 ResBlocks of the three
+# levels -> conv_post -> iSTFT, reaches 6912 samples = 14.4 frames (the mel path 13.7), 15 whole frames, + 1 for the window edge's own
+# reflect paddings.
+HIFT_F0_HALO = 5
+HIFT_DECODE_HALO = 16
 
 
 def _tts_inventory() -> "OrderedDict[str, tuple]":
