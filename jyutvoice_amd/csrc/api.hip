@@ -177,6 +177,7 @@ int jv_create(jv_context** out, int device, int max_batch, int max_frames, int m
   c.no_res_qkv = getenv("JV_NO_RES_QKV") != nullptr;
   c.no_ln_fold = getenv("JV_NO_LN_FOLD") != nullptr;
   c.no_temb_pre = getenv("JV_NO_TEMB_PRE") != nullptr;
+  c.no_cfg_share = getenv("JV_NO_CFG_SHARE") != nullptr;
   c.no_hiftconv = getenv("JV_NO_HIFTCONV") != nullptr;
   c.no_hift_pair = getenv("JV_NO_HIFT_PAIR") != nullptr;
   c.max_frames = max_frames;

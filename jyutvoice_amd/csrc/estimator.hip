@@ -13,8 +13,9 @@
 namespace jv {
 
 // The route of a call over M rows.  `temb_pre`: the step's time embedding is precomputed (cfm_solve); `compact`: the rows are
-// laid out compactly; the mode switches, the tile height and the load-time weight bits are read here and nowhere else.
-EstRoute est_route(const Context& c, long M, bool temb_pre, bool compact, int attn_chunk) {
+// laid out compactly; `res_one` = false: the caller rules the whole-resnet launch out; the mode switches, the tile height and the
+// load-time weight bits are read here and nowhere else.
+EstRoute est_route(const Context& c, long M, bool temb_pre, bool compact, int attn_chunk, bool res_one) {
   const EstimatorW& e = c.est;
   EstRoute r;
   const int tile = rowgemm_tile((int)M);
@@ -65,7 +66,7 @@ EstRoute est_route(const Context& c, long M, bool temb_pre, bool compact, int at
   // measured bound (not the first resnet's), fragment-order weights for block1 | res_conv and for block2, the step's time
   // embedding shared by all rows (cfm_solve), a tile height that keeps the launch in as many rounds as the two it replaces.
   // JV_NO_RES_PAIR=1: two.
-  const bool one = r.rows && !c.no_res_pair && !c.no_res_fold && temb_pre && rowres_fits((int)M);
+  const bool one = res_one && r.rows && !c.no_res_pair && !c.no_res_fold && temb_pre && rowres_fits((int)M);
   // A workgroup reads its neighbours' rows as halo, so the launch never writes the buffer it reads: the mid stages alternate the
   // trunk between w.h and w.h2 (free: the launch keeps block1's output in LDS).  Decided for the trunk as a whole -- an even
   // number of stages, ALL paired, brings it back to w.h; one resnet that cannot (an unusable h2_bound) would run its two

@@ -202,8 +202,27 @@ int solve_compact(Context& c, Geo& g, const int* h_lens, int B, int T, hipStream
   return JV_OK;
 }
 
+// After a solve's shared first step (solve_loop): the B - 1 twin slots the step did not compute take slot B's running maxima,
+// which is what B identical twins would have left in them -- the later steps derive their fp16x3 scales from these slots
+__global__ void amax_share_kernel(float* __restrict__ amax, int stride, int B) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;      // [3 buffers][B - 1 slots]
+  if (i >= 3 * (B - 1)) return;
+  const int k = i / (B - 1), j = i - k * (B - 1);
+  amax[k * stride + B + 1 + j] = amax[k * stride + B];
+}
+
+// are the B clamped lengths the host holds all the same?  (null: no lengths were passed, every utterance has T frames)
+bool lens_all_equal(const int* h_lens, int B, int T) {
+  if (!h_lens) return true;
+  const int l0 = std::min(std::max(h_lens[0], 0), T);
+  for (int b = 1; b < B; ++b)
+    if (std::min(std::max(h_lens[b], 0), T) != l0) return false;
+  return true;
+}
+
 // the Euler loop on packed row buffers (w.mu, w.cond, w.x = z, w.lens2, row metadata): the result is left in w.x
-int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timesteps, hipStream_t st) {
+// lens_equal: the host knows that all B utterances have the same number of frames (it learns so without a copy of its own)
+int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timesteps, bool lens_equal, hipStream_t st) {
   FlowWs& w = *c.flow;
   JV_HIP(hipMemsetAsync(w.step_ctr, 0, sizeof(int), st));
   JV_HIP(hipMemsetAsync(w.amax, 0, sizeof(float) * 3 * w.amax_stride, st));      // trunk bounds: maxima over the whole solve
@@ -215,31 +234,66 @@ int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timest
   g.temb_pre = !c.no_temb_pre && n_timesteps <= TS_MAX;
   if (g.temb_pre) JV_TRY(time_embedding(c, w.t_table, 1, n_timesteps, w.ts_sin, w.ts_1, w.ts_mish, w.ts_emb, st));
   const EstRoute route = est_route(c, g.M, g.temb_pre, g.uoff != nullptr, c.attn_chunk);      // one route for every step (and for a captured one)
-  auto euler_step = [&](hipStream_t s) -> int {
+  // one Euler step over `gg` / `rt` with `ntwin` unconditional twins: B of them, or the one shared twin of step 0 (the row tables
+  // were built for 2B samples: the first B + 1 are a prefix of them), after which the slots it stands for take its maxima
+  auto euler_step = [&](hipStream_t s, const Geo& gg, const EstRoute& rt, int ntwin) -> int {
+    const bool one_twin = ntwin < B;
     hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(256), 0, s, w.t_table, w.dt_table, w.step_ctr, w.t_cur, w.dt_cur,
                        g.temb_pre ? w.ts_emb : nullptr, w.temb);
-    JV_TRY(assemble_xin(w.x, w.mu, w.spks, w.cond, w.xin, B, FLOW_G, g.S, T, g.M, s, g.uoff, w.row_sample, w.rowmask));
-    JV_TRY(estimator_body(c, g, route, s));
-    return euler_cfg(w.x, w.d, B, FLOW_G, g.S, T, w.dt_cur, 0, 0.7f, s, g.uoff, w.lens2);
+    JV_TRY(assemble_xin(w.x, w.mu, w.spks, w.cond, w.xin, B, ntwin, FLOW_G, gg.S, T, gg.M, s, gg.uoff, w.row_sample, w.rowmask));
+    JV_TRY(estimator_body(c, gg, rt, s));
+    JV_TRY(euler_cfg(w.x, w.d, B, FLOW_G, gg.S, T, w.dt_cur, 0, 0.7f, s, gg.uoff, w.lens2, one_twin));
+    if (one_twin) {
+      hipLaunchKernelGGL(amax_share_kernel, dim3((unsigned)cdiv(3 * (B - 1), 64)), dim3(64), 0, s, w.amax, w.amax_stride, B);
+      JV_HIP(hipGetLastError());
+    }
+    return JV_OK;
   };
+  int done = 0;      // steps enqueued so far
+  // ONE unconditional twin for the first step.  Every utterance starts from the same noise prefix, a twin has mu = spks = cond = 0
+  // and t is one scalar: with equal lengths the B twins of step 0 are one sample B times over, so the step runs on B + 1 samples
+  // -- the twin at slot B, reading x of utterance 0 -- and every utterance's CFG update reads that slot.  An utterance's bits do
+  // not depend on the batch or the tile height, but they do differ across the split-K seam: the shorter geometry has to stay on
+  // the row-owning side of it as well.  JV_NO_CFG_SHARE=1: 2B samples in every step.  
+  const long M0 = flow_rows(B + 1, T);
+  if (!c.no_cfg_share && lens_equal && B >= 2 && !g.uoff && M0 > PARTIAL_ROWS && rowgemm_tile((int)M0) != 0) {
+    Geo g0 = g;
+    g0.B2 = B + 1; g0.M = M0; g0.alg_rows = 0;      // (the profiler's frames: (B + 1) T)
+    // ... and every resnet has to take the same launches in both geometries: the one-launch form (which has to fit its rounds,
+    // rowres_fits: a function of the row count) alternates the trunk between w.h and w.h2, the others keep it in w.h, and the
+    // running maxima are kept per BUFFER -- a step 0 on other buffers would leave other maxima, the conditional samples'
+    // included, to the later steps.  Where only the shorter geometry would fit the one-launch form, step 0 does without it
+    auto same_resnets = [](const EstRoute& a, const EstRoute& b) {
+      for (int i = 0; i < EST_NRES; ++i)
+        if (a.stage[i].res != b.stage[i].res || a.stage[i].rows != b.stage[i].rows) return false;
+      return true;
+    };
+    EstRoute route0 = est_route(c, M0, g.temb_pre, false, c.attn_chunk);
+    if (!same_resnets(route0, route)) route0 = est_route(c, M0, g.temb_pre, false, c.attn_chunk, false);
+    if (same_resnets(route0, route)) {      // (always eager: a captured step is a 2B step)
+      JV_TRY(euler_step(st, g0, route0, 1));
+      done = 1;
+    }
+  }
   // The in-library profiler brackets every launch with events, which a capture would turn into graph nodes: eager then.
   const bool use_graph = c.step_graphs && !prof_on() && n_timesteps > 1 && !g.uoff;      // (a captured step is keyed by (B, T): uniform geometry only)
   if (!use_graph) {
-    for (int s = 0; s < n_timesteps; ++s) JV_TRY(euler_step(st));
+    for (int s = done; s < n_timesteps; ++s) JV_TRY(euler_step(st, g, route, B));
   } else {
     FlowWs::StepGraph* sg = nullptr;
     for (auto& e : w.graphs)
       if (e.B == B && e.T == T && e.chunk == c.attn_chunk && e.pre == (int)g.temb_pre) sg = &e;
-    int first = 0;
+    // first solve of this geometry: one 2B step runs eagerly (it also performs the one-time kernel attribute setup), the next
+    // one is captured; it does not execute during capture, so the replay loop starts from it
     if (!sg) {
-      // first solve of this geometry: step 0 runs eagerly (it also performs the one-time kernel attribute setup),
-      // step 1 is captured; it does not execute during capture, so the replay loop starts from it
-      JV_TRY(euler_step(st));
-      first = 1;
-      JV_HIP(hipEventRecord(w.ev_in, st));
-      JV_HIP(hipStreamWaitEvent(w.gstream, w.ev_in, 0));
+      JV_TRY(euler_step(st, g, route, B));
+      ++done;
+    }
+    JV_HIP(hipEventRecord(w.ev_in, st));
+    JV_HIP(hipStreamWaitEvent(w.gstream, w.ev_in, 0));
+    if (!sg) {
       JV_HIP(hipStreamBeginCapture(w.gstream, hipStreamCaptureModeThreadLocal));
-      const int rc = euler_step(w.gstream);
+      const int rc = euler_step(w.gstream, g, route, B);
       hipGraph_t graph = nullptr;
       const hipError_t ce = hipStreamEndCapture(w.gstream, &graph);
       if (rc != JV_OK) {
@@ -259,11 +313,8 @@ int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timest
       }
       w.graphs.push_back({B, T, c.attn_chunk, (int)g.temb_pre, graph, exec});
       sg = &w.graphs.back();
-    } else {
-      JV_HIP(hipEventRecord(w.ev_in, st));
-      JV_HIP(hipStreamWaitEvent(w.gstream, w.ev_in, 0));
     }
-    for (int s = first; s < n_timesteps; ++s) JV_HIP(hipGraphLaunch(sg->exec, w.gstream));
+    for (int s = done; s < n_timesteps; ++s) JV_HIP(hipGraphLaunch(sg->exec, w.gstream));
     JV_HIP(hipEventRecord(w.ev_out, w.gstream));
     JV_HIP(hipStreamWaitEvent(st, w.ev_out, 0));
   }
@@ -307,7 +358,9 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
   // z = rand_noise[:, :, :T] * temperature, the same prefix for every utterance (flow_matching.py:385)
   JV_TRY(cf_to_rows(c.noise, 0, NOISE_FRAMES, B, 80, T, w.x, 80, 0, FLOW_G, g.S, temperature, clens, st, g.uoff));
 
-  JV_TRY(solve_loop(c, g, spks, B, T, n_timesteps, st));
+  // (equal lengths: known where none were passed or where the ragged check brought them down)
+  const bool lens_equal = !lens_dev || (ragged_candidate && lens_all_equal(w.h_lens, B, T));
+  JV_TRY(solve_loop(c, g, spks, B, T, n_timesteps, lens_equal, st));
   // unpack
   return rows_to_cf(w.x, 80, 0, FLOW_G, g.S, mel, 80L * T, B, 80, T, lens_dev ? w.lens2 : nullptr, st, g.uoff);
 }
@@ -365,7 +418,7 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
   // z = rand_noise[:, :, :p_b + y_b] * temperature: column j is frame j of the utterance's own sequence (flow_matching.py:385)
   JV_TRY(cf_to_rows(c.noise, 0, NOISE_FRAMES, B, 80, T, w.x, 80, 0, FLOW_G, g.S, temperature, clens, st, g.uoff));
 
-  JV_TRY(solve_loop(c, g, spks, B, T, n_timesteps, st));
+  JV_TRY(solve_loop(c, g, spks, B, T, n_timesteps, lens_all_equal(w.h_sum, B, T), st));
   // unpack: the generated frames only (jyutvoice_tts.py:244 `decoder_outputs[:, :, mel_len1:]`), zeros behind y_b
   return rows_to_cf_from(w.x, 80, FLOW_G, g.S, prompt_lens, y_lens, mel, 80L * Ty, B, 80, Ty, st, g.uoff);
 }
@@ -437,7 +490,7 @@ int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* t
 
   const int chunk_was = c.attn_chunk;
   c.attn_chunk = streaming ? T2M_EST_CHUNK : 0;
-  const int rc = solve_loop(c, g, spks, B, T, n_timesteps, st);
+  const int rc = solve_loop(c, g, spks, B, T, n_timesteps, lens_all_equal(w.h_sum, B, T), st);
   c.attn_chunk = chunk_was;
   JV_TRY(rc);
   if (mel_lens) JV_HIP(hipMemcpyAsync(mel_lens, yl, sizeof(int) * B, hipMemcpyDeviceToDevice, st));

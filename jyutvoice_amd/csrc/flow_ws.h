@@ -115,7 +115,8 @@ struct EstRoute {
 };
 
 // estimator.hip
-EstRoute est_route(const Context& c, long M, bool temb_pre, bool compact, int attn_chunk);
+// res_one = false: no whole-resnet launch even where it fits (a solve's shared first step keeps the later steps' resnet route)
+EstRoute est_route(const Context& c, long M, bool temb_pre, bool compact, int attn_chunk, bool res_one = true);
 int time_embedding(Context& c, const float* t, int t_stride, int n, float* sin_buf, float* h1, float* hm, float* emb, hipStream_t st);
 // the estimator body on prepared inputs: ws.xin [rows,320], ws.rowmask/row_sample/lens2, ws.t_dev [B2] -> ws.d [rows,80]
 int estimator_body(Context& c, const Geo& g, const EstRoute& rt, hipStream_t st);

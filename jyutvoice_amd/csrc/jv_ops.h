@@ -24,14 +24,15 @@ int pack_prompted(const float* mu_y, int Ty, const float* prompt_h, int Ph, cons
                   const int* clens = nullptr);
 int rows_to_cf_from(const float* src, int ld, int G, int S, const int* first, const int* lens, float* dst, long dst_bstride,
                     int B, int C, int T, hipStream_t st, const int* uoff = nullptr);
-int assemble_xin(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int G, int S,
-                 int L, long rows2, hipStream_t st, const int* uoff = nullptr, const int* row_sample = nullptr,
+// ntwin: the unconditional twin slots to fill behind the B conditional ones (B, or 1: the twin a solve's first step shares)
+int assemble_xin(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int ntwin, int G,
+                 int S, int L, long rows2, hipStream_t st, const int* uoff = nullptr, const int* row_sample = nullptr,
                  const unsigned char* rowmask = nullptr);
 int assemble_xin_plain(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int G,
                        int S, int L, long rows, hipStream_t st);
 int time_sinusoid(const float* t, int t_stride, float* out, int B, hipStream_t st);
 int euler_cfg(float* x, const float* d, int B, int G, int S, int L, const float* dt_table, int step, float rate,
-              hipStream_t st, const int* uoff = nullptr, const int* lens = nullptr);
+              hipStream_t st, const int* uoff = nullptr, const int* lens = nullptr, bool one_twin = false);      // one_twin: every utterance reads the twin at slot B
 int ln_epilogue_rows(float* x, const float* g, const float* b, float eps, long rows, int C, int act,
                      const unsigned char* rowmask, const float* rowvec, const int* row_sample, int rowvec_ld, const float* res,
                      long ldr, float scale, hipStream_t st, float* amax_out = nullptr, int amax_G = 0, int amax_S = 0,

@@ -494,10 +494,12 @@ int rows_to_cf_from(const float* src, int ld, int G, int S, const int* first, co
 // ---- flow estimator input: [x | mu | spks | cond] per row, CFG rows appended ---------------------------
 // rows of utterance b' < B are conditional; b' >= B are the unconditional twin of b' - B (mu = spks = cond = 0),
 // jyutvoice/flow/flow_matching.py:246-251.  x/mu/cond are row buffers of 80 columns with geometry (G,S).
+// ntwin: the twin slots to fill, B .. B + ntwin - 1 (B: one per utterance; 1: the one twin a solve's first step shares, x of
+// utterance 0 -- flow.hip solve_loop)
 __global__ __launch_bounds__(256) void assemble_xin_kernel(const float* __restrict__ x, const float* __restrict__ mu,
                                                            const float* __restrict__ spks, const float* __restrict__ cond,
-                                                           float* __restrict__ xin, int B, int G, int S, int L, long rows2,
-                                                           const int* __restrict__ uoff, const int* __restrict__ row_sample,
+                                                           float* __restrict__ xin, int B, int ntwin, int G, int S, int L,
+                                                           long rows2, const int* __restrict__ uoff, const int* __restrict__ row_sample,
                                                            const unsigned char* __restrict__ rowmask) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;   // one f32x4 (4 of 320 columns) per thread
   const long r = idx / 80;
@@ -509,7 +511,7 @@ __global__ __launch_bounds__(256) void assemble_xin_kernel(const float* __restri
     // compact geometry (row_meta): the row's utterance and validity come from the row tables, its frame from uoff
     const int b2 = uoff ? row_sample[r] : (int)(rel / S);
     const int t = uoff ? (rowmask[r] ? (int)(r - uoff[b2]) : L) : (int)(rel - (long)b2 * S);
-    if (b2 < 2 * B && t < L) {
+    if (b2 < B + ntwin && t < L) {
       const bool un = b2 >= B;
       const int b = un ? b2 - B : b2;
       const long sr = uoff ? (long)uoff[b] + t : (long)G + (long)b * S + t;
@@ -525,11 +527,12 @@ __global__ __launch_bounds__(256) void assemble_xin_kernel(const float* __restri
   *reinterpret_cast<f32x4*>(xin + r * 320 + 4 * c4) = v;
 }
 
-int assemble_xin(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int G, int S,
-                 int L, long rows2, hipStream_t st, const int* uoff, const int* row_sample, const unsigned char* rowmask) {
+int assemble_xin(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int ntwin, int G,
+                 int S, int L, long rows2, hipStream_t st, const int* uoff, const int* row_sample, const unsigned char* rowmask) {
   if (uoff && (!row_sample || !rowmask)) return fail(JV_ERR_ARG, "assemble_xin: the compact geometry needs the row tables");
+  if (ntwin < 1 || ntwin > B) return fail(JV_ERR_ARG, "assemble_xin: between one twin slot and one per utterance");
   hipLaunchKernelGGL(assemble_xin_kernel, dim3((unsigned)cdivl(rows2 * 80, 256)), dim3(256), 0, st, x, mu, spks, cond, xin,
-                     B, G, S, L, rows2, uoff, row_sample, rowmask);
+                     B, ntwin, G, S, L, rows2, uoff, row_sample, rowmask);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }
@@ -586,9 +589,10 @@ int time_sinusoid(const float* t, int t_stride, float* out, int B, hipStream_t s
 
 // ---- Euler step with classifier-free guidance: x += dt * ((1+r) d_cond - r d_uncond) ----------------------
 // d holds 2B utterances (geometry G,S); step scalars come from a device table so the loop never syncs.
+// one_twin (uniform geometry): every utterance reads the one twin at slot B (a solve's shared first step)
 __global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ x, const float* __restrict__ d, int B, int G, int S,
                                                         int L, const float* __restrict__ dt_table, int step, float rate,
-                                                        const int* __restrict__ uoff, const int* __restrict__ lens) {
+                                                        const int* __restrict__ uoff, const int* __restrict__ lens, bool one_twin) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;   // f32x4 index over B*L*20
   const long per_b = (long)L * 20;
   if (idx >= per_b * B) return;
@@ -597,7 +601,7 @@ __global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ x, c
   const long t = rem / 20;
   if (uoff && t >= lens[b]) return;      // compact geometry: the rows behind an utterance's frames are the next utterance's
   const long r = uoff ? (long)uoff[b] + t : (long)G + (long)b * S + t;
-  const long ru = uoff ? (long)uoff[b + B] + t : r + (long)B * S;      // the unconditional twin's row
+  const long ru = uoff ? (long)uoff[b + B] + t : (long)G + (long)(B + (one_twin ? 0 : b)) * S + t;      // the unconditional twin's row
   const int cc = (int)(rem % 20) * 4;
   const float dt = dt_table[step];
   const f32x4 dc = *reinterpret_cast<const f32x4*>(d + r * 80 + cc);
@@ -609,10 +613,11 @@ __global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ x, c
 }
 
 int euler_cfg(float* x, const float* d, int B, int G, int S, int L, const float* dt_table, int step, float rate,
-              hipStream_t st, const int* uoff, const int* lens) {
+              hipStream_t st, const int* uoff, const int* lens, bool one_twin) {
   if (uoff && !lens) return fail(JV_ERR_ARG, "euler_cfg: the compact geometry needs the lengths");
+  if (uoff && one_twin) return fail(JV_ERR_ARG, "euler_cfg: one shared twin exists in the uniform geometry only");
   hipLaunchKernelGGL(euler_cfg_kernel, dim3((unsigned)cdivl((long)B * L * 20, 256)), dim3(256), 0, st, x, d, B, G, S, L,
-                     dt_table, step, rate, uoff, lens);
+                     dt_table, step, rate, uoff, lens, one_twin);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

@@ -22,7 +22,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 SWITCHES = ["JV_NO_ROWGEMM", "JV_DMA_A", "JV_NO_FFN_FUSE", "JV_NO_BLOCK_FUSE", "JV_NO_QKV_SPLIT", "JV_NO_LN_FOLD", "JV_NO_RES_FOLD",
-            "JV_NO_RES_PAIR", "JV_NO_RES_QKV", "JV_NO_TEMB_PRE", "JV_NO_COMPACT", "JV_FF_STAGGER", "JV_EXACT_RANGE", "JV_STEP_GRAPH",
+            "JV_NO_RES_PAIR", "JV_NO_RES_QKV", "JV_NO_TEMB_PRE", "JV_NO_CFG_SHARE", "JV_NO_COMPACT", "JV_FF_STAGGER", "JV_EXACT_RANGE", "JV_STEP_GRAPH",
             "JV_NO_HIFTCONV", "JV_NO_HIFT_PAIR"]
 SETTINGS = {"default": {}}
 SETTINGS.update({s: {s: "1"} for s in SWITCHES})
