@@ -10,7 +10,7 @@
 //   * the WHOLE window -- 80 NG + (k - 1) d rows x C channels -- goes through Snake and the plane split ONCE, into LDS
 //     (130 x 256, 210 x 128 or 370 x 64 values: 93 - 139 KB), and every tap of every chunk reads it in place at a row offset:
 //     no staging, no DMA and no barrier inside the main loop;
-//   * the weights arrive in fragment order through the register double buffer with hand-counted waits (rowgemm_wd_kernel);
+//   * the weights arrive in fragment order through the register double buffer with hand-counted waits (WFragBuf: row_mainloop.h);
 //   * v_mfma_f32_16x16x32_f16; the epilogue (bias, residuals, scaling, accumulation, measured-bound tracking) runs per wave
 //     through a private transposition patch, no workgroup barrier: one wave's stores run under the others' MFMAs.
 // Arithmetic: the tile kernels' (same Snake evaluation, same per-utterance power-of-two scale from the measured bound, products
@@ -95,19 +95,12 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
 #pragma unroll
     for (int pl = 0; pl < 2; ++pl) wp[nt][pl] = p.Wf + (long)pl * p.wf_plane + (long)(2 * cp + nt) * 512 + lane * 8;
   int wk = 0;
-  rg_u32x4 bq[2][2][2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) bq[i >> 2][(i >> 1) & 1][i & 1] = rg_u32x4{0u, 0u, 0u, 0u};
-  auto load_frag = [](rg_u32x4& dst, const unsigned short* ptr) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(dst) : "v"(ptr) : "memory");
-  };
+  WFragBuf<2> bq;
+  bq.zero();
   auto load_w = [&](auto par_tag, auto nttag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    load_frag(bq[par][nt][0], wp[nt][0]);
-    load_frag(bq[par][nt][1], wp[nt][1]);
-  };
-  auto landed_w = [](rg_u32x4& b00, rg_u32x4& b01, rg_u32x4& b10, rg_u32x4& b11) {
-    asm volatile("" : "+v"(b00), "+v"(b01), "+v"(b10), "+v"(b11)::"memory");
+    bq.template load<par, nt, 0>(wp[nt][0]);
+    bq.template load<par, nt, 1>(wp[nt][1]);
   };
   auto advance_w = [&]() {      // + C / 16 blocks x 1 KB (512 halves) per step; past the end: back to the first step (weights that exist)
     constexpr long WSTEP = 512L * (C / 16);
@@ -226,8 +219,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
   rg_f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
   if (p.bias) b4 = *reinterpret_cast<const rg_f32x4*>(p.bias + ncol);
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   rg_lds_barrier();      // the operand image is complete: the only barrier ahead of the epilogue
 
   // ---- main loop: step ks = (tap j = ks / NCH, chunk c = ks % NCH); A fragments of row tile mt at window row
@@ -242,11 +234,8 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
   auto read_a = [&](auto par_tag, const int c, const int j) {
     constexpr int par = decltype(par_tag)::value;
     const int lrow = r16 + j * p.dil;
-    const unsigned char* const a = gimg + c * CS + lrow * 64 + ((kq ^ rg_key(lrow)) << 4);
-#pragma unroll
-    for (int mt = 0; mt < RT; ++mt)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) af[par][mt][pl] = *reinterpret_cast<const rg_u32x4*>(a + pl * PS + mt * 1024);
+    const unsigned char* const a = gimg + c * CS + lrow * 64 + afrag_slot(lrow, kq);
+    afrag_read<RT>(af[par], a, PS);
   };
   int nc = 1, nj = 0;      // chunk and tap of the NEXT step
   read_a(std::integral_constant<int, 0>{}, 0, 0);
@@ -256,14 +245,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
       constexpr int nt = decltype(nttag)::value;
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt) {
-        rg_f32x4 t = acc[mt][nt];
-        auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-          t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-        };
-        mm(af[par][mt][1], bq[par][nt][0]);      // smallest terms first, as everywhere
-        mm(af[par][mt][0], bq[par][nt][1]);
-        mm(af[par][mt][0], bq[par][nt][0]);
-        acc[mt][nt] = t;
+        acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
       }
       __builtin_amdgcn_sched_barrier(0);
       load_w(par_tag, nttag);
@@ -273,7 +255,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
     // W0(s+1) and W1(s); behind W0(s+1): W1(s+1) and W0(s+2) = NWL loads (rowgemm_wa_kernel)
     block(std::integral_constant<int, 0>{});
     rg_wait_vmcnt<NWL>();
-    landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+    bq.template landed_mid<par>();
     if (!last) read_a(std::integral_constant<int, par ^ 1>{}, nc, nj);
     __builtin_amdgcn_sched_barrier(0);
     block(std::integral_constant<int, 1>{});
@@ -371,10 +353,9 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
       cur = nxt;
     }
   }
-  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (rowgemm_wd_kernel)
+  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
 }
 
 }  // namespace jv

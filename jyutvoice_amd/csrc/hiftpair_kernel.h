@@ -20,7 +20,7 @@
 //   5. per-wave epilogue: + bias + x (re-read: 41 KB per workgroup, L2-warm) (+ a second residual), scaling, accumulation,
 //      measured-bound tracking of what is stored -- hiftconv_kernel's.
 // The weights of both convolutions arrive as ONE fragment stream (k-step major fragments: the second's steps follow the first's,
-// registry.hip) through the register double buffer with hand-counted waits (rowgemm_wd_kernel's rules; tools/check_rowgemm_isa.py).
+// registry.hip) through the register double buffer with hand-counted waits (WFragBuf's rules: row_mainloop.h; tools/check_rowgemm_isa.py).
 //
 // The intermediate's fp16x3 scale.  Unfused, the first launch MEASURES max |xt| per utterance and the second derives its power
 // of two from it.  Here no such maximum exists before the intermediate is consumed, so the scale comes from a BOUND instead:
@@ -130,19 +130,12 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
 #endif
   constexpr int NB = JV_HP_WBUF;
   static_assert(NB == 2 || NB == 3, "two or three weight buffers");
-  rg_u32x4 bq[NB][2][2];
-#pragma unroll
-  for (int i = 0; i < 4 * NB; ++i) bq[i >> 2][(i >> 1) & 1][i & 1] = rg_u32x4{0u, 0u, 0u, 0u};
-  auto load_frag = [](rg_u32x4& dst, const unsigned short* ptr) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(dst) : "v"(ptr) : "memory");
-  };
+  WFragBuf<NB> bq;
+  bq.zero();
   auto load_w = [&](auto par_tag, auto nttag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    load_frag(bq[par][nt][0], wp[nt][0]);
-    load_frag(bq[par][nt][1], wp[nt][1]);
-  };
-  auto landed_w = [](rg_u32x4& b00, rg_u32x4& b01, rg_u32x4& b10, rg_u32x4& b11) {
-    asm volatile("" : "+v"(b00), "+v"(b01), "+v"(b10), "+v"(b11)::"memory");
+    bq.template load<par, nt, 0>(wp[nt][0]);
+    bq.template load<par, nt, 1>(wp[nt][1]);
   };
   auto advance_w = [&]() {      // + C / 16 blocks x 1 KB (512 halves) per step; past the end: back to the first step (weights that exist)
     constexpr long WSTEP = 512L * (C / 16);
@@ -276,9 +269,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
   rg_f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
   if (p.b2) b4 = *reinterpret_cast<const rg_f32x4*>(p.b2 + ncol);
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
-  if constexpr (NB == 3) landed_w(bq[NB - 1][0][0], bq[NB - 1][0][1], bq[NB - 1][1][0], bq[NB - 1][1][1]);
+  bq.landed_all();
   rg_lds_barrier();      // the window's image is complete
 
   // ---- the two products: step ks = (tap j = ks / NCH, chunk c = ks % NCH); A fragments of row tile mt at image row
@@ -289,11 +280,8 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
   auto read_a = [&](auto par_tag, const int c, const int j) {
     constexpr int par = decltype(par_tag)::value;
     const int lrow = r16 + j * idil;
-    const unsigned char* const a = img + grp * RG * 64 + c * ics + lrow * 64 + ((kq ^ rg_key(lrow)) << 4);
-#pragma unroll
-    for (int mt = 0; mt < RT; ++mt)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) af[par][mt][pl] = *reinterpret_cast<const rg_u32x4*>(a + pl * ips + mt * 1024);
+    const unsigned char* const a = img + grp * RG * 64 + c * ics + lrow * 64 + afrag_slot(lrow, kq);
+    afrag_read<RT>(af[par], a, ips);
   };
   int nc = 1, nj = 0;      // chunk and tap of the NEXT step
   // a step multiplies the A fragments of parity `par` (requested by the step before) with the weight buffer `buf` and
@@ -304,14 +292,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
       constexpr int nt = decltype(nttag)::value;
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt) {
-        rg_f32x4 t = acc[mt][nt];
-        auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-          t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-        };
-        mm(af[par][mt][1], bq[buf][nt][0]);      // smallest terms first, as everywhere
-        mm(af[par][mt][0], bq[buf][nt][1]);
-        mm(af[par][mt][0], bq[buf][nt][0]);
-        acc[mt][nt] = t;
+        acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[buf][nt][0], bq.q[buf][nt][1]);
       }
       __builtin_amdgcn_sched_barrier(0);
       load_w(buf_tag, nttag);
@@ -321,7 +302,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
     // wait: W0(s+1) and W1(s); behind W0(s+1): W1(s+1) .. W0(s+NB) = 2 (NB - 1) load pairs (rowgemm_wa_kernel's count at NB = 2)
     block(std::integral_constant<int, 0>{});
     rg_wait_vmcnt<NWL * (NB - 1)>();
-    landed_w(bq[buf][1][0], bq[buf][1][1], bq[(buf + 1) % NB][0][0], bq[(buf + 1) % NB][0][1]);
+    bq.template landed_mid<buf>();
     if (!last) read_a(std::integral_constant<int, par ^ 1>{}, nc, nj);
     __builtin_amdgcn_sched_barrier(0);
     block(std::integral_constant<int, 1>{});
@@ -482,11 +463,9 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
       cur = nxt;
     }
   }
-  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (rowgemm_wd_kernel)
+  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
-  if constexpr (NB == 3) landed_w(bq[NB - 1][0][0], bq[NB - 1][0][1], bq[NB - 1][1][0], bq[NB - 1][1][1]);
+  bq.landed_all();
 }
 
 }  // namespace jv

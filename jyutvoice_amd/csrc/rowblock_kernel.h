@@ -19,7 +19,7 @@
 // the 64-byte groups of a row are XOR-ed with bits 2..3 of the row, which keeps the MFMA-layout writes on 64 distinct banks
 // and the row pass's 16-byte reads aligned.
 //
-// The weight fragments of all four linears arrive through ONE register double buffer (rowgemm_wd_kernel explains the
+// The weight fragments of all four linears arrive through ONE register double buffer (WFragBuf, row_mainloop.h; rowgemm_wd_kernel explains the
 // hand-counted waits): the loader walks a sequence of 8-step segments -- Wo k 0..7, Wo k 8..15, then per hidden chunk
 // W1[chunk] and W2[k-steps of the chunk], then the six 256-column chunks of Wqkv -- two steps ahead of the MFMAs, and
 // wraps around to the first segment past the end (those loads land in registers nothing reads).
@@ -237,19 +237,12 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
         wp[nt][pl] = base + (long)pl * plane + ((long)k0 * nbm + blk0 + 2 * wave + nt) * 512 + lane * 8;
   };
   quad_ptrs(0);
-  rg_u32x4 bq[2][2][2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) bq[i >> 2][(i >> 1) & 1][i & 1] = rg_u32x4{0u, 0u, 0u, 0u};
-  auto load_frag = [](rg_u32x4& dst, const unsigned short* ptr) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(dst) : "v"(ptr) : "memory");
-  };
+  WFragBuf<2> bq;
+  bq.zero();
   auto load_w = [&](auto par_tag, auto nttag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    load_frag(bq[par][nt][0], wp[nt][0]);
-    load_frag(bq[par][nt][1], wp[nt][1]);
-  };
-  auto landed_w = [](rg_u32x4& b00, rg_u32x4& b01, rg_u32x4& b10, rg_u32x4& b11) {
-    asm volatile("" : "+v"(b00), "+v"(b01), "+v"(b10), "+v"(b11)::"memory");
+    bq.template load<par, nt, 0>(wp[nt][0]);
+    bq.template load<par, nt, 1>(wp[nt][1]);
   };
   auto advance_w = [&]() {
     if (++wj == 4) {
@@ -264,26 +257,15 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
     }
   };
 
-  const int fslot = (kq ^ rg_key(r16)) << 4;
-  const int a_off = r16 * 64 + fslot;
+  const int a_off = afrag_off(r16, kq);
   rg_u32x4 af[2][RT][2];
   auto read_a = [&](auto par_tag, const unsigned char* st) {
     constexpr int par = decltype(par_tag)::value;
-#pragma unroll
-    for (int mt = 0; mt < RT; ++mt)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) af[par][mt][pl] = *reinterpret_cast<const rg_u32x4*>(st + a_off + pl * A_PLANE + mt * 1024);
+    afrag_read<RT>(af[par], st + a_off, A_PLANE);
   };
   auto mfma_block = [&](auto par_tag, auto nttag, rg_f32x4 (&acc)[RT][2], auto mt_tag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value, mt = decltype(mt_tag)::value;
-    rg_f32x4 t = acc[mt][nt];
-    auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-      t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-    };
-    mm(af[par][mt][1], bq[par][nt][0]);      // smallest terms first, as everywhere
-    mm(af[par][mt][0], bq[par][nt][1]);
-    mm(af[par][mt][0], bq[par][nt][0]);
-    acc[mt][nt] = t;
+    acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
   };
 
   // ---- prologue: ring stages 0..2, W of steps 0 and 1; everything waited for once ----
@@ -304,8 +286,7 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
     }
   }
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   // A warm-up value is "used" (an empty asm) where the wait costs nothing and is dead from then on.  Kept alive to the end
   // of the kernel it crossed the feed-forward loop -- in scratch: the compiler spilled it right behind the load, i.e. put an
   // s_waitcnt vmcnt(0) on a load that is an L2 miss BY DESIGN in front of phase A's epilogue (6 k cycles in the stamps).
@@ -354,7 +335,7 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
       } else {
         rg_wait_vmcnt<NWL>();
       }
-      landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+      bq.template landed_mid<par>();
       rg_barrier();
       const int s3n = s3 == 2 ? 0 : s3 + 1;
       if (s + 1 < KSA) read_a(std::integral_constant<int, par ^ 1>{}, hreg + s3n * STAGE);
@@ -512,7 +493,7 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
     block(std::integral_constant<int, 0>{});
     if (!waited) rg_wait_vmcnt<NWL>();
     waited = false;
-    landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+    bq.template landed_mid<par>();
     if (st_next) read_a(std::integral_constant<int, par ^ 1>{}, st_next);
     __builtin_amdgcn_sched_barrier(0);
     block(std::integral_constant<int, 1>{});
@@ -779,10 +760,9 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
       stamp();      // 18 + 2 c: chunk epilogue done
     }
   }
-  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (rowgemm_wd_kernel)
+  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   stamp();      // last: drained
 }
 

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
     }
   };
 
-  const int w_off = (wave * 32 + r16) * 64 + ((kq ^ rg_key(r16)) << 4);      // + pl * W_PLANE + nt * 1024
+  const int w_off = (wave * 32 + r16) * 64 + afrag_slot(r16, kq);      // + pl * W_PLANE + nt * 1024
 
   rg_f32x4 acc[RT][2];
 #pragma unroll
@@ -245,20 +245,13 @@ __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
       auto group = [&](auto mtag) {
         constexpr int mt = decltype(mtag)::value;
         const int row = mt * 16 + r16 + j;
-        const int a_off = row * 64 + ((kq ^ rg_key(row)) << 4);
+        const int a_off = afrag_off(row, kq);
         rg_u32x4 a[2];
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) a[pl] = *reinterpret_cast<const rg_u32x4*>(sa + pl * A_PLANE + a_off);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          rg_f32x4 t = acc[mt][nt];
-          auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-          };
-          mm(a[1], b[nt][0]);
-          mm(a[0], b[nt][1]);
-          mm(a[0], b[nt][0]);
-          acc[mt][nt] = t;
+          acc[mt][nt] = h3_mma(acc[mt][nt], a[0], a[1], b[nt][0], b[nt][1]);
         }
         if (more) {
           if constexpr (mt < PPW) issue_piece(std::integral_constant<int, (mt < PPW ? mt : 0)>{}, nstage);
@@ -388,7 +381,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
   }
 
   // ---- W: fragment order over K = NJ Cin (k = j Cin + 32 c is fragment step j NCH + c), a register double buffer loaded by
-  // inline asm with counted waits -- rowgemm_wd_kernel's, including its rules (tools/check_rowgemm_isa.py covers this kernel)
+  // inline asm with counted waits -- WFragBuf and its rules (row_mainloop.h; tools/check_rowgemm_isa.py covers this kernel)
   const unsigned short* wbase[2][2];
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
@@ -396,19 +389,12 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
     for (int pl = 0; pl < 2; ++pl) wbase[nt][pl] = p.Wf + (long)pl * p.wf_plane + (long)(wave * 2 + nt) * 512 + lane * 8;
   long woff = 0;       // halves: fragment step of the NEXT step to load, x 16 column blocks x 512 (k-step major: pack_wfrag)
   int wj = 0, wc = 0;  // its tap and chunk
-  rg_u32x4 bq[2][2][2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) bq[i >> 2][(i >> 1) & 1][i & 1] = rg_u32x4{0u, 0u, 0u, 0u};
-  auto load_frag = [](rg_u32x4& dst, const unsigned short* ptr) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(dst) : "v"(ptr) : "memory");
-  };
+  WFragBuf<2> bq;
+  bq.zero();
   auto load_w = [&](auto par_tag, auto nttag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    load_frag(bq[par][nt][0], wbase[nt][0] + woff);
-    load_frag(bq[par][nt][1], wbase[nt][1] + woff);
-  };
-  auto landed_w = [](rg_u32x4& b00, rg_u32x4& b01, rg_u32x4& b10, rg_u32x4& b11) {
-    asm volatile("" : "+v"(b00), "+v"(b01), "+v"(b10), "+v"(b11)::"memory");
+    bq.template load<par, nt, 0>(wbase[nt][0] + woff);
+    bq.template load<par, nt, 1>(wbase[nt][1] + woff);
   };
   auto advance_w = [&]() {      // (c, j) -> (c, j + 1): + NCH steps; (c, NJ - 1) -> (c + 1, 0): + 1 - (NJ - 1) NCH; past the end: back to 0
     if (++wj == NJ) {
@@ -550,8 +536,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
   if (NCH > 1) load_A(1);
   // both steps' fragments (and everything older) have landed once only the A loads of chunk 1 are outstanding
   if (NCH > 1) rg_wait_vmcnt<NI>(); else rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   stamp();      // 2: first window staged, first fragments landed
 
   // One step = (chunk c, tap j): block 0 (column block 0 x all row groups, A fragments at row offset j of the chunk's window),
@@ -576,7 +561,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
 #pragma unroll
     for (int mt = 0; mt < RT; ++mt) {
       const int row = mt * 16 + r16 + jrow;
-      const int a_off = row * 64 + ((kq ^ rg_key(row)) << 4);
+      const int a_off = afrag_off(row, kq);
 #pragma unroll
       for (int pl = 0; pl < 2; ++pl) af[mt][pl] = *reinterpret_cast<const rg_u32x4*>(sa + pl * A_PLANE + a_off);
     }
@@ -585,14 +570,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
       constexpr int nt = decltype(nttag)::value;
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt) {
-        rg_f32x4 t = ac[mt][nt];
-        auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-          t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-        };
-        mm(af[mt][1], bq[par][nt][0]);
-        mm(af[mt][0], bq[par][nt][1]);
-        mm(af[mt][0], bq[par][nt][0]);
-        ac[mt][nt] = t;
+        ac[mt][nt] = h3_mma(ac[mt][nt], af[mt][0], af[mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
       }
       __builtin_amdgcn_sched_barrier(0);
       load_w(par_tag, nttag);
@@ -601,7 +579,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
     auto blocks = [&](rg_f32x4 (&ac)[RT][2]) {
       block(std::integral_constant<int, 0>{}, ac);
       if (j == 1 && c + 2 < NCH) rg_wait_vmcnt<NWL + NI>(); else rg_wait_vmcnt<NWL>();
-      landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+      bq.template landed_mid<par>();
       block(std::integral_constant<int, 1>{}, ac);
     };
     if constexpr (j == 3) blocks(accr); else blocks(acc);      // (res_conv's step: the second accumulator)
@@ -763,9 +741,8 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
       if (mrow < p.M) *(__attribute__((address_space(1))) rg_f32x4*)(p.res_out + mrow * 256 + 4 * lane) = v;
     }
   }
-  rg_wait_vmcnt<0>();      // the wrapped-around W loads: bq stays reserved until they have landed (rowgemm_wd_kernel)
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  rg_wait_vmcnt<0>();      // the wrapped-around W loads: bq stays reserved until they have landed (WFragBuf, rule c)
+  bq.landed_all();
   asm volatile("" ::"v"(warm));
   stamp();      // 7 (6 without the res_conv pass): every store of this wave acknowledged
 }

@@ -26,7 +26,7 @@
 
 #include "jv_common.h"
 #include "jv_device.h"
-#include "row_tail.h"
+#include "row_mainloop.h"
 
 namespace jv {
 
@@ -82,11 +82,6 @@ constexpr int RG_SLAB_ROWS = 32;
 constexpr int RG_SLAB_BYTES = RG_SLAB_ROWS * RG_SLD * 4;
 template <int RT> constexpr int rg_stage_bytes() { return 2 * 16 * RT * 64 + 2 * 256 * 64; }
 template <int RT> constexpr int rg_lds_bytes() { return 3 * rg_stage_bytes<RT>() + RG_SLAB_BYTES; }
-
-// 16-byte slot key of a row inside its 16-row group: with 64-byte rows (32 fp16), lane l of a 16x16x32 fragment read
-// takes row l & 15, k-slot l >> 4; XOR-ing bit 1 of the slot with bit 2 of the row puts the 16 lanes of every
-// ds_read_b128 lane group on 16 distinct 16-byte bank slots (brute-forced over the four lane groups of MI355X_MICROARCH.md)
-__device__ __forceinline__ int rg_key(int r) { return ((r >> 2) & 1) << 1; }
 
 template <int N>
 __device__ __forceinline__ void rg_wait_vmcnt() {
@@ -199,9 +194,8 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
   };
 
   // per-lane fragment addresses inside a stage
-  const int fslot = (kq ^ rg_key(r16)) << 4;
-  const int a_off = r16 * 64 + fslot;                                   // + pl * A_PLANE + mt * 1024
-  const int w_off = W_OFF + (wave * 32 + r16) * 64 + fslot;             // + pl * W_PLANE + nt * 1024
+  const int a_off = afrag_off(r16, kq);                                              // + pl * A_PLANE + mt * 1024
+  const int w_off = W_OFF + (wave * 32 + r16) * 64 + afrag_slot(r16, kq);            // + pl * W_PLANE + nt * 1024
 
   rg_f32x4 acc[RT][2];
   issue_all(0);
@@ -245,14 +239,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
         for (int pl = 0; pl < 2; ++pl) a[pl] = *reinterpret_cast<const rg_u32x4*>(st + a_off + pl * A_PLANE + mt * 1024);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          rg_f32x4 t = acc[mt][nt];
-          auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-          };
-          mm(a[1], b[nt][0]);      // smallest terms first, as the tile kernels do
-          mm(a[0], b[nt][1]);
-          mm(a[0], b[nt][0]);
-          acc[mt][nt] = t;
+          acc[mt][nt] = h3_mma(acc[mt][nt], a[0], a[1], b[nt][0], b[nt][1]);
         }
         // this group's share of the next-but-one step's DMA: pieces mt, mt + RT, ... of the wave's list
         if (more) {
@@ -491,24 +478,14 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
     for (int pl = 0; pl < 2; ++pl) wbase[nt][pl] = p.Wf + (long)pl * p.wf_plane + (long)(wave * 2 + nt) * 512 + lane * 8;
   long woff = 0;
   int wk = 0;
-  // The register double buffer is loaded and waited for by hand (inline asm): left to the compiler, the wait in front of
-  // the first MFMA of a step becomes s_waitcnt vmcnt(0) -- its bookkeeping gives up on loads carried around the loop --
-  // and the two steps of lookahead are gone.  The asm load is invisible to that bookkeeping, so (a) nothing but the MFMAs
-  // below may read bq, which the "+v" operands of wait_w order behind the counted wait, and (b) the register allocator
-  // must not copy bq while a load is in flight: tools/check_rowgemm_isa.py checks the built code object for both.
-  rg_u32x4 bq[2][2][2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) bq[i >> 2][(i >> 1) & 1][i & 1] = rg_u32x4{0u, 0u, 0u, 0u};
-  auto load_frag = [](rg_u32x4& dst, const unsigned short* ptr) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(dst) : "v"(ptr) : "memory");
-  };
+  // The register double buffer, loaded and waited for by hand: WFragBuf (row_mainloop.h) has the rules that make it sound.
+  // This kernel's own part is the walker below and the derivation of its counted wait, ahead of `step`.
+  WFragBuf<2> bq;
+  bq.zero();
   auto load_w = [&](auto par_tag, auto nttag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    load_frag(bq[par][nt][0], wbase[nt][0] + woff);
-    load_frag(bq[par][nt][1], wbase[nt][1] + woff);
-  };
-  auto landed_w = [](rg_u32x4& b00, rg_u32x4& b01, rg_u32x4& b10, rg_u32x4& b11) {
-    asm volatile("" : "+v"(b00), "+v"(b01), "+v"(b10), "+v"(b11)::"memory");
+    bq.template load<par, nt, 0>(wbase[nt][0] + woff);
+    bq.template load<par, nt, 1>(wbase[nt][1] + woff);
   };
   int wc = 0;
   const long wstep = 512L * 16 * NC;      // a k-step on: N / 16 column blocks x 1 KB (512 halves) per plane
@@ -524,8 +501,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
     }
   };
 
-  const int fslot = (kq ^ rg_key(r16)) << 4;
-  const int a_off = r16 * 64 + fslot;
+  const int a_off = afrag_off(r16, kq);
 
   rg_f32x4 acc[RT][2];
   // A fragments, double-buffered in registers by step parity: the reads of step s + 1 are issued in the middle of step s
@@ -533,10 +509,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
   auto read_a = [&](auto par_tag, int stage) {
     constexpr int par = decltype(par_tag)::value;
     const unsigned char* const st = rg_lds + stage * STAGE;
-#pragma unroll
-    for (int mt = 0; mt < RT; ++mt)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) af[par][mt][pl] = *reinterpret_cast<const rg_u32x4*>(st + a_off + pl * A_PLANE + mt * 1024);
+    afrag_read<RT>(af[par], st + a_off, A_PLANE);
   };
   // prologue: A of steps 0, 1, 2 into the three stages, W of steps 0 and 1 into the two register buffers (K % 64 == 0: there
   // are at least two steps); everything is waited for once, then step 0's fragments are read
@@ -556,8 +529,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
   if constexpr (PPW > 1) issue_piece(std::integral_constant<int, 1>{}, 2);
   advance();
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   rg_barrier();
   read_a(std::integral_constant<int, 0>{}, 0);
 
@@ -599,14 +571,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
       auto group = [&](auto mtag, auto nttag) {
         constexpr int mt = decltype(mtag)::value, nt = decltype(nttag)::value;
         if (!JV_ABLATE(p, 2)) {
-          rg_f32x4 t = acc[mt][nt];
-          auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-          };
-          mm(af[par][mt][1], bq[par][nt][0]);      // smallest terms first, as the tile kernels do
-          mm(af[par][mt][0], bq[par][nt][1]);
-          mm(af[par][mt][0], bq[par][nt][0]);
-          acc[mt][nt] = t;
+          acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         if constexpr (nt == 1 && mt < PPW) {
           if (more_a) issue_piece(std::integral_constant<int, (mt < PPW ? mt : 0)>{}, s3);
@@ -630,7 +595,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
         else rg_wait_vmcnt<NWL + PPW - 1>();
       }
       waited = false;
-      landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+      bq.template landed_mid<par>();
       if (!JV_ABLATE(p, 4)) rg_barrier();
       const int s3n = s3 == 2 ? 0 : s3 + 1;      // (s + 1) % 3
       if (!JV_ABLATE(p, 8)) read_a(std::integral_constant<int, par ^ 1>{}, s3n);
@@ -797,8 +762,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
   // dead after the last step (the single-chunk residual epilogues) it kept a pointer there, which such a load then
   // overwrote (a memory fault).  The empty asm below makes every bq register live up to this point.
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   asm volatile("" ::"v"(warm));
 }
 
@@ -875,19 +839,12 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
     for (int pl = 0; pl < 2; ++pl) wbase[nt][pl] = p.Wf + (long)pl * p.wf_plane + (long)(wave * 2 + nt) * 512 + lane * 8;
   long woff = 16L * 512 * c0;      // (chunk c, step ks) sits (ks N/16 + 16 c) KB into a plane
   int wk = 0, wc = c0;
-  rg_u32x4 bq[2][2][2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) bq[i >> 2][(i >> 1) & 1][i & 1] = rg_u32x4{0u, 0u, 0u, 0u};
-  auto load_frag = [](rg_u32x4& dst, const unsigned short* ptr) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(dst) : "v"(ptr) : "memory");
-  };
+  WFragBuf<2> bq;
+  bq.zero();
   auto load_w = [&](auto par_tag, auto nttag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    load_frag(bq[par][nt][0], wbase[nt][0] + woff);
-    load_frag(bq[par][nt][1], wbase[nt][1] + woff);
-  };
-  auto landed_w = [](rg_u32x4& b00, rg_u32x4& b01, rg_u32x4& b10, rg_u32x4& b11) {
-    asm volatile("" : "+v"(b00), "+v"(b01), "+v"(b10), "+v"(b11)::"memory");
+    bq.template load<par, nt, 0>(wbase[nt][0] + woff);
+    bq.template load<par, nt, 1>(wbase[nt][1] + woff);
   };
   const long wstep = 512L * (p.N >> 4);      // a k-step on: N / 16 column blocks x 1 KB per plane
   auto advance_w = [&]() {      // back to this workgroup's first chunk after its last
@@ -908,21 +865,16 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
   load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
   advance_w();
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   rg_barrier();      // every wave's A pieces are in LDS: the only barrier ahead of the epilogues
 
-  const int fslot = (kq ^ rg_key(r16)) << 4;
-  const int a_off = r16 * 64 + fslot;
+  const int a_off = afrag_off(r16, kq);
   rg_f32x4 acc[RT][2];
   rg_u32x4 af[2][RT][2];
   auto read_a = [&](auto par_tag, int stage) {
     constexpr int par = decltype(par_tag)::value;
     const unsigned char* const st = rg_lds + stage * STAGE;
-#pragma unroll
-    for (int mt = 0; mt < RT; ++mt)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) af[par][mt][pl] = *reinterpret_cast<const rg_u32x4*>(st + a_off + pl * A_PLANE + mt * 1024);
+    afrag_read<RT>(af[par], st + a_off, A_PLANE);
   };
   read_a(std::integral_constant<int, 0>{}, 0);
 
@@ -945,14 +897,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
         constexpr int nt = decltype(nttag)::value;
 #pragma unroll
         for (int mt = 0; mt < RT; ++mt) {
-          rg_f32x4 t = acc[mt][nt];
-          auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-          };
-          mm(af[par][mt][1], bq[par][nt][0]);      // smallest terms first, as the tile kernels do
-          mm(af[par][mt][0], bq[par][nt][1]);
-          mm(af[par][mt][0], bq[par][nt][0]);
-          acc[mt][nt] = t;
+          acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         load_w(par_tag, nttag);
@@ -961,7 +906,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
       block(std::integral_constant<int, 0>{});
       if (!waited) rg_wait_vmcnt<NWL>();      // (first step of a chunk: waited for ahead of the epilogue's stores, below)
       waited = false;
-      landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+      bq.template landed_mid<par>();
       read_a(std::integral_constant<int, par ^ 1>{}, ks1);
       __builtin_amdgcn_sched_barrier(0);
       block(std::integral_constant<int, 1>{});
@@ -1018,10 +963,9 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
       }
     }
   }
-  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (rowgemm_wd_kernel)
+  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   asm volatile("" ::"v"(warm));
 }
 
@@ -1130,19 +1074,15 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
     }
   long off1 = 0, off2 = 0;      // halves: where the NEXT step to load sits in W1f / W2f
   int wph = 0, wk = 0, wcc = 0; // its phase, k-step, chunk
-  rg_u32x4 bq[2][2][2];
+  // WFragBuf's registers and rules (row_mainloop.h), as a plain array under its two asm statements: as a WFragBuf the phase
+  // loops of the tile height 4 gain two s_waitcnt (profiles/row_mainloop_isa.md)
+  rg_u32x4 bq[2][2][2];      // [buffer = step % 2][column block nt][plane]
 #pragma unroll
   for (int i = 0; i < 8; ++i) bq[i >> 2][(i >> 1) & 1][i & 1] = rg_u32x4{0u, 0u, 0u, 0u};
-  auto load_frag = [](rg_u32x4& dst, const unsigned short* ptr) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(dst) : "v"(ptr) : "memory");
-  };
   auto load_w = [&](auto par_tag, auto nttag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    load_frag(bq[par][nt][0], wph ? w2base[nt][0] + off2 : w1base[nt][0] + off1);
-    load_frag(bq[par][nt][1], wph ? w2base[nt][1] + off2 : w1base[nt][1] + off1);
-  };
-  auto landed_w = [](rg_u32x4& b00, rg_u32x4& b01, rg_u32x4& b10, rg_u32x4& b11) {
-    asm volatile("" : "+v"(b00), "+v"(b01), "+v"(b10), "+v"(b11)::"memory");
+    wfrag_load(bq[par][nt][0], wph ? w2base[nt][0] + off2 : w1base[nt][0] + off1);
+    wfrag_load(bq[par][nt][1], wph ? w2base[nt][1] + off2 : w1base[nt][1] + off1);
   };
   auto advance_w = [&]() {
     // k-step major fragments: W1f (64 column blocks): block 16 c + 2 wave + nt, k-step ks -> (64 ks + 16 c) 512 halves past the
@@ -1166,12 +1106,11 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
   load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
   advance_w();
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  wfrag_landed(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
+  wfrag_landed(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
   rg_barrier();      // X is in LDS for every wave
 
-  const int fslot = (kq ^ rg_key(r16)) << 4;
-  const int a_off = r16 * 64 + fslot;
+  const int a_off = afrag_off(r16, kq);
   rg_f32x4 acc1[RT][2], acc2[RT][2];
 #pragma unroll
   for (int mt = 0; mt < RT; ++mt)
@@ -1185,10 +1124,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
   rg_u32x4 af[2][RT][2];
   auto read_a = [&](auto par_tag, const unsigned char* st) {
     constexpr int par = decltype(par_tag)::value;
-#pragma unroll
-    for (int mt = 0; mt < RT; ++mt)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) af[par][mt][pl] = *reinterpret_cast<const rg_u32x4*>(st + a_off + pl * A_PLANE + mt * 1024);
+    afrag_read<RT>(af[par], st + a_off, A_PLANE);
   };
   auto step = [&](auto par_tag, rg_f32x4 (&acc)[RT][2], const unsigned char* st, const unsigned char* st_next, const bool have) {
     constexpr int par = decltype(par_tag)::value;
@@ -1198,14 +1134,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
       constexpr int nt = decltype(nttag)::value;
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt) {
-        rg_f32x4 t = acc[mt][nt];
-        auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-          t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-        };
-        mm(af[par][mt][1], bq[par][nt][0]);      // smallest terms first, as everywhere
-        mm(af[par][mt][0], bq[par][nt][1]);
-        mm(af[par][mt][0], bq[par][nt][0]);
-        acc[mt][nt] = t;
+        acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq[par][nt][0], bq[par][nt][1]);
       }
       __builtin_amdgcn_sched_barrier(0);
       load_w(par_tag, nttag);
@@ -1213,7 +1142,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
     };
     block(std::integral_constant<int, 0>{});
     rg_wait_vmcnt<NWL>();
-    landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+    wfrag_landed(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
     if (st_next) read_a(std::integral_constant<int, par ^ 1>{}, st_next);
     __builtin_amdgcn_sched_barrier(0);
     block(std::integral_constant<int, 1>{});
@@ -1354,9 +1283,9 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
       }
     }
   }
-  rg_wait_vmcnt<0>();      // the wrapped-around W loads: bq stays reserved until they have landed
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  rg_wait_vmcnt<0>();      // the wrapped-around W loads: bq stays reserved until they have landed (WFragBuf, rule c)
+  wfrag_landed(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
+  wfrag_landed(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
   asm volatile("" ::"v"(warm));
 }
 

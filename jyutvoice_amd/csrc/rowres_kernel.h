@@ -114,7 +114,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
   };
   float warm = warm_lines(p.Wf1, p.wf1_plane, ((long)256 * 4 * p.Cin * 2) >> 7), warm2 = 0.f;
 
-  // ---- W walker: one register double buffer for both products (rowgemm_wd_kernel's rules) ----
+  // ---- W walker: one register double buffer for both products (WFragBuf's rules: row_mainloop.h) ----
   const unsigned short* wbase[2][2];
   auto set_wbase = [&](const unsigned short* wf, long plane) {
 #pragma unroll
@@ -126,19 +126,12 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
   long woff = 0;       // halves: fragment step of the NEXT step to load, x 16 column blocks x 512
   int wj = 0, wc = 0;  // its tap and chunk
   int wnj = 4, wnch = NCH;      // taps per chunk and chunks of the matrix being walked (product 1: 4 x NCH; product 2: 3 x 8)
-  rg_u32x4 bq[2][2][2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) bq[i >> 2][(i >> 1) & 1][i & 1] = rg_u32x4{0u, 0u, 0u, 0u};
-  auto load_frag = [](rg_u32x4& dst, const unsigned short* ptr) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(dst) : "v"(ptr) : "memory");
-  };
+  WFragBuf<2> bq;
+  bq.zero();
   auto load_w = [&](auto par_tag, auto nttag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    load_frag(bq[par][nt][0], wbase[nt][0] + woff);
-    load_frag(bq[par][nt][1], wbase[nt][1] + woff);
-  };
-  auto landed_w = [](rg_u32x4& b00, rg_u32x4& b01, rg_u32x4& b10, rg_u32x4& b11) {
-    asm volatile("" : "+v"(b00), "+v"(b01), "+v"(b10), "+v"(b11)::"memory");
+    bq.template load<par, nt, 0>(wbase[nt][0] + woff);
+    bq.template load<par, nt, 1>(wbase[nt][1] + woff);
   };
   auto advance_w = [&]() {      // step (c, j) is fragment step j nch + c; (c, nj - 1) -> (c + 1, 0); past the end: back to 0
     if (++wj == wnj) {
@@ -249,8 +242,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
   store_A(0);
   if (NCH > 1) load_A(1);
   if (NCH > 1) rg_wait_vmcnt<NI>(); else rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
 
   // ================================ product 1 (rowconv_wd_kernel<RT, true>'s step) ================================
   {
@@ -270,7 +262,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt) {
         const int row = mt * 16 + r16 + jrow;
-        const int a_off = row * 64 + ((kq ^ rg_key(row)) << 4);
+        const int a_off = afrag_off(row, kq);
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) af[mt][pl] = *reinterpret_cast<const rg_u32x4*>(sa + pl * A_PLANE + a_off);
       }
@@ -279,14 +271,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
         constexpr int nt = decltype(nttag)::value;
 #pragma unroll
         for (int mt = 0; mt < RT; ++mt) {
-          rg_f32x4 t = ac[mt][nt];
-          auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-          };
-          mm(af[mt][1], bq[par][nt][0]);
-          mm(af[mt][0], bq[par][nt][1]);
-          mm(af[mt][0], bq[par][nt][0]);
-          ac[mt][nt] = t;
+          ac[mt][nt] = h3_mma(ac[mt][nt], af[mt][0], af[mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         load_w(par_tag, nttag);
@@ -295,7 +280,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
       auto blocks = [&](rg_f32x4 (&ac)[RT][2]) {
         block(std::integral_constant<int, 0>{}, ac);
         if (j == 1 && c + 2 < NCH) rg_wait_vmcnt<NWL + NI>(); else rg_wait_vmcnt<NWL>();
-        landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+        bq.template landed_mid<par>();
         block(std::integral_constant<int, 1>{}, ac);
       };
       if constexpr (j == 3) blocks(accr); else blocks(acc);
@@ -333,8 +318,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
 
   // the wrapped-around loads of the last two steps land in registers nothing reads; then block2's first two steps are requested
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   asm volatile("" ::"v"(warm), "v"(warm2));
   // (QKV) to_q | to_k | to_v's fragments into this XCD's L2 a whole product ahead: cold, every step of product 3 began with
   // an HBM round trip taken by all workgroups at once -- 47 us for the product, what it takes as a launch of its own
@@ -402,8 +386,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
   }
   rg_wait_vmcnt<0>();      // block2's first fragments
   asm volatile("" ::"v"(warm3));      // (issued an epilogue ago)
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
   rg_lds_barrier();      // the image is complete (and the slab has been read: epilogue 2 writes it again)
 
   // ================================ product 2: block2 over the resident image ================================
@@ -418,7 +401,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt) {
         const int row = mt * 16 + r16 + j;      // (rows R, R + 1 of the last tile lie in the next plane: garbage into discarded output rows)
-        const unsigned char* const a = rr_lds + c * STAGE + row * 64 + ((kq ^ rg_key(row)) << 4);
+        const unsigned char* const a = rr_lds + c * STAGE + row * 64 + afrag_slot(row, kq);
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) af[par][mt][pl] = *reinterpret_cast<const rg_u32x4*>(a + pl * XP);
       }
@@ -430,14 +413,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
         constexpr int nt = decltype(nttag)::value;
 #pragma unroll
         for (int mt = 0; mt < RT; ++mt) {
-          rg_f32x4 t = acc[mt][nt];
-          auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-          };
-          mm(af[par][mt][1], bq[par][nt][0]);
-          mm(af[par][mt][0], bq[par][nt][1]);
-          mm(af[par][mt][0], bq[par][nt][0]);
-          acc[mt][nt] = t;
+          acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         load_w(par_tag, nttag);
@@ -445,7 +421,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
       };
       block(std::integral_constant<int, 0>{});
       rg_wait_vmcnt<NWL>();
-      landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+      bq.template landed_mid<par>();
       if (!last) read_a(std::integral_constant<int, par ^ 1>{}, nc, nj);
       __builtin_amdgcn_sched_barrier(0);
       block(std::integral_constant<int, 1>{});
@@ -553,8 +529,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
     // product 2's wrapped-around loads land in registers nothing reads; then q | k | v's first two steps are requested (HERE, behind
     // the row pass: requested ahead of it the 32 fragment registers pushed the pass's values into scratch)
     rg_wait_vmcnt<0>();
-    landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-    landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+    bq.landed_all();
     set_wbase(p.Wqf, p.wqf_plane);
     woff = 0;
     load_w(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
@@ -565,21 +540,17 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
     advance_q();
     rg_lds_barrier();      // the image is complete; the slab has been read: the patches go over it
     rg_wait_vmcnt<0>();      // (the fragments' round trip passes under the barrier; the row stores are waited for with them)
-    landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-    landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+    bq.landed_all();
     constexpr long LDQ = 512, LDKV = 1024;
     constexpr int NPATCH = RT >= 3 ? 2 : 1;      // (RT = 2: the slab is 32 KB, eight pairs of patches are 36)
     const float inv_q = 1.0f / p.lnf_scale;
     float* const ws0 = slab + wave * (NPATCH * 16 * 36);
     const int prow = lane >> 3, pc4 = (lane & 7) * 4;
     rg_u32x4 af[2][RT][2];
-    const int a_off = r16 * 64 + ((kq ^ rg_key(r16)) << 4);
+    const int a_off = afrag_off(r16, kq);
     auto read_a = [&](auto par_tag, const int ks) {
       constexpr int par = decltype(par_tag)::value;
-#pragma unroll
-      for (int mt = 0; mt < RT; ++mt)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) af[par][mt][pl] = *reinterpret_cast<const rg_u32x4*>(rr_lds + ks * STAGE + a_off + pl * XP + mt * 1024);
+      afrag_read<RT>(af[par], rr_lds + ks * STAGE + a_off, XP);
     };
     bool waited = true;      // (the wait was done ahead of an epilogue's memory operations: rowblock_kernel's step)
     auto step = [&](auto par_tag, const int ks_next) {
@@ -588,14 +559,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
         constexpr int nt = decltype(nttag)::value;
 #pragma unroll
         for (int mt = 0; mt < RT; ++mt) {
-          rg_f32x4 t = acc[mt][nt];
-          auto mm = [&](const rg_u32x4& x, const rg_u32x4& y) {
-            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, x), __builtin_bit_cast(rg_f16x8, y), t, 0, 0, 0);
-          };
-          mm(af[par][mt][1], bq[par][nt][0]);
-          mm(af[par][mt][0], bq[par][nt][1]);
-          mm(af[par][mt][0], bq[par][nt][0]);
-          acc[mt][nt] = t;
+          acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         load_w(par_tag, nttag);
@@ -604,7 +568,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
       block(std::integral_constant<int, 0>{});
       if (!waited) rg_wait_vmcnt<NWL>();
       waited = false;
-      landed_w(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
+      bq.template landed_mid<par>();
       if (ks_next >= 0) read_a(std::integral_constant<int, par ^ 1>{}, ks_next);
       __builtin_amdgcn_sched_barrier(0);
       block(std::integral_constant<int, 1>{});
@@ -677,10 +641,9 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
       }
     }
   }
-  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (rowgemm_wd_kernel)
+  // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
   rg_wait_vmcnt<0>();
-  landed_w(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
-  landed_w(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
+  bq.landed_all();
 }
 
 }  // namespace jv

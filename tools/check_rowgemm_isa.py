@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Build-time check of the hand-managed register double buffer of the W-direct kernels: rowgemm_wd_kernel, rowgemm_wa_kernel,
-rowffn_kernel (rowgemm_kernel.h), rowconv_wd_kernel (rowconv_kernel.h), rowblock_kernel (rowblock_kernel.h) hiftconv_kernel and hiftpair_kernel
-(hiftconv_kernel.h: the vocoder's 72 ResBlock convolutions).
+"""Build-time check of the hand-managed register buffer of the W-direct kernels -- WFragBuf in jyutvoice_amd/csrc/row_mainloop.h,
+which states the rules checked here: rowgemm_wd_kernel, rowgemm_wa_kernel, rowffn_kernel (rowgemm_kernel.h), rowconv_wd_kernel
+(rowconv_kernel.h), rowres_kernel (rowres_kernel.h), rowblock_kernel (rowblock_kernel.h), hiftconv_kernel and hiftpair_kernel
+(hiftconv_kernel.h, hiftpair_kernel.h: the vocoder's 72 ResBlock convolutions).
 
 The weight fragments are loaded by inline asm (global_load_dwordx4) and waited for by a counted s_waitcnt the compiler does
 not know about.  That is only sound if, in the generated code, the destination registers of those loads are touched by
@@ -17,7 +18,11 @@ Footprints: --resources prints, for every kernel of rowgemm.hip, rowblock.hip an
 offset (where the AGPRs begin), next free SGPR, private segment (scratch) and group segment (static LDS) size, from the same
 compile; --resources=PATH also writes the table as JSON (profiles/row_kernels_resources.json is one such file).
 
-usage: python tools/check_rowgemm_isa.py [--resources[=PATH]]   (exit code 0 = clean)"""
+Texts: --keep-asm=DIR keeps the assembly of every kernel of those three files, one text per kernel, as
+DIR/<source file>/<mangled name>.s (from the kernel's label to the end of its .amdhsa_kernel block): what tools/isa_compare.py
+compares between two commits.
+
+usage: python tools/check_rowgemm_isa.py [--resources[=PATH]] [--keep-asm=DIR]   (exit code 0 = clean)"""
 import json
 import os
 import re
@@ -147,7 +152,17 @@ def kernel_resources(asm):
     return out
 
 
+def kernel_texts(asm):
+    """{kernel name: its text, label to .end_amdhsa_kernel} of an assembly text"""
+    out = {}
+    for name in kernel_resources(asm):
+        m = re.search(r"^" + re.escape(name) + r":.*?^\s*\.amdhsa_kernel\s+" + re.escape(name) + r"\n.*?\.end_amdhsa_kernel\n", asm, re.S | re.M)
+        out[name] = m.group(0)
+    return out
+
+
 def main():
+    keep = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--keep-asm=")), None)
     res_arg = next((a for a in sys.argv[1:] if a == "--resources" or a.startswith("--resources=")), None)
     s = ""
     s_row = ""      # the three row-owning translation units alone: what the footprint table covers
@@ -162,6 +177,11 @@ def main():
             s += open(out).read()
             if src in SRCS:
                 s_row += open(out).read()
+                if keep:
+                    os.makedirs(os.path.join(keep, os.path.basename(src)), exist_ok=True)
+                    for name, text in kernel_texts(open(out).read()).items():
+                        with open(os.path.join(keep, os.path.basename(src), name + ".s"), "w") as f:
+                            f.write(text)
             # -S does not run the assembler over the inline asm: an operand the assembler rejects only shows with -c
             r = subprocess.run([CLANG] + [f for f in FLAGS if f != "-S"] + ["-c", "-o", os.path.join(d, os.path.basename(src) + ".o"), src],
                                capture_output=True, text=True)
