@@ -14,13 +14,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "jv_common.h"
-#include "jv_device.h"
+#include "attention_common.h"
 
 namespace jv {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KV_STRIDE = 68;
 
@@ -33,13 +29,9 @@ __global__ __launch_bounds__(64 * NW) void attn64_kernel(const AttnArgs p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r32 = lane & 31, half = lane >> 5;
-  // flat grid, remapped so that each XCD gets a contiguous run of (b, h, q-tile) triples with the q-tile fastest: the
-  // q-tiles of one (b, h) then share that head's K/V in one L2 (round 1: FETCH_SIZE was 2.3x the algorithmic bytes)
   int b, h, qt;
   {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);      // (XCD-contiguous (b, h, q-tile) triples: attention_common.h)
     const int nqt = (p.L + 32 * NW - 1) / (32 * NW);
     qt = lid % nqt;
     h = (lid / nqt) % p.H;
@@ -158,14 +150,7 @@ __global__ __launch_bounds__(64 * NW) void attn64_kernel(const AttnArgs p) {
   const int qi = q0 + r32;
   if (active && qi < p.L) {
     const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
-    float* dst = p.out + (rowbase + qi) * p.ldo + h * 64 + 4 * half;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4 a = {o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv};
-      const f32x4 c = {o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv};
-      *reinterpret_cast<f32x4*>(dst + 8 * g) = a;
-      *reinterpret_cast<f32x4*>(dst + 32 + 8 * g) = c;
-    }
+    store_o_f32(p.out + (rowbase + qi) * p.ldo + h * 64 + 4 * half, o0, o1, inv);
   }
 }
 
@@ -177,39 +162,17 @@ __global__ __launch_bounds__(64 * NW) void attn64_kernel(const AttnArgs p) {
 // row holds key swap_bits23(p): P goes from the softmax to the MFMA with three conversions and no data movement.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-// unpadded tiles [NP planes][32 keys][128 B] and [NP][64 d][64 B]; slot keys: a ds_read_b128 lane group
-// holds every key parity twice per value of (key >> 1) & 7, and every 64-byte quadrant once per value of (row >> 2) & 3
-constexpr int XK_PLANE = 32 * 128, XV_PLANE = 64 * 64;
-__device__ __forceinline__ int xk_swz(int key) { return (key >> 1) & 7; }
+// unpadded tiles [NP planes][32 keys][128 B] (KV_PLANE, kv_k_swz: attention_common.h) and [NP][64 d][64 B]; the V^T slot key: a
+// ds_read_b128 lane group holds every 64-byte quadrant once per value of (row >> 2) & 3
+constexpr int XV_PLANE = 64 * 64;
 __device__ __forceinline__ int xv_swz(int row) { return (row >> 2) & 3; }
-
-// combine a value with its partner lane's (lane ^ 32: the two lanes that hold one query's keys) in one VALU op:
-// v_permlane32_swap_b32 (gfx950) returns {own half | partner's low half, partner's high half | own}; ds_bpermute, what
-// __shfl_xor compiles to, is an LDS round trip
-__device__ __forceinline__ float half_max(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float half_sum(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // NP = 3: six bf16 products of (h, m, l) planes; NP = 2: three fp16 products of (h, l) planes (conv_gemm_x6.hip)
 template <int NP>
 __device__ __forceinline__ f32x16 mfma_planes(const u32x4 (&a)[NP], const u32x4 (&b)[NP], f32x16 c) {
   if constexpr (NP == 2) {
-    auto mm = [&](const u32x4& x, const u32x4& y) {
-      c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, x), __builtin_bit_cast(f16x8, y), c, 0, 0, 0);
-    };
-    mm(a[1], b[0]);
-    mm(a[0], b[1]);
-    mm(a[0], b[0]);
+    return h3_mma32(a, b, c);
   } else {
     auto mm = [&](const u32x4& x, const u32x4& y) {
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, y), c, 0, 0, 0);
@@ -241,7 +204,7 @@ __device__ __forceinline__ void split_pair(const float x0, const float x1, unsig
 // probabilities are kept as p * 2^10 (<= 1024; the factor cancels in the normalisation), and v_scale leaves with 1 / l.
 template <int NW, int WPE, int NP>
 __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs p) {
-  constexpr int XK_TILE = NP * XK_PLANE, XV_TILE = NP * XV_PLANE;
+  constexpr int XK_TILE = NP * KV_PLANE, XV_TILE = NP * XV_PLANE;
   // Two buffers per operand, one barrier per key tile: tile kt + 1 is split and stored into the other buffer while tile kt
   // is being used.  Rows are unpadded (K: 128 B = 64 d, V^T: 64 B = 32 keys) with XOR-swizzled 16-byte slots, which keeps
   // the ds_read_b128 fragment fetches conflict-free and the two buffers within 48 KiB (three workgroups per CU).
@@ -252,13 +215,9 @@ __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs 
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r32 = lane & 31, half = lane >> 5;
-  // flat grid, remapped so that each XCD gets a contiguous run of (b, h, q-tile) triples with the q-tile fastest: the
-  // q-tiles of one (b, h) then share that head's K/V in one L2 (round 1: FETCH_SIZE was 2.3x the algorithmic bytes)
   int b, h, qt;
   {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);      // (XCD-contiguous (b, h, q-tile) triples: attention_common.h)
     const int nqt = (p.L + 32 * NW - 1) / (32 * NW);
     qt = lid % nqt;
     h = (lid / nqt) % p.H;
@@ -271,7 +230,7 @@ __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs 
 
   // Q planes: lane (query, half) holds d = 16 s + 8 half + j for k-step s, pre-scaled by log2(e)/8
   u32x4 q[4][NP];
-  const float qsc = 0.125f * 1.44269504088896340736f * (NP == 2 ? p.q_scale : 1.f);
+  const float qsc = q_prescale(NP == 2 ? p.q_scale : 1.f);
   const float ksc = NP == 2 ? p.k_scale : 1.f, vsc = NP == 2 ? p.v_scale : 1.f;
   const float sinv = NP == 2 ? 1.0f / (p.q_scale * p.k_scale) : 1.f;      // powers of two: exact
   constexpr float pshift = NP == 2 ? 10.f : 0.f;
@@ -285,13 +244,17 @@ __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs 
         t0 = *reinterpret_cast<const f32x4*>(src + 16 * s);
         t1 = *reinterpret_cast<const f32x4*>(src + 16 * s + 4);
       }
+      if constexpr (NP == 2) {
+        q_split8(t0, t1, qsc, q[s][0], q[s][1]);
+      } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float x0 = (e < 2 ? t0[2 * e] : t1[2 * e - 4]) * qsc, x1 = (e < 2 ? t0[2 * e + 1] : t1[2 * e - 3]) * qsc;
-        unsigned o[NP];
-        split_pair<NP>(x0, x1, o);
+        for (int e = 0; e < 4; ++e) {
+          const float x0 = (e < 2 ? t0[2 * e] : t1[2 * e - 4]) * qsc, x1 = (e < 2 ? t0[2 * e + 1] : t1[2 * e - 3]) * qsc;
+          unsigned o[NP];
+          split_pair<NP>(x0, x1, o);
 #pragma unroll
-        for (int pl = 0; pl < NP; ++pl) q[s][pl][e] = o[pl];
+          for (int pl = 0; pl < NP; ++pl) q[s][pl][e] = o[pl];
+        }
       }
     }
   }
@@ -352,9 +315,9 @@ __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs 
         split_pair<NP>(pk[i][0], pk[i][1], o0_);
         split_pair<NP>(pk[i][2], pk[i][3], o1_);
       }
-      unsigned char* dst = bK + key * 128 + ((((c4 >> 1) ^ xk_swz(key)) << 4) | ((c4 & 1) << 3));
+      unsigned char* dst = bK + key * 128 + ((((c4 >> 1) ^ kv_k_swz(key)) << 4) | ((c4 & 1) << 3));
 #pragma unroll
-      for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<u32x2*>(dst + pl * XK_PLANE) = u32x2{o0_[pl], o1_[pl]};
+      for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<u32x2*>(dst + pl * KV_PLANE) = u32x2{o0_[pl], o1_[pl]};
     }
 #pragma unroll
     for (int j = 0; j < NVG; ++j) {             // 4 consecutive keys stay consecutive under the bit swap
@@ -399,9 +362,9 @@ __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs 
 #pragma unroll
     for (int st = 0; st < 4; ++st) {
       u32x4 a[NP];
-      const int ko = ((2 * st + half) ^ xk_swz(r32)) << 4;
+      const int ko = ((2 * st + half) ^ kv_k_swz(r32)) << 4;
 #pragma unroll
-      for (int pl = 0; pl < NP; ++pl) a[pl] = *reinterpret_cast<const u32x4*>(kr + pl * XK_PLANE + ko);
+      for (int pl = 0; pl < NP; ++pl) a[pl] = *reinterpret_cast<const u32x4*>(kr + pl * KV_PLANE + ko);
       if (!JV_ABLATE(p, 16)) s = mfma_planes<NP>(a, q[st], s);
       else s[st] += __uint_as_float(a[0][0] ^ a[1][1]);
     }
@@ -483,6 +446,7 @@ __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs 
       }
       return;
     }
+    // (store_o_f32, written out: behind the out2 branch's return the helper's body was emitted twice, 46 lines per kernel)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const f32x4 a = {o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv};

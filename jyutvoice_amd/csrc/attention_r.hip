@@ -16,69 +16,26 @@
 //   * the row sum of P stays a per-lane partial (this lane's keys) until the end: one cross-lane reduction per query and
 //     launch instead of one per key tile; only the running maximum crosses lanes per tile (two row / half exchanges);
 //   * 512 workgroups at 32 x 300 frames = two per CU, one round.
-// Arithmetic: attention_pl.hip's (scales, base-2 softmax on raw v_exp_f32, P kept as p * 2^10, products hh' + hl' + lh'
+// Arithmetic: attention_common.h's pieces, as in attention_pl.hip (scales, base-2 softmax on raw v_exp_f32, P kept as p * 2^10, products hh' + hl' + lh'
 // smallest first); the contraction over d runs in two 32-deep MFMAs instead of four 16-deep ones and the row sums are
 // grouped per lane, so results agree with that kernel to rounding, not bit for bit.
 #include <math.h>
 #include <stdlib.h>
 
-#include "jv_common.h"
-#include "jv_device.h"
+#include "attention_common.h"
+#include "row_mainloop.h"      // h3_mma: the fp16x3 step on v_mfma_f32_16x16x32_f16
 
 namespace jv {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int AR_PLANE = 32 * 128;                 // one plane of a 32-key tile: 128 bytes (64 d) per key
-constexpr int AR_STAGE = 4 * AR_PLANE;             // K h, K l, V h, V l
 constexpr int AR_NW = 4;
-
-// 16-byte slot keys of a key row (128 B = 8 slots), brute-forced against the LDS lane groups of MI355X_MICROARCH.md:
-// K is read by rows (ds_read_b128: 16 keys x 4 consecutive slots per instruction), V transposed (ds_read_b64_tr_b16: a
-// 32-lane half takes 8 keys x 32 contiguous bytes) -- both conflict-free with these
-__device__ __forceinline__ int ark_swz(int key) { return (key >> 1) & 7; }
-__device__ __forceinline__ int arv_swz(int key) { return ((key >> 1) & 3) << 1; }
-
-__device__ __forceinline__ f32x4 ar_mfma3(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x4 c) {
-  auto mm = [&](const u32x4& x, const u32x4& y) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, x), __builtin_bit_cast(f16x8, y), c, 0, 0, 0);
-  };
-  mm(a[1], b[0]);      // smallest terms first, as everywhere
-  mm(a[0], b[1]);
-  mm(a[0], b[0]);
-  return c;
-}
-// max / sum over the four lanes that share a query (lane, lane ^ 16, lane ^ 32, lane ^ 48), in every one of them
-__device__ __forceinline__ float ar_q_max(float v) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float ar_q_sum(float v) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-template <int N>
-__device__ __forceinline__ void ar_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void ar_barrier() { asm volatile("s_barrier" ::: "memory"); }
-__device__ __forceinline__ void ar_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int QT, int NST>
 __global__ __launch_bounds__(64 * AR_NW, 2) void attn64_r_kernel(const AttnArgs p) {
   // the K / V ring; after the key loop each wave's [2 planes][16 queries][128 B] output patch (4 KB per wave)
-  __shared__ __attribute__((aligned(256))) unsigned char lds[NST * AR_STAGE];
-  static_assert(NST * AR_STAGE >= AR_NW * 2 * 16 * 128, "the output patches fit the ring");
+  __shared__ __attribute__((aligned(256))) unsigned char lds[NST * KV_STAGE];
+  static_assert(NST * KV_STAGE >= AR_NW * 2 * 16 * 128, "the output patches fit the ring");
   constexpr int PPW = 16 / AR_NW;      // DMA pieces per wave and key tile
   constexpr int QW = 16 * QT;          // queries per wave
   const int tid = threadIdx.x, lane = tid & 63;
@@ -93,29 +50,21 @@ __global__ __launch_bounds__(64 * AR_NW, 2) void attn64_r_kernel(const AttnArgs 
   const long rowbase = (long)p.G + (long)b * p.S;
   const bool active = q0 < p.L;
 
-  // ---- this wave's DMA pieces of a key tile (attention_pl.hip): piece pc = wave + 4 i -> operand pc >> 3 (K, V), plane
-  // (pc >> 2) & 1, 8-key group pc & 3; lane L lands on key 8 g + (L >> 3), slot L & 7 and fetches the slot the read side maps there
+  // ---- this wave's DMA pieces of a key tile (attention_common.h: kv_piece)
   const unsigned short* src[PPW];
   int dst[PPW], krel[PPW];
   const int kstride = p.kv_ld;
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
-    const int pc = wave + AR_NW * i;
-    const int opv = pc >> 3, pl = (pc >> 2) & 1, g = pc & 3;
-    const int key = 8 * g + (lane >> 3);
-    const int slot = (lane & 7) ^ (opv ? arv_swz(key) : ark_swz(key));
-    krel[i] = key;
-    src[i] = p.kv2 + (long)pl * p.kv2_plane + rowbase * kstride + opv * 512 + h * 64 + 8 * slot;
-    dst[i] = (2 * opv + pl) * AR_PLANE + g * 1024;
+    const KvPiece pc = kv_piece(wave + AR_NW * i, lane);
+    const int slot = kv_slot<VT_8x32>(pc.opv, pc.krel, lane);
+    krel[i] = pc.krel;
+    src[i] = p.kv2 + (long)pc.pl * p.kv2_plane + rowbase * kstride + pc.opv * 512 + h * 64 + 8 * slot;
+    dst[i] = pc.dst;
   }
   auto issue = [&](int k0, int stage) {
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      // rows past the last valid key are clamped to it: their scores are masked to -inf below, P is exactly 0 there
-      const int key = min(k0 + krel[i], len - 1);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[i] + (long)key * kstride),
-                                       (__attribute__((address_space(3))) void*)(lds + stage * AR_STAGE + dst[i]), 16, 0, 0);
-    }
+    for (int i = 0; i < PPW; ++i) kv_issue_piece(src[i], dst[i], krel[i], kstride, k0, len, lds + stage * KV_STAGE);
   };
   const int nkt = (len + 31) >> 5;
   if (nkt > 0) issue(0, 0);
@@ -123,7 +72,7 @@ __global__ __launch_bounds__(64 * AR_NW, 2) void attn64_r_kernel(const AttnArgs 
 
   // ---- Q planes: B operand of S^T = K Q^T.  Lane (query r16, kq) holds d = 32 ds + 8 kq + j, pre-scaled by log2(e) / 8 * q_scale
   u32x4 qf[QT][2][2];
-  const float qsc = 0.125f * 1.44269504088896340736f * p.q_scale;
+  const float qsc = q_prescale(p.q_scale);
   const float sinv = 1.0f / (p.q_scale * p.k_scale);      // powers of two: exact
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
@@ -136,13 +85,7 @@ __global__ __launch_bounds__(64 * AR_NW, 2) void attn64_r_kernel(const AttnArgs 
         t0 = *reinterpret_cast<const f32x4*>(qs + 32 * ds);
         t1 = *reinterpret_cast<const f32x4*>(qs + 32 * ds + 4);
       }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float x0 = (e < 2 ? t0[2 * e] : t1[2 * e - 4]) * qsc, x1 = (e < 2 ? t0[2 * e + 1] : t1[2 * e - 3]) * qsc;
-        const Split2 sp = split2h_pair(x0, x1);
-        qf[t][ds][0][e] = sp.h;
-        qf[t][ds][1][e] = sp.l;
-      }
+      q_split8(t0, t1, qsc, qf[t][ds][0], qf[t][ds][1]);
     }
   }
 
@@ -157,17 +100,17 @@ __global__ __launch_bounds__(64 * AR_NW, 2) void attn64_r_kernel(const AttnArgs 
   }
 
   // per-lane read offsets inside a stage
-  const int k_row = r16 * 128;                                   // K: + kb * 2048 + pl * AR_PLANE + slot
+  const int k_row = r16 * 128;                                   // K: + kb * 2048 + pl * KV_PLANE + slot
   const int vq = r16 >> 2, vp = lane & 3;                        // V^T: key within its 4-block, 8-byte piece (4 d)
   for (int kt = 0; kt < nkt; ++kt) {
     const int k0 = kt * 32;
-    if (NST > 2 && kt + 1 < nkt) ar_wait_vmcnt<PPW>(); else ar_wait_vmcnt<0>();
-    ar_barrier();
+    if (NST > 2 && kt + 1 < nkt) wait_vmcnt<PPW>(); else wait_vmcnt<0>();
+    bare_barrier();
     if (NST > 2) { if (kt + 2 < nkt) issue(k0 + 64, (kt + 2) % NST); }
     else if (kt + 1 < nkt) issue(k0 + 32, (kt + 1) % NST);
     if (!active) continue;
-    const unsigned char* const sK = lds + (kt % NST) * AR_STAGE;
-    const unsigned char* const sV = sK + 2 * AR_PLANE;
+    const unsigned char* const sK = lds + (kt % NST) * KV_STAGE;
+    const unsigned char* const sV = sK + 2 * KV_PLANE;
 
     // ---- S^T[key][query] = sum_d K[key][d] Q[query][d]: each K fragment read once, used by all QT query tiles
     f32x4 s[QT][2];
@@ -179,11 +122,11 @@ __global__ __launch_bounds__(64 * AR_NW, 2) void attn64_r_kernel(const AttnArgs 
       for (int ds = 0; ds < 2; ++ds) {
         u32x4 a[2];
         const int key = 16 * kb + r16;
-        const int ko = ((4 * ds + kq) ^ ark_swz(key)) << 4;
+        const int ko = ((4 * ds + kq) ^ kv_k_swz(key)) << 4;
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) a[pl] = *reinterpret_cast<const u32x4*>(sK + pl * AR_PLANE + kb * 2048 + k_row + ko);
+        for (int pl = 0; pl < 2; ++pl) a[pl] = *reinterpret_cast<const u32x4*>(sK + pl * KV_PLANE + kb * 2048 + k_row + ko);
 #pragma unroll
-        for (int t = 0; t < QT; ++t) s[t][kb] = ar_mfma3(a, qf[t][ds], s[t][kb]);
+        for (int t = 0; t < QT; ++t) s[t][kb] = h3_mma(s[t][kb], a[0], a[1], qf[t][ds][0], qf[t][ds][1]);
       }
 
     // ---- softmax (base 2), per query tile; P leaves as the B operand of the PV product
@@ -199,7 +142,7 @@ __global__ __launch_bounds__(64 * AR_NW, 2) void attn64_r_kernel(const AttnArgs 
       }
       float mt = fmaxf(fmaxf(fmaxf(s[t][0][0], s[t][0][1]), fmaxf(s[t][0][2], s[t][0][3])),
                        fmaxf(fmaxf(s[t][1][0], s[t][1][1]), fmaxf(s[t][1][2], s[t][1][3])));
-      mt = ar_q_max(mt) * sinv;
+      mt = q_max(mt) * sinv;
       const float m_new = fmaxf(m_run[t], mt);
       const float alpha = __builtin_amdgcn_exp2f(m_run[t] - m_new);
       float lt = 0.f;
@@ -237,27 +180,24 @@ __global__ __launch_bounds__(64 * AR_NW, 2) void attn64_r_kernel(const AttnArgs 
         for (int rd = 0; rd < 2; ++rd) {
           const int key = 16 * rd + 4 * kq + vq;
           const int byte = (16 * db + 4 * vp) * 2;
-          const int off = key * 128 + ((((byte >> 4) ^ arv_swz(key)) << 4) | (byte & 15));
-          const fp16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-              (__attribute__((address_space(3))) fp16x4*)(const_cast<unsigned char*>(sV) + pl * AR_PLANE + off));
-          const u32x2 u = __builtin_bit_cast(u32x2, v);
+          const u32x2 u = vt_read4(sV + pl * KV_PLANE + vt_off(key, byte, kv_v_swz<VT_8x32>(key)));
           a[pl][2 * rd] = u[0];
           a[pl][2 * rd + 1] = u[1];
         }
 #pragma unroll
-      for (int t = 0; t < QT; ++t) o[t][db] = ar_mfma3(a, pb[t], o[t][db]);
+      for (int t = 0; t < QT; ++t) o[t][db] = h3_mma(o[t][db], a[0], a[1], pb[t][0], pb[t][1]);
     }
   }
 
   // ---- result: O / l as the output projection's operand (fp16 planes), each wave through its own 4 KB patch of the idle
   // ring so that every store instruction writes whole 128-byte rows
-  ar_lds_barrier();      // every wave is done with the ring
+  lds_barrier();      // every wave is done with the ring
   if (!active) return;
   unsigned char* const so = lds + wave * (2 * 16 * 128);      // [2 planes][16 queries][128 B]
   const float vsc = p.v_scale;
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
-    const float l = ar_q_sum(l_run[t]);
+    const float l = q_sum(l_run[t]);
     const float inv = l > 0.f ? (1.0f / vsc) / l : 0.f;
     const int qbase = q0 + 16 * t;
     if (qbase >= p.L) break;      // (wave-uniform)
@@ -300,42 +240,20 @@ void launch_r(const AttnArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// queries per workgroup = 64 QT: the QT in {2 .. 5} that covers L with the fewest padded queries (workgroups x 64 QT), the
-// taller tile on a tie (each K / V fragment is then used for more queries).  300 frames -> 5, 512 -> 4, 128 -> 2
-int attention64_r_tiles(int L) {
-  int best = 5;
-  long best_q = 1L << 40;
-  for (int qt = 5; qt >= 2; --qt) {
-    const long padded = (long)cdiv(L, 64 * qt) * 64 * qt;
-    if (padded < best_q) { best = qt; best_q = padded; }
-  }
-  return best;
-}
-
 // same contract as attention64_planes() (attention_pl.hip); no chunk-causal mask (streaming stays on attention64_planes)
 int attention64_rows(const AttnArgs& a, hipStream_t st) {
   if (a.B <= 0 || a.L <= 0) return JV_OK;
-  if (!a.kv2 || (a.kv_ld & 7) || !(a.q_scale > 0.f && a.k_scale > 0.f && a.v_scale > 0.f) || (a.ld & 3) || (a.ldo & 7) || a.chunk > 0)
-    return fail(JV_ERR_ARG, "attention64_rows: needs K/V planes, the three scales, aligned strides, no chunk mask");
-  const bool prof = prof_on();
-  if (prof) prof_begin(st);
-  int qt = attention64_r_tiles(a.L);
+  JV_TRY(attn_planes_check(a, "attention64_rows", false));
+  int qt = attention64_tiles(a.L);
   if (const char* f = dyn_env("JV_ATTN_QT")) qt = atoi(f);
   const bool st3 = dyn_env("JV_ATTN_NST2") == nullptr;
-  switch (qt) {
-    case 2: if (st3) launch_r<2, 3>(a, st); else launch_r<2, 2>(a, st); break;
-    case 3: if (st3) launch_r<3, 3>(a, st); else launch_r<3, 2>(a, st); break;
-    case 4: if (st3) launch_r<4, 3>(a, st); else launch_r<4, 2>(a, st); break;
-    case 5: if (st3) launch_r<5, 3>(a, st); else launch_r<5, 2>(a, st); break;
-    default: return fail(JV_ERR_ARG, "attention64_rows: bad tile count");
-  }
-  if (prof) {
-    static const char* const names[6] = {"", "", "attn64_r<128 q>", "attn64_r<192 q>", "attn64_r<256 q>", "attn64_r<320 q>"};
-    const double bh = (double)a.B * a.H;
-    prof_end(st, names[qt], 4.0 * bh * a.L * a.L * 64.0, 4.0 * bh * a.L * 64.0 * 4.0);
-  }
-  JV_HIP(hipGetLastError());
-  return JV_OK;
+  static const char* const names[6] = {"", "", "attn64_r<128 q>", "attn64_r<192 q>", "attn64_r<256 q>", "attn64_r<320 q>"};
+  return dispatch_rt(qt, "attention64_rows: bad tile count", [&](auto qc) {
+    return attn_bracket(a, st, names[qc], [&] {
+      if (st3) launch_r<decltype(qc)::value, 3>(a, st);
+      else launch_r<decltype(qc)::value, 2>(a, st);
+    });
+  });
 }
 
 }  // namespace jv

@@ -13,35 +13,21 @@
 // IF they sit behind it in the same wave's program order and do not depend on it.  This kernel writes the loop that way: the
 // MFMAs of two neighbouring tiles and the softmax of the one between them are independent by construction, and
 // sched_group_barrier interleaves them one MFMA to four vector instructions.
-// Arithmetic: attention_pl.hip's, term for term (32x32x16 MFMAs, the same scales, base-2 softmax on raw v_exp_f32, P kept as
-// p * 2^10, products hh' + hl' + lh' smallest first, the same lazy reference maximum, every sum in the same order): the two
+// Arithmetic: attention_common.h's pieces as attention_pl.hip calls them, term for term (32x32x16 MFMAs, the same scales,
+// base-2 softmax on raw v_exp_f32, P kept as p * 2^10, products hh' + hl' + lh' smallest first, the same lazy reference maximum, every sum in the same order): the two
 // forms agree bit for bit, so an utterance's mel does not depend on which of them its batch size selects.
 #include <math.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
-#include "jv_common.h"
-#include "jv_device.h"
+#include "attention_common.h"
 
 namespace jv {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int AS_PLANE = 32 * 128;                 // one plane of a 32-key tile: 128 bytes (64 d) per key
-constexpr int AS_STAGE = 4 * AS_PLANE;             // K h, K l, V h, V l
 constexpr int AS_NW = 2;
-
-// LDS slot keys: attention_pl.hip's (K read by rows with ds_read_b128, V transposed with ds_read_b64_tr_b16)
-__device__ __forceinline__ int ask_swz(int key) { return (key >> 1) & 7; }
-__device__ __forceinline__ int asv_swz(int key) { return ((key >> 1) & 1) << 2; }
 
 // v_max3_f32 without the canonicalising v_max x, x the IEEE-mode fmaxf puts on operands of unknown origin (asm results)
 __device__ __forceinline__ float as_max3(const float a, const float b, const float c) {
@@ -49,30 +35,7 @@ __device__ __forceinline__ float as_max3(const float a, const float b, const flo
   asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 }
-__device__ __forceinline__ float as_half_max(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float as_half_sum(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ f32x16 as_mfma3(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x16 c) {
-  auto mm = [&](const u32x4& x, const u32x4& y) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, x), __builtin_bit_cast(f16x8, y), c, 0, 0, 0);
-  };
-  mm(a[1], b[0]);      // smallest terms first, as everywhere
-  mm(a[0], b[1]);
-  mm(a[0], b[0]);
-  return c;
-}
 __device__ __forceinline__ int wave_of(const unsigned tid) { return __builtin_amdgcn_readfirstlane((int)(tid >> 6)); }
-template <int N>
-__device__ __forceinline__ void as_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void as_barrier() { asm volatile("s_barrier" ::: "memory"); }
-__device__ __forceinline__ void as_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- explicit register residency.  A 512-register wave's upper 256 registers are AGPRs: matrix instructions, LDS and
 // global loads can address them, vector instructions cannot.  Left to the compiler they are spill space -- first build: 640
@@ -164,10 +127,10 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
   // the K / V ring; after the key loop each wave's [2 planes][32 queries][128 B] output patch (8 KB per wave)
   // ... and, behind the ring, the LOW planes of the waves' Q operands ([QT][4 k-steps][64 lanes][16 B] per wave, lane-linear;
   // the high planes pass through the same bytes on their way into AGPRs): read back per (tile, k-step) where the MFMA needs it
-  __shared__ __attribute__((aligned(256))) unsigned char lds[NST * AS_STAGE + AS_NW * QT * 4 * 1024];
-  static_assert(NST * AS_STAGE >= AS_NW * 2 * 32 * 128, "the output patches fit the ring");
+  __shared__ __attribute__((aligned(256))) unsigned char lds[NST * KV_STAGE + AS_NW * QT * 4 * 1024];
+  static_assert(NST * KV_STAGE >= AS_NW * 2 * 32 * 128, "the output patches fit the ring");
   static_assert(NST == 2, "the rotated loop keeps one tile in flight beside the one in registers");
-  unsigned char* const qlo = lds + NST * AS_STAGE + wave_of(threadIdx.x) * (QT * 4 * 1024) + (threadIdx.x & 63) * 16;
+  unsigned char* const qlo = lds + NST * KV_STAGE + wave_of(threadIdx.x) * (QT * 4 * 1024) + (threadIdx.x & 63) * 16;
   constexpr int PPW = 16 / AS_NW;      // DMA pieces per wave and key tile
   constexpr int QW = 32 * QT;          // queries per wave
   const int tid = threadIdx.x, lane = tid & 63;
@@ -178,35 +141,26 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
   const int h = (blockIdx.x / nqt) % p.H;
   const int b = blockIdx.x / (nqt * p.H);
   const int q0 = qt * AS_NW * QW + wave * QW;
-  const int len = p.lens ? min(p.lens[b], p.L) : p.L;
-  // compact geometry (AttnArgs::uoff): the utterance owns len rows; what lies behind them is the next utterance
-  const long rowbase = p.uoff ? (long)p.uoff[b] : (long)p.G + (long)b * p.S;
-  const int Lq = p.uoff ? len : p.L;
+  const AttnGeo geo(p, b);
+  const int len = geo.len, Lq = geo.Lq;
+  const long rowbase = geo.rowbase;
   const bool active = q0 < Lq;
 
-  // ---- this wave's DMA pieces of a key tile (attention_pl.hip): piece pc = wave + 2 i -> operand pc >> 3, plane (pc >> 2) & 1,
-  // 8-key group pc & 3; lane L lands on key 8 g + (L >> 3), slot L & 7
+  // ---- this wave's DMA pieces of a key tile (attention_common.h: kv_piece)
   const unsigned short* src[PPW];
   int dst[PPW], krel[PPW];
   const int kstride = p.kv_ld;
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
-    const int pc = wave + AS_NW * i;
-    const int opv = pc >> 3, pl = (pc >> 2) & 1, g = pc & 3;
-    const int key = 8 * g + (lane >> 3);
-    const int slot = (lane & 7) ^ (opv ? asv_swz(key) : ask_swz(key));
-    krel[i] = key;
-    src[i] = p.kv2 + (long)pl * p.kv2_plane + rowbase * kstride + opv * 512 + h * 64 + 8 * slot;
-    dst[i] = (2 * opv + pl) * AS_PLANE + g * 1024;
+    const KvPiece pc = kv_piece(wave + AS_NW * i, lane);
+    const int slot = kv_slot<VT_4x64>(pc.opv, pc.krel, lane);
+    krel[i] = pc.krel;
+    src[i] = p.kv2 + (long)pc.pl * p.kv2_plane + rowbase * kstride + pc.opv * 512 + h * 64 + 8 * slot;
+    dst[i] = pc.dst;
   }
-  auto issue_piece = [&](const int i, int k0, int stage) {
-    const int key = min(k0 + krel[i], len - 1);      // rows past the last valid key: clamped (masked to -inf below)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[i] + (long)key * kstride),
-                                     (__attribute__((address_space(3))) void*)(lds + stage * AS_STAGE + dst[i]), 16, 0, 0);
-  };
   auto issue = [&](int k0, int stage) {
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) issue_piece(i, k0, stage);
+    for (int i = 0; i < PPW; ++i) kv_issue_piece(src[i], dst[i], krel[i], kstride, k0, len, lds + stage * KV_STAGE);
   };
   const int nkt = (len + 31) >> 5;
   if (nkt > 0) issue(0, 0);
@@ -214,7 +168,7 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
   // ---- Q planes: lane (query r32, half) holds d = 16 s + 8 half + j for k-step s, pre-scaled by log2(e) / 8 * q_scale.
   // High planes: staged through the wave's LDS patch and read back INTO AGPRs (ds_read with an "a" destination: the only
   // way to have the tuple defined there); low planes: left in the patch.
-  const float qsc = 0.125f * 1.44269504088896340736f * p.q_scale;
+  const float qsc = q_prescale(p.q_scale);
   const float sinv = 1.0f / (p.q_scale * p.k_scale);      // powers of two: exact
   // High planes stay in registers (80 for five tiles), low planes go to the wave's LDS patch and come back per (tile, k-step).
   // (the next tile's global loads are issued ahead of this tile's arithmetic)
@@ -244,13 +198,7 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
     for (int s = 0; s < 4; ++s) {
       const f32x4 t0 = qraw[t % QD][2 * s], t1 = qraw[t % QD][2 * s + 1];
       u32x4 lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float x0 = (e < 2 ? t0[2 * e] : t1[2 * e - 4]) * live, x1 = (e < 2 ? t0[2 * e + 1] : t1[2 * e - 3]) * live;
-        const Split2 sp = split2h_pair(x0, x1);
-        qh[t][s][e] = sp.h;
-        lo[e] = sp.l;
-      }
+      q_split8(t0, t1, live, qh[t][s], lo);
       *reinterpret_cast<u32x4*>(qlo + (t * 4 + s) * 1024) = lo;      // (read back by this lane only: no barrier needed)
     }
   }
@@ -274,19 +222,19 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
   unsigned ka[4], va[2];
 #pragma unroll
-  for (int st = 0; st < 4; ++st) ka[st] = lds0 + k_off + (((2 * st + half) ^ ask_swz(r32)) << 4);
+  for (int st = 0; st < 4; ++st) ka[st] = lds0 + k_off + (((2 * st + half) ^ kv_k_swz(r32)) << 4);
 #pragma unroll
   for (int db = 0; db < 2; ++db) {
-    const int key = 4 * half + vq, byte = (db * 32 + vg * 16 + 4 * vp) * 2;      // (asv_swz depends on vq only)
-    va[db] = lds0 + 2 * AS_PLANE + key * 128 + ((((byte >> 4) ^ asv_swz(key)) << 4) | (byte & 15));
+    const int key = 4 * half + vq, byte = (db * 32 + vg * 16 + 4 * vp) * 2;      // (kv_v_swz<VT_4x64> depends on vq only)
+    va[db] = lds0 + 2 * KV_PLANE + key * 128 + ((((byte >> 4) ^ kv_v_swz<VT_4x64>(key)) << 4) | (byte & 15));      // (vt_off, written out)
   }
   auto read_kf = [&](const int stage) {
     as_for<8>([&](auto fc) {
       constexpr int F = decltype(fc)::value, st = F >> 1, pl = F & 1;
       (void)ka, (void)stage;
-      const unsigned addr = ka[st] + stage * AS_STAGE;
+      const unsigned addr = ka[st] + stage * KV_STAGE;
       asm volatile("ds_read_b128 a[%1:%2], %0 offset:%3" ::"v"(addr), "n"(AS_KF + 4 * F), "n"(AS_KF + 4 * F + 3),
-                   "n"(pl * AS_PLANE)
+                   "n"(pl * KV_PLANE)
                    : "memory");
     });
     AS_FENCE();
@@ -295,16 +243,16 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
     as_for<16>([&](auto fc) {
       constexpr int X = decltype(fc)::value, F = X >> 1, rd = X & 1, st = F >> 2, db = (F >> 1) & 1, pl = F & 1;
       (void)va, (void)stage;
-      const unsigned addr = va[db] + stage * AS_STAGE;
+      const unsigned addr = va[db] + stage * KV_STAGE;
       asm volatile("ds_read_b64_tr_b16 a[%1:%2], %0 offset:%3" ::"v"(addr), "n"(AS_VF + 4 * F + 2 * rd),
-                   "n"(AS_VF + 4 * F + 2 * rd + 1), "n"(pl * AS_PLANE + (16 * st + 8 * rd) * 128)
+                   "n"(AS_VF + 4 * F + 2 * rd + 1), "n"(pl * KV_PLANE + (16 * st + 8 * rd) * 128)
                    : "memory");
     });
     AS_FENCE();
   };
   if (nkt > 0) {      // tile 0 has landed: the second tile's DMA goes out, the first one's fragments come in
-    as_wait_vmcnt<0>();
-    as_barrier();
+    wait_vmcnt<0>();
+    bare_barrier();
     if (EXPER != 1 && nkt > 1) issue(32, 1);
     if (active) {
       read_kf(0);
@@ -343,9 +291,9 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
         const Split2 a0 = split2h_pair(as_agpr<R>() * sc, as_agpr<R + 1>() * sc);
         const Split2 a1 = split2h_pair(as_agpr<R + 2>() * sc, as_agpr<R + 3>() * sc);
         // d = 32 db + 8 g + 4 half .. + 3: 8 bytes, the half of 16-byte chunk 4 db + g of the query's row; chunks XOR-keyed by
-        // the row (ask_swz) -- unkeyed, the 32 rows of a store put 16 lanes on each bank pair (PMC: 4.9 M conflict cycles of
+        // the row (kv_k_swz) -- unkeyed, the 32 rows of a store put 16 lanes on each bank pair (PMC: 4.9 M conflict cycles of
         // 7.0 M LDS-active per launch), keyed two
-        unsigned char* dp = so + r32 * 128 + (((4 * db + g) ^ ask_swz(r32)) << 4) + 8 * half;
+        unsigned char* dp = so + r32 * 128 + (((4 * db + g) ^ kv_k_swz(r32)) << 4) + 8 * half;
         *reinterpret_cast<u32x2*>(dp) = u32x2{a0.h, a1.h};
         *reinterpret_cast<u32x2*>(dp + 32 * 128) = u32x2{a0.l, a1.l};
       });
@@ -355,7 +303,7 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
       for (int it = 0; it < 8; ++it) {
         const int pl = it >> 2, qrow = (it & 3) * 8 + (lane >> 3), piece = lane & 7;
         const int qi = qbase + qrow;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(so + (pl * 32 + qrow) * 128 + ((piece ^ ask_swz(qrow)) << 4));
+        const u32x4 v = *reinterpret_cast<const u32x4*>(so + (pl * 32 + qrow) * 128 + ((piece ^ kv_k_swz(qrow)) << 4));
         if (qi < Lq) *(__attribute__((address_space(1))) u32x4*)(p.out2 + (long)pl * p.out2_plane + (rowbase + qi) * p.ldo + h * 64 + piece * 8) = v;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the patch is rewritten by the next tile
@@ -451,7 +399,7 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
           add2(I - 12);
         } else {
           split(7);
-          l_run[t] = l_run[t] * w.alpha + as_half_sum(w.lt);
+          l_run[t] = l_run[t] * w.alpha + half_sum(w.lt);
         }
       };
 
@@ -485,15 +433,15 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
           as_agpr_scale16<AS_O + 32 * T + 16>(w.alpha);
           AS_FENCE();
           if constexpr (EDGE && T > 0) {      // tile T - 1 is complete: out it goes
-            write_tile(std::integral_constant<int, T - 1>{}, lds + ((kt + 1) % NST) * AS_STAGE + wave * (2 * 32 * 128));
+            write_tile(std::integral_constant<int, T - 1>{}, lds + ((kt + 1) % NST) * KV_STAGE + wave * (2 * 32 * 128));
             AS_FENCE();
           }
           stamp(2 + T);
         });
       }
       if constexpr (!EDGE) {      // the next tile has landed (issued a tile ago); this tile's stage is free (its fragments are
-        as_wait_vmcnt<0>();       // in registers, on both waves once they meet here): the tile after next goes there
-        as_barrier();
+        wait_vmcnt<0>();       // in registers, on both waves once they meet here): the tile after next goes there
+        bare_barrier();
         if (EXPER != 1 && kt + 2 < nkt) issue(k0 + 64, kt % NST);      // (issued piecewise in the gaps of the tail's MFMAs it
         if (active) read_kf((kt + 1) % NST);                            //  measured slower: 55.2 vs 53.0 us per launch)
       }
@@ -501,7 +449,7 @@ __global__ __launch_bounds__(64 * AS_NW, 1) void attn64_s_kernel(const AttnArgs 
       if (work) {      // ---- tail: the PV product of the last tile
         as_for<12>([&](auto ic) { pv_mfma(ic, std::integral_constant<int, QT - 1>{}); });
         AS_FENCE();
-        if constexpr (EDGE) write_tile(std::integral_constant<int, QT - 1>{}, lds + ((kt + 1) % NST) * AS_STAGE + wave * (2 * 32 * 128));
+        if constexpr (EDGE) write_tile(std::integral_constant<int, QT - 1>{}, lds + ((kt + 1) % NST) * KV_STAGE + wave * (2 * 32 * 128));
       }
       stamp(8);
       if constexpr (!EDGE) {
@@ -572,17 +520,6 @@ void launch_s(const AttnArgs& a, hipStream_t st) {
 
 }  // namespace
 
-static int single_qt(const AttnArgs& a) {
-  // queries per workgroup = 64 QT: the QT in {2 .. 5} with the fewest padded queries, the taller tile on a tie
-  int qt = 5;
-  long best = 1L << 40;
-  for (int c = 5; c >= 2; --c) {
-    const long padded = (long)cdiv(a.L, 64 * c) * 64 * c;
-    if (padded < best) { qt = c; best = padded; }
-  }
-  return qt;
-}
-
 // Is this the form to use?  One wave per SIMD means 512 workgroups are one round of the chip and 513 are two: the form pays
 // when its workgroups fill their rounds (32 or 64 utterances of <= 320 frames x 8 heads: 512 / 1024); at 40 utterances
 // (640 workgroups: 1.25 rounds run as 2) attn64_pl's small workgroups lose less.  tests/test_gpu_regimes.py holds the seam.
@@ -591,7 +528,7 @@ bool attention64_single_fits(const AttnArgs& a) {
   // ragged batch (compact geometry): one workgroup per head is as long as its utterance's keys and queries, and with one round
   // of workgroups the launch is as long as the longest -- attn64_pl's 128-query workgroups even the lengths out
   if (a.uoff) return false;
-  const long wgs = (long)cdiv(a.L, AS_NW * 32 * single_qt(a)) * a.H * a.B;
+  const long wgs = (long)cdiv(a.L, AS_NW * 32 * attention64_tiles(a.L)) * a.H * a.B;
   const long slots = (long)cdiv(wgs, 512) * 512;
   return wgs * 100 >= slots * 85;
 }
@@ -599,27 +536,13 @@ bool attention64_single_fits(const AttnArgs& a) {
 // same contract as attention64_planes() (attention_pl.hip); no chunk-causal mask
 int attention64_single(const AttnArgs& a, hipStream_t st) {
   if (a.B <= 0 || a.L <= 0) return JV_OK;
-  if (!a.kv2 || (a.kv_ld & 7) || !(a.q_scale > 0.f && a.k_scale > 0.f && a.v_scale > 0.f) || (a.ld & 3) || (a.ldo & 7) || a.chunk > 0)
-    return fail(JV_ERR_ARG, "attention64_single: needs K/V planes, the three scales, aligned strides, no chunk mask");
-  int qt = single_qt(a);
+  JV_TRY(attn_planes_check(a, "attention64_single", false));
+  int qt = attention64_tiles(a.L);
   if (const char* f = dyn_env("JV_ATTN_QT")) qt = atoi(f);
-  if (qt < 2 || qt > 5) return fail(JV_ERR_ARG, "attention64_single: bad tile count");      // before the profiler's start event
-  const bool prof = prof_on();
-  if (prof) prof_begin(st);
-  switch (qt) {
-    case 2: launch_s<2, 2>(a, st); break;
-    case 3: launch_s<3, 2>(a, st); break;
-    case 4: launch_s<4, 2>(a, st); break;
-    case 5: launch_s<5, 2>(a, st); break;
-    default: return fail(JV_ERR_ARG, "attention64_single: bad tile count");
-  }
-  if (prof) {
-    static const char* const names[6] = {"", "", "attn64_s<128 q>", "attn64_s<192 q>", "attn64_s<256 q>", "attn64_s<320 q>"};
-    const double bh = (double)a.B * a.H;
-    prof_end(st, names[qt], 4.0 * bh * a.L * a.L * 64.0, 4.0 * bh * a.L * 64.0 * 4.0);
-  }
-  JV_HIP(hipGetLastError());
-  return JV_OK;
+  static const char* const names[6] = {"", "", "attn64_s<128 q>", "attn64_s<192 q>", "attn64_s<256 q>", "attn64_s<320 q>"};
+  return dispatch_rt(qt, "attention64_single: bad tile count", [&](auto qc) {      // (fails before the profiler's start event)
+    return attn_bracket(a, st, names[qc], [&] { launch_s<decltype(qc)::value, 2>(a, st); });
+  });
 }
 
 }  // namespace jv

@@ -218,9 +218,9 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
   rg_f32x4 cs4 = *reinterpret_cast<const rg_f32x4*>(p.colscale + ncol);
   rg_f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
   if (p.bias) b4 = *reinterpret_cast<const rg_f32x4*>(p.bias + ncol);
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
-  rg_lds_barrier();      // the operand image is complete: the only barrier ahead of the epilogue
+  lds_barrier();      // the operand image is complete: the only barrier ahead of the epilogue
 
   // ---- main loop: step ks = (tap j = ks / NCH, chunk c = ks % NCH); A fragments of row tile mt at window row
   // 80 grp + 16 mt + r16 + j dil (the 16-byte slot key depends on r16 + j dil alone) ----
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
     // this wave's memory operations in program order: ... W0(s+1), W1(s+1) | W0(s+2), <wait>, W1(s+2) | ...; needed at the wait:
     // W0(s+1) and W1(s); behind W0(s+1): W1(s+1) and W0(s+2) = NWL loads (rowgemm_wa_kernel)
     block(std::integral_constant<int, 0>{});
-    rg_wait_vmcnt<NWL>();
+    wait_vmcnt<NWL>();
     bq.template landed_mid<par>();
     if (!last) read_a(std::integral_constant<int, par ^ 1>{}, nc, nj);
     __builtin_amdgcn_sched_barrier(0);
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
     }
   }
   // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
 }
 

@@ -268,9 +268,9 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
   rg_f32x4 cs4 = *reinterpret_cast<const rg_f32x4*>(p.cs2 + ncol);
   rg_f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
   if (p.b2) b4 = *reinterpret_cast<const rg_f32x4*>(p.b2 + ncol);
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
-  rg_lds_barrier();      // the window's image is complete
+  lds_barrier();      // the window's image is complete
 
   // ---- the two products: step ks = (tap j = ks / NCH, chunk c = ks % NCH); A fragments of row tile mt at image row
   // 80 grp + 16 mt + r16 + j dil (the 16-byte slot key depends on r16 + j dil alone) ----
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
     // this wave's memory operations in program order: ... W0(s+NB-1), W1(s+NB-1) | W0(s+NB), <wait>, W1(s+NB) | ...; needed at the
     // wait: W0(s+1) and W1(s); behind W0(s+1): W1(s+1) .. W0(s+NB) = 2 (NB - 1) load pairs (rowgemm_wa_kernel's count at NB = 2)
     block(std::integral_constant<int, 0>{});
-    rg_wait_vmcnt<NWL * (NB - 1)>();
+    wait_vmcnt<NWL * (NB - 1)>();
     bq.template landed_mid<buf>();
     if (!last) read_a(std::integral_constant<int, par ^ 1>{}, nc, nj);
     __builtin_amdgcn_sched_barrier(0);
@@ -326,7 +326,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
   product(std::integral_constant<int, 0>{});      // the intermediate, before its bias, x scale1 x 2^e
 
   // ---- the intermediate: + bias -> mask -> Snake2 -> x scale2 -> planes, over the window's image ----
-  rg_lds_barrier();      // every wave is done reading the window
+  lds_barrier();      // every wave is done reading the window
   {
     unsigned char* const hs = img + cp * CS2 + grp * RG * 64;      // this wave's 32 channels are chunk cp, its rows group grp
     const int key = (kq & 1) << 1;      // rg_key of image row 80 grp + 16 mt + 4 kq + e (bit 2 of it is bit 0 of kq)
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
       }
     }
   }
-  rg_lds_barrier();      // the intermediate's image is complete
+  lds_barrier();      // the intermediate's image is complete
   ips = PS2; ics = CS2; idil = 1;
   product(std::integral_constant<int, KS1>{});
 
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
     }
   }
   // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
 }
 

@@ -177,6 +177,18 @@ __device__ __forceinline__ Split2 split2h_pair(const float x0, const float x1) {
   return {__builtin_bit_cast(unsigned, h), __builtin_bit_cast(unsigned, l)};
 }
 
+// Hand-counted waits and bare barriers of the kernels that keep LDS-DMA or asm loads in flight across a barrier (the
+// row-owning kernels, the attention kernels): the place and the count are the kernel's, the instruction is written here once.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// Bare barriers (the "memory" clobber keeps the compiler from moving LDS / global accesses across them; s_barrier itself
+// waits for no counter).  __syncthreads() would add s_waitcnt vmcnt(0): in a main loop that drains the steps of LDS-DMA
+// kept in flight, in an epilogue it waits for the row stores to be acknowledged.
+__device__ __forceinline__ void bare_barrier() { asm volatile("s_barrier" ::: "memory"); }
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // Attention's running softmax (attention_pl.hip, attention_s.hip -- the same rule in both, so an utterance's result does not
 // depend on which of them its batch selects): the exponent's reference maximum moves only when a key tile's maximum exceeds it
 // by more than ATTN_LAZY (base-2 units).  P = p 2^10 can then reach 2^(10 + ATTN_LAZY) = 2^14 < 65504, and the accumulated

@@ -285,13 +285,13 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
       advance_w();
     }
   }
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
   // A warm-up value is "used" (an empty asm) where the wait costs nothing and is dead from then on.  Kept alive to the end
   // of the kernel it crossed the feed-forward loop -- in scratch: the compiler spilled it right behind the load, i.e. put an
   // s_waitcnt vmcnt(0) on a load that is an L2 miss BY DESIGN in front of phase A's epilogue (6 k cycles in the stamps).
   asm volatile("" ::"v"(warm));
-  rg_barrier();
+  bare_barrier();
   stamp();      // 1: prologue done
   read_a(std::integral_constant<int, 0>{}, hreg);
 
@@ -330,13 +330,13 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
       };
       block(std::integral_constant<int, 0>{});
       if (s + 2 < KSA) {
-        if (my_pieces == PPW) rg_wait_vmcnt<NWL + PPW>();
-        else rg_wait_vmcnt<NWL + PPW - 1>();
+        if (my_pieces == PPW) wait_vmcnt<NWL + PPW>();
+        else wait_vmcnt<NWL + PPW - 1>();
       } else {
-        rg_wait_vmcnt<NWL>();
+        wait_vmcnt<NWL>();
       }
       bq.template landed_mid<par>();
-      rg_barrier();
+      bare_barrier();
       const int s3n = s3 == 2 ? 0 : s3 + 1;
       if (s + 1 < KSA) read_a(std::integral_constant<int, par ^ 1>{}, hreg + s3n * STAGE);
       __builtin_amdgcn_sched_barrier(0);
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
   stamp();      // 2: phase A loop done
   // what the first step of phase B waits for in its middle -- W0(17), W1(16) -- has only W1(17) behind it so far; counted
   // HERE, ahead of the epilogue's own loads and stores (vmcnt retires in order: counting behind them would wait for them)
-  rg_wait_vmcnt<2>();
+  wait_vmcnt<2>();
 
   // the row pass shared by the two residual epilogues: rows [wave NRW, + NRW) of the tile, RT at a time, from the slab:
   //   v = slab * cs + bias + res -> dst rows (+ tracking); LN: LayerNorm_256(v) * sc -> fp16 planes into the operand image X
@@ -458,16 +458,16 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
     rg_f32x4 rpre[NRW];
     prefetch_rows(p.h, rpre);
     xstamp();      // 18: loads requested
-    rg_lds_barrier();      // every wave is done reading the ring: the slab goes over it
+    lds_barrier();      // every wave is done reading the ring: the slab goes over it
     xstamp();      // 19
     acc_to_slab(acc1);
-    rg_lds_barrier();
+    lds_barrier();
     xstamp();      // 20: slab written
     cs4 = cs4 * p.inv_a_scale_o;      // (first use of a loaded value: HERE, behind the barriers that hide the loads' ~2 k cycles, not in front of them)
     if (!JV_ABLATE(p, 16)) row_pass(cs4, b4, rpre, facts_h, p.h, LDH, p.amax_h, true, gg, bb, p.a_scale1, nullptr);
     xstamp();      // 21: row pass done (this wave)
     asm volatile("" ::"v"(warm2), "v"(warm1));      // (issued a whole row pass ago / in the middle of phase A)
-    rg_lds_barrier();      // X is complete, the slab has been read: the upper half is free for H
+    lds_barrier();      // X is complete, the slab has been read: the upper half is free for H
   }
   stamp();      // 3: epilogue A done
 
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
       __builtin_amdgcn_sched_barrier(0);
     };
     block(std::integral_constant<int, 0>{});
-    if (!waited) rg_wait_vmcnt<NWL>();
+    if (!waited) wait_vmcnt<NWL>();
     waited = false;
     bq.template landed_mid<par>();
     if (st_next) read_a(std::integral_constant<int, par ^ 1>{}, st_next);
@@ -591,9 +591,9 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
       p1_run(c > 0);
       stamp();      // 4 + 3 c: phase 1 done
       if (c == NCH - 1) warm_q();
-      if (c > 0) rg_lds_barrier();      // every wave is done reading the previous chunk's H
+      if (c > 0) lds_barrier();      // every wave is done reading the previous chunk's H
       gelu_pass();
-      rg_lds_barrier();      // H complete
+      lds_barrier();      // H complete
       stamp();      // 5 + 3 c: GELU done
       p2_run(0, KS, false, c + 1 < NCH ? rg_lds : nullptr);
       stamp();      // 6 + 3 c: phase 2 done
@@ -634,18 +634,18 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
             p1_run(true);
           }
         }
-        rg_lds_barrier();
+        lds_barrier();
         stamp();      // 5 + 3 c, 6 + 3 c
       }
       // I2(c): X second(c) k 4..7 | Y second(c) k 0..3
       p2_run(hx ? 4 : 0, 4, false, nullptr);
-      if (more) rg_lds_barrier();      // (the last one is the epilogue's)
+      if (more) lds_barrier();      // (the last one is the epilogue's)
       stamp();      // 7 + 3 c
     }
     if (!hx) p2_run(4, 4, false, nullptr);      // Y's last four steps
   }
   xstamp();      // B0: loop done
-  rg_wait_vmcnt<2>();      // what the next step's middle needs (if there is one), ahead of the epilogue's own memory operations
+  wait_vmcnt<2>();      // what the next step's middle needs (if there is one), ahead of the epilogue's own memory operations
   xstamp();      // B1: fragments of the next steps landed
   if constexpr (QKV) asm volatile("" ::"v"(warm3));      // (issued at the last GELU pass)
 
@@ -663,17 +663,17 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
     rg_f32x4 rpre[NRW];
     prefetch_rows(p.h, rpre);
     xstamp();      // 22: loads requested
-    rg_lds_barrier();      // every wave is done with X and H
+    lds_barrier();      // every wave is done with X and H
     xstamp();      // 23
     acc_to_slab(acc2);
-    rg_lds_barrier();
+    lds_barrier();
     xstamp();      // 24: slab written
     cs4 = cs4 * p.inv_h_scale;
     if (!JV_ABLATE(p, 16))
       row_pass(cs4, b4, rpre, facts_o, p.out, QKV ? LDH : p.ldo, p.amax_out, ln_b, gg, bb, ln_b ? p.a_scale_q : 1.f,
                QKV ? nullptr : p.ln_out);      // (q|k|v follows only where out is the trunk itself)
     xstamp();      // 25: row pass done
-    if constexpr (QKV) rg_lds_barrier();      // X is complete, the slab has been read: the patches go over it
+    if constexpr (QKV) lds_barrier();      // X is complete, the slab has been read: the patches go over it
   }
   stamp();      // 16: epilogue B done
 
@@ -704,7 +704,7 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
       }
       stamp();      // 17 + 2 c: chunk loop done
       if (c + 1 < NCQ) {
-        rg_wait_vmcnt<2>();
+        wait_vmcnt<2>();
         waited = true;
       }
       // the chunk's epilogue, per wave, through its private 16 x 36-float patch (rowgemm_wa_kernel): q -> fp32 rows, k / v -> planes
@@ -761,7 +761,7 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
     }
   }
   // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
   stamp();      // last: drained
 }

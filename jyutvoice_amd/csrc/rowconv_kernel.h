@@ -222,10 +222,10 @@ __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
       // W(s) has landed once at most the operations issued after it are outstanding: W(s + 1), and the A loads of chunk
       // c + 2 when they were issued behind W(s + 1) or W(s + 2) (the end of step (c, 0))
       if (!JV_ABLATE(p, 4)) {
-        if (s + 1 >= total) rg_wait_vmcnt<0>();
-        else if (j != 0 && c + 2 < NCH && !JV_ABLATE(p, 8)) rg_wait_vmcnt<PPW + NI>();
-        else rg_wait_vmcnt<PPW>();
-        rg_lds_barrier();      // (+ this wave's A-plane stores of the previous chunk step are complete)
+        if (s + 1 >= total) wait_vmcnt<0>();
+        else if (j != 0 && c + 2 < NCH && !JV_ABLATE(p, 8)) wait_vmcnt<PPW + NI>();
+        else wait_vmcnt<PPW>();
+        lds_barrier();      // (+ this wave's A-plane stores of the previous chunk step are complete)
       }
       const bool more = s + 2 < total && !JV_ABLATE(p, 1);
       const int nstage = (s + 2) % 3;
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
   // passes through a slab of their own, two barriers each, the tail took 13 - 19 us of a 50 us launch.)
   if (JV_ABLATE(p, 16)) return;
   const bool mish = p.act == ACT_MISH;      // (uniform) the one activation the estimator uses here
-  rg_lds_barrier();      // every wave is done reading the ring
+  lds_barrier();      // every wave is done reading the ring
   float* const slab = reinterpret_cast<float*>(rc_lds);
 #pragma unroll
   for (int mt = 0; mt < RT; ++mt)
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
       for (int e = 0; e < 4; ++e) slab[(mt * 16 + kq * 4 + e) * RG_SLD + wave * 32 + nt * 16 + r16] = acc[mt][nt][e];
-  rg_lds_barrier();
+  lds_barrier();
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
     constexpr int RPW = RT;      // rows per wave and group: the wave owns tile rows 2 RT wave ... 2 RT wave + 2 RT - 1
@@ -530,12 +530,12 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
     if (p.res_bias) br4 = *reinterpret_cast<const rg_f32x4*>(p.res_bias + 4 * lane);
   }
   stamp();      // 1: row facts and staging addresses set up
-  rg_wait_vmcnt<0>();      // the first window's rows (and the first fragments, needed two lines down anyway)
+  wait_vmcnt<0>();      // the first window's rows (and the first fragments, needed two lines down anyway)
   landed_a();
   store_A(0);
   if (NCH > 1) load_A(1);
   // both steps' fragments (and everything older) have landed once only the A loads of chunk 1 are outstanding
-  if (NCH > 1) rg_wait_vmcnt<NI>(); else rg_wait_vmcnt<0>();
+  if (NCH > 1) wait_vmcnt<NI>(); else wait_vmcnt<0>();
   bq.landed_all();
   stamp();      // 2: first window staged, first fragments landed
 
@@ -549,9 +549,9 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
     constexpr int par = decltype(par_tag)::value, j = decltype(jtag)::value;
     constexpr int jrow = j < 3 ? j : 2;      // res_conv's step reads the output row itself: tap 2's row offset
     if (j == 0) {
-      rg_lds_barrier();      // every thread's plane stores of this chunk's window are complete; the other buffer is free
+      lds_barrier();      // every thread's plane stores of this chunk's window are complete; the other buffer is free
       if (c + 1 < NCH) {      // its registers were loaded a chunk ago and waited for at step (c - 1, 2) ...
-        if (c == 0) rg_wait_vmcnt<0>();      // ... except chunk 1's, issued just ahead of the loop (nothing else is in flight yet)
+        if (c == 0) wait_vmcnt<0>();      // ... except chunk 1's, issued just ahead of the loop (nothing else is in flight yet)
         landed_a();
         store_A((c + 1) & 1);
       }
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
     };
     auto blocks = [&](rg_f32x4 (&ac)[RT][2]) {
       block(std::integral_constant<int, 0>{}, ac);
-      if (j == 1 && c + 2 < NCH) rg_wait_vmcnt<NWL + NI>(); else rg_wait_vmcnt<NWL>();
+      if (j == 1 && c + 2 < NCH) wait_vmcnt<NWL + NI>(); else wait_vmcnt<NWL>();
       bq.template landed_mid<par>();
       block(std::integral_constant<int, 1>{}, ac);
     };
@@ -713,7 +713,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
   {
     RowIn in0, in1;
     request(std::integral_constant<int, 0>{}, in0);      // (rowinfo was written by this workgroup's threads ahead of the main loop's barriers)
-    rg_lds_barrier();
+    lds_barrier();
     stamp();      // 4: slab written, barrier passed
     request(std::integral_constant<int, 1>{}, in1);
     rows(std::integral_constant<int, 0>{}, in0);
@@ -724,14 +724,14 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
   if constexpr (RES) {
     // ---- res_conv's rows: a second pass through the same slab -- res_out = acc_r * res_cs / a_scale + res_bias, fp32 rows that
     // block2's launch adds.  (A masked input row was staged as zeros: its output is the bias, as in a launch of its own.)
-    rg_lds_barrier();      // every wave has read its rows of the first pass
+    lds_barrier();      // every wave has read its rows of the first pass
 #pragma unroll
     for (int mt = 0; mt < RT; ++mt)
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
         for (int e = 0; e < 4; ++e) slab[(mt * 16 + kq * 4 + e) * RG_SLD + wave * 32 + nt * 16 + r16] = accr[mt][nt][e];
-    rg_lds_barrier();
+    lds_barrier();
 #pragma unroll
     for (int jj = 0; jj < 2 * RT; ++jj) {
       const int trow = wave * 2 * RT + jj;
@@ -741,7 +741,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
       if (mrow < p.M) *(__attribute__((address_space(1))) rg_f32x4*)(p.res_out + mrow * 256 + 4 * lane) = v;
     }
   }
-  rg_wait_vmcnt<0>();      // the wrapped-around W loads: bq stays reserved until they have landed (WFragBuf, rule c)
+  wait_vmcnt<0>();      // the wrapped-around W loads: bq stays reserved until they have landed (WFragBuf, rule c)
   bq.landed_all();
   asm volatile("" ::"v"(warm));
   stamp();      // 7 (6 without the res_conv pass): every store of this wave acknowledged

@@ -83,16 +83,6 @@ constexpr int RG_SLAB_BYTES = RG_SLAB_ROWS * RG_SLD * 4;
 template <int RT> constexpr int rg_stage_bytes() { return 2 * 16 * RT * 64 + 2 * 256 * 64; }
 template <int RT> constexpr int rg_lds_bytes() { return 3 * rg_stage_bytes<RT>() + RG_SLAB_BYTES; }
 
-template <int N>
-__device__ __forceinline__ void rg_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// Bare barriers (the "memory" clobber keeps the compiler from moving LDS / global accesses across them; s_barrier itself
-// waits for no counter).  __syncthreads() would add s_waitcnt vmcnt(0): in the main loop that drains the two steps of
-// LDS-DMA kept in flight, in the epilogue it waits for the row stores to be acknowledged.
-__device__ __forceinline__ void rg_barrier() { asm volatile("s_barrier" ::: "memory"); }
-__device__ __forceinline__ void rg_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <int RT, int EPI>
 __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
@@ -185,11 +175,11 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
   // all but this wave's `keep` youngest pieces have landed (keep = one step's worth, or 0)
   auto wait_landed = [&](bool next_in_flight) {
     if (!next_in_flight) {
-      rg_wait_vmcnt<0>();
+      wait_vmcnt<0>();
     } else if (my_pieces == PPW) {
-      rg_wait_vmcnt<PPW>();
+      wait_vmcnt<PPW>();
     } else {
-      rg_wait_vmcnt<PPW - 1>();
+      wait_vmcnt<PPW - 1>();
     }
   };
 
@@ -218,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
       // reading the stage that step s + 2 will overwrite (it was read in step s - 1)
       if (!JV_ABLATE(p, 4)) {
         wait_landed(s + 1 < total);
-        rg_barrier();
+        bare_barrier();
       }
       const bool more = s + 2 < total && !JV_ABLATE(p, 1);
       const int nstage = (s + 2) % 3;
@@ -355,7 +345,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
       // one 256-column chunk: nothing left to prefetch, so the whole tile goes through ONE slab laid over the idle ring and
       // every wave takes its 2 RT rows RT at a time (loads, reductions and conversions of RT rows overlap).  In 32-row passes
       // through the small slab, two barriers each, this tail was 10 us of a 44 us launch.
-      rg_lds_barrier();      // every wave is done reading the ring
+      lds_barrier();      // every wave is done reading the ring
       float* const big = reinterpret_cast<float*>(rg_lds);
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt)
@@ -363,7 +353,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
           for (int e = 0; e < 4; ++e) big[(mt * 16 + kq * 4 + e) * RG_SLD + wave * 32 + nt * 16 + r16] = acc[mt][nt][e];
-      rg_lds_barrier();
+      lds_barrier();
       rows_body(std::integral_constant<int, RT>{}, big, wave * 2 * RT, wave * 2 * RT);
       rows_body(std::integral_constant<int, RT>{}, big, wave * 2 * RT + RT, wave * 2 * RT + RT);
     } else {
@@ -379,9 +369,9 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
                 slab[(ml * 16 + kq * 4 + e) * RG_SLD + wave * 32 + nt * 16 + r16] = acc[2 * ps + ml][nt][e];
           }
         }
-        rg_lds_barrier();
+        lds_barrier();
         rows_body(std::integral_constant<int, RG_SLAB_ROWS / 8>{}, slab, ps * 32 + wave * (RG_SLAB_ROWS / 8), wave * (RG_SLAB_ROWS / 8));
-        rg_lds_barrier();      // the slab is rewritten by the next pass / chunk
+        lds_barrier();      // the slab is rewritten by the next pass / chunk
       }
     }
   }
@@ -528,9 +518,9 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
   issue_piece(std::integral_constant<int, 0>{}, 2);
   if constexpr (PPW > 1) issue_piece(std::integral_constant<int, 1>{}, 2);
   advance();
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
-  rg_barrier();
+  bare_barrier();
   read_a(std::integral_constant<int, 0>{}, 0);
 
   int s = 0, s3 = 0;      // step, step % 3
@@ -591,12 +581,12 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
       // (the first step after a chunk's epilogue: what it needs was waited for BEFORE the epilogue's stores were issued,
       // below -- counting here would wait for those stores, vmcnt being in order)
       if (!waited) {
-        if (my_pieces == PPW) rg_wait_vmcnt<NWL + PPW>();
-        else rg_wait_vmcnt<NWL + PPW - 1>();
+        if (my_pieces == PPW) wait_vmcnt<NWL + PPW>();
+        else wait_vmcnt<NWL + PPW - 1>();
       }
       waited = false;
       bq.template landed_mid<par>();
-      if (!JV_ABLATE(p, 4)) rg_barrier();
+      if (!JV_ABLATE(p, 4)) bare_barrier();
       const int s3n = s3 == 2 ? 0 : s3 + 1;      // (s + 1) % 3
       if (!JV_ABLATE(p, 8)) read_a(std::integral_constant<int, par ^ 1>{}, s3n);
       __builtin_amdgcn_sched_barrier(0);
@@ -613,8 +603,8 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
     if (c + 1 < NC) {
       // the next step's middle needs A(s + 1), W0(s + 1), W1(s); behind the youngest of them, W0(s + 1), only A(s + 2) and
       // W1(s + 1) have been issued so far
-      if (my_pieces == PPW) rg_wait_vmcnt<2 + PPW>();
-      else rg_wait_vmcnt<2 + PPW - 1>();
+      if (my_pieces == PPW) wait_vmcnt<2 + PPW>();
+      else wait_vmcnt<2 + PPW - 1>();
       waited = true;
     }
 
@@ -751,7 +741,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
       for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
         for (int e = 0; e < 4; ++e) big[(mt * 16 + kq * 4 + e) * RG_SLD + wave * 32 + nt * 16 + r16] = acc[mt][nt][e];
-    rg_lds_barrier();
+    lds_barrier();
     if (!JV_ABLATE(p, 64)) {
       rows_body(std::integral_constant<int, RT>{}, big, wave * 2 * RT, wave * 2 * RT, std::integral_constant<int, 0>{});
       rows_body(std::integral_constant<int, RT>{}, big, wave * 2 * RT + RT, wave * 2 * RT + RT, std::integral_constant<int, RT>{});
@@ -761,7 +751,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
   // stay RESERVED until they have landed -- the compiler does not know about the asm loads in flight, and once it saw bq
   // dead after the last step (the single-chunk residual epilogues) it kept a pointer there, which such a load then
   // overwrote (a memory fault).  The empty asm below makes every bq register live up to this point.
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
   asm volatile("" ::"v"(warm));
 }
@@ -864,9 +854,9 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
   load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
   load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
   advance_w();
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
-  rg_barrier();      // every wave's A pieces are in LDS: the only barrier ahead of the epilogues
+  bare_barrier();      // every wave's A pieces are in LDS: the only barrier ahead of the epilogues
 
   const int a_off = afrag_off(r16, kq);
   rg_f32x4 acc[RT][2];
@@ -904,7 +894,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
         __builtin_amdgcn_sched_barrier(0);
       };
       block(std::integral_constant<int, 0>{});
-      if (!waited) rg_wait_vmcnt<NWL>();      // (first step of a chunk: waited for ahead of the epilogue's stores, below)
+      if (!waited) wait_vmcnt<NWL>();      // (first step of a chunk: waited for ahead of the epilogue's stores, below)
       waited = false;
       bq.template landed_mid<par>();
       read_a(std::integral_constant<int, par ^ 1>{}, ks1);
@@ -918,7 +908,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
       step(std::integral_constant<int, 1>{});
     }
     if (c + 1 < c1) {      // what the next step's wait needs -- W0(s + 1), W1(s) -- has only W1(s + 1) behind it so far
-      rg_wait_vmcnt<2>();
+      wait_vmcnt<2>();
       waited = true;
     }
 
@@ -964,7 +954,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
     }
   }
   // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
   asm volatile("" ::"v"(warm));
 }
@@ -1105,10 +1095,10 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
   load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
   load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
   advance_w();
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   wfrag_landed(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
   wfrag_landed(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
-  rg_barrier();      // X is in LDS for every wave
+  bare_barrier();      // X is in LDS for every wave
 
   const int a_off = afrag_off(r16, kq);
   rg_f32x4 acc1[RT][2], acc2[RT][2];
@@ -1141,7 +1131,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
       __builtin_amdgcn_sched_barrier(0);
     };
     block(std::integral_constant<int, 0>{});
-    rg_wait_vmcnt<NWL>();
+    wait_vmcnt<NWL>();
     wfrag_landed(bq[par][1][0], bq[par][1][1], bq[par ^ 1][0][0], bq[par ^ 1][0][1]);
     if (st_next) read_a(std::integral_constant<int, par ^ 1>{}, st_next);
     __builtin_amdgcn_sched_barrier(0);
@@ -1169,7 +1159,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
       step(std::integral_constant<int, 1>{}, acc1, rg_lds + (ks + 1) * STAGE, ks + 2 < KS ? rg_lds + (ks + 2) * STAGE : nullptr, true);
     }
     // ---- GELU -> planes, into stage `wave` of H (rows mt 16 + 4 kq + e, k = 16 nt + r16 of that stage) ----
-    if (c > 0) rg_lds_barrier();      // every wave is done reading the previous chunk's H
+    if (c > 0) lds_barrier();      // every wave is done reading the previous chunk's H
     {
       unsigned char* const hs = rg_lds + H_OFF + wave * STAGE;
       const int key = (kq & 1) << 1;      // rg_key(row): bit 2 of the row = bit 0 of kq
@@ -1192,7 +1182,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
           }
         }
     }
-    rg_lds_barrier();      // H complete
+    lds_barrier();      // H complete
     // ---- phase 2 ----
 #pragma unroll 1
     for (int ks = 0; ks < KS; ks += 2) {
@@ -1237,7 +1227,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
     gg = *reinterpret_cast<const rg_f32x4*>(p.ln_g + 4 * lane);
     bb = *reinterpret_cast<const rg_f32x4*>(p.ln_b + 4 * lane);
   }
-  rg_lds_barrier();      // every wave is done with X and H: the slab goes over them
+  lds_barrier();      // every wave is done with X and H: the slab goes over them
   float* const big = reinterpret_cast<float*>(rg_lds);
 #pragma unroll
   for (int mt = 0; mt < RT; ++mt)
@@ -1245,7 +1235,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
       for (int e = 0; e < 4; ++e) big[(mt * 16 + kq * 4 + e) * RG_SLD + wave * 32 + nt * 16 + r16] = acc2[mt][nt][e];
-  rg_lds_barrier();
+  lds_barrier();
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
     rg_f32x4 v[RT];
@@ -1283,7 +1273,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
       }
     }
   }
-  rg_wait_vmcnt<0>();      // the wrapped-around W loads: bq stays reserved until they have landed (WFragBuf, rule c)
+  wait_vmcnt<0>();      // the wrapped-around W loads: bq stays reserved until they have landed (WFragBuf, rule c)
   wfrag_landed(bq[0][0][0], bq[0][0][1], bq[0][1][0], bq[0][1][1]);
   wfrag_landed(bq[1][0][0], bq[1][0][1], bq[1][1][0], bq[1][1][1]);
   asm volatile("" ::"v"(warm));

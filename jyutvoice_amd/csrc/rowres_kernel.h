@@ -237,11 +237,11 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
       acc[mt][nt] = rg_f32x4{0.f, 0.f, 0.f, 0.f};
       accr[mt][nt] = rg_f32x4{0.f, 0.f, 0.f, 0.f};
     }
-  rg_wait_vmcnt<0>();      // the first window's rows, the facts, the first fragments
+  wait_vmcnt<0>();      // the first window's rows, the facts, the first fragments
   landed_a();
   store_A(0);
   if (NCH > 1) load_A(1);
-  if (NCH > 1) rg_wait_vmcnt<NI>(); else rg_wait_vmcnt<0>();
+  if (NCH > 1) wait_vmcnt<NI>(); else wait_vmcnt<0>();
   bq.landed_all();
 
   // ================================ product 1 (rowconv_wd_kernel<RT, true>'s step) ================================
@@ -250,9 +250,9 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
       constexpr int par = decltype(par_tag)::value, j = decltype(jtag)::value;
       constexpr int jrow = j < 3 ? j : 2;      // res_conv's step reads the h2 row's own row of x: tap 2's row offset
       if (j == 0) {
-        rg_lds_barrier();      // every thread's plane stores of this chunk's window are complete; the other buffer is free
+        lds_barrier();      // every thread's plane stores of this chunk's window are complete; the other buffer is free
         if (c + 1 < NCH) {
-          if (c == 0) rg_wait_vmcnt<0>();
+          if (c == 0) wait_vmcnt<0>();
           landed_a();
           store_A((c + 1) & 1);
         }
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
       };
       auto blocks = [&](rg_f32x4 (&ac)[RT][2]) {
         block(std::integral_constant<int, 0>{}, ac);
-        if (j == 1 && c + 2 < NCH) rg_wait_vmcnt<NWL + NI>(); else rg_wait_vmcnt<NWL>();
+        if (j == 1 && c + 2 < NCH) wait_vmcnt<NWL + NI>(); else wait_vmcnt<NWL>();
         bq.template landed_mid<par>();
         block(std::integral_constant<int, 1>{}, ac);
       };
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
   const float inv2 = 1.0f / scale2;
 
   // the wrapped-around loads of the last two steps land in registers nothing reads; then block2's first two steps are requested
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
   asm volatile("" ::"v"(warm), "v"(warm2));
   // (QKV) to_q | to_k | to_v's fragments into this XCD's L2 a whole product ahead: cold, every step of product 3 began with
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
 
   // ================================ epilogue 1: h2 -> the operand image; res_conv's rows -> registers ================================
   acc_to_slab(acc);      // (the slab is the upper half: nothing of product 1 lives there)
-  rg_lds_barrier();      // slab complete; every wave is done with the window buffers: the image goes over them
+  lds_barrier();      // slab complete; every wave is done with the window buffers: the image goes over them
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
     rg_f32x4 v[RT];
@@ -374,9 +374,9 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
       *reinterpret_cast<rg_u32x2*>(d + XP) = y2.l;
     }
   }
-  rg_lds_barrier();      // every wave has read its slab rows: res_conv's product goes through the slab next
+  lds_barrier();      // every wave has read its slab rows: res_conv's product goes through the slab next
   acc_to_slab(accr);
-  rg_lds_barrier();
+  lds_barrier();
   rg_f32x4 res[NRW];      // res_conv(x * mask) of this wave's output rows t = wave NRW + j: h2 row t + 2
 #pragma unroll
   for (int j = 0; j < NRW; ++j) {
@@ -384,10 +384,10 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
     const int srow = t + 2 < R ? t + 2 : R - 1;      // (t >= RO: no output row)
     res[j] = *reinterpret_cast<const rg_f32x4*>(slab + rb_slab(srow, 4 * lane)) * (csr * lane_bcast(f_invo, j)) + br;
   }
-  rg_wait_vmcnt<0>();      // block2's first fragments
+  wait_vmcnt<0>();      // block2's first fragments
   asm volatile("" ::"v"(warm3));      // (issued an epilogue ago)
   bq.landed_all();
-  rg_lds_barrier();      // the image is complete (and the slab has been read: epilogue 2 writes it again)
+  lds_barrier();      // the image is complete (and the slab has been read: epilogue 2 writes it again)
 
   // ================================ product 2: block2 over the resident image ================================
 #pragma unroll
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
         __builtin_amdgcn_sched_barrier(0);
       };
       block(std::integral_constant<int, 0>{});
-      rg_wait_vmcnt<NWL>();
+      wait_vmcnt<NWL>();
       bq.template landed_mid<par>();
       if (!last) read_a(std::integral_constant<int, par ^ 1>{}, nc, nj);
       __builtin_amdgcn_sched_barrier(0);
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
     woff = ((long)qks * 96 + qc * 16) * 512;
   };
   acc_to_slab(acc);      // (the slab was last read before product 2's barrier)
-  rg_lds_barrier();      // (and every wave is done reading the image: the LayerNorm1 planes go over it below)
+  lds_barrier();      // (and every wave is done reading the image: the LayerNorm1 planes go over it below)
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
     rg_f32x4 v[RT];
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
   if constexpr (QKV) {
     // product 2's wrapped-around loads land in registers nothing reads; then q | k | v's first two steps are requested (HERE, behind
     // the row pass: requested ahead of it the 32 fragment registers pushed the pass's values into scratch)
-    rg_wait_vmcnt<0>();
+    wait_vmcnt<0>();
     bq.landed_all();
     set_wbase(p.Wqf, p.wqf_plane);
     woff = 0;
@@ -538,8 +538,8 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
     load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
     load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
     advance_q();
-    rg_lds_barrier();      // the image is complete; the slab has been read: the patches go over it
-    rg_wait_vmcnt<0>();      // (the fragments' round trip passes under the barrier; the row stores are waited for with them)
+    lds_barrier();      // the image is complete; the slab has been read: the patches go over it
+    wait_vmcnt<0>();      // (the fragments' round trip passes under the barrier; the row stores are waited for with them)
     bq.landed_all();
     constexpr long LDQ = 512, LDKV = 1024;
     constexpr int NPATCH = RT >= 3 ? 2 : 1;      // (RT = 2: the slab is 32 KB, eight pairs of patches are 36)
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
         __builtin_amdgcn_sched_barrier(0);
       };
       block(std::integral_constant<int, 0>{});
-      if (!waited) rg_wait_vmcnt<NWL>();
+      if (!waited) wait_vmcnt<NWL>();
       waited = false;
       bq.template landed_mid<par>();
       if (ks_next >= 0) read_a(std::integral_constant<int, par ^ 1>{}, ks_next);
@@ -588,7 +588,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
         step(std::integral_constant<int, 1>{}, ks + 2 < 8 ? ks + 2 : (c + 1 < 6 ? 0 : -1));
       }
       if (c + 1 < 6) {
-        rg_wait_vmcnt<2>();
+        wait_vmcnt<2>();
         waited = true;
       }
       // the chunk's epilogue, per wave, through its private 16 x 36-float patches: q -> fp32 rows, k / v -> planes
@@ -642,7 +642,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
     }
   }
   // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
-  rg_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   bq.landed_all();
 }
 

@@ -649,6 +649,47 @@ def test_attention_single_equals_planes_bit_for_bit(dev, monkeypatch, B, L, lens
         assert torch.equal(pl16[sl], s16[sl]), b
 
 
+@pytest.mark.parametrize("form,ring,B,L,lens", [(None, "JV_ATTN_NST3", 3, 70, [70, 1, 33]),
+                                                ("JV_OP_ATTN_ROWS", "JV_ATTN_NST2", 2, 129, [129, 64])])
+def test_attention_ring_depth(dev, monkeypatch, form, ring, B, L, lens):
+    """The two instantiations of the shared K / V piece table (attention_common.h: KvPieces) that no other test reaches:
+    attn64_pl's three-stage ring at four waves (JV_ATTN_NST3; 70 frames is the smallest shape that selects four waves: three
+    key tiles, a one-key utterance, a straddled last tile) and attn64_r's two-stage ring (JV_ATTN_NST2; five key tiles, a
+    ragged mask).  Against fp64 with the bound of the tests above, and EQUAL to the default ring depth: the depth moves
+    bytes, not arithmetic."""
+    from jyutvoice_amd.engine import op_attention_planes
+    monkeypatch.delenv("JV_OP_ATTN_SINGLE", raising=False)
+    monkeypatch.delenv("JV_OP_ATTN_ROWS", raising=False)
+    if form:
+        monkeypatch.setenv(form, "1")
+    g = torch.Generator().manual_seed(B * 1000 + L + 23)
+    G, gap = 4, 4
+    S = L + gap
+    rows = G + B * S + 8
+    qkv = torch.randn(rows, 1536, generator=g)
+    qkv[:, 512:1024] *= 3.0
+    lens_t = torch.tensor(lens, dtype=torch.int32)
+    bounds = tuple(4.0 * float(qkv[:, o:o + 512].abs().max()) for o in (0, 512, 1024))
+
+    def run():
+        return [op_attention_planes(qkv.to(dev), lens_t.to(dev), B, G, S, L, bounds, planes_out=po).cpu() for po in (False, True)]
+
+    monkeypatch.delenv(ring, raising=False)
+    base = run()
+    monkeypatch.setenv(ring, "1")
+    got = run()
+    for b in range(B):
+        blk = qkv[G + b * S: G + b * S + L].double()
+        q, k, v = (blk[:, i * 512:(i + 1) * 512].view(L, 8, 64).transpose(0, 1) for i in range(3))
+        s = q @ k.transpose(1, 2) / 8.0
+        s[:, :, lens[b]:] = -1e10
+        want = (torch.softmax(s, -1) @ v).transpose(0, 1).reshape(L, 512)
+        sl = slice(G + b * S, G + b * S + L)
+        for o, o0 in zip(got, base):
+            assert float((o[sl].double() - want).abs().max()) < 5e-6, b
+            assert torch.equal(o[sl], o0[sl]), b
+
+
 @pytest.mark.parametrize("k,dil,C,rows", [(11, 5, 64, 1500), (7, 3, 128, 700), (3, 1, 256, 333), (11, 5, 256, 250), (7, 1, 64, 321),
                                           (3, 5, 128, 161), (11, 1, 128, 40)])
 def test_hiftconv(dev, k, dil, C, rows):

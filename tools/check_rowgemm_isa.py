@@ -20,7 +20,9 @@ compile; --resources=PATH also writes the table as JSON (profiles/row_kernels_re
 
 Texts: --keep-asm=DIR keeps the assembly of every kernel of those three files, one text per kernel, as
 DIR/<source file>/<mangled name>.s (from the kernel's label to the end of its .amdhsa_kernel block): what tools/isa_compare.py
-compares between two commits.
+compares between two commits.  It also keeps the kernels of the four attention files (attention.hip, attention_pl.hip,
+attention_r.hip, attention_s.hip and the latter's tuning build as attention_s.hip.tune), compiled with the library's per-file
+flags: texts only, none of the checks above looks at the three files it compiles for this.
 
 usage: python tools/check_rowgemm_isa.py [--resources[=PATH]] [--keep-asm=DIR]   (exit code 0 = clean)"""
 import json
@@ -34,6 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRCS = [os.path.join(ROOT, "jyutvoice_amd", "csrc", f) for f in ("rowgemm.hip", "rowblock.hip", "hiftconv.hip")]
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 ATTN_S = os.path.join(ROOT, "jyutvoice_amd", "csrc", "attention_s.hip")
+ATTN_KEEP = [os.path.join(ROOT, "jyutvoice_amd", "csrc", f) for f in ("attention.hip", "attention_pl.hip", "attention_r.hip")]
 sys.path.insert(0, ROOT)
 from jyutvoice_amd.build import FILE_FLAGS, FLAGS as LIB_FLAGS      # exactly the flags the library is built with (-fPIC, JV_EXTRA_FLAGS, ...)
 
@@ -167,6 +170,12 @@ def main():
     s = ""
     s_row = ""      # the three row-owning translation units alone: what the footprint table covers
     with tempfile.TemporaryDirectory() as d:
+        def keep_texts(out):      # DIR/<source file>[.tune]/<mangled name>.s
+            sub = os.path.join(keep, os.path.basename(out)[:-2])
+            os.makedirs(sub, exist_ok=True)
+            for name, text in kernel_texts(open(out).read()).items():
+                with open(os.path.join(sub, name + ".s"), "w") as f:
+                    f.write(text)
         for src, extra in [(f, []) for f in SRCS + [ATTN_S]] + [(ATTN_S, ["-DJV_TUNING"])]:      # (the tuning build's variants too)
             out = os.path.join(d, os.path.basename(src) + (".tune" if extra else "") + ".s")
             FLAGS = FLAGS0 + FILE_FLAGS.get(os.path.basename(src), []) + extra
@@ -177,17 +186,21 @@ def main():
             s += open(out).read()
             if src in SRCS:
                 s_row += open(out).read()
-                if keep:
-                    os.makedirs(os.path.join(keep, os.path.basename(src)), exist_ok=True)
-                    for name, text in kernel_texts(open(out).read()).items():
-                        with open(os.path.join(keep, os.path.basename(src), name + ".s"), "w") as f:
-                            f.write(text)
+            if keep:
+                keep_texts(out)
             # -S does not run the assembler over the inline asm: an operand the assembler rejects only shows with -c
             r = subprocess.run([CLANG] + [f for f in FLAGS if f != "-S"] + ["-c", "-o", os.path.join(d, os.path.basename(src) + ".o"), src],
                                capture_output=True, text=True)
             if r.returncode != 0:
                 print(r.stderr[-3000:])
                 return 2
+        for src in ATTN_KEEP if keep else []:      # texts only: nothing below checks these
+            out = os.path.join(d, os.path.basename(src) + ".s")
+            r = subprocess.run([CLANG] + FLAGS0 + FILE_FLAGS.get(os.path.basename(src), []) + ["-o", out, src], capture_output=True, text=True)
+            if r.returncode != 0:
+                print(r.stderr[-3000:])
+                return 2
+            keep_texts(out)
     if res_arg:
         table = kernel_resources(s_row)
         print(f"{'vgpr':>5} {'accum':>5} {'sgpr':>5} {'scratch':>7} {'lds':>6}  kernel")
