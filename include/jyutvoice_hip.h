@@ -198,6 +198,22 @@ int jv_flow_token2mel_partial(jv_context* ctx, const int64_t* prompt_tokens, con
                               const int64_t* token_lens, const float* prompt_feat, const int32_t* feat_lens, const float* embedding,
                               int P, int N, int F, int streaming, int n_timesteps, float temperature, const float* t_span_host,
                               float* mel, int32_t* mel_lens, void* stream);
+/* A look-ahead context PER UTTERANCE -- a batch that mixes partial sequences (sessions in mid-stream) with whole ones (sessions
+ * that finish): the whole-sequence entries with one more argument, ctx_lens [B] int32 on the device, each entry 0 or 3.  Of
+ * utterance b's m_b = p_b + n_b tokens the last ctx_b are look-ahead context only, as above; every length and mask, the solve and
+ * the unpack run on L_b = m_b - ctx_b.  The buffers keep the whole-sequence widths: h [B, 2 (P + N), 80], mel [B, 80, 2 (P + N)];
+ * h_lens receives 2 L_b, mel_lens 2 L_b - f_b; 0 <= f_b <= min(F, 2 L_b).  B > 1 is the B = 1 entries looped over the utterances
+ * (jv_flow_*_partial where ctx_b = 3, the whole-sequence entry where it is 0).  The token counts and ctx_lens come down to the host
+ * and are checked before anything is launched on them -- the call's one synchronisation; jv_flow_encoder_fwd_ctx, which has no
+ * other, takes one for this: ctx_b outside {0, 3} or m_b - ctx_b < 1 is JV_ERR_ARG naming the utterance.  `streaming` is one flag
+ * for the call. */
+int jv_flow_encoder_fwd_ctx(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                            const int64_t* token_lens, const int32_t* ctx_lens, int B, int P, int N, int streaming, float* h,
+                            int32_t* h_lens, void* stream);
+int jv_flow_token2mel_ctx(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                          const int64_t* token_lens, const int32_t* ctx_lens, const float* prompt_feat, const int32_t* feat_lens,
+                          const float* embedding, int B, int P, int N, int F, int streaming, int n_timesteps, float temperature,
+                          const float* t_span_host, float* mel, int32_t* mel_lens, void* stream);
 
 /* jv_load_mel_basis / jv_mel_spectrogram: the prompt-mel front-end, `extract_speech_feat` of infer.py:166-186 ->
  * `mel_spectrogram` of jyutvoice/utils/audio.py:18-63 (24 kHz, n_fft = win = 1920 periodic Hann, hop 480, reflect pad 720,
@@ -386,6 +402,22 @@ int jv_hift_source_seeded(jv_context* ctx, const float* f0, const float* phase, 
  * sequential fp64 recurrence that simply resumes, and a sample is a pure function of (its frame's start sum, f0, index). */
 int jv_hift_source_cont(jv_context* ctx, const float* f0, const float* phase, uint64_t seed, uint32_t call, int64_t sample0, double* cum,
                         int B, int T, float* s, void* stream);
+/* jv_hift_source_cont_rows: jv_hift_source_cont with every row an independent signal -- the sessions of a streaming server in one
+ * launch.  seeds, calls, sample0, lens: [B] on the device (seeds, sample0 and cum 8-byte aligned).  Row b's noise is keyed by
+ * seeds[b] and counted (sample0[b] + n, utterance 0, calls[b]); its frame scan resumes from cum[b] over lens[b] frames (clamped
+ * to [0, T]) and leaves the sums after exactly those frames in cum[b]; s[b] is zeros behind 480 lens[b].  A row with lens[b] = 0 is
+ * not touched: neither s[b] nor cum[b] is written.  Row b equals jv_hift_source_cont at B = 1 with that row's scalars and its first
+ * lens[b] frames bit for bit, whichever slot it sits in. */
+int jv_hift_source_cont_rows(jv_context* ctx, const float* f0, const float* phase, const uint64_t* seeds, const uint32_t* calls,
+                             const int64_t* sample0, const int32_t* lens, double* cum, int B, int T, float* s, void* stream);
+/* jv_slab_copy: B column slabs between two [rows, C, width] fp32 buffers in one launch -- the state moves of a batch of streaming
+ * sessions (append, window gather, crop).  desc: [B, 5] int32 on the device, (src_row, src_col, dst_row, dst_col, n):
+ * dst[dst_row, :, dst_col + j] = src[src_row, :, src_col + j] for j < n <= span and, with zero_fill != 0, zero for n <= j < span
+ * (cut at dst_width).  A descriptor that does not fit its buffers, or whose n is negative or above span, moves nothing.  The
+ * buffers must not overlap; slabs of one call must not overlap in the destination.  Owns no memory and uses none of the
+ * workspace: what a caller keeps in such buffers survives jv_reserve. */
+int jv_slab_copy(jv_context* ctx, const float* src, int src_rows, int src_width, float* dst, int dst_rows, int dst_width, int C,
+                 const int32_t* desc, int B, int span, int zero_fill, void* stream);
 int jv_hift_decode(jv_context* ctx, const float* mel, const float* s, const int32_t* lens, int B, int T, float* wav,
                    void* stream);
 

@@ -38,6 +38,8 @@ mel extractor.  Instead this CLI takes their outputs directly:
                              to OUTPUT with _000, _001, ... before the extension.  A prompt mel longer than the request's
                              2 * tokens frames is trimmed to them.  --streaming: the chunk-causal masks of the encoder and the
                              estimator (streaming=True of flow.py:300-358).  With --synthetic 1: key-hashed weights.
+    --stream-sessions S      with --token2wav --stream-hop K: the requests run through ONE server (jyutvoice_amd.stream.Token2WavServer),
+                             S sessions at a time, each step one batched solve and one batched vocoder advance for all of them
     --stream-hop K           with --token2wav: every request runs through a streaming session of its own
                              (jyutvoice_amd.stream.Token2WavStream, always on the streaming masks), its tokens pushed K at a time;
                              the same files are written, and the time to the first audio is printed per request
@@ -265,7 +267,12 @@ def token2wav_list(reqs, args, device):
     for b, f in enumerate(feats):
         prompt_feat[b, : f.shape[0]] = f
 
-    if args.stream_hop:
+    if args.stream_sessions and not args.stream_hop:
+        raise SystemExit("--stream-sessions needs --stream-hop")
+    if args.stream_hop and args.stream_sessions:
+        wav, samples = token2wav_server(args, flow, hift, token, token_len, prompt_token, prompt_token_len, prompt_feat, feat_len,
+                                        embedding)
+    elif args.stream_hop:
         wav, samples = token2wav_sessions(args, flow, hift, token, token_len, prompt_token, prompt_token_len, prompt_feat, feat_len,
                                           embedding)
     else:
@@ -328,6 +335,57 @@ def token2wav_sessions(args, flow, hift, token, token_len, prompt_token, prompt_
     return wav, samples
 
 
+def token2wav_server(args, flow, hift, token, token_len, prompt_token, prompt_token_len, prompt_feat, feat_len, embedding):
+    """--stream-hop K --stream-sessions S: the requests through ONE Token2WavServer, S sessions at a time, every live session
+    receiving K tokens per step -> (wav [B, longest], samples [B]).  A request takes a slot as soon as one is free."""
+    import torch
+
+    from jyutvoice_amd.stream import Token2WavServer
+    if args.stream_hop < 1 or args.stream_sessions < 1:
+        raise SystemExit("--stream-hop and --stream-sessions must be positive")
+    if not args.streaming:
+        print("--stream-hop: a session always runs on the streaming masks (--streaming is implied)")
+    B = token.shape[0]
+    try:
+        server = Token2WavServer(flow, hift, min(args.stream_sessions, B), max(int(token_len.max()), 1), n_timesteps=args.n_timesteps,
+                                 max_prompt_tokens=max(int(prompt_token_len.max()), (int(feat_len.max()) + 1) // 2))
+    except ValueError as e:
+        raise SystemExit(f"{args.token2wav}: {e}")
+    pieces, live, pos, waiting, steps = [[] for _ in range(B)], {}, {}, list(range(B)), 0
+    start = time.time()
+    while waiting or live:
+        try:
+            while waiting and len(live) < server.max_sessions:
+                b = waiting.pop(0)
+                p, f = int(prompt_token_len[b]), int(feat_len[b])
+                live[b] = server.open(prompt_token[b:b + 1, :p], prompt_feat[b:b + 1, :f], embedding[b:b + 1])
+                pos[b] = 0
+            for b, sid in live.items():
+                n = int(token_len[b])
+                if pos[b] < n:
+                    server.push(sid, token[b, pos[b]:min(pos[b] + args.stream_hop, n)])
+                    pos[b] = min(pos[b] + args.stream_hop, n)
+                else:
+                    server.close(sid)
+            out = server.step()
+        except ValueError as e:
+            raise SystemExit(f"{args.token2wav}: {e}")
+        steps += 1
+        for b, sid in list(live.items()):
+            if sid in out:
+                pieces[b].append(out[sid])
+            if server.finished(sid):
+                del live[b]
+    torch.cuda.synchronize()
+    print(f"{B} requests, {server.max_sessions} sessions at a time, hops of {args.stream_hop}: {steps} steps in {time.time() - start:.3f} s")
+    waves = [torch.cat(p, dim=1)[0] for p in pieces]
+    samples = torch.tensor([w.shape[0] for w in waves], dtype=torch.int64)
+    wav = torch.zeros(B, int(samples.max()), device=waves[0].device)
+    for b, w in enumerate(waves):
+        wav[b, : w.shape[0]] = w
+    return wav, samples
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="JyutVoice TTS inference on MI355X (jyutvoice_amd)")
     p.add_argument("--text", default=None, help="Text to synthesize (needs the reference's G2P front-end; see --tokens)")
@@ -350,6 +408,8 @@ def main(argv=None):
     p.add_argument("--streaming", action="store_true", help="--token2wav: chunk-causal masks in the flow encoder and the estimator")
     p.add_argument("--stream-hop", type=int, default=0, metavar="K",
                    help="--token2wav: a streaming session per request, its tokens pushed K at a time")
+    p.add_argument("--stream-sessions", type=int, default=0, metavar="S",
+                   help="--token2wav --stream-hop K: serve the list through one Token2WavServer, S sessions at a time")
     p.add_argument("--synthetic", type=int, default=0, help="use N synthetic tokens and synthetic weights")
     p.add_argument("--synthetic-prompt", type=int, default=0, help="with --synthetic: K synthetic prompt tokens (voice-cloning path)")
     p.add_argument("--seed", type=int, default=0, help="seed of the vocoder's source-noise draws")

@@ -60,6 +60,8 @@ SIGNATURES = {
     "jv_flow_token2mel": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "jv_flow_encoder_fwd_partial": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "jv_flow_token2mel_partial": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
+    "jv_flow_encoder_fwd_ctx": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "jv_flow_token2mel_ctx": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "jv_encoder_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "jv_load_mel_basis": (_i, [_p, _p, _i64, _i, _p]),
     "jv_mel_spectrogram": (_i, [_p, _p, _i, _i, _p, _p]),
@@ -85,6 +87,8 @@ SIGNATURES = {
     "jv_hift_source": (_i, [_p, _p, _p, _p, _i, _i, _p, _p]),
     "jv_hift_source_seeded": (_i, [_p, _p, _p, C.c_uint64, C.c_uint32, _i, _i, _p, _p]),
     "jv_hift_source_cont": (_i, [_p, _p, _p, C.c_uint64, C.c_uint32, _i64, _p, _i, _i, _p, _p]),
+    "jv_hift_source_cont_rows": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
+    "jv_slab_copy": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p]),
     "jv_hift_decode": (_i, [_p, _p, _p, _p, _i, _i, _p, _p]),
     "jv_op_conv_gemm": (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _p, _p, _f, _p, _p, _p, _p]),
     "jv_op_attention": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),

@@ -515,6 +515,20 @@ int jv_flow_token2mel_partial(jv_context* ctx, const int64_t* prompt_tokens, con
                             static_cast<hipStream_t>(stream), 3);
 }
 
+int jv_flow_token2mel_ctx(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                          const int64_t* token_lens, const int32_t* ctx_lens, const float* prompt_feat, const int32_t* feat_lens,
+                          const float* embedding, int B, int P, int N, int F, int streaming, int n_timesteps, float temperature,
+                          const float* t_span_host, float* mel, int32_t* mel_lens, void* stream) {
+  CTX_GUARD(ctx);
+  if (!token_lens || !ctx_lens || !feat_lens || !embedding || !mel || (N > 0 && !tokens) ||
+      (P > 0 && (!prompt_tokens || !prompt_lens)) || (F > 0 && !prompt_feat))
+    return jv::fail(JV_ERR_ARG, "jv_flow_token2mel_ctx: null tensor");
+  return jv::flow_token2mel(ctx->c, reinterpret_cast<const long*>(prompt_tokens), reinterpret_cast<const long*>(prompt_lens),
+                            reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_lens), prompt_feat, feat_lens,
+                            embedding, B, P, N, F, streaming, n_timesteps, temperature, t_span_host, mel, mel_lens,
+                            static_cast<hipStream_t>(stream), 0, ctx_lens);
+}
+
 // conv_gemm through the fp16x3 main loop with a MEASURED bound: amax_in = device float >= max |A| (e.g. the amax_out of
 // the launch that produced A), a_extra = what the prologue can add; amax_out (optional) receives max |out| (test hook)
 int jv_op_conv_h3_measured(const float* A, int64_t a_rows, int M, int Cin, int ntaps, int tap_row0, int dil, const float* W,

@@ -431,9 +431,13 @@ constexpr int T2M_EST_CHUNK = 50;      // the estimator's static_chunk_size in f
 // of mu (Ty = 0) and the condition prefix has a length of its own.
 // ctx = 3 (jv_flow_token2mel_partial; flow.py:327-336): the last three tokens are look-ahead context of the encoder only, so the
 // sequence is L = P + N - 3 tokens and everything from h onwards -- lengths, masks, the solve, the unpack -- runs on 2 L frames.
+// ctx_lens (jv_flow_token2mel_ctx; ctx = 0): a context per utterance, 0 or 3 tokens.  Utterance b runs on L_b = p_b + n_b - ctx_b
+// tokens in buffers of the whole sequence's width, Tm = 2 (P + N).  Its lengths come down FIRST and are checked before anything
+// is launched on them (flow_ctx_lengths): that is the call's one synchronisation, and the f_b come down with it.
 int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const float* prompt_feat,
                    const int* feat_lens, const float* embedding, int B, int P, int N, int F, int streaming, int n_timesteps,
-                   float temperature, const float* t_span_host, float* mel, int* mel_lens, hipStream_t st, int ctx) {
+                   float temperature, const float* t_span_host, float* mel, int* mel_lens, hipStream_t st, int ctx,
+                   const int* ctx_lens) {
   if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "flow decoder weights not finalized (JV_MODEL_FLOW or JV_MODEL_TTS)");
   if (!c.ready[MODEL_PROMPT]) return fail(JV_ERR_STATE, "prompt encoder weights not finalized");
   if (B < 1 || P < 0 || N < 0 || P + N < 1 || F < 0) return fail(JV_ERR_ARG, "jv_flow_token2mel: B, P + N must be positive, P, N, F non-negative");
@@ -453,14 +457,27 @@ int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* t
   float* const spks = w.tsin;
   int* const hl = w.t2m_lens;
   int* const yl = w.t2m_lens + c.max_batch;
-  JV_TRY(flow_encoder_fwd(c, ptok, plen, tok, len, B, P, N, streaming, h, hl, st, ctx));
-  JV_TRY(speaker_projection(c, embedding, B, spks, st));
-
   std::vector<float> tt, dts;
-  JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
-  JV_HIP(hipMemcpyAsync(w.h_lens, hl, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-  JV_HIP(hipMemcpyAsync(w.h_lens + B, feat_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-  JV_HIP(hipStreamSynchronize(st));
+  if (ctx_lens) {
+    if (ctx != 0) return fail(JV_ERR_ARG, "jv_flow_token2mel_ctx: one context for the call or one per utterance, not both");
+    std::vector<int> enc_lens, f_host;
+    JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
+    JV_TRY(flow_ctx_lengths("jv_flow_token2mel_ctx", plen, len, ctx_lens, feat_lens, B, P, N, enc_lens, &f_host, st));
+    for (int b = 0; b < B; ++b) {
+      w.h_lens[b] = 2 * enc_lens[b];
+      w.h_lens[B + b] = f_host[b];
+    }
+    JV_TRY(flow_encoder_fwd_ctx(c, ptok, plen, tok, len, ctx_lens, B, P, N, streaming, h, hl, st, true));
+    JV_TRY(speaker_projection(c, embedding, B, spks, st));
+  } else {
+    JV_TRY(flow_encoder_fwd(c, ptok, plen, tok, len, B, P, N, streaming, h, hl, st, ctx));
+    JV_TRY(speaker_projection(c, embedding, B, spks, st));
+
+    JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
+    JV_HIP(hipMemcpyAsync(w.h_lens, hl, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+    JV_HIP(hipMemcpyAsync(w.h_lens + B, feat_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+    JV_HIP(hipStreamSynchronize(st));
+  }
   int T = 0;
   for (int b = 0; b < B; ++b) {
     const int tb = w.h_lens[b], f = w.h_lens[B + b];

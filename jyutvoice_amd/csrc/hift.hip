@@ -25,6 +25,9 @@ int hiftpair(const HiftPairArgs& a, int C, hipStream_t st);
 int f0_head(const float* h, const float* w, const float* bias, float* f0, int B, int T, int G, int S, hipStream_t st);
 int sine_source(const float* f0, const float* phase, const float* noise, const float* lin_w, const float* lin_b, float* frac,
                 float* s, int B, int T, hipStream_t st, unsigned long long seed, unsigned call, long sample0 = 0, double* cum_io = nullptr);
+int sine_source_rows(const float* f0, const float* phase, const float* lin_w, const float* lin_b, float* frac, float* s, int B, int T,
+                     const unsigned long long* seeds, const unsigned* calls, const long* sample0, const int* lens, double* cum,
+                     hipStream_t st);
 // (uoff3: optional first rows of the utterances at level 3 -- the compact geometry of ragged batches, below)
 int stft_rows(const float* s, float* out, const int* lens, int B, int T, int G3, int S3, long rows, hipStream_t st, const int* uoff3 = nullptr);
 int reflect_fix(float* x, int B, int G3, int S3, int C, hipStream_t st, const int* uoff3 = nullptr);
@@ -300,6 +303,13 @@ int hift_source(Context& c, const float* f0, const float* phase, const float* no
   return sine_source(f0, phase, noise, c.hift.src_lin_w, c.hift.src_lin_b, c.hws->frac, s, B, T, st, seed, call, sample0, cum);
 }
 
+// every row the continuation of a signal of its own: (seed, call, sample0, frames, running sums) per row, all on the device
+int hift_source_rows(Context& c, const float* f0, const float* phase, const unsigned long long* seeds, const unsigned* calls,
+                     const long* sample0, const int* lens, double* cum, int B, int T, float* s, hipStream_t st) {
+  JV_TRY(check(c, B, T));
+  return sine_source_rows(f0, phase, c.hift.src_lin_w, c.hift.src_lin_b, c.hws->frac, s, B, T, seeds, calls, sample0, lens, cum, st);
+}
+
 int hift_decode(Context& c, const float* mel, const float* s, const int* lens, int B, int T, float* wav, hipStream_t st) {
   JV_TRY(check(c, B, T));
   HiftWs& w = *c.hws;
@@ -422,6 +432,17 @@ int jv_hift_source_cont(jv_context* ctx, const float* f0, const float* phase, ui
   if (reinterpret_cast<uintptr_t>(cum) & 7) return jv::fail(JV_ERR_ARG, "jv_hift_source_cont: cum must be 8-byte aligned");
   JV_HIP(hipSetDevice(ctx->c.device));
   return jv::hift_source(ctx->c, f0, phase, nullptr, B, T, s, static_cast<hipStream_t>(stream), seed, call, (long)sample0, cum);
+}
+
+int jv_hift_source_cont_rows(jv_context* ctx, const float* f0, const float* phase, const uint64_t* seeds, const uint32_t* calls,
+                             const int64_t* sample0, const int32_t* lens, double* cum, int B, int T, float* s, void* stream) {
+  if (!ctx || !f0 || !phase || !seeds || !calls || !sample0 || !lens || !cum || !s)
+    return jv::fail(JV_ERR_ARG, "jv_hift_source_cont_rows: null argument");
+  if ((reinterpret_cast<uintptr_t>(cum) | reinterpret_cast<uintptr_t>(seeds) | reinterpret_cast<uintptr_t>(sample0)) & 7)
+    return jv::fail(JV_ERR_ARG, "jv_hift_source_cont_rows: cum, seeds and sample0 must be 8-byte aligned");
+  JV_HIP(hipSetDevice(ctx->c.device));
+  return jv::hift_source_rows(ctx->c, f0, phase, reinterpret_cast<const unsigned long long*>(seeds), calls,
+                              reinterpret_cast<const long*>(sample0), lens, cum, B, T, s, static_cast<hipStream_t>(stream));
 }
 
 int jv_hift_decode(jv_context* ctx, const float* mel, const float* s, const int32_t* lens, int B, int T, float* wav,

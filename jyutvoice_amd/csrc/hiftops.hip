@@ -81,14 +81,18 @@ __device__ __forceinline__ bool frame_adds_exact(const double start, const float
 // cum_io (jv_hift_source_cont, else null): the running sums [B, 9] of the frames that came before this call, read here and
 // replaced by the sums after its last frame -- the recurrence below simply resumes, so a signal produced piece by piece walks
 // through the same fp64 values as the one-shot scan
+// lens (jv_hift_source_cont_rows, else null): row b scans its first lens[b] frames only (clamped to [0, T]); a row of length 0
+// leaves its sums alone
 __global__ void sine_frame_scan_kernel(const float* __restrict__ f0, double* __restrict__ start, int B, int T,
-                                       double* __restrict__ cum_io) {
+                                       double* __restrict__ cum_io, const int* __restrict__ lens) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * 9) return;
   const int b = idx / 9, h = idx - b * 9;
+  const int len = lens ? min(max(lens[b], 0), T) : T;
+  if (len == 0) return;
   const float mult = (float)(h + 1);
   double cum = cum_io ? cum_io[idx] : 0.0;
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < len; ++t) {
     start[(long)idx * T + t] = cum;
     const float F = f0[b * T + t] * mult / 24000.0f;
     if (frame_adds_exact(cum, F)) {
@@ -128,17 +132,41 @@ __device__ __forceinline__ void box_muller(unsigned a, unsigned b, float& z0, fl
 // noise == nullptr: the nine N(0,1) draws of a sample come from Philox keyed by (seed_lo, seed_hi), counter (utterance,
 // sample, call, 3 blocks) -- generator.py:171 draws them with torch.randn_like, whose values no caller can depend on.
 // sample0: the index of this call's first sample in the signal it continues (0 unless jv_hift_source_cont); only the counter sees it
+// rows (jv_hift_source_cont_rows, else null pointers): every row is a signal of its own -- key seeds[b], counter (sample0[b] + n,
+// utterance 0, calls[b], block), lens[b] frames (clamped to [0, T]): zeros behind them, and a row of length 0 is not written at all.
+// The arithmetic of a sample is the one code for both forms, so a row equals the B = 1 continuation with its scalars bit for bit
+struct SourceRows {
+  const unsigned long long* seeds;
+  const unsigned* calls;
+  const long* sample0;
+  const int* lens;
+};
 __global__ __launch_bounds__(256) void source_mix_kernel(const float* __restrict__ f0, const double* __restrict__ start,
                                                          const float* __restrict__ phase, const float* __restrict__ noise,
                                                          const float* __restrict__ lin_w, const float* __restrict__ lin_b,
                                                          float* __restrict__ s, int B, int T, unsigned seed_lo, unsigned seed_hi,
-                                                         unsigned call, long sample0) {
+                                                         unsigned call, long sample0, SourceRows rows) {
   const long n_per = (long)T * 480;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= n_per * B) return;
   const int b = (int)(idx / n_per);
   const long n = idx - (long)b * n_per;
   const int t = (int)(n / 480), k = (int)(n - (long)t * 480);
+  unsigned utt = (unsigned)b;
+  if (rows.lens) {
+    const int len = min(max(rows.lens[b], 0), T);
+    if (len == 0) return;
+    if (t >= len) {
+      s[idx] = 0.f;
+      return;
+    }
+    const unsigned long long seed = rows.seeds[b];
+    seed_lo = (unsigned)seed;
+    seed_hi = (unsigned)(seed >> 32);
+    call = rows.calls[b];
+    sample0 = rows.sample0[b];
+    utt = 0u;
+  }
   const float f = f0[b * T + t];
   const float uv = f > 10.0f ? 1.f : 0.f;
   const float namp = uv * 0.003f + (1.f - uv) * 0.1f / 3.f;
@@ -147,7 +175,7 @@ __global__ __launch_bounds__(256) void source_mix_kernel(const float* __restrict
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       unsigned r[4];
-      philox4x32_10((unsigned)(n + sample0), (unsigned)b, call, (unsigned)j, seed_lo, seed_hi, r);
+      philox4x32_10((unsigned)(n + sample0), utt, call, (unsigned)j, seed_lo, seed_hi, r);
       box_muller(r[0], r[1], z[4 * j], z[4 * j + 1]);
       box_muller(r[2], r[3], z[4 * j + 2], z[4 * j + 3]);
     }
@@ -178,9 +206,21 @@ int sine_source(const float* f0, const float* phase, const float* noise, const f
                 float* s, int B, int T, hipStream_t st, unsigned long long seed, unsigned call, long sample0, double* cum_io) {
   // `frac` (sized [B, 9, 480 T] floats by hift_ws_create) now only holds the [B, 9, T] frame-start sums, as doubles
   double* start = reinterpret_cast<double*>(frac);
-  hipLaunchKernelGGL(sine_frame_scan_kernel, dim3(cdiv(B * 9, 64)), dim3(64), 0, st, f0, start, B, T, cum_io);
+  hipLaunchKernelGGL(sine_frame_scan_kernel, dim3(cdiv(B * 9, 64)), dim3(64), 0, st, f0, start, B, T, cum_io, nullptr);
   hipLaunchKernelGGL(source_mix_kernel, dim3((unsigned)cdivl((long)B * T * 480, 256)), dim3(256), 0, st, f0, start, phase, noise,
-                     lin_w, lin_b, s, B, T, (unsigned)seed, (unsigned)(seed >> 32), call, sample0);
+                     lin_w, lin_b, s, B, T, (unsigned)seed, (unsigned)(seed >> 32), call, sample0, SourceRows{});
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
+// the same two launches with (seed, call, sample0, frames) per row, all on the device (jv_hift_source_cont_rows)
+int sine_source_rows(const float* f0, const float* phase, const float* lin_w, const float* lin_b, float* frac, float* s, int B, int T,
+                     const unsigned long long* seeds, const unsigned* calls, const long* sample0, const int* lens, double* cum,
+                     hipStream_t st) {
+  double* start = reinterpret_cast<double*>(frac);
+  hipLaunchKernelGGL(sine_frame_scan_kernel, dim3(cdiv(B * 9, 64)), dim3(64), 0, st, f0, start, B, T, cum, lens);
+  hipLaunchKernelGGL(source_mix_kernel, dim3((unsigned)cdivl((long)B * T * 480, 256)), dim3(256), 0, st, f0, start, phase, nullptr,
+                     lin_w, lin_b, s, B, T, 0u, 0u, 0u, 0L, SourceRows{seeds, calls, sample0, lens});
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

@@ -211,7 +211,8 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
 
 int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const float* prompt_feat,
                    const int* feat_lens, const float* embedding, int B, int P, int N, int F, int streaming, int n_timesteps,
-                   float temperature, const float* t_span_host, float* mel, int* mel_lens, hipStream_t st, int ctx = 0);
+                   float temperature, const float* t_span_host, float* mel, int* mel_lens, hipStream_t st, int ctx = 0,
+                   const int* ctx_lens = nullptr);
 
 // encoder.hip: Linear(192 -> 80)(F.normalize(spk)) (jyutvoice_tts.py:175-176, flow.py:315-316)
 int speaker_projection(Context& c, const float* spk, int B, float* spks_out, hipStream_t st);
@@ -220,6 +221,11 @@ int speaker_projection(Context& c, const float* spk, int B, float* spks_out, hip
 int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int Tk, float* h_out, hipStream_t st);
 int flow_encoder_fwd(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, int B, int P, int N,
                      int streaming, float* h_out, int* h_lens, hipStream_t st, int ctx = 0);
+// per-utterance contexts (jv_flow_encoder_fwd_ctx / jv_flow_token2mel_ctx): the host-side check of the length vectors, then the encoder
+int flow_ctx_lengths(const char* who, const long* plen, const long* len, const int* ctx_lens, const int* extra, int B, int P, int N,
+                     std::vector<int>& enc_lens, std::vector<int>* extra_host, hipStream_t st);
+int flow_encoder_fwd_ctx(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const int* ctx_lens, int B,
+                         int P, int N, int streaming, float* h_out, int* h_lens, hipStream_t st, bool checked);
 // the three-GEMM relative-position attention of a conformer block on explicit buffers (prompt.hip); chunk as rel_attention
 int rel_attention_gemm(const float* qkv, const float* p, const float* u, const float* v, float* qu, float* qv, float* ac, float* bd,
                        float* vt, float* att, const long* len, int len_mul, int B, int T, int G, int S, int chunk, hipStream_t st);

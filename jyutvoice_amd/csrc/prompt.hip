@@ -19,6 +19,10 @@
 // (upsample_encoder.py:110-121).  They sit in the first rows of the gap behind the L = P + N - ctx encoded ones; a second row mask
 // (mask1c) lets conv1, and nothing else, read them.  ctx = 0 is the whole-sequence path, launch for launch.
 #include <math.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "../../include/jyutvoice_hip.h"
 #include "jv_model.h"
@@ -29,6 +33,8 @@ namespace jv {
 int prompt_embed(const long* ptok, const long* plen, int P, const long* tok, const long* len, int N, const float* emb, float* rows,
                  int B, int G, int S, int vocab, hipStream_t st);
 int sum_lens(const long* plen, int P, const long* len, int N, int B, long* sum, int* out32, int mul, int ctx, hipStream_t st);
+int sum_lens_ctx(const long* plen, int P, const long* len, int N, int B, long* sum, int* out32, int mul, const int* ctxv,
+                 int* with_ctx, hipStream_t st);
 int rel_pos_table(float* pe, const float* div, int T, hipStream_t st);
 int add_pos_bias(const float* qkv, const float* u, const float* v, float* qu, float* qv, long rows, hipStream_t st);
 int rel_softmax(float* ac, const float* bd, const long* len, int len_mul, int B, int H, int T, int ld, int ldb, int chunk,
@@ -58,6 +64,7 @@ struct PromptWs {
   float *ac = nullptr, *bd = nullptr, *vt = nullptr;
   unsigned char *mask1 = nullptr, *mask2 = nullptr, *mask1c = nullptr;      // mask1c: mask1 + the look-ahead context rows
   int* lens_i = nullptr;
+  int* lens_c = nullptr;      // [B] L_b + ctx_b of a call with per-utterance contexts: the rows mask1c marks
 };
 
 void prompt_ws_destroy(Context& c) {
@@ -109,6 +116,7 @@ int ensure_ws(Context& c, int B, int Tk, bool quad) {
   JV_TRY(A(reinterpret_cast<void**>(&w->mask2), R));
   JV_TRY(A(reinterpret_cast<void**>(&w->mask1c), R));
   JV_TRY(A(reinterpret_cast<void**>(&w->lens_i), sizeof(int) * nb));
+  JV_TRY(A(reinterpret_cast<void**>(&w->lens_c), sizeof(int) * nb));
   return JV_OK;
 }
 
@@ -194,8 +202,11 @@ int conformer_block(Context& c, const ConfBlockW& k, int B, int T, int G, int S,
 // lengths p_b + n_b - ctx on the device.  fused / streaming: the attention route and the chunk masks of conformer_block.
 // ctx > 0 (< P_GAP): the last ctx tokens of the P + N are context of the look-ahead convolution only; every length below is the
 // encoded one, T1 = P + N - ctx
+// lens_c (with ctx = 0): every utterance has a context of its own, 0 or 3 tokens.  The buffers keep the width of the whole
+// sequence, T1 = P + N; utterance b's context rows sit right behind its L_b = len[b] encoded ones -- rows that are padding to
+// everything but conv1 -- and lens_c[b] = L_b + ctx_b is what mask1c marks
 int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const long* tok, const long* tlen, int N, const long* len,
-                   int B, bool fused, bool streaming, int ctx, float* h_out, hipStream_t st) {
+                   int B, bool fused, bool streaming, int ctx, float* h_out, hipStream_t st, const int* lens_c = nullptr) {
   PromptWs& w = *c.pws;
   const PromptW& e = c.prompt;
   const long AR = w.rows;
@@ -208,6 +219,7 @@ int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const 
   JV_TRY(row_meta(w.mask1, nullptr, w.lens_i, B, 1, P_G, S1, T1, AR, 1, 0, st));
   JV_TRY(row_meta(w.mask2, nullptr, w.lens_i, B, 1, P_G, S2, T2, AR, 2, 0, st));
   if (ctx > 0) JV_TRY(row_meta(w.mask1c, nullptr, w.lens_i, B, 1, P_G, S1, T1 + ctx, AR, 1, ctx, st));      // rows [0, len + ctx)
+  if (lens_c) JV_TRY(row_meta(w.mask1c, nullptr, lens_c, B, 1, P_G, S1, T1, AR, 1, 0, st));                 // rows [0, len_b + ctx_b)
 
   // ---- stage 1: embedding -> Linear + LayerNorm (* sqrt 512) -> look-ahead convs -> 6 blocks ---------------------------
   JV_TRY(fill(w.y, 0.f, M1 * 512, st));                     // gap rows of the embedding buffer must read as zero tokens
@@ -220,7 +232,7 @@ int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const 
   // embedded context rows), bias; LeakyReLU(0.01) is conv2's prologue
   a = lin_args(w.x, 512, AR, M1, e.look1, w.y, 512);
   a.tap_row0 = 0;
-  a.rowmask_in = ctx > 0 ? w.mask1c : w.mask1;
+  a.rowmask_in = ctx > 0 || lens_c ? w.mask1c : w.mask1;
   JV_TRY(conv_gemm(a, 1, st));
   // conv2: rows t-2 .. t of leaky(conv1) over the valid frames (zeros before the start), + bias + x
   a = lin_args(w.y, 512, AR, M1, e.look2, w.ln, 512);
@@ -281,6 +293,56 @@ int flow_encoder_fwd(Context& c, const long* ptok, const long* plen, const long*
   return encoder_stages(c, ptok, plen, P, tok, len, N, w.lens64, B, true, streaming != 0, ctx, h_out, st);
 }
 
+// The lengths of a call with per-utterance contexts, on the host: the token counts and ctx_lens come down (one synchronisation, the
+// call's only one) and are checked before anything is launched on them.  enc_lens[b] receives L_b = m_b - ctx_b.  A wrong context
+// is a wrong sequence end, which a clamp would turn into other frames silently: rejected, naming the utterance.
+int flow_ctx_lengths(const char* who, const long* plen, const long* len, const int* ctx_lens, const int* extra, int B, int P, int N,
+                     std::vector<int>& enc_lens, std::vector<int>* extra_host, hipStream_t st) {
+  if (B < 1 || P < 0 || N < 0) return fail(JV_ERR_ARG, std::string(who) + ": B must be positive, P and N non-negative");
+  std::vector<long> pl(B, 0), tl(B, 0);
+  std::vector<int> cx(B, 0);
+  if (P > 0) JV_HIP(hipMemcpyAsync(pl.data(), plen, sizeof(long) * B, hipMemcpyDeviceToHost, st));
+  JV_HIP(hipMemcpyAsync(tl.data(), len, sizeof(long) * B, hipMemcpyDeviceToHost, st));
+  JV_HIP(hipMemcpyAsync(cx.data(), ctx_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  if (extra && extra_host) {
+    extra_host->assign(B, 0);
+    JV_HIP(hipMemcpyAsync(extra_host->data(), extra, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  }
+  JV_HIP(hipStreamSynchronize(st));
+  enc_lens.assign(B, 0);
+  for (int b = 0; b < B; ++b) {
+    const long m = std::min(std::max(pl[b], 0L), (long)P) + std::min(std::max(tl[b], 0L), (long)N);
+    char msg[200];
+    if (cx[b] != 0 && cx[b] != PR_LOOKAHEAD) {
+      snprintf(msg, sizeof msg, "%s: utterance %d: context %d: the look-ahead length (3 tokens) or nothing", who, b, cx[b]);
+      return fail(JV_ERR_ARG, msg);
+    }
+    if (m - cx[b] < 1) {
+      snprintf(msg, sizeof msg, "%s: utterance %d: %ld tokens with a context of %d: at least one encoded token is needed", who, b, m,
+               cx[b]);
+      return fail(JV_ERR_ARG, msg);
+    }
+    enc_lens[b] = (int)(m - cx[b]);
+  }
+  return JV_OK;
+}
+
+// jv_flow_encoder_fwd_ctx: flow_encoder_fwd with a context per utterance (ctx_lens: device int32 [B], each 0 or 3), h [B, 2 (P + N), 80]
+// with zeros behind 2 L_b.  checked: the caller has run flow_ctx_lengths on these vectors already
+int flow_encoder_fwd_ctx(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const int* ctx_lens, int B,
+                         int P, int N, int streaming, float* h_out, int* h_lens, hipStream_t st, bool checked) {
+  if (P < 0 || N < 0) return fail(JV_ERR_ARG, "jv_flow_encoder_fwd_ctx: P and N must be non-negative");
+  JV_TRY(check_encoder_call(c, B, P + N));
+  if (!checked) {
+    std::vector<int> enc_lens;
+    JV_TRY(flow_ctx_lengths("jv_flow_encoder_fwd_ctx", plen, len, ctx_lens, nullptr, B, P, N, enc_lens, nullptr, st));
+  }
+  JV_TRY(ensure_ws(c, B, P + N, false));
+  PromptWs& w = *c.pws;
+  JV_TRY(sum_lens_ctx(plen, P, len, N, B, w.lens64, h_lens, 2, ctx_lens, w.lens_c, st));
+  return encoder_stages(c, ptok, plen, P, tok, len, N, w.lens64, B, true, streaming != 0, 0, h_out, st, w.lens_c);
+}
+
 }  // namespace jv
 
 extern "C" {
@@ -301,6 +363,17 @@ int jv_flow_encoder_fwd(jv_context* ctx, const int64_t* prompt_tokens, const int
   return jv::flow_encoder_fwd(ctx->c, reinterpret_cast<const long*>(prompt_tokens), reinterpret_cast<const long*>(prompt_lens),
                               reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_lens), B, P, N, streaming, h,
                               h_lens, static_cast<hipStream_t>(stream));
+}
+
+int jv_flow_encoder_fwd_ctx(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                            const int64_t* token_lens, const int32_t* ctx_lens, int B, int P, int N, int streaming, float* h,
+                            int32_t* h_lens, void* stream) {
+  if (!ctx || !h || !token_lens || !ctx_lens || (N > 0 && !tokens) || (P > 0 && (!prompt_tokens || !prompt_lens)))
+    return jv::fail(JV_ERR_ARG, "jv_flow_encoder_fwd_ctx: null argument");
+  JV_HIP(hipSetDevice(ctx->c.device));
+  return jv::flow_encoder_fwd_ctx(ctx->c, reinterpret_cast<const long*>(prompt_tokens), reinterpret_cast<const long*>(prompt_lens),
+                                  reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_lens), ctx_lens, B, P, N,
+                                  streaming, h, h_lens, static_cast<hipStream_t>(stream), false);
 }
 
 int jv_flow_encoder_fwd_partial(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,

@@ -59,6 +59,29 @@ int sum_lens(const long* plen, int P, const long* len, int N, int B, long* sum, 
   return JV_OK;
 }
 
+// The vector form (jv_flow_token2mel_ctx): utterance b has a context of its own, c_b = clamp(ctxv[b], 0, 3).  sum[b] = L_b =
+// max(m_b - c_b, 0) with m_b the clamped token count, out32[b] = mul * L_b, and with_ctx[b] = min(L_b + c_b, m_b): the rows conv1
+// may read (mask1c of prompt.hip).  The host has rejected any other ctxv before this runs; the clamps keep the kernel in bounds
+__global__ void sum_lens_ctx_kernel(const long* __restrict__ plen, int P, const long* __restrict__ len, int N, int B,
+                                    long* __restrict__ sum, int* __restrict__ out32, int mul, const int* __restrict__ ctxv,
+                                    int* __restrict__ with_ctx) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const long m = (P > 0 ? min(max(plen[b], 0L), (long)P) : 0L) + min(max(len[b], 0L), (long)N);
+  const long c = min(max(ctxv[b], 0), 3);
+  const long s = max(m - c, 0L);
+  sum[b] = s;
+  if (out32) out32[b] = (int)s * mul;
+  with_ctx[b] = (int)min(s + c, m);
+}
+
+int sum_lens_ctx(const long* plen, int P, const long* len, int N, int B, long* sum, int* out32, int mul, const int* ctxv,
+                 int* with_ctx, hipStream_t st) {
+  hipLaunchKernelGGL(sum_lens_ctx_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, plen, P, len, N, B, sum, out32, mul, ctxv, with_ctx);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
 // pe[m][2i] = sin(r * w_i), pe[m][2i+1] = cos(r * w_i), r = T - 1 - m (relative position i - j), m < 2T - 1.
 // w_i = exp(2i * -(ln 1e4 / 512)) comes from the host (`div`, the reference's own torch expression, embedding.py:239-242):
 // at |r| ~ 1000 one ulp of w_i moves the angle by 6e-5, so the frequencies are not recomputed here.  The reference

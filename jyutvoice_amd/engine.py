@@ -351,6 +351,44 @@ class Engine:
                                                  _ptr(ml), _stream(self.device)))
         return mel, ml
 
+    def flow_encoder_ctx(self, prompt_token, prompt_len, token, token_len, ctx_lens, streaming=False):
+        """jv_flow_encoder_fwd_ctx: flow_encoder with a look-ahead context per utterance (ctx_lens [B], each 0 or 3) ->
+        (h [B, 2*(P+N), 80], h_lens int32 [B] = 2 (p_b + n_b - ctx_b)); zeros behind"""
+        B, N = token.shape
+        P = 0 if prompt_token is None else prompt_token.shape[1]
+        tok, tl = self._tok(token), self._tok(token_len)
+        ptok, pl = (self._tok(prompt_token), self._tok(prompt_len)) if P > 0 else (None, None)
+        cl = self._lens32("flow_encoder_ctx", ctx_lens, B)
+        h = torch.empty(B, 2 * (P + N), spec.N_FEATS, device=self.device)
+        hl = torch.empty(B, dtype=torch.int32, device=self.device)
+        check(self.lib.jv_flow_encoder_fwd_ctx(self._h, _ptr(ptok), _ptr(pl), _ptr(tok), _ptr(tl), _ptr(cl), B, P, N,
+                                               1 if streaming else 0, _ptr(h), _ptr(hl), _stream(self.device)))
+        return h, hl
+
+    def flow_token2mel_ctx(self, prompt_token, prompt_len, token, token_len, ctx_lens, prompt_feat, feat_len, embedding,
+                           streaming=False, n_timesteps=10, temperature=1.0, t_span=None):
+        """jv_flow_token2mel_ctx: flow_token2mel with a look-ahead context per utterance (ctx_lens [B], each 0 or 3) ->
+        (mel [B, 80, 2*(P+N)], mel_lens int32 [B] = 2 (p_b + n_b - ctx_b) - f_b)"""
+        B, N = token.shape
+        P = 0 if prompt_token is None else prompt_token.shape[1]
+        F = 0 if prompt_feat is None else prompt_feat.shape[1]
+        tok, tl = self._tok(token), self._tok(token_len)
+        ptok, pl = (self._tok(prompt_token), self._tok(prompt_len)) if P > 0 else (None, None)
+        cl = self._lens32("flow_token2mel_ctx", ctx_lens, B)
+        pf = _f32(prompt_feat, self.device) if F > 0 else None
+        fl = feat_len.to(device=self.device, dtype=torch.int32).contiguous()
+        emb = _f32(embedding, self.device)
+        mel = torch.empty(B, spec.N_FEATS, 2 * (P + N), device=self.device)
+        ml = torch.empty(B, dtype=torch.int32, device=self.device)
+        ts = None
+        if t_span is not None:
+            ts_host = t_span.detach().to("cpu", torch.float32).contiguous()
+            ts = (C.c_float * ts_host.numel())(*ts_host.tolist())
+        check(self.lib.jv_flow_token2mel_ctx(self._h, _ptr(ptok), _ptr(pl), _ptr(tok), _ptr(tl), _ptr(cl), _ptr(pf), _ptr(fl), _ptr(emb),
+                                             B, P, N, F, 1 if streaming else 0, int(n_timesteps), float(temperature), ts, _ptr(mel),
+                                             _ptr(ml), _stream(self.device)))
+        return mel, ml
+
     # ---- encoder --------------------------------------------------------------------------------------
     def encoder(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed):
         B, Tt = x.shape
@@ -503,6 +541,60 @@ class Engine:
         check(self.lib.jv_hift_source_cont(self._h, _ptr(f0), _ptr(phase), C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint32(call & 0xFFFFFFFF),
                                            C.c_int64(sample0), _ptr(cum), B, T, _ptr(s), _stream(self.device)))
         return s
+
+    def _dev_vec(self, who, name, t, dtype, B):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (B,) or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dtype} [{B}] tensor on {self.device}, got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
+        return t
+
+    def hift_source_cont_rows(self, f0, phase, seeds, calls, sample0, lens, cum, out=None):
+        """jv_hift_source_cont_rows: every row the continuation of a signal of its own.  f0 [B, T]; phase [B, 9]; seeds int64 [B]
+        (the uint64 key's bit pattern), calls int32 [B] (uint32 likewise), sample0 int64 [B], lens int32 [B], cum float64 [B, 9]: all on
+        the device, nothing is copied.  -> s [B, 1, 480 T]; a row with lens 0 is not written (with `out` it keeps what it held)."""
+        who = "hift_source_cont_rows()"
+        B, T = f0.shape
+        if cum.dtype != torch.float64 or tuple(cum.shape) != (B, 9) or cum.device != self.device or not cum.is_contiguous():
+            raise ValueError(f"{who}: cum must be a contiguous float64 [{B}, 9] tensor on {self.device}, got "
+                             f"{cum.dtype} {tuple(cum.shape)} on {cum.device}")
+        seeds = self._dev_vec(who, "seeds", seeds, torch.int64, B)
+        calls = self._dev_vec(who, "calls", calls, torch.int32, B)
+        sample0 = self._dev_vec(who, "sample0", sample0, torch.int64, B)
+        lens = self._dev_vec(who, "lens", lens, torch.int32, B)
+        f0, phase = _f32(f0, self.device), _f32(phase, self.device)
+        if tuple(phase.shape) != (B, 9):
+            raise ValueError(f"{who}: phase must be [{B}, 9], got {tuple(phase.shape)}")
+        n = T * spec.HIFT_UPSAMPLE_TOTAL
+        if out is None:
+            out = torch.zeros(B, 1, n, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (B, 1, n) or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"{who}: out must be a contiguous float32 [{B}, 1, {n}] tensor on {self.device}")
+        check(self.lib.jv_hift_source_cont_rows(self._h, _ptr(f0), _ptr(phase), _ptr(seeds), _ptr(calls), _ptr(sample0), _ptr(lens),
+                                                _ptr(cum), B, T, _ptr(out), _stream(self.device)))
+        return out
+
+    def slab_copy(self, src, dst, desc, span: int, zero_fill: bool = False):
+        """jv_slab_copy: src [rows, C, width], dst [rows', C, width'] (or 2-D, C = 1): contiguous float32 on the device; desc int32
+        [B, 5] on the device, rows of (src_row, src_col, dst_row, dst_col, n); span: the widest slab (with zero_fill: every slab's
+        destination is zeros from n up to span).  One launch, in place on `dst`."""
+        who = "slab_copy()"
+        for name, t in (("src", src), ("dst", dst)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (2, 3) or t.device != self.device
+                    or not t.is_contiguous()):
+                raise ValueError(f"{who}: {name} must be a contiguous float32 [rows, C, width] or [rows, width] tensor on {self.device}")
+        cs, cd = (1 if src.dim() == 2 else src.shape[1]), (1 if dst.dim() == 2 else dst.shape[1])
+        if cs != cd:
+            raise ValueError(f"{who}: src has {cs} channels, dst {cd}")
+        if (not isinstance(desc, torch.Tensor) or desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 5
+                or desc.device != self.device or not desc.is_contiguous()):
+            raise ValueError(f"{who}: desc must be a contiguous int32 [B, 5] tensor on {self.device}")
+        if span < 0:
+            raise ValueError(f"{who}: span must be non-negative, got {span}")
+        if src.numel() == 0 or dst.numel() == 0 or desc.shape[0] == 0 or span == 0:
+            return dst
+        check(self.lib.jv_slab_copy(self._h, _ptr(src), src.shape[0], src.shape[-1], _ptr(dst), dst.shape[0], dst.shape[-1], cs,
+                                    _ptr(desc), desc.shape[0], int(span), 1 if zero_fill else 0, _stream(self.device)))
+        return dst
 
     def hift_decode(self, mel, s, lens=None):
         B, _, T = mel.shape

@@ -18,7 +18,11 @@ first frames of `inference` on any longer sequence (jyutvoice_amd/stream.py buil
 Extension (opt-in): `inference(..., batched=True)` accepts B > 1 and is defined as the B = 1 reference looped over the utterances
 with every tensor cut to the utterance's own length: tokens `token[b, :token_len[b]]`, prompt `prompt_token[b, :prompt_token_len[b]]`,
 `prompt_feat[b, :prompt_feat_len[b]]`.  Nothing behind a length is read.  The mel comes back [B, 80, max_b y_b] with utterance b in
-`[:y_b]`, y_b = 2 (p_b + n_b) - f_b, zeros behind; `mel_lengths` holds the y_b of the last call."""
+`[:y_b]`, y_b = 2 (p_b + n_b) - f_b, zeros behind; `mel_lengths` holds the y_b of the last call.
+
+Extension: `inference_partial_batch(..., ctx_lens)` is both extensions at once -- a batch whose utterance b is a partial sequence
+(`ctx_lens[b]` = 3: `inference_partial`) or a whole one (0: `inference`), in one library call (jv_flow_token2mel_ctx): the step of a
+server that advances several streaming sessions together (jyutvoice_amd/stream.py, `Token2WavServer`)."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -222,6 +226,67 @@ class CausalMaskedDiffWithXvec:
                                                t_span=t_span)
         self.mel_lengths = lens
         return mel[:, :, :spec.PROMPT_UP_STRIDE * L - F].float(), None
+
+
+    @torch.inference_mode()
+    def inference_partial_batch(self, token, token_len, prompt_token, prompt_token_len, prompt_feat, prompt_feat_len, embedding,
+                                ctx_lens, streaming=True, n_timesteps: int = 10, temperature: float = 1.0):
+        """A batch that mixes partial and whole sequences -> (mel [B, 80, max_b y_b] float32, mel_lens int32 [B] on the device).
+        Defined as the B = 1 calls looped over the utterances, every tensor cut to the utterance's own length as in
+        `inference(batched=True)`: `inference_partial` where ctx_lens[b] = 3 (the last three of the p_b + n_b tokens are look-ahead
+        context only), `inference(finalize=True)` where it is 0.  L_b = p_b + n_b - ctx_lens[b] tokens are encoded, f_b =
+        prompt_feat_len[b] prompt frames cut, y_b = 2 L_b - f_b frames come back in `[b, :, :y_b]`, zeros behind.  Nothing behind a
+        length is read.  One library call (jv_flow_token2mel_ctx): what a streaming server runs per step for all its sessions."""
+        who = "inference_partial_batch()"
+        if token.dim() != 2:
+            raise ValueError(f"{who}: token must be [B, N], got {tuple(token.shape)}")
+        B, N = token.shape
+        if prompt_token is None:
+            prompt_token = torch.zeros(B, 0, dtype=torch.int64)
+        if prompt_token.dim() != 2 or prompt_token.shape[0] != B:
+            raise ValueError(f"{who}: prompt_token must be [{B}, P], got {tuple(prompt_token.shape)}")
+        P = prompt_token.shape[1]
+        if prompt_feat is None:
+            prompt_feat = torch.zeros(B, 0, spec.N_FEATS)
+        if prompt_feat.dim() != 3 or prompt_feat.shape[0] != B or prompt_feat.shape[2] != spec.N_FEATS:
+            raise ValueError(f"{who}: prompt_feat must be [{B}, frames, {spec.N_FEATS}], got {tuple(prompt_feat.shape)}")
+        if embedding.dim() != 2 or tuple(embedding.shape) != (B, spec.SPK_EMBED_DIM):
+            raise ValueError(f"{who}: embedding must be [{B}, {spec.SPK_EMBED_DIM}], got {tuple(embedding.shape)}")
+        F = prompt_feat.shape[1]
+        n_host = _host_ints(token_len, "token_len", B)
+        p_host = _host_ints(prompt_token_len, "prompt_token_len", B) if P > 0 else [0] * B
+        f_host = _host_ints(prompt_feat_len, "prompt_feat_len", B) if F > 0 else [0] * B
+        c_host = _host_ints(torch.as_tensor(ctx_lens), "ctx_lens", B)
+        y_host = []
+        for b in range(B):
+            if not 0 <= n_host[b] <= N:
+                raise ValueError(f"{who}: utterance {b}: token_len {n_host[b]} outside [0, {N}]")
+            if not 0 <= p_host[b] <= P:
+                raise ValueError(f"{who}: utterance {b}: prompt_token_len {p_host[b]} outside [0, {P}]")
+            if c_host[b] not in (0, spec.PROMPT_LOOKAHEAD):
+                raise ValueError(f"{who}: utterance {b}: ctx_lens {c_host[b]}: the look-ahead length {spec.PROMPT_LOOKAHEAD} (a partial "
+                                 "sequence) or 0 (a whole one)")
+            m = p_host[b] + n_host[b]
+            if c_host[b] and m < spec.PROMPT_LOOKAHEAD + 1:
+                raise ValueError(f"{who}: utterance {b}: {m} tokens: at least {spec.PROMPT_LOOKAHEAD + 1} are needed (the last "
+                                 f"{spec.PROMPT_LOOKAHEAD} are look-ahead context only)")
+            if m < 1:
+                raise ValueError(f"{who}: utterance {b}: no tokens")
+            L = m - c_host[b]
+            if not 0 <= f_host[b] <= F or f_host[b] > spec.PROMPT_UP_STRIDE * L:
+                raise ValueError(f"{who}: utterance {b}: prompt_feat has {f_host[b]} frames (of {F}) but the {L} encoded tokens give only "
+                                 f"{spec.PROMPT_UP_STRIDE * L}")
+            y_host.append(spec.PROMPT_UP_STRIDE * L - f_host[b])
+        if not self._loaded:
+            raise RuntimeError(f"{_NAME}: load_state_dict() has not been called")
+        eng = self._rt().ensure(B, spec.PROMPT_UP_STRIDE * (P + N), 1)
+        t_span = 1 - torch.cos(torch.linspace(0, 1, n_timesteps + 1) * 0.5 * torch.pi)      # flow_matching.py:387-389
+        mel, lens = eng.flow_token2mel_ctx(prompt_token if P > 0 else None, torch.tensor(p_host), token, torch.tensor(n_host),
+                                           torch.tensor(c_host, dtype=torch.int32), prompt_feat if F > 0 else None,
+                                           torch.tensor(f_host, dtype=torch.int32), embedding, streaming=bool(streaming),
+                                           n_timesteps=n_timesteps, temperature=temperature, t_span=t_span)
+        self.mel_lengths = lens
+        return mel[:, :, :max(y_host)].float(), lens
 
 
 def load_flow(flow_path, device="cuda:0", decoder: str = "own", runtime=None):
