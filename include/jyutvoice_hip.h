@@ -471,10 +471,18 @@ int jv_op_attention_planes(const float* qkv, int64_t rows, const int32_t* lens, 
 /* jv_op_hiftconv: the vocoder's ResBlock convolution (hiftconv_kernel.h; jyutvoice/hifigan/generator.py:90-97):
  * out = ((Conv1d(C, C, ntaps, dilation dil, same padding)(Snake_alpha(A)) + bias) + res1 + res2) * out_scale (+ out when
  * accumulate) on a [rows, C] row buffer, C = 64 / 128 / 256, W [C][ntaps * C] tap-major, rows with rowmask == 0 read as zero;
- * amax_in: one device float >= max |A|, a_extra: max 1 / (alpha + 1e-9); amax_out (optional): max |out| is folded into it. */
+ * amax_in: slot_nb device floats, each >= max |A| over its utterance's rows, slot(row) = clamp((row - slot_G) / slot_S, 0,
+ * slot_nb - 1) or, slot_map != NULL, slot_map[row] (as in jv_op_hiftpair); slot_G = slot_S = 0, slot_nb = 1, slot_map = NULL:
+ * one slot for every row.  a_extra: max 1 / (alpha + 1e-9); amax_out (optional, slot_nb floats): max |out| over the rows
+ * with rowmask != 0 is folded into the row's slot. */
 int jv_op_hiftconv(const float* A, int64_t rows, int C, int ntaps, int dil, const float* W, const float* bias, const float* alpha,
                    const uint8_t* rowmask, const float* res1, const float* res2, float out_scale, int accumulate,
-                   const float* amax_in, float a_extra, float* amax_out, float* out, void* stream);
+                   const float* amax_in, float a_extra, int slot_G, int slot_S, int slot_nb, const int32_t* slot_map,
+                   float* amax_out, float* out, void* stream);
+/* jv_hift_lds_bytes: host only, no device needed.  The dynamic LDS one workgroup of the vocoder's row-owning ResBlock kernels
+ * asks for: pair = 0 hiftconv_kernel<C, NG>, pair = 1 hiftpair_kernel<C, NG, ntaps>, NG = row groups of 80 rows per workgroup;
+ * -1 where the library has no such instantiation. */
+int jv_hift_lds_bytes(int pair, int C, int NG, int ntaps, int dil);
 /* jv_op_rowconv: the estimator's causal k = 3 convolution to 256 channels at chip-filling batch sizes (rowconv_kernel.h):
  * out[m] = tail(sum_j A[m - 2 + j] W_j + bias), tail = LayerNorm_256 (ln_g != NULL) -> act -> rows with rowmask == 0 := 0 ->
  * + rowvec (one [256] vector here) -> + res; A's fp16x3 scale comes from *amax_in (>= max |A|), amax_out receives max |out|

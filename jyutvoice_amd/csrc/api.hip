@@ -17,6 +17,7 @@ int hiftconv(const HiftConvArgs& a, int C, hipStream_t st);   // hiftconv.hip
 int rowgemm(const RowGemmArgs& a, int epi, hipStream_t st);   // rowgemm.hip
 int rowconv(const RowConvArgs& a, hipStream_t st);
 int hiftpair(const HiftPairArgs& a, int C, hipStream_t st);   // hiftconv.hip
+int hift_lds_bytes(int pair, int C, int NG, int ntaps, int dil);
 int rowres(const RowResArgs& a, hipStream_t st);              // rowgemm.hip
 int rowffn(const RowFfnArgs& a, hipStream_t st);
 int rowblock(const RowBlockArgs& a, bool qkv, hipStream_t st);   // rowblock.hip
@@ -904,11 +905,14 @@ int jv_op_rowconv(const float* A, int64_t rows, int M, int Cin, const float* W, 
 }
 
 // hiftconv (hiftconv_kernel.h): out = ((Conv1d_k,dil(Snake_alpha(A)) + bias) + res1 + res2) * out_scale (+ out when accumulate) on a
-// [rows, C] row buffer, C = 64 / 128 / 256; W [C][ntaps * C] tap-major; amax_in / amax_out: one slot (test hook)
+// [rows, C] row buffer, C = 64 / 128 / 256; W [C][ntaps * C] tap-major; amax_in / amax_out: slot_nb per-utterance slots, addressed
+// by (slot_G, slot_S, slot_nb) or by slot_map [rows] as in jv_op_hiftpair; (0, 0, 1, NULL) is one slot for every row (test hook)
 int jv_op_hiftconv(const float* A, int64_t rows, int C, int ntaps, int dil, const float* W, const float* bias, const float* alpha,
                    const uint8_t* rowmask, const float* res1, const float* res2, float out_scale, int accumulate,
-                   const float* amax_in, float a_extra, float* amax_out, float* out, void* stream) {
+                   const float* amax_in, float a_extra, int slot_G, int slot_S, int slot_nb, const int32_t* slot_map,
+                   float* amax_out, float* out, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (slot_nb < 1) return jv::fail(JV_ERR_ARG, "jv_op_hiftconv: needs at least one utterance slot");
   const int K = ntaps * C;
   void* scratch = nullptr;
   const size_t n = (size_t)C * K;
@@ -923,11 +927,13 @@ int jv_op_hiftconv(const float* A, int64_t rows, int C, int ntaps, int dil, cons
   jv::HiftConvArgs a{};
   a.A = A; a.a_rows = rows; a.M = (int)rows; a.ntaps = ntaps; a.dil = dil; a.tap_row0 = -(dil * (ntaps - 1) / 2); a.rowmask_in = rowmask;
   a.alpha = alpha; a.Wf = wf; a.wf_plane = (long)n; a.colscale = cs; a.bias = bias;
-  a.amax_in = amax_in; a.a_extra = a_extra; a.slot_G = 0; a.slot_S = 0; a.slot_nb = 1;
+  a.amax_in = amax_in; a.a_extra = a_extra; a.slot_G = slot_G; a.slot_S = slot_S; a.slot_nb = slot_nb; a.slot_map = slot_map;
   a.out = out; a.res1 = res1; a.res2 = res2; a.out_scale = out_scale; a.accumulate = accumulate;
   a.amax_out = amax_out; a.amax_mask = rowmask;
   return jv::hiftconv(a, C, st);
 }
+
+int jv_hift_lds_bytes(int pair, int C, int NG, int ntaps, int dil) { return jv::hift_lds_bytes(pair, C, NG, ntaps, dil); }
 
 // attention64_planes (attention_pl.hip) on an fp32 qkv matrix: K and V are split into planes here the way the qkv GEMM's
 // epilogue writes them; planes_out = 1: the result as fp16 planes [2][rows][512] of value * out2_scale (test hook)

@@ -202,6 +202,12 @@ int resblock(const ResBlockW& rb, const HGeo& g, int lvl, int C, long rows, long
              float* am_tmp, float* am_dst, bool h3, bool rowconv, bool pair, hipStream_t st) {
   const int dils[3] = {1, 3, 5};
   const float* in = cur;
+  // what every launch of this block shares: the row buffer's extent, the level's utterance slots, the profiler's real rows
+  auto rows_and_slots = [&](auto& a) {
+    a.a_rows = alloc; a.M = (int)rows;
+    a.slot_G = g.G[lvl]; a.slot_S = g.S[lvl]; a.slot_nb = g.B; a.slot_map = g.rsample[lvl];
+    a.alg_rows = g.frames ? g.frames * LVL_MUL[lvl] : (long)g.B * g.L[lvl];
+  };
   // The pair of convolutions of each dilation in ONE launch (hiftpair_kernel.h) at 64 / 128 channels.  A workgroup reads its
   // neighbours' rows as halo, so a pair never writes the buffer it reads: cur -> r -> tmp -> dst (the unfused form's
   // intermediate buffer is free), each buffer with its own bound slots.
@@ -214,15 +220,14 @@ int resblock(const ResBlockW& rb, const HGeo& g, int lvl, int C, long rows, long
     for (int j = 0; j < 3; ++j) {
       const bool last = j == 2;
       HiftPairArgs a{};
-      a.A = in; a.a_rows = alloc; a.M = (int)rows; a.ntaps = rb.k; a.dil = dils[j]; a.rowmask = mask;
+      rows_and_slots(a);
+      a.A = in; a.ntaps = rb.k; a.dil = dils[j]; a.rowmask = mask;
       a.alpha1 = rb.a1[j]; a.alpha2 = rb.a2[j];
       a.Wf = rb.wfp[j]; a.wf_plane = (long)C * 2 * rb.k * C;
       a.cs1 = rb.c1[j].colscale; a.b1 = rb.c1[j].bias; a.cs2 = rb.c2[j].colscale; a.b2 = rb.c2[j].bias;
       a.amax_in = am_in; a.e1 = rb.e1[j]; a.e2 = rb.e2[j]; a.l1max = rb.l1max[j]; a.b1max = rb.b1max[j];
-      a.slot_G = g.G[lvl]; a.slot_S = g.S[lvl]; a.slot_nb = g.B; a.slot_map = g.rsample[lvl];
       a.out = bufs[j]; a.res2 = last ? extra_res : nullptr; a.out_scale = last ? scale : 1.f; a.accumulate = last ? accumulate : 0;
       a.amax_out = ams[j];
-      a.alg_rows = g.frames ? g.frames * LVL_MUL[lvl] : (long)g.B * g.L[lvl];
       JV_TRY(hiftpair(a, C, st));
       in = bufs[j];
       am_in = ams[j];
@@ -233,12 +238,12 @@ int resblock(const ResBlockW& rb, const HGeo& g, int lvl, int C, long rows, long
   auto rc = [&](const GemmW& w, const float* A, const float* alpha, float extra, float* am_in, int tap_row0, int dil, float* out,
                 const float* res1, const float* res2, float out_scale, int acc, float* am_out) -> int {
     HiftConvArgs a{};
-    a.A = A; a.a_rows = alloc; a.M = (int)rows; a.ntaps = w.ntaps; a.dil = dil; a.tap_row0 = tap_row0; a.rowmask_in = mask;
+    rows_and_slots(a);
+    a.A = A; a.ntaps = w.ntaps; a.dil = dil; a.tap_row0 = tap_row0; a.rowmask_in = mask;
     a.alpha = alpha; a.Wf = w.wf; a.wf_plane = (long)w.N * w.ntaps * w.Cin; a.colscale = w.colscale; a.bias = w.bias;
-    a.amax_in = am_in; a.a_extra = extra; a.slot_G = g.G[lvl]; a.slot_S = g.S[lvl]; a.slot_nb = g.B; a.slot_map = g.rsample[lvl];
+    a.amax_in = am_in; a.a_extra = extra;
     a.out = out; a.res1 = res1; a.res2 = res2; a.out_scale = out_scale; a.accumulate = acc;
     a.amax_out = am_out; a.amax_mask = mask;
-    a.alg_rows = g.frames ? g.frames * LVL_MUL[lvl] : (long)g.B * g.L[lvl];
     return hiftconv(a, C, st);
   };
   for (int j = 0; j < 3; ++j) {

@@ -32,6 +32,21 @@ int hp_launch(const HiftPairArgs& a, hipStream_t st) {
 }
 }  // namespace
 
+// Host only: the dynamic LDS a launch of hiftconv_kernel<C, NG> (pair = 0) or hiftpair_kernel<C, NG, ntaps> (pair = 1) asks for
+// -- the total of hift_common.h's layout -- or -1 where no such instantiation exists (tests/test_hift_lds_host.py)
+int hift_lds_bytes(int pair, int C, int NG, int ntaps, int dil) {
+  switch ((pair ? 1000 : 0) + C + NG) {
+    case 64 + 2: return hc_lds_bytes<64, 2>(ntaps, dil);
+    case 64 + 4: return hc_lds_bytes<64, 4>(ntaps, dil);
+    case 128 + 1: return hc_lds_bytes<128, 1>(ntaps, dil);
+    case 128 + 2: return hc_lds_bytes<128, 2>(ntaps, dil);
+    case 256 + 1: return hc_lds_bytes<256, 1>(ntaps, dil);
+    case 1000 + 64 + 2: return hp_lds_bytes<64, 2>(ntaps, dil);
+    case 1000 + 128 + 2: return hp_lds_bytes<128, 2>(ntaps, dil);
+    default: return -1;
+  }
+}
+
 // A ResBlock's convolution pair in one launch (hiftpair_kernel.h): out = ((Conv1d_k(Snake2(Conv1d_k,d(Snake1(A)) + b1)) + b2) + A +
 // res2) * out_scale (+ out), C = 64 / 128.  `out` must not alias A: a workgroup reads its neighbours' rows as halo.
 int hiftpair(const HiftPairArgs& a, int C, hipStream_t st) {

@@ -17,7 +17,7 @@
 // hh' + hl' + lh' smallest first, fp32 accumulate over K ascending); 16x16x32 instead of 32x32x16 MFMAs sum a 32-deep step
 // in another internal order, so results agree with the tile kernels to rounding.
 #pragma once
-#include "rowgemm_kernel.h"
+#include "hift_common.h"
 
 namespace jv {
 
@@ -45,34 +45,17 @@ struct HiftConvArgs {
   long alg_rows;
 };
 
-__device__ __attribute__((aligned(64))) const float hc_zero_page[16] = {};
-__device__ __attribute__((aligned(16))) const unsigned char hc_ones_page[16] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-
-__device__ __forceinline__ void hc_atomic_max(float* slot, unsigned v) {      // integer max of the bit pattern of a non-negative float
-  __hip_atomic_fetch_max((__attribute__((address_space(1))) unsigned*)slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-constexpr int HC_RT = 5, HC_RG = 16 * HC_RT;      // rows per wave (row group)
 // NG row groups of 80 rows per workgroup; a workgroup has NG * C / 32 waves (each a 80 x 32 tile)
 template <int NG> constexpr int hc_rows() { return HC_RG * NG; }
 template <int C, int NG> constexpr int hc_threads() { return 64 * NG * (C / 32); }
-// window rows, padded: a multiple of 8 plus 1 (an ODD row count puts consecutive chunks 64 bytes apart modulo the 256-byte
-// bank row instead of on top of each other -- the staging stores of a wave span two to eight chunks)
-inline int hc_wrpad(int R, int ntaps, int dil) { return ((R + (ntaps - 1) * dil + 7) & ~7) + 1; }
-template <int C, int NG> inline int hc_lds_bytes(int ntaps, int dil) {
-  const int R = hc_rows<NG>(), wr = hc_wrpad(R, ntaps, dil);
-  return ((wr * 4 + 255) & ~255) + R * 8 + (C / 32) * 2 * wr * 64 + NG * (C / 32) * 16 * 36 * 4;
-}
+template <int C, int NG> inline int hc_lds_bytes(int ntaps, int dil) { return hc_lds_layout<C, NG, false>(ntaps, dil).total; }
 
 template <int C, int NG>
 __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const HiftConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hc_lds[];
   constexpr int RT = HC_RT, RG = HC_RG;
   constexpr int NCH = C / 32, CW = C / 32, R = RG * NG, NT = 64 * NG * CW;
-  constexpr int C4 = C / 4;                     // float4 per row
-  constexpr int RPI = NT / C4;                  // window rows staged per pass of the workgroup
   static_assert(R + 56 <= NT, "one window row per thread in the facts pass");
-  constexpr int NWL = 4;
   typedef const __attribute__((address_space(1))) unsigned char* gbytes;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -83,53 +66,30 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
   const int WRP = ((WR + 7) & ~7) + 1;
   const int PS = WRP * 64, CS = 2 * PS;         // plane and chunk strides of the operand image
   const int KS = p.ntaps * NCH;                 // 32-deep steps (even: NCH is)
+  const HcLds L = hc_lds_layout<C, NG, false>(p.ntaps, p.dil);
   float* const wscale = reinterpret_cast<float*>(hc_lds);                                   // [WRP]: < 0 = the row reads as zero
-  int2* const rowinfo = reinterpret_cast<int2*>(hc_lds + ((WRP * 4 + 255) & ~255));         // [R]
-  unsigned char* const img = reinterpret_cast<unsigned char*>(rowinfo) + R * 8;            // [NCH][2][WRP][64 B]
-  float* const patch = reinterpret_cast<float*>(img + NCH * CS) + wave * (16 * 36);
+  int2* const rowinfo = reinterpret_cast<int2*>(hc_lds + L.rowinfo);                        // [R]
+  unsigned char* const img = hc_lds + L.img;                                                // [NCH][2][WRP][64 B]
+  float* const patch = reinterpret_cast<float*>(hc_lds + L.patch) + wave * (16 * 36);
 
-  // ---- W: fragment order, [plane][KS][C / 16 blocks][64 lanes][8 halves] (k-step major); this wave's column blocks are 2 cp + nt ----
-  const unsigned short* wp[2][2];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) wp[nt][pl] = p.Wf + (long)pl * p.wf_plane + (long)(2 * cp + nt) * 512 + lane * 8;
-  int wk = 0;
+  // ---- W: this wave's fragment stream through the register double buffer; steps 0 and 1 are requested here ----
+  HcWeights<C> w;
+  w.start(p.Wf, p.wf_plane, cp, lane);
   WFragBuf<2> bq;
   bq.zero();
-  auto load_w = [&](auto par_tag, auto nttag) {
-    constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    bq.template load<par, nt, 0>(wp[nt][0]);
-    bq.template load<par, nt, 1>(wp[nt][1]);
-  };
-  auto advance_w = [&]() {      // + C / 16 blocks x 1 KB (512 halves) per step; past the end: back to the first step (weights that exist)
-    constexpr long WSTEP = 512L * (C / 16);
-    const long d = ++wk == KS ? WSTEP - WSTEP * KS : WSTEP;
-    if (wk == KS) wk = 0;
+  // the weights start first: everything below is global-load latency they spend in flight.  (A counted loop that the compiler
+  // unrolls, on purpose: as straight-line steps, here or in the walker, the same loads leave hiftpair_kernel<128,2,11> with four
+  // VGPRs more -- profiles/hift_common_isa.md)
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) wp[nt][pl] += d;
-  };
-  // the weights start first: everything below is global-load latency they spend in flight
-  load_w(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-  load_w(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-  advance_w();
-  load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-  load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-  advance_w();
+  for (int b = 0; b < 2; ++b) {
+    if (b == 0) { w.template load<0, 0>(bq); w.template load<0, 1>(bq); }
+    if (b == 1) { w.template load<1, 0>(bq); w.template load<1, 1>(bq); }
+    w.advance(KS);
+  }
 
   // ---- per-row facts: the window rows' scales (one level of unconditional loads on clamped indices: rowconv_wd_kernel) ----
-  auto slot_of = [&](const long row) -> int {
-    if (p.slot_map) {      // compact geometry of ragged batches (hift.hip): by table; every caller clamps `row` to the buffer
-      const int q = p.slot_map[row];
-      return q < 0 ? 0 : (q >= p.slot_nb ? p.slot_nb - 1 : q);
-    }
-    if (p.slot_S <= 0) return 0;
-    const int q = (int)((row - p.slot_G) / p.slot_S);
-    return q < 0 ? 0 : (q >= p.slot_nb ? p.slot_nb - 1 : q);
-  };
-  constexpr int RI_TRACK = 1 << 30;
+  auto slot_of = [&](const long row) { return hc_slot_of(p, row); };
+  constexpr int RI_TRACK = HC_RI_TRACK;
   {
     // (WR <= R + 50 < NT: one window row and one output row per thread)
     const long ar = (long)m0 + p.tap_row0 + tid;
@@ -151,68 +111,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
   __syncthreads();
 
   // ---- the window, once: fp32 rows -> Snake -> x scale -> two fp16 planes, chunk-major operand image ----
-  {
-    const int c4 = tid % C4, r0 = tid / C4;      // this thread's four channels, its first window row
-    const rg_f32x4 al = *reinterpret_cast<const rg_f32x4*>(p.alpha + 4 * c4);
-    rg_f32x4 ai;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ai[e] = 1.0f / (al[e] + 1e-9f);
-    const int chunk = c4 >> 3, cslot = (c4 & 7) >> 1, chalf = (c4 & 1) << 3;
-    const float* const abase = p.A + ((long)m0 + p.tap_row0) * C + 4 * c4;
-    // four rows in flight per thread and pass.  (All 12 - 17 of a thread's rows at once measured SLOWER on the same box: the
-    // vocoder stage 32.2 ms against 24.6 -- the loop below is then one 8 000-line unrolled body, and two co-resident workgroups
-    // hide each other's latency anyway.)
-#ifndef JV_HC_U
-#define JV_HC_U 4
-#endif
-    constexpr int U = JV_HC_U;
-    for (int rb = r0; rb < WR; rb += U * RPI) {
-      rg_f32x4 x[U];
-      float sc[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int r = rb + u * RPI;
-        sc[u] = r < WR ? wscale[r] : -1.f;
-        // (explicitly GLOBAL loads; a row that reads as zero is fetched from a page of zeros and never multiplied: guard rows
-        // may hold anything)
-        const float* src = sc[u] >= 0.f ? abase + (long)r * C : hc_zero_page;
-        x[u] = *(const __attribute__((address_space(1))) rg_f32x4*)src;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int r = rb + u * RPI;
-        if (r >= WR) continue;
-        rg_f32x4 v = x[u];
-        if (sc[u] >= 0.f) {
-          float arg[4];
-          bool big = false;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            arg[e] = v[e] * al[e];
-            big = big || fabsf(arg[e]) > 32768.f;      // false for NaN, which sin2_small propagates
-          }
-          if (snake_args_small(big)) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] + ai[e] * sin2_small(arg[e]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float sn = sinf(arg[e]);
-              v[e] = v[e] + ai[e] * (sn * sn);
-            }
-          }
-          v = v * sc[u];
-        } else {
-          v = rg_f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        const Split2 s0 = split2h_pair(v[0], v[1]);
-        const Split2 s1 = split2h_pair(v[2], v[3]);
-        unsigned char* d = img + chunk * CS + r * 64 + (((cslot ^ rg_key(r))) << 4) + chalf;
-        *reinterpret_cast<rg_u32x2*>(d) = rg_u32x2{s0.h, s1.h};
-        *reinterpret_cast<rg_u32x2*>(d + PS) = rg_u32x2{s0.l, s1.l};
-      }
-    }
-  }
+  hc_stage_window<C, NT>(p.A + ((long)m0 + p.tap_row0) * C, WR, (const hc_lds_f32*)wscale, p.alpha, (hc_lds_u8*)img, CS, PS, tid);
   // the per-column constants of the epilogue, requested here so that their latency is not paid behind the main loop
   const int ncol = 32 * cp + 4 * (lane & 7);      // this lane's four columns in the row-wise passes
   rg_f32x4 cs4 = *reinterpret_cast<const rg_f32x4*>(p.colscale + ncol);
@@ -239,28 +138,9 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
   };
   int nc = 1, nj = 0;      // chunk and tap of the NEXT step
   read_a(std::integral_constant<int, 0>{}, 0, 0);
-  auto step = [&](auto par_tag, const bool last) {
+  auto step = [&](auto par_tag, const bool last) {      // hc_step at NB = 2: buffer = parity
     constexpr int par = decltype(par_tag)::value;
-    auto block = [&](auto nttag) {
-      constexpr int nt = decltype(nttag)::value;
-#pragma unroll
-      for (int mt = 0; mt < RT; ++mt) {
-        acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      load_w(par_tag, nttag);
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    // this wave's memory operations in program order: ... W0(s+1), W1(s+1) | W0(s+2), <wait>, W1(s+2) | ...; needed at the wait:
-    // W0(s+1) and W1(s); behind W0(s+1): W1(s+1) and W0(s+2) = NWL loads (rowgemm_wa_kernel)
-    block(std::integral_constant<int, 0>{});
-    wait_vmcnt<NWL>();
-    bq.template landed_mid<par>();
-    if (!last) read_a(std::integral_constant<int, par ^ 1>{}, nc, nj);
-    __builtin_amdgcn_sched_barrier(0);
-    block(std::integral_constant<int, 1>{});
-    advance_w();
-    if (++nc == NCH) { nc = 0; ++nj; }
+    hc_step<NCH, par, par>(acc, af, bq, w, KS, nc, nj, last, read_a);
   };
 #pragma unroll 1
   for (int ks = 0; ks < KS; ks += 2) {
@@ -268,91 +148,9 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftconv_kernel(const H
     step(std::integral_constant<int, 1>{}, ks + 2 >= KS);
   }
 
-  // ---- epilogue, per wave (no workgroup barrier): 16 rows at a time through the wave's private 16 x 36-float patch (MFMA
-  // layout in: lane = column, 4 rows; rows out: 8 lanes x 16 B per row), so that every store writes whole 128-byte row segments
-  {
-    const int prow = lane >> 3;
-    const float* const r1b = p.res1 ? p.res1 + ncol : nullptr;
-    const float* const r2b = p.res2 ? p.res2 + ncol : nullptr;
-    float* const ob = p.out + ncol;
-    const int rowb = grp * RG;
-    struct RowIn { rg_f32x4 r1[2], r2[2], pv[2]; float inv[2]; int info[2]; bool ok[2]; };
-    auto request = [&](const int mt, RowIn& in) {      // the two 8-row halves of row tile mt
-#pragma unroll
-      for (int ps = 0; ps < 2; ++ps) {
-        const int trow = rowb + mt * 16 + ps * 8 + prow;
-        const long m = (long)m0 + trow;
-        in.ok[ps] = m < p.M;
-        const long mc = in.ok[ps] ? m : (long)p.M - 1;
-        const int2 ri = rowinfo[trow];
-        in.inv[ps] = __uint_as_float((unsigned)ri.x);
-        in.info[ps] = ri.y;
-        const rg_f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        in.r1[ps] = r1b ? *(const __attribute__((address_space(1))) rg_f32x4*)(r1b + mc * C) : z;
-        in.r2[ps] = r2b ? *(const __attribute__((address_space(1))) rg_f32x4*)(r2b + mc * C) : z;
-        in.pv[ps] = p.accumulate ? *(const __attribute__((address_space(1))) rg_f32x4*)(ob + mc * C) : z;
-      }
-    };
-    auto finish = [&](const int mt, const RowIn& in) {
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) patch[(kq * 4 + e) * 36 + nt * 16 + r16] = acc[mt][nt][e];
-      unsigned u = 0u;
-#pragma unroll
-      for (int ps = 0; ps < 2; ++ps) {
-        const int trow = rowb + mt * 16 + ps * 8 + prow;
-        const long m = (long)m0 + trow;
-        rg_f32x4 x = *reinterpret_cast<const rg_f32x4*>(patch + (ps * 8 + prow) * 36 + 4 * (lane & 7));
-        x = x * in.inv[ps];      // 1 / the power of two the row's utterance was staged with
-        rg_f32x4 t = x * cs4 + b4;
-        t = (t + in.r1[ps]) + in.r2[ps];
-        const rg_f32x4 res = t * p.out_scale + in.pv[ps];
-        if (in.ok[ps]) {
-          *(__attribute__((address_space(1))) rg_f32x4*)(ob + m * C) = res;
-          if (in.info[ps] & RI_TRACK) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u = max(u, __float_as_uint(res[e]) & 0x7fffffffu);
-          }
-        }
-      }
-      if (p.amax_out) {
-        // the 16 rows of a tile almost always belong to one utterance: one wave-level maximum, one atomic -- and none once the
-        // slot already holds a larger value (a plain, cacheable read of it: a slot only grows).  Rows of two utterances: per lane.
-        const int s_lo = rowinfo[rowb + mt * 16].y & (RI_TRACK - 1), s_hi = rowinfo[rowb + mt * 16 + 15].y & (RI_TRACK - 1);
-        if (s_lo == s_hi) {
-          // (explicitly GLOBAL, like every load and store here: a flat access counts on lgkmcnt too and would sit in every LDS wait)
-          const unsigned seen = *(const __attribute__((address_space(1))) unsigned*)(p.amax_out + s_lo);
-          if (__builtin_amdgcn_ballot_w64(u > seen) != 0) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o));
-            if (lane == 0) hc_atomic_max(p.amax_out + s_lo, u);
-          }
-        } else {
-#pragma unroll
-          for (int ps = 0; ps < 2; ++ps) {
-            unsigned v = 0u;
-            const int trow = rowb + mt * 16 + ps * 8 + prow;
-            const long m = (long)m0 + trow;
-            if (in.ok[ps] && (in.info[ps] & RI_TRACK)) {
-              const rg_f32x4 res = *(const __attribute__((address_space(1))) rg_f32x4*)(ob + m * C);      // (this lane's own store)
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v = max(v, __float_as_uint(res[e]) & 0x7fffffffu);
-              hc_atomic_max(p.amax_out + (in.info[ps] & (RI_TRACK - 1)), v);
-            }
-          }
-        }
-      }
-    };
-    RowIn cur, nxt;
-    request(0, cur);
-#pragma unroll
-    for (int mt = 0; mt < RT; ++mt) {
-      if (mt + 1 < RT) request(mt + 1, nxt);      // a tile ahead: its loads travel while this one is finished
-      finish(mt, cur);
-      cur = nxt;
-    }
-  }
+  // ---- epilogue, per wave (no workgroup barrier): every row m < M, both residuals optional ----
+  hc_epilogue<C, false>(HcStore{p.M, p.out, p.res1, p.res2, p.out_scale, p.accumulate, p.amax_out}, acc, (hc_lds_f32*)patch,
+                        (const hc_lds_i32x2*)rowinfo, grp * RG, 0, m0, cs4, b4, ncol, lane);
   // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
   wait_vmcnt<0>();
   bq.landed_all();

@@ -60,12 +60,7 @@ struct HiftPairArgs {
 };
 
 template <int NG> constexpr int hp_rows() { return HC_RG * NG; }
-template <int C, int NG> inline int hp_lds_bytes(int ntaps, int dil) {
-  const int R = hp_rows<NG>();
-  const int w1 = hc_wrpad(R, ntaps, dil), w2 = hc_wrpad(R, ntaps, 1);
-  const int wr = w1 > w2 ? w1 : w2;
-  return ((w1 * 4 + 255) & ~255) + R * 16 + (C / 32) * 2 * wr * 64 + NG * (C / 32) * 16 * 36 * 4;
-}
+template <int C, int NG> inline int hp_lds_bytes(int ntaps, int dil) { return hc_lds_layout<C, NG, true>(ntaps, dil).total; }
 
 template <int N, class F, int... Is>
 __device__ __forceinline__ void hp_for_impl(F&& f, std::integer_sequence<int, Is...>) {
@@ -85,10 +80,7 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
   extern __shared__ __attribute__((aligned(16))) unsigned char hc_lds[];
   constexpr int RT = HC_RT, RG = HC_RG;
   constexpr int NCH = C / 32, CW = C / 32, R = RG * NG, NT = 64 * NG * CW;
-  constexpr int C4 = C / 4;                     // float4 per row
-  constexpr int RPI = NT / C4;                  // window rows staged per pass of the workgroup
   static_assert(R + 56 <= NT, "one window row per thread in the facts pass");
-  constexpr int NWL = 4;
   typedef const __attribute__((address_space(1))) unsigned char* gbytes;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -106,21 +98,15 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
   const int PS2 = WRP2 * 64, CS2 = 2 * PS2;     // ... and of the intermediate's, laid over it
   constexpr int KS1 = k * NCH;                  // 32-deep steps per convolution (even: NCH is)
   constexpr int KS = 2 * KS1;
+  const HcLds L = hc_lds_layout<C, NG, true>(k, p.dil);
   float* const wscale = reinterpret_cast<float*>(hc_lds);                                   // [WRP]: < 0 = the row reads as zero
-  float* const yinv1 = reinterpret_cast<float*>(hc_lds + ((WRP * 4 + 255) & ~255));         // [R]: 1 / scale1 of the intermediate row's utterance
-  float* const ysc2 = yinv1 + R;                                                            // [R]: scale2 of it; < 0 = the row reads as zero
-  int2* const rowinfo = reinterpret_cast<int2*>(ysc2 + R);                                  // [R]: output rows (x = bits of 1 / scale2)
-  unsigned char* const img = reinterpret_cast<unsigned char*>(rowinfo) + R * 8;            // [NCH][2][max(WRP, WRP2)][64 B]
-  const int wrm = WRP > WRP2 ? WRP : WRP2;
-  float* const patch = reinterpret_cast<float*>(img + NCH * 2 * wrm * 64) + wave * (16 * 36);
+  float* const yinv1 = reinterpret_cast<float*>(hc_lds + L.yinv1);                          // [R]: 1 / scale1 of the intermediate row's utterance
+  float* const ysc2 = reinterpret_cast<float*>(hc_lds + L.ysc2);                            // [R]: scale2 of it; < 0 = the row reads as zero
+  int2* const rowinfo = reinterpret_cast<int2*>(hc_lds + L.rowinfo);                        // [R]: output rows (x = bits of 1 / scale2)
+  unsigned char* const img = hc_lds + L.img;                                                // [NCH][2][max(WRP, WRP2)][64 B]
+  float* const patch = reinterpret_cast<float*>(hc_lds + L.patch) + wave * (16 * 36);
 
-  // ---- W: fragment order, [plane][KS][C / 16 blocks][64 lanes][8 halves] (k-step major); this wave's column blocks are 2 cp + nt ----
-  const unsigned short* wp[2][2];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) wp[nt][pl] = p.Wf + (long)pl * p.wf_plane + (long)(2 * cp + nt) * 512 + lane * 8;
-  int wk = 0;
+  // ---- W: this wave's fragment stream of BOTH convolutions through the register buffers; steps 0 .. NB - 1 are requested here ----
   // NB weight buffers: a step's fragments are requested NB steps ahead.  Two (the trunk kernels' double buffer) is 1.5 steps
   // of lookahead at the first wait -- at ONE wave per SIMD and workgroup, as here, less than an L2 round trip (rowblock's
   // staggered schedule measured it: 930 cycles per step for a lone wave against 480 of MFMA issue); this kernel has the 16
@@ -130,46 +116,25 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
 #endif
   constexpr int NB = JV_HP_WBUF;
   static_assert(NB == 2 || NB == 3, "two or three weight buffers");
+  HcWeights<C> w;
+  w.start(p.Wf, p.wf_plane, cp, lane);
   WFragBuf<NB> bq;
   bq.zero();
-  auto load_w = [&](auto par_tag, auto nttag) {
-    constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value;
-    bq.template load<par, nt, 0>(wp[nt][0]);
-    bq.template load<par, nt, 1>(wp[nt][1]);
-  };
-  auto advance_w = [&]() {      // + C / 16 blocks x 1 KB (512 halves) per step; past the end: back to the first step (weights that exist)
-    constexpr long WSTEP = 512L * (C / 16);
-    const long d = ++wk == KS ? WSTEP - WSTEP * KS : WSTEP;
-    if (wk == KS) wk = 0;
+  // the weights start first: everything below is global-load latency they spend in flight.  (A counted loop that the compiler
+  // unrolls, on purpose: as straight-line steps, here or in the walker, the same loads leave hiftpair_kernel<128,2,11> with four
+  // VGPRs more -- profiles/hift_common_isa.md)
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) wp[nt][pl] += d;
-  };
-  // the weights start first: everything below is global-load latency they spend in flight
-  load_w(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-  load_w(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-  advance_w();
-  load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-  load_w(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-  advance_w();
-  if constexpr (NB == 3) {
-    load_w(std::integral_constant<int, NB - 1>{}, std::integral_constant<int, 0>{});
-    load_w(std::integral_constant<int, NB - 1>{}, std::integral_constant<int, 1>{});
-    advance_w();
+  for (int b = 0; b < NB; ++b) {
+    if (b == 0) { w.template load<0, 0>(bq); w.template load<0, 1>(bq); }
+    if (b == 1) { w.template load<1, 0>(bq); w.template load<1, 1>(bq); }
+    if (b == 2) { w.template load<NB - 1, 0>(bq); w.template load<NB - 1, 1>(bq); }
+    w.advance(KS);
   }
 
-  // ---- per-row facts (one level of unconditional loads on clamped indices: rowconv_wd_kernel) ----
-  auto slot_of = [&](const long row) -> int {
-    if (p.slot_map) {      // compact geometry of ragged batches (hift.hip): by table; every caller clamps `row` to the buffer
-      const int q = p.slot_map[row];
-      return q < 0 ? 0 : (q >= p.slot_nb ? p.slot_nb - 1 : q);
-    }
-    if (p.slot_S <= 0) return 0;
-    const int q = (int)((row - p.slot_G) / p.slot_S);
-    return q < 0 ? 0 : (q >= p.slot_nb ? p.slot_nb - 1 : q);
-  };
-  constexpr int RI_TRACK = 1 << 30;
+  // ---- per-row facts (one level of unconditional loads on clamped indices: rowconv_wd_kernel).  Written out in both kernels:
+  // this one has the intermediate's scale and mask ----
+  auto slot_of = [&](const long row) { return hc_slot_of(p, row); };
+  constexpr int RI_TRACK = HC_RI_TRACK;
   {
     // window row tid <-> global row m0 - h2 - h1 + tid; intermediate row tid <-> m0 - h2 + tid; output row tid <-> m0 + tid
     const long ar = (long)m0 - h2 - h1 + tid;
@@ -199,61 +164,8 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
   }
   __syncthreads();
 
-  // ---- the window, once: fp32 rows -> Snake1 -> x scale -> two fp16 planes, chunk-major operand image (hiftconv_kernel) ----
-  {
-    const int c4 = tid % C4, r0 = tid / C4;      // this thread's four channels, its first window row
-    const rg_f32x4 al = *reinterpret_cast<const rg_f32x4*>(p.alpha1 + 4 * c4);
-    rg_f32x4 ai;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ai[e] = 1.0f / (al[e] + 1e-9f);
-    const int chunk = c4 >> 3, cslot = (c4 & 7) >> 1, chalf = (c4 & 1) << 3;
-    const float* const abase = p.A + ((long)m0 - h2 - h1) * C + 4 * c4;
-    constexpr int U = 4;
-    for (int rb = r0; rb < WR; rb += U * RPI) {
-      rg_f32x4 x[U];
-      float sc[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int r = rb + u * RPI;
-        sc[u] = r < WR ? wscale[r] : -1.f;
-        const float* src = sc[u] >= 0.f ? abase + (long)r * C : hc_zero_page;
-        x[u] = *(const __attribute__((address_space(1))) rg_f32x4*)src;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int r = rb + u * RPI;
-        if (r >= WR) continue;
-        rg_f32x4 v = x[u];
-        if (sc[u] >= 0.f) {
-          float arg[4];
-          bool big = false;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            arg[e] = v[e] * al[e];
-            big = big || fabsf(arg[e]) > 32768.f;      // false for NaN, which sin2_small propagates
-          }
-          if (snake_args_small(big)) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] + ai[e] * sin2_small(arg[e]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float sn = sinf(arg[e]);
-              v[e] = v[e] + ai[e] * (sn * sn);
-            }
-          }
-          v = v * sc[u];
-        } else {
-          v = rg_f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        const Split2 s0 = split2h_pair(v[0], v[1]);
-        const Split2 s1 = split2h_pair(v[2], v[3]);
-        unsigned char* d = img + chunk * CS + r * 64 + (((cslot ^ rg_key(r))) << 4) + chalf;
-        *reinterpret_cast<rg_u32x2*>(d) = rg_u32x2{s0.h, s1.h};
-        *reinterpret_cast<rg_u32x2*>(d + PS) = rg_u32x2{s0.l, s1.l};
-      }
-    }
-  }
+  // ---- the window, once: fp32 rows -> Snake1 -> x scale -> two fp16 planes, chunk-major operand image ----
+  hc_stage_window<C, NT>(p.A + ((long)m0 - h2 - h1) * C, WR, (const hc_lds_f32*)wscale, p.alpha1, (hc_lds_u8*)img, CS, PS, tid);
   // per-column constants: this lane's columns in the MFMA layout (the intermediate) and in the row-wise passes (the epilogue)
   float cs1c[2], b1c[2], al2c[2], ai2c[2];
 #pragma unroll
@@ -284,30 +196,8 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
     afrag_read<RT>(af[par], a, ips);
   };
   int nc = 1, nj = 0;      // chunk and tap of the NEXT step
-  // a step multiplies the A fragments of parity `par` (requested by the step before) with the weight buffer `buf` and
-  // refills that buffer for the step NB ahead
   auto step = [&](auto buf_tag, auto par_tag, const bool last) {
-    constexpr int buf = decltype(buf_tag)::value, par = decltype(par_tag)::value;
-    auto block = [&](auto nttag) {
-      constexpr int nt = decltype(nttag)::value;
-#pragma unroll
-      for (int mt = 0; mt < RT; ++mt) {
-        acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[buf][nt][0], bq.q[buf][nt][1]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      load_w(buf_tag, nttag);
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    // this wave's memory operations in program order: ... W0(s+NB-1), W1(s+NB-1) | W0(s+NB), <wait>, W1(s+NB) | ...; needed at the
-    // wait: W0(s+1) and W1(s); behind W0(s+1): W1(s+1) .. W0(s+NB) = 2 (NB - 1) load pairs (rowgemm_wa_kernel's count at NB = 2)
-    block(std::integral_constant<int, 0>{});
-    wait_vmcnt<NWL * (NB - 1)>();
-    bq.template landed_mid<buf>();
-    if (!last) read_a(std::integral_constant<int, par ^ 1>{}, nc, nj);
-    __builtin_amdgcn_sched_barrier(0);
-    block(std::integral_constant<int, 1>{});
-    advance_w();
-    if (++nc == NCH) { nc = 0; ++nj; }
+    hc_step<NCH, decltype(buf_tag)::value, decltype(par_tag)::value>(acc, af, bq, w, KS, nc, nj, last, read_a);
   };
   // product P0 / KS1 (P0 = its first step's number over both products): weight buffer (P0 + i) % NB, A parity i & 1 (KS1 is even)
   auto product = [&](auto p0_tag) {
@@ -341,6 +231,8 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
         const int slot = (2 * nt + (r16 >> 3)) ^ key;
+        // (Snake as in hc_stage_window, hift_common.h, per column and with the masked rows out of the range test; written out: a
+        // shared helper re-shapes this pass's branches, profiles/hift_common_isa.md)
         float g4[4], arg[4];
         bool big = false;
 #pragma unroll
@@ -379,90 +271,9 @@ __global__ __launch_bounds__(64 * NG * (C / 32), 2) void hiftpair_kernel(const H
   ips = PS2; ics = CS2; idil = 1;
   product(std::integral_constant<int, KS1>{});
 
-  // ---- epilogue, per wave (hiftconv_kernel): 16 rows at a time through the wave's private patch; out = ((acc + b2) + x + res2)
-  // * out_scale (+ previous out) for tile rows < RO ----
-  {
-    const int prow = lane >> 3;
-    const float* const r1b = p.A + ncol;
-    const float* const r2b = p.res2 ? p.res2 + ncol : nullptr;
-    float* const ob = p.out + ncol;
-    const int rowb = grp * RG;
-    struct RowIn { rg_f32x4 r1[2], r2[2], pv[2]; float inv[2]; int info[2]; bool ok[2]; };
-    auto request = [&](const int mt, RowIn& in) {      // the two 8-row halves of row tile mt
-#pragma unroll
-      for (int ps = 0; ps < 2; ++ps) {
-        const int trow = rowb + mt * 16 + ps * 8 + prow;
-        const long m = (long)m0 + trow;
-        in.ok[ps] = trow < RO && m < p.M;
-        const long mc = in.ok[ps] ? m : (m < p.M ? m : (long)p.M - 1);
-        const int2 ri = rowinfo[trow];
-        in.inv[ps] = __uint_as_float((unsigned)ri.x);
-        in.info[ps] = ri.y;
-        const rg_f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        in.r1[ps] = *(const __attribute__((address_space(1))) rg_f32x4*)(r1b + mc * C);
-        in.r2[ps] = r2b ? *(const __attribute__((address_space(1))) rg_f32x4*)(r2b + mc * C) : z;
-        in.pv[ps] = p.accumulate ? *(const __attribute__((address_space(1))) rg_f32x4*)(ob + mc * C) : z;
-      }
-    };
-    auto finish = [&](const int mt, const RowIn& in) {
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) patch[(kq * 4 + e) * 36 + nt * 16 + r16] = acc[mt][nt][e];
-      unsigned u = 0u;
-#pragma unroll
-      for (int ps = 0; ps < 2; ++ps) {
-        const int trow = rowb + mt * 16 + ps * 8 + prow;
-        const long m = (long)m0 + trow;
-        rg_f32x4 x = *reinterpret_cast<const rg_f32x4*>(patch + (ps * 8 + prow) * 36 + 4 * (lane & 7));
-        x = x * in.inv[ps];      // 1 / the power of two the row's utterance was staged with
-        rg_f32x4 t = x * cs4 + b4;
-        t = (t + in.r1[ps]) + in.r2[ps];
-        const rg_f32x4 res = t * p.out_scale + in.pv[ps];
-        if (in.ok[ps]) {
-          *(__attribute__((address_space(1))) rg_f32x4*)(ob + m * C) = res;
-          if (in.info[ps] & RI_TRACK) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u = max(u, __float_as_uint(res[e]) & 0x7fffffffu);
-          }
-        }
-      }
-      if (p.amax_out) {
-        // the 16 rows of a tile almost always belong to one utterance: one wave-level maximum, one atomic -- and none once the
-        // slot already holds a larger value (hiftconv_kernel).  Rows of two utterances: per lane.
-        const int s_lo = rowinfo[rowb + mt * 16].y & (RI_TRACK - 1), s_hi = rowinfo[rowb + mt * 16 + 15].y & (RI_TRACK - 1);
-        if (s_lo == s_hi) {
-          const unsigned seen = *(const __attribute__((address_space(1))) unsigned*)(p.amax_out + s_lo);
-          if (__builtin_amdgcn_ballot_w64(u > seen) != 0) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o));
-            if (lane == 0) hc_atomic_max(p.amax_out + s_lo, u);
-          }
-        } else {
-#pragma unroll
-          for (int ps = 0; ps < 2; ++ps) {
-            unsigned v = 0u;
-            const int trow = rowb + mt * 16 + ps * 8 + prow;
-            const long m = (long)m0 + trow;
-            if (in.ok[ps] && (in.info[ps] & RI_TRACK)) {
-              const rg_f32x4 res = *(const __attribute__((address_space(1))) rg_f32x4*)(ob + m * C);      // (this lane's own store)
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v = max(v, __float_as_uint(res[e]) & 0x7fffffffu);
-              hc_atomic_max(p.amax_out + (in.info[ps] & (RI_TRACK - 1)), v);
-            }
-          }
-        }
-      }
-    };
-    RowIn cur, nxt;
-    request(0, cur);
-#pragma unroll
-    for (int mt = 0; mt < RT; ++mt) {
-      if (mt + 1 < RT) request(mt + 1, nxt);      // a tile ahead: its loads travel while this one is finished
-      finish(mt, cur);
-      cur = nxt;
-    }
-  }
+  // ---- epilogue, per wave: out = ((acc + b2) + x + res2) * out_scale (+ previous out) for tile rows < RO (x re-read as res1) ----
+  hc_epilogue<C, true>(HcStore{p.M, p.out, p.A, p.res2, p.out_scale, p.accumulate, p.amax_out}, acc, (hc_lds_f32*)patch,
+                       (const hc_lds_i32x2*)rowinfo, grp * RG, RO, m0, cs4, b4, ncol, lane);
   // the wrapped-around W loads of the last two steps: bq stays reserved until they have landed (WFragBuf, rule c)
   wait_vmcnt<0>();
   bq.landed_all();

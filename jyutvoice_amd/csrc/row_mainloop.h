@@ -2,7 +2,8 @@
 // rowblock_kernel, rowres_kernel, rowconv_wd_kernel, hiftconv_kernel, hiftpair_kernel), in ONE place: the weight-fragment
 // register buffer, the fp16x3 MFMA triple and the A-fragment read.  As in row_tail.h the pieces take and return values or
 // references; addresses, the weight walkers (advance_w, quad_ptrs) and the PLACE of every load, counted wait and barrier stay
-// in the kernels, each of which keeps the order it chose and the derivation of its own wait count.
+// in the kernels, each of which keeps the order it chose and the derivation of its own wait count.  (The vocoder's two,
+// hiftconv_kernel and hiftpair_kernel, were one text twice: their walker and step are shared a level up, in hift_common.h.)
 #pragma once
 #include "row_tail.h"
 

@@ -730,18 +730,23 @@ def op_rowconv(A, W, bias=None, ln=None, act="none", rowmask=None, rowvec=None, 
     return out
 
 
-def op_hiftconv(A, W, bias, alpha, ntaps, dil, rowmask=None, res1=None, res2=None, out_scale=1.0, prev=None, amax_out=None):
+def op_hiftconv(A, W, bias, alpha, ntaps, dil, rowmask=None, res1=None, res2=None, out_scale=1.0, prev=None, amax_out=None,
+                amax_in=None, slots=None):
     """hiftconv_kernel.h: the vocoder's ResBlock convolution on a [rows, C] row buffer (C = 64 / 128 / 256); W [C, ntaps * C]
-    tap-major; prev: accumulate onto this tensor"""
+    tap-major; prev: accumulate onto this tensor.  amax_in: per-utterance bounds of A with slots = (G, S, nb) or an int32 [rows]
+    row -> utterance table (op_hiftpair's); both None: one slot for every row, its bound measured here"""
     lib = _lib.load()
     rows, C = A.shape
     out = prev.clone() if prev is not None else torch.empty(rows, C, device=A.device)
-    masked = A if rowmask is None else A * rowmask[:, None].to(A.dtype)
-    amax_in = torch.nan_to_num(masked).abs().max().reshape(1)
+    if amax_in is None:
+        masked = A if rowmask is None else A * rowmask[:, None].to(A.dtype)
+        amax_in = torch.nan_to_num(masked).abs().max().reshape(1)
+    table = slots if torch.is_tensor(slots) else None
+    G, S, nb = (0, 0, int(amax_in.numel())) if (table is not None or slots is None) else slots
     extra = float((1.0 / (alpha + 1e-9)).max())
     check(lib.jv_op_hiftconv(_ptr(A), rows, C, int(ntaps), int(dil), _ptr(W), _ptr(bias), _ptr(alpha), _ptr(rowmask), _ptr(res1),
-                             _ptr(res2), float(out_scale), 1 if prev is not None else 0, _ptr(amax_in), extra, _ptr(amax_out),
-                             _ptr(out), _stream(A.device)))
+                             _ptr(res2), float(out_scale), 1 if prev is not None else 0, _ptr(amax_in), extra, int(G), int(S), int(nb),
+                             _ptr(table), _ptr(amax_out), _ptr(out), _stream(A.device)))
     return out
 
 

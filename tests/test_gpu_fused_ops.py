@@ -213,6 +213,15 @@ def ref_hiftpair(p, dtype=torch.float64, mut=None):
     return {"out": out + c["prev"]}
 
 
+def ref_hiftconv(p, dtype=torch.float64):
+    """hiftconv_kernel.h: out = ((Conv1d_k,dil(Snake(A mask)) + b) + res1 + res2) out_scale + prev, "same" padding"""
+    c = cast(p, dtype)
+    k, dil = p["k"], p["dil"]
+    a = torch.where(p["mask"][:, None] != 0, c["A"], torch.zeros((), dtype=dtype))
+    y = conv_rows(snake(a, c["alpha1"]), c["W1"], k, -(dil * (k - 1) // 2), dil) + c["b1"]
+    return {"out": ((y + c["res1"]) + c["res2"]) * p["out_scale"] + c["prev"]}
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # inputs that discriminate: LayerNorm gains over [0.5, 2.5] with offsets, biases everywhere, weight rows of very different scale,
 # residual rows over six decades, a time embedding of order 1, Snake alphas down to 0.05, utterances of scale 1e-3 / 1 / 30
@@ -314,11 +323,11 @@ def hift_rows(k):
 
 
 @functools.lru_cache(maxsize=None)
-def hiftpair_inputs(C, k, dil, seed=4):
+def hiftpair_inputs(C, k, dil, seed=4, lead=16):
     """about 2 (160 - (k - 1)) + 37 rows: three workgroups, the last one ragged; three utterances with 32-row gaps and ragged tails"""
     total = hift_rows(k)
-    T = (total - 16) // 3 - 32
-    geo = geometry(lens=(T, T - 13, T - 29), T=T, total=total, lead=16, gap=32)
+    T = (total - lead) // 3 - 32
+    geo = geometry(lens=(T, T - 13, T - 29), T=T, total=total, lead=lead, gap=32)
     M = geo["M"]
     g = _gen(seed + 1000 * C + 10 * k + dil)
     utt_scale = torch.tensor([1e-3, 1.0, 30.0])
@@ -335,10 +344,21 @@ def hiftpair_inputs(C, k, dil, seed=4):
 
 
 @functools.lru_cache(maxsize=None)
+def hiftconv_inputs(C, k, dil, seed=5):
+    """hiftpair_inputs' rows, utterances and first convolution with a first residual, behind 8 leading rows: an utterance's first
+    row is then never a multiple of 16 (the stride is 115 / 112 / 109 rows at k = 3 / 7 / 11; behind 16 rows, k = 3 has 16 + 112 b)"""
+    p = dict(hiftpair_inputs(C, k, dil, seed, lead=8))
+    geo = p["geo"]
+    p["res1"] = torch.randn(geo["M"], C, generator=_gen(seed + 7)) * torch.tensor([1e-3, 1.0, 30.0])[geo["slot"].long()][:, None]
+    return p
+
+
+@functools.lru_cache(maxsize=None)
 def refs(kind, *key):
     """(inputs, fp64 reference, fp32 floor chain) of a case, computed once and shared"""
-    p = {"rowblock": rowblock_inputs, "rowffn": rowffn_inputs, "rowres": rowres_inputs, "hiftpair": hiftpair_inputs}[kind](*key)
-    f = {"rowblock": ref_rowblock, "rowffn": ref_rowffn, "rowres": ref_rowres, "hiftpair": ref_hiftpair}[kind]
+    p = {"rowblock": rowblock_inputs, "rowffn": rowffn_inputs, "rowres": rowres_inputs, "hiftpair": hiftpair_inputs,
+         "hiftconv": hiftconv_inputs}[kind](*key)
+    f = {"rowblock": ref_rowblock, "rowffn": ref_rowffn, "rowres": ref_rowres, "hiftpair": ref_hiftpair, "hiftconv": ref_hiftconv}[kind]
     return p, f(p), f(p, torch.float32)
 
 
@@ -737,3 +757,42 @@ def test_hiftpair_race_screen(dev):
     for i in range(10):
         noise.normal_()
         same_bits(first, run_pair(dev, p), live(p["geo"]), ("out",))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# hiftconv: the utterance slots (one slot: tests/test_gpu_ops.py::test_hiftconv)
+def run_conv(dev, p, table=False, scale_utt=None):
+    """one call of jv_op_hiftconv with both residuals, out_scale = 1/3 and accumulation onto prev; masked rows of A hold NaN"""
+    from jyutvoice_amd.engine import op_hiftconv
+    geo = p["geo"]
+    A, amax = p["A"].clone(), p["amax_in"].clone()
+    if scale_utt is not None:
+        A[utt_rows(geo, scale_utt)] *= 1000.0
+        amax[scale_utt] *= 1000.0
+    w = to_dev(p, dev, ("W1", "b1", "alpha1", "res1", "res2", "prev"))
+    amax_out = torch.zeros(3, device=dev)
+    out = op_hiftconv(dirty(A, geo["mask"]).to(dev), w["W1"], w["b1"], w["alpha1"], p["k"], p["dil"], rowmask=geo["mask"].to(dev),
+                      res1=w["res1"], res2=w["res2"], out_scale=p["out_scale"], prev=w["prev"], amax_out=amax_out, amax_in=amax.to(dev),
+                      slots=geo["slot"].to(dev) if table else (geo["lead"], geo["S"], 3))
+    return {"out": out, "amax_out": amax_out}
+
+
+@pytest.mark.parametrize("C,k,dil", [(256, 3, 1), (256, 11, 5), (128, 7, 3), (64, 11, 1)])
+def test_hiftconv_utterance_slots(dev, C, k, dil):
+    """hiftconv_kernel with per-utterance slots against fp64: three to five workgroups (hift_rows(k) rows, 80 or 160 each), three
+    utterances of scale 1e-3 / 1 / 30 with their own measured bounds through both slot addressings, 16-row tiles that hold rows of
+    two utterances (the per-lane branch of the tracked maximum), both residuals, out_scale = 1/3, accumulation, masked rows
+    holding NaN, the tracked maximum exact per utterance, utterances independent of one another"""
+    p, r64, r32 = refs("hiftconv", C, k, dil)
+    geo = p["geo"]
+    sel, slot = live(geo), geo["slot"]
+    # workgroups and their row tiles start at multiples of 16: a tile straddles when an utterance's first row is no multiple of 16
+    assert all(s % 16 for s in geo["start"][1:])
+    assert sum(1 for t in range(0, geo["M"] - 15, 16) if slot[t] != slot[t + 15]) >= 2
+    got = run_conv(dev, p)
+    hold(f"hiftconv_slots/C{C}/k{k}/d{dil}", got["out"], r64["out"], r32["out"], sel)
+    assert torch.equal(got["amax_out"].cpu(), tracked(got["out"], geo))
+    same_bits(got, run_conv(dev, p, table=True), sel, ("out", "amax_out"))
+    big = run_conv(dev, p, scale_utt=1)
+    same_bits(got, big, sel & (slot != 1), ("out",))
+    assert torch.equal(got["amax_out"][[0, 2]], big["amax_out"][[0, 2]])

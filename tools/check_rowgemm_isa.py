@@ -2,7 +2,7 @@
 """Build-time check of the hand-managed register buffer of the W-direct kernels -- WFragBuf in jyutvoice_amd/csrc/row_mainloop.h,
 which states the rules checked here: rowgemm_wd_kernel, rowgemm_wa_kernel, rowffn_kernel (rowgemm_kernel.h), rowconv_wd_kernel
 (rowconv_kernel.h), rowres_kernel (rowres_kernel.h), rowblock_kernel (rowblock_kernel.h), hiftconv_kernel and hiftpair_kernel
-(hiftconv_kernel.h, hiftpair_kernel.h: the vocoder's 72 ResBlock convolutions).
+(hiftconv_kernel.h, hiftpair_kernel.h over hift_common.h: the vocoder's 72 ResBlock convolutions).
 
 The weight fragments are loaded by inline asm (global_load_dwordx4) and waited for by a counted s_waitcnt the compiler does
 not know about.  That is only sound if, in the generated code, the destination registers of those loads are touched by
