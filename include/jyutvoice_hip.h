@@ -123,12 +123,29 @@ int jv_flow_set_graph(jv_context* ctx, int on);
  * Both meet the same operator-level bound against fp64 (tests/test_gpu_ops.py).  Applies to this context's estimator,
  * solver and vocoder calls. */
 int jv_flow_set_contraction(jv_context* ctx, int exact_range);
+/* jv_flow_set_precision: the estimator as the reference's fp16 TensorRT plan runs it (scripts/export_onnx.py:342-361,
+ * `fp16 = True`; flow_matching.py:267-297).  JV_PRECISION_FP32 (default): every contraction at fp32 accuracy, as
+ * jv_flow_set_contraction describes.  JV_PRECISION_FP16 (or JV_EST_FP16=1 in the environment at jv_create): in an estimator
+ * evaluation (jv_flow_estimator_step / _masked, every jv_cfm_solve* and jv_flow_token2mel*) each contraction that the route
+ * would run fp16x3 issues the hi x hi product alone -- operands rounded to fp16 (11 significant bits) under the same
+ * power-of-two scales, products exact in fp32, fp32 accumulation.  Nothing else changes: scales, bounds, the planes producers
+ * write (both; the lo plane is not multiplied), the fp32 residual stream, epilogues, LayerNorm, softmax, routes, regimes and
+ * launch geometry; the contractions that run bf16x6 (the first resnet's input convolutions, the time MLP, any layer whose
+ * bound is unusable: jv_flow_contraction_info); the encoders, the prompt path and the vocoder.  The invariances of the fp32
+ * mode (batch row = its B = 1 run, compact = padded, streamed prefix = one-shot) hold inside the mode with the same bounds.
+ * A configuration call like jv_flow_set_contraction: it waits for the device and drops captured step graphs.  FP16 together
+ * with exact_range = 1 is a contradiction (bf16x6 has nothing to drop): whichever of the two setters comes second returns
+ * JV_ERR_STATE. */
+#define JV_PRECISION_FP32 0
+#define JV_PRECISION_FP16 1
+int jv_flow_set_precision(jv_context* ctx, int precision);
 /* jv_flow_contraction_info: what the load-time range proofs of the last jv_finalize(JV_MODEL_TTS) concluded for the
  * estimator's 56 transformer blocks (transformer.py:355-443; registry.hip), so that a caller -- or a test with a hostile
  * checkpoint -- can see which layers took the fp16x3 engine and which stayed on bf16x6 because their bound was unusable
  * (non-finite or beyond 1e30).  out[0] = blocks, out[1] = blocks whose four linears AND attention all have a usable bound,
  * out[2] = linears (of 4 per block) with a usable bound, out[3] = blocks whose attention operands (q, k, v) have one.
- * n = number of int32 slots in out (>= 4). */
+ * n = number of int32 slots in out (>= 4); with n >= 5, out[4] = the precision mode (jv_flow_set_precision), which changes none
+ * of the other four. */
 int jv_flow_contraction_info(const jv_context* ctx, int32_t* out, int n);
 /* jv_cfm_solve: CausalConditionalCFM.forward + ConditionalCFM.solve_euler (flow_matching.py:356-401, 215-265):
  * fixed noise prefix * temperature, cosine schedule, n_timesteps Euler steps with CFG rate 0.7.
@@ -448,6 +465,11 @@ int jv_op_attention(const float* qkv, const int32_t* lens, int B, int G, int S, 
 int jv_op_rel_attention(const float* qkv, const float* p, const float* u, const float* v, const int64_t* lens, int B, int T, int G,
                         int S, int len_mul, int chunk, int fused, float* out, void* stream);
 float jv_h3_scale_for_bound(float bound);   /* host only: the power of two chosen for a proven bound (0 = unusable) */
+/* process-wide (the jv_op_* hooks take no context): fp16x3 products per step of the hooks jv_op_linear_h3,
+ * jv_op_conv_h3_measured, jv_op_attention_h3, jv_op_attention_planes, jv_op_rowgemm, jv_op_rowgemm_qkv, jv_op_rowconv, jv_op_rowres
+ * and jv_op_rowblock -- 3 (default), or 1 = the hi x hi product alone, what JV_PRECISION_FP16 selects on a context.  Read by those
+ * hooks and by nothing on the production path. */
+int jv_op_set_products(int np);
 int jv_op_conv_h3_measured(const float* A, int64_t a_rows, int M, int Cin, int ntaps, int tap_row0, int dil, const float* W,
                            int N, const float* bias, int act, int prologue, const float* alpha, float slope,
                            const uint8_t* rowmask, const float* res, const float* amax_in, float a_extra, float* amax_out,

@@ -222,6 +222,8 @@ def token2wav_list(reqs, args, device):
     from jyutvoice_amd.engine import JV_MODEL_TTS
     from jyutvoice_amd.runtime import Runtime, get_runtime
     rt = Runtime(str(device)) if JV_MODEL_TTS in get_runtime(device).sds else None
+    if rt is not None:
+        rt.set_precision(args.estimator_precision)
     if args.synthetic:
         flow = CausalMaskedDiffWithXvec(vocab_size=6561, input_frame_rate=25, device=device, runtime=rt)
         sd = synth.prompt_state_dict()
@@ -412,6 +414,9 @@ def main(argv=None):
                    help="--token2wav --stream-hop K: serve the list through one Token2WavServer, S sessions at a time")
     p.add_argument("--synthetic", type=int, default=0, help="use N synthetic tokens and synthetic weights")
     p.add_argument("--synthetic-prompt", type=int, default=0, help="with --synthetic: K synthetic prompt tokens (voice-cloning path)")
+    p.add_argument("--estimator-precision", default="fp32", choices=["fp32", "fp16"],
+                   help="fp16: the CFM estimator as the reference's fp16 TensorRT plan runs it (fp16 operands, fp32 accumulation); "
+                        "encoders and vocoder unchanged (every route: ids, --token2wav, streaming, server)")
     p.add_argument("--seed", type=int, default=0, help="seed of the vocoder's source-noise draws")
     p.add_argument("--sample_rate", type=int, default=24000, help="sample rate of the written audio (resampled on the GPU)")
     p.add_argument("--dump-ref-features", default=None, metavar="DIR",
@@ -433,6 +438,8 @@ def main(argv=None):
         raise SystemExit("no AMD GPU visible: jyutvoice_amd has no CPU path")
     device = torch.device("cuda:0")
     print(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
+    from jyutvoice_amd.runtime import get_runtime
+    get_runtime(device).set_precision(args.estimator_precision)      # every route below runs on this runtime's context
     if args.token2wav:
         return token2wav_list(json.load(open(args.token2wav)), args, device)
     tts, hift = jyutvoice_amd.build_default(device)

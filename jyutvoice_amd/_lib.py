@@ -17,6 +17,9 @@ JV_MODEL_HIFT = 1
 JV_MODEL_PROMPT = 2
 JV_MODEL_FLOW = 3      # the decoder.* / spk_embed_affine_layer.* part of JV_MODEL_TTS (jv_finalize only)
 
+JV_PRECISION_FP32 = 0
+JV_PRECISION_FP16 = 1     # jv_flow_set_precision: the estimator's fp16x3 contractions issue the hi x hi product alone
+
 ACT = {"none": 0, "relu": 1, "gelu": 2, "mish": 3, "elu": 4, "silu": 5}
 PRO = {"none": 0, "snake": 1, "lrelu": 2}
 
@@ -53,6 +56,7 @@ SIGNATURES = {
     "jv_flow_set_streaming": (_i, [_p, _i]),
     "jv_flow_set_graph": (_i, [_p, _i]),
     "jv_flow_set_contraction": (_i, [_p, _i]),
+    "jv_flow_set_precision": (_i, [_p, _i]),
     "jv_flow_contraction_info": (_i, [_p, _p, _i]),
     "jv_cfm_solve": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p]),
     "jv_cfm_solve_prompted": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p]),
@@ -94,6 +98,7 @@ SIGNATURES = {
     "jv_op_attention": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "jv_op_rel_attention": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "jv_h3_scale_for_bound": (_f, [_f]),
+    "jv_op_set_products": (_i, [_i]),
     "jv_op_conv_h3_measured": (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _p, _p, _p, _f, _p, _p, _p]),
     "jv_op_attention_h3": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _f, _p, _p]),
     "jv_op_linear_h3": (_i, [_p, _i64, _i, _i, _p, _i, _p, _i, _p, _f, _i, _p, _p]),

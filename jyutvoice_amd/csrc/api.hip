@@ -167,6 +167,11 @@ int jv_create(jv_context** out, int device, int max_batch, int max_frames, int m
   c.max_batch = max_batch;
   c.step_graphs = getenv("JV_STEP_GRAPH") != nullptr;
   c.exact_range = getenv("JV_EXACT_RANGE") != nullptr;
+  c.est_fp16 = getenv("JV_EST_FP16") != nullptr;
+  if (c.est_fp16 && c.exact_range) {
+    delete ctx;
+    return jv::fail(JV_ERR_STATE, "jv_create: JV_EST_FP16 (one fp16 product) and JV_EXACT_RANGE (bf16x6 everywhere) contradict each other");
+  }
   c.dma_a = getenv("JV_DMA_A") != nullptr;
   c.no_rowgemm = getenv("JV_NO_ROWGEMM") != nullptr;
   c.no_ffn_fuse = getenv("JV_NO_FFN_FUSE") != nullptr;
@@ -342,6 +347,9 @@ int jv_flow_set_graph(jv_context* ctx, int on) {
 // any stream, graph replays) before it touches the workspace, so nothing in flight sees half of each mode.
 int jv_flow_set_contraction(jv_context* ctx, int exact_range) {
   CTX_GUARD(ctx);
+  if (exact_range != 0 && ctx->c.est_fp16)
+    return jv::fail(JV_ERR_STATE, "jv_flow_set_contraction: exact_range = 1 (bf16x6 everywhere) contradicts JV_PRECISION_FP16 "
+                                  "(jv_flow_set_precision), which has nothing to drop from bf16x6; set the precision back first");
   if (ctx->c.exact_range != (exact_range != 0)) {
     JV_HIP(hipDeviceSynchronize());
     jv::flow_graphs_drop(ctx->c);                  // captured steps hold the old kernels
@@ -349,6 +357,23 @@ int jv_flow_set_contraction(jv_context* ctx, int exact_range) {
     JV_HIP(hipDeviceSynchronize());
   }
   ctx->c.exact_range = exact_range != 0;
+  return JV_OK;
+}
+
+// (the planes keep their layout in both precisions: the attention buffer need not be forgotten)
+int jv_flow_set_precision(jv_context* ctx, int precision) {
+  CTX_GUARD(ctx);
+  if (precision != JV_PRECISION_FP32 && precision != JV_PRECISION_FP16)
+    return jv::fail(JV_ERR_ARG, "jv_flow_set_precision: JV_PRECISION_FP32 or JV_PRECISION_FP16");
+  const bool fp16 = precision == JV_PRECISION_FP16;
+  if (fp16 && ctx->c.exact_range)
+    return jv::fail(JV_ERR_STATE, "jv_flow_set_precision: JV_PRECISION_FP16 contradicts exact_range = 1 (jv_flow_set_contraction: bf16x6 "
+                                  "everywhere has no product to drop); set the contraction back first");
+  if (ctx->c.est_fp16 != fp16) {
+    JV_HIP(hipDeviceSynchronize());
+    jv::flow_graphs_drop(ctx->c);      // captured steps hold the other mode's kernels
+  }
+  ctx->c.est_fp16 = fp16;
   return JV_OK;
 }
 
@@ -362,6 +387,7 @@ int jv_flow_contraction_info(const jv_context* ctx, int32_t* out, int n) {
       ++blocks; lin += b.lin_h3; att += b.attn_h3; all += b.rows_ok;
     }
   out[0] = blocks; out[1] = all; out[2] = lin; out[3] = att;
+  if (n >= 5) out[4] = ctx->c.est_fp16 ? JV_PRECISION_FP16 : JV_PRECISION_FP32;
   return JV_OK;
 }
 
@@ -411,6 +437,14 @@ int jv_op_conv_gemm(const float* A, int64_t a_rows, int M, int Cin, int ntaps, i
   return jv::conv_gemm(a, 1, static_cast<hipStream_t>(stream));
 }
 
+// products per fp16x3 step of the operator hooks below (jv_op_set_products): process-wide, never read by a context's calls
+static int g_op_products = 3;
+int jv_op_set_products(int np) {
+  if (np != 1 && np != 3) return jv::fail(JV_ERR_ARG, "jv_op_set_products: 3 (fp16x3) or 1 (the hi x hi product alone)");
+  g_op_products = np;
+  return JV_OK;
+}
+
 // host logic of the fp16x3 scale choice (no device work): largest power of two s with bound * s <= 60000, 0 = unusable
 float jv_h3_scale_for_bound(float bound) { return jv::h3_scale_for_bound(bound); }
 
@@ -446,6 +480,7 @@ int jv_op_linear_h3(const float* A, int64_t rows, int M, int K, const float* W, 
     if (presplit == 1) JV_TRY(jv::split2h_rows(A, K, ap, (long)an, rows, K, sc, st));
     a.A2 = ap; a.a2_plane = (long)an; a.lda2 = K;
   }
+  a.np = g_op_products;
   return jv::conv_gemm(a, 1, st);
 }
 
@@ -564,6 +599,7 @@ int jv_op_conv_h3_measured(const float* A, int64_t a_rows, int M, int Cin, int n
     JV_TRY(jv::split3_planes(W, planes3, (long)n, st));
     a.W3 = planes3; a.w3_plane = (long)n;
   }
+  a.np = g_op_products;
   return jv::conv_gemm(a, 1, st);
 }
 
@@ -577,6 +613,7 @@ int jv_op_attention_h3(const float* qkv, const int32_t* lens, int B, int G, int 
   at.k_scale = jv::h3_scale_for_bound(k_bound);
   at.v_scale = jv::h3_scale_for_bound(v_bound);
   if (!(at.q_scale > 0.f && at.k_scale > 0.f && at.v_scale > 0.f)) return jv::fail(JV_ERR_ARG, "jv_op_attention_h3: unusable bound");
+  at.np = g_op_products;
   return jv::attention64(at, static_cast<hipStream_t>(stream));
 }
 
@@ -612,6 +649,7 @@ int jv_op_rowgemm(const float* A, int64_t rows, int M, int K, const float* W, in
   a.out2_scale = out2_scale;
   a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = 1e-5f;
   a.amax_out = amax_out;
+  a.np = g_op_products;
   return jv::rowgemm(a, epi, st);
 }
 
@@ -646,6 +684,7 @@ int jv_op_rowgemm_qkv(const float* A, const uint16_t* A2, int64_t rows, int M, i
   a.nsplit = nsplit; a.rt = rt;
   a.out = q; a.ldo = 512;
   a.out2 = kv2; a.out2_plane = (long)rows * 1024; a.ldo2 = 1024; a.out2_scale = ks; a.out2_scale2 = vs;
+  a.np = g_op_products;
   return jv::rowgemm(a, jv::RG_QKV, st);
 }
 
@@ -704,6 +743,7 @@ int jv_op_rowres(const float* x, int64_t rows, int M, int Cin, const uint8_t* ro
   } else if (Wq || lnf_out) {
     return jv::fail(JV_ERR_ARG, "jv_op_rowres: the following block's planes and q | k | v need its LayerNorm1");
   }
+  a.np = g_op_products;
   return jv::rowres(a, st);
 }
 
@@ -805,12 +845,14 @@ int jv_op_rowblock(const float* att, float* h, int64_t rows, int M, int mode, in
     a.W2 = m.planes; a.w2_plane = m.n(); a.ldw = K; a.colscale = m.cs; a.a_scale = a_scale;
     a.Wf = m.wf; a.wf_plane = m.n();
     a.bias = bias; a.ln_eps = 1e-5f; a.out2_scale = 1.f;
+    a.np = g_op_products;
     return a;
   };
   // the feed-forward (+ the next LayerNorm1) from the LayerNorm3 planes `xin`, as one launch or two (estimator.hip: block_rows)
   auto feed_forward = [&](const unsigned short* xin, unsigned short* ln_dst) -> int {
     if (fused >= 0) {
       jv::RowFfnArgs f{};
+      f.np = g_op_products;
       f.A2 = xin; f.a2_plane = R * 256; f.a_rows = rows; f.lda2 = 256; f.M = M;
       f.W1f = w1.wf; f.w1f_plane = w1.n(); f.cs1 = w1.cs; f.b1 = b1; f.a_scale1 = sc_1;
       f.h_scale = sc_h;
@@ -841,6 +883,7 @@ int jv_op_rowblock(const float* att, float* h, int64_t rows, int M, int mode, in
 
   if (fused == 1) {
     jv::RowBlockArgs f{};
+    f.np = g_op_products;
     f.A2 = ap; f.a2_plane = R * 512; f.a_rows = rows; f.M = M;
     f.Wof = wo.wf; f.wof_plane = wo.n(); f.cso = wo.cs; f.bo = bo; f.a_scale_o = sc_o;
     f.h = h; f.ln3_g = ln3_g; f.ln3_b = ln3_b;
@@ -901,6 +944,7 @@ int jv_op_rowconv(const float* A, int64_t rows, int M, int Cin, const float* W, 
   if (ln_g) { a.ln = 1; a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = 1e-5f; }
   a.act = act; a.rowmask_out = rowmask; a.rowvec = rowvec; a.rowvec_ld = N; a.res = res; a.ldr = N;
   a.amax_out = amax_out; a.row_mask = rowmask;
+  a.np = g_op_products;
   return jv::rowconv(a, st);
 }
 
@@ -954,6 +998,9 @@ int jv_op_attention_planes(const float* qkv, int64_t rows, const int32_t* lens, 
   JV_TRY(jv::split2h_rows(qkv + 1024, 1536, kv + 512, plane, rows, 512, at.v_scale, st, 1024));
   at.kv2 = kv; at.kv2_plane = plane; at.kv_ld = 1024;
   if (out2) { at.out2 = out2; at.out2_plane = (long)rows * 512; at.out2_scale = out2_scale; }
+  at.np = g_op_products;
+  if (at.np == 1 && chunk == 0 && (jv::dyn_env("JV_OP_ATTN_ROWS") || jv::dyn_env("JV_OP_ATTN_SINGLE")))
+    return jv::fail(JV_ERR_STATE, "jv_op_attention_planes: attention_r / attention_s have no one-product form");
   if (chunk == 0 && jv::dyn_env("JV_OP_ATTN_ROWS")) return jv::attention64_rows(at, st);      // the row-owning form (attention_r.hip)
   if (chunk == 0 && jv::dyn_env("JV_OP_ATTN_SINGLE")) return jv::attention64_single(at, st);  // one wave per SIMD (attention_s.hip)
   return jv::attention64_planes(at, st);

@@ -168,11 +168,12 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int XV_PLANE = 64 * 64;
 __device__ __forceinline__ int xv_swz(int row) { return (row >> 2) & 3; }
 
-// NP = 3: six bf16 products of (h, m, l) planes; NP = 2: three fp16 products of (h, l) planes (conv_gemm_x6.hip)
-template <int NP>
+// NP = 3: six bf16 products of (h, m, l) planes; NP = 2: three fp16 products of (h, l) planes (conv_gemm_x6.hip), or -- HP = 1,
+// AttnArgs::np -- the h h' product alone
+template <int NP, int HP = 3>
 __device__ __forceinline__ f32x16 mfma_planes(const u32x4 (&a)[NP], const u32x4 (&b)[NP], f32x16 c) {
   if constexpr (NP == 2) {
-    return h3_mma32(a, b, c);
+    return h3_mma32<HP>(a, b, c);
   } else {
     auto mm = [&](const u32x4& x, const u32x4& y) {
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, y), c, 0, 0, 0);
@@ -202,7 +203,7 @@ __device__ __forceinline__ void split_pair(const float x0, const float x1, unsig
 // NP = 2 (fp16x3): q, k, v are multiplied by the exact powers of two p.q_scale, p.k_scale, p.v_scale, which the caller
 // chose from PROVEN bounds so that nothing reaches fp16's 65504; the scores are scaled back inside the exp2 argument, the
 // probabilities are kept as p * 2^10 (<= 1024; the factor cancels in the normalisation), and v_scale leaves with 1 / l.
-template <int NW, int WPE, int NP>
+template <int NW, int WPE, int NP, int HP = 3>
 __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs p) {
   constexpr int XK_TILE = NP * KV_PLANE, XV_TILE = NP * XV_PLANE;
   // Two buffers per operand, one barrier per key tile: tile kt + 1 is split and stored into the other buffer while tile kt
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs 
       const int ko = ((2 * st + half) ^ kv_k_swz(r32)) << 4;
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl) a[pl] = *reinterpret_cast<const u32x4*>(kr + pl * KV_PLANE + ko);
-      if (!JV_ABLATE(p, 16)) s = mfma_planes<NP>(a, q[st], s);
+      if (!JV_ABLATE(p, 16)) s = mfma_planes<NP, HP>(a, q[st], s);
       else s[st] += __uint_as_float(a[0][0] ^ a[1][1]);
     }
     if (!JV_ABLATE(p, 32)) {
@@ -414,11 +415,11 @@ __global__ __launch_bounds__(64 * NW, WPE) void attn64_x6_kernel(const AttnArgs 
       const int vo = ((2 * st + half) ^ xv_swz(r32)) << 4;       // rows r32 and r32 + 32 share the key
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl) a[pl] = *reinterpret_cast<const u32x4*>(vr + pl * XV_PLANE + vo);
-      if (!JV_ABLATE(p, 8)) o0 = mfma_planes<NP>(a, pb, o0);
+      if (!JV_ABLATE(p, 8)) o0 = mfma_planes<NP, HP>(a, pb, o0);
       else o0[st] += __uint_as_float(a[0][0] ^ a[1][1] ^ pb[0][0] ^ pb[1][1]);
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl) a[pl] = *reinterpret_cast<const u32x4*>(vr + (pl * 64 + 32) * 64 + vo);
-      if (!JV_ABLATE(p, 8)) o1 = mfma_planes<NP>(a, pb, o1);
+      if (!JV_ABLATE(p, 8)) o1 = mfma_planes<NP, HP>(a, pb, o1);
       else o1[st] += __uint_as_float(a[0][0] ^ a[1][1]);
     }
     }
@@ -462,7 +463,8 @@ namespace {
 template <int NW>
 void launch_x6(const AttnArgs& a, hipStream_t st) {
   const dim3 grid(cdiv(a.L, 32 * NW) * a.H * a.B);
-  if (a.q_scale > 0.f) hipLaunchKernelGGL((attn64_x6_kernel<NW, (NW == 2 ? 2 : 3), 2>), grid, dim3(64 * NW), 0, st, a);
+  if (a.q_scale > 0.f && a.np == 1) hipLaunchKernelGGL((attn64_x6_kernel<NW, (NW == 2 ? 2 : 3), 2, 1>), grid, dim3(64 * NW), 0, st, a);
+  else if (a.q_scale > 0.f) hipLaunchKernelGGL((attn64_x6_kernel<NW, (NW == 2 ? 2 : 3), 2>), grid, dim3(64 * NW), 0, st, a);
   else hipLaunchKernelGGL((attn64_x6_kernel<NW, (NW == 2 ? 2 : 3), 3>), grid, dim3(64 * NW), 0, st, a);
 }
 
@@ -499,7 +501,8 @@ int attention64(const AttnArgs& a, hipStream_t st) {
     static const char* const names[9] = {"", "", "attn64_x6<2 waves>", "attn64_x6<3 waves>", "attn64_x6<4 waves>", "attn64_x6<5 waves>",
                                          "attn64_x6<6 waves>", "attn64_x6<7 waves>", "attn64_x6<8 waves>"};
     static const char* const names_h3[9] = {"", "", "attn64_h3<2 waves>", "", "attn64_h3<4 waves>", "", "", "", "attn64_h3<8 waves>"};
-    name = a.q_scale > 0.f ? names_h3[nw] : names[nw];
+    static const char* const names_h1[9] = {"", "", "attn64_h3<2 waves,np1>", "", "attn64_h3<4 waves,np1>", "", "", "", "attn64_h3<8 waves,np1>"};
+    name = a.q_scale > 0.f ? (a.np == 1 ? names_h1 : names_h3)[nw] : names[nw];
   }
   if (prof) {
     // algorithmic (full-length) figure of SURVEY.md 8(d): QK^T + PV = 4*L*L*64 per head; q,k,v,o once

@@ -75,13 +75,17 @@ __device__ __forceinline__ float q_sum(float v) {
 }
 
 // ---- fp16x3 on v_mfma_f32_32x32x16_f16: c + (a_hi + a_lo)(b_hi + b_lo) without the lo lo term, smallest terms first (the
-// 16x16x32 twin is h3_mma of row_mainloop.h) ----
+// 16x16x32 twin is h3_mma of row_mainloop.h); NP = 1: the hi hi product alone (the estimator's FP16 mode) ----
+template <int NP = 3>
 __device__ __forceinline__ f32x16 h3_mma32(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x16 c) {
   auto mm = [&](const u32x4& x, const u32x4& y) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, x), __builtin_bit_cast(f16x8, y), c, 0, 0, 0);
   };
-  mm(a[1], b[0]);
-  mm(a[0], b[1]);
+  static_assert(NP == 3 || NP == 1, "three products or the hi hi product alone");
+  if constexpr (NP == 3) {
+    mm(a[1], b[0]);
+    mm(a[0], b[1]);
+  }
   mm(a[0], b[0]);
   return c;
 }

@@ -25,7 +25,7 @@ namespace {
 
 constexpr int PL_NSTAGE = 3;
 
-template <int NW, int NST>
+template <int NW, int NST, int NP = 3>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : (NST == 2 ? 4 : 3)) void attn64_pl_kernel(const AttnArgs p) {
   // the ring, reused at the end for the [2 planes][32 NW queries][128 B] output image
   constexpr int LDS_BYTES = NST * KV_STAGE > 2 * 32 * NW * 128 ? NST * KV_STAGE : 2 * 32 * NW * 128;
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : (NST == 2 ? 4 : 3)) void att
       const int ko = ((2 * st + half) ^ kv_k_swz(r32)) << 4;
 #pragma unroll
       for (int pl = 0; pl < 2; ++pl) a[pl] = *reinterpret_cast<const u32x4*>(sK + pl * KV_PLANE + k_off + ko);
-      s = h3_mma32(a, q[st], s);
+      s = h3_mma32<NP>(a, q[st], s);
     }
     if (__builtin_amdgcn_ballot_w64(k0 + 32 > kend) != 0) {      // wave-uniform: only tiles that straddle a mask edge
 #pragma unroll
@@ -181,8 +181,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : (NST == 2 ? 4 : 3)) void att
             a[pl][2 * rd + 1] = u[1];
           }
         }
-        if (db == 0) o0 = h3_mma32(a, pb, o0);
-        else o1 = h3_mma32(a, pb, o1);
+        if (db == 0) o0 = h3_mma32<NP>(a, pb, o0);
+        else o1 = h3_mma32<NP>(a, pb, o1);
       }
     }
   }
@@ -232,7 +232,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : (NST == 2 ? 4 : 3)) void att
 
 template <int NW, int NST = PL_NSTAGE>
 void launch_pl(const AttnArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((attn64_pl_kernel<NW, NST>), dim3(cdiv(a.L, 32 * NW) * a.H * a.B), dim3(64 * NW), 0, st, a);
+  const dim3 grid(cdiv(a.L, 32 * NW) * a.H * a.B);
+  if (a.np == 1) hipLaunchKernelGGL((attn64_pl_kernel<NW, NST, 1>), grid, dim3(64 * NW), 0, st, a);
+  else hipLaunchKernelGGL((attn64_pl_kernel<NW, NST>), grid, dim3(64 * NW), 0, st, a);
 }
 
 }  // namespace
@@ -246,7 +248,8 @@ int attention64_planes(const AttnArgs& a, hipStream_t st) {
   if (const char* f = dyn_env("JV_ATTN_NW")) nw = atoi(f);
   if (nw != 2 && nw != 4) nw = 8;
   static const char* const names[9] = {"", "", "attn64_pl<2 waves>", "", "attn64_pl<4 waves>", "", "", "", "attn64_pl<8 waves>"};
-  return attn_bracket(a, st, names[nw], [&] {
+  static const char* const names1[9] = {"", "", "attn64_pl<2 waves,np1>", "", "attn64_pl<4 waves,np1>", "", "", "", "attn64_pl<8 waves,np1>"};
+  return attn_bracket(a, st, (a.np == 1 ? names1 : names)[nw], [&] {
     if (nw == 2) launch_pl<2>(a, st);
     // two stages (32 KB, <= 128 VGPRs): four workgroups per CU instead of three -- the fourth hides more of the others'
     // barriers and softmax chains than the third stage hid of the DMA latency (175.1 -> 171.7 ms per pass, same box)

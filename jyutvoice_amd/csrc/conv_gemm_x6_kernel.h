@@ -66,7 +66,9 @@ __device__ __forceinline__ void split3x8(const float (&x)[8], u32x4& h, u32x4& m
 // NP: planes per operand.  3: bf16 (h, m, l), six products, any fp32 operand.  2: fp16 (h, l) of A * a_scale and of the
 // per-row scaled W (p.W2), three products h h' + h l' + l h' (dropped: l l', relative 2^-22) -- half the matrix-pipe,
 // LDS and DMA work for operands whose range a load-time bound has proven (ConvGemmArgs::W2).
-template <int BM, int BN, int WM, int WN, int PRO, int EPI, int NA2, int NWB, int NP>
+// HP (NP = 2 only): products per step of the fp16 planes.  3: fp16x3 as above.  1: h h' alone (ConvGemmArgs::np, the estimator's
+// FP16 mode) -- every load, store, DMA and barrier as at 3: the l planes are staged and not multiplied.
+template <int BM, int BN, int WM, int WN, int PRO, int EPI, int NA2, int NWB, int NP, int HP = 3>
 __global__ __launch_bounds__(256, (BM == 64 && BN == 64 && PRO == PRO_NONE && EPI != 4) ? 5 : 2) void conv_gemm_x6_kernel(const ConvGemmArgs p, const int tiles_n) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int MT = WM / 32, NT = WN / 32;
@@ -84,6 +86,7 @@ __global__ __launch_bounds__(256, (BM == 64 && BN == 64 && PRO == PRO_NONE && EP
   constexpr bool APL = NA2 == 3;                 // A arrives as fp16 planes (p.A2) by LDS-DMA, double-buffered like W
   static_assert(!APL || (NP == 2 && NWB == 2 && PRO == PRO_NONE), "pre-split A: fp16x3, two buffers, plain prologue");
   static_assert(NP == 2 || NP == 3, "two fp16 or three bf16 planes");
+  static_assert(HP == 3 || (HP == 1 && NP == 2), "one product: fp16 planes only");
   constexpr int NR = (AQ || APL) ? 1 : NA2, NG = AQ ? 1 : 2;
   const int arow = AQ ? tid >> 2 : tid >> 1, kpart = AQ ? tid & 3 : tid & 1;
   const int koff = (AQ ? 8 : 16) * kpart;
@@ -303,8 +306,10 @@ __global__ __launch_bounds__(256, (BM == 64 && BN == 64 && PRO == PRO_NONE && EP
             auto mm = [&](const u32x4& x, const u32x4& y) {
               t = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, x), __builtin_bit_cast(f16x8, y), t, 0, 0, 0);
             };
-            mm(a[mt][1], b[nt][0]);      // smallest terms first
-            mm(a[mt][0], b[nt][1]);
+            if constexpr (HP == 3) {
+              mm(a[mt][1], b[nt][0]);      // smallest terms first
+              mm(a[mt][0], b[nt][1]);
+            }
             mm(a[mt][0], b[nt][0]);
           } else {
             auto mm = [&](const u32x4& x, const u32x4& y) {
@@ -335,13 +340,13 @@ size_t x6_lds_bytes(const ConvGemmArgs& a, int nwb = 1) {
   return (size_t)(a.W2 ? 2 : 3) * ((a.A2 ? 2 : 1) * win + nwb * BN) * ROWB;
 }
 
-template <int BM, int BN, int WM, int WN, int PRO, int EPI, int NA2, int NWB, int NP>
+template <int BM, int BN, int WM, int WN, int PRO, int EPI, int NA2, int NWB, int NP, int HP = 3>
 int x6_launch4(const ConvGemmArgs& a_in, hipStream_t st) {
   static bool raised[64] = {};      // per device: the attribute belongs to the kernel's image on the current device
   int dev = 0;
   JV_HIP(hipGetDevice(&dev));
   if (!raised[dev & 63]) {
-    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_x6_kernel<BM, BN, WM, WN, PRO, EPI, NA2, NWB, NP>),
+    JV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_x6_kernel<BM, BN, WM, WN, PRO, EPI, NA2, NWB, NP, HP>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     raised[dev & 63] = true;
   }
@@ -364,7 +369,7 @@ int x6_launch4(const ConvGemmArgs& a_in, hipStream_t st) {
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, st);
-    hipLaunchKernelGGL((conv_gemm_x6_kernel<BM, BN, WM, WN, PRO, EPI, NA2, NWB, NP>), dim3(nwg, a.ksplit > 1 ? a.ksplit : 1), dim3(256), lds, st, b, tiles_n);      // (the splits of a tile share its stamp slot: the last writer's)
+    hipLaunchKernelGGL((conv_gemm_x6_kernel<BM, BN, WM, WN, PRO, EPI, NA2, NWB, NP, HP>), dim3(nwg, a.ksplit > 1 ? a.ksplit : 1), dim3(256), lds, st, b, tiles_n);      // (the splits of a tile share its stamp slot: the last writer's)
     (void)hipEventRecord(e1, st);
     (void)hipStreamSynchronize(st);
     float ms = 0.f;
@@ -387,13 +392,13 @@ int x6_launch4(const ConvGemmArgs& a_in, hipStream_t st) {
     }
     return JV_OK;
   }
-  hipLaunchKernelGGL((conv_gemm_x6_kernel<BM, BN, WM, WN, PRO, EPI, NA2, NWB, NP>), dim3(tiles_m * tiles_n, a.ksplit > 1 ? a.ksplit : 1),
+  hipLaunchKernelGGL((conv_gemm_x6_kernel<BM, BN, WM, WN, PRO, EPI, NA2, NWB, NP, HP>), dim3(tiles_m * tiles_n, a.ksplit > 1 ? a.ksplit : 1),
                      dim3(256), lds, st, a, tiles_n);
   if (prof) {
     static const std::string name = std::string(NP == 2 ? "conv_gemm_h3<" : "conv_gemm_x6<") + std::to_string(BM) + "x" + std::to_string(BN) +
                                     (PRO == PRO_SNAKE ? ",snake" : PRO == PRO_LRELU ? ",lrelu" : "") +
                                     (NA2 == 3 ? ",dmaA" : "") +
-                                    ((EPI & 7) == 1 ? ",gelu" : EPI == 2 ? ",res" : EPI == 4 ? ",generic" : "") + ">";
+                                    ((EPI & 7) == 1 ? ",gelu" : EPI == 2 ? ",res" : EPI == 4 ? ",generic" : "") + (HP == 1 ? ",np1" : "") + ">";
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     const double k = (double)(a.alg_k > 0 ? a.alg_k : a.ntaps * a.Cin);
     const double bytes = 4.0 * (rows * a.Cin + (double)a.N * k + rows * a.N * (1 + (a.res1 ? 1 : 0) + (a.res2 ? 1 : 0)));
@@ -403,8 +408,12 @@ int x6_launch4(const ConvGemmArgs& a_in, hipStream_t st) {
   return JV_OK;
 }
 
+// (the one-product form exists where the estimator launches: plain prologue)
 template <int BM, int BN, int WM, int WN, int PRO, int EPI, int NA2, int NWB>
 int x6_launch3(const ConvGemmArgs& a, hipStream_t st) {
+  if constexpr (PRO == PRO_NONE) {
+    if (a.W2 && a.np == 1) return x6_launch4<BM, BN, WM, WN, PRO, EPI, NA2, NWB, 2, 1>(a, st);
+  }
   if (a.W2) return x6_launch4<BM, BN, WM, WN, PRO, EPI, NA2, NWB, 2>(a, st);
   return x6_launch4<BM, BN, WM, WN, PRO, EPI, NA2, NWB, 3>(a, st);
 }
@@ -415,6 +424,7 @@ int x6_launch3(const ConvGemmArgs& a, hipStream_t st) {
 template <int BM, int BN, int WM, int WN, int PRO, int EPI>
 int x6_launch2(const ConvGemmArgs& a, hipStream_t st) {
   if constexpr (PRO == PRO_NONE) {
+    if (a.A2 && a.np == 1) return x6_launch4<BM, BN, WM, WN, PRO, EPI, 3, 2, 2, 1>(a, st);
     if (a.A2) return x6_launch4<BM, BN, WM, WN, PRO, EPI, 3, 2, 2>(a, st);      // conv_gemm_x6() checked the preconditions
   }
   const int win = BM + (a.ntaps - 1) * a.tap_dil;

@@ -20,6 +20,10 @@ EstRoute est_route(const Context& c, long M, bool temb_pre, bool compact, int at
   EstRoute r;
   const int tile = rowgemm_tile((int)M);
   r.exact = c.exact_range; r.compact = compact; r.attn_chunk = attn_chunk;
+  // FP16 mode (jv_flow_set_precision; never together with exact_range): one product per fp16x3 step, and every plane-fed
+  // attention on attn64_pl -- attn64_s has no one-product slot sequence (DESIGN.md 5 "FP16 mode")
+  r.np = c.est_fp16 && !c.exact_range ? 1 : 3;
+  r.attn_single = r.np == 3;
   // the row-owning kernels (rowgemm_kernel.h, rowconv_kernel.h: LayerNorm / Mish / mask / time embedding / residual in the
   // epilogue, no stand-alone row-wise pass) when the batch fills the chip, else the tile kernels
   r.rows = !c.exact_range && !c.no_rowgemm && tile > 0;
@@ -116,6 +120,8 @@ struct Est {
   Context& c; FlowWs& w; const EstimatorW& e;
   const Geo& g; const EstRoute& rt; hipStream_t st;
   const long R = w.rows_alloc;          // rows of every workspace buffer (plane stride of the fp16 images kept in them)
+  // every launcher of a call takes the route's product count in its argument record (`np`: read only where the launch runs fp16x3)
+  int conv(ConvGemmArgs& a) { a.np = rt.np; return conv_gemm(a, 1, st); }
   float* const skip = w.cat + 256;      // columns [256,512) of the concat buffer
 
   // ---- trunk convolutions: fp16x3 from the measured bound of the trunk buffers (not for A = xin, which assemble_xin writes)
@@ -153,7 +159,7 @@ struct Est {
     p.res1 = nullptr; p.amax_out = nullptr;
     p.out = w.partial; p.ldo = 256;
     p.ksplit = std::min(rt.ksplit, a.Cin >> 5); p.split_stride = (long)a.M * 256;
-    JV_TRY(conv_gemm(p, 1, st));
+    JV_TRY(conv(p));
     SplitKReduceArgs r{};
     r.partial = w.partial; r.ksplit = p.ksplit; r.split_stride = p.split_stride; r.rows = a.M;
     r.bias = a.bias; r.ln = a.ln; r.ln_g = a.ln_g; r.ln_b = a.ln_b; r.ln_eps = a.ln_eps; r.act = a.act;
@@ -171,8 +177,9 @@ struct Est {
   // a fourth fragment step per chunk and lands in w.res (RowConvArgs::res_out)
   int conv3(ConvGemmArgs& a, const GemmW& m, const BtbW* follow = nullptr, const ResnetW* fold = nullptr) {
     if (rt.ksplit > 1 && (a.W3 || a.W2) && (a.ldw & 7) == 0) return splitk(a, follow ? &follow->n1 : nullptr, w.ln);
-    if (!rt.rows || !a.amax_in) return conv_gemm(a, 1, st);
+    if (!rt.rows || !a.amax_in) return conv(a);
     RowConvArgs r{};
+    r.np = rt.np;
     r.A = a.A; r.lda = a.lda; r.a_rows = a.a_rows; r.M = a.M; r.Cin = a.Cin; r.rowmask_in = a.rowmask_in;
     r.W2 = m.w2; r.w2_plane = (long)m.n_rows * m.ldw; r.ldw = m.ldw; r.colscale = m.colscale;
     r.Wf = m.wf; r.wf_plane = (long)m.N * m.ntaps * m.Cin;
@@ -211,6 +218,7 @@ struct Est {
     if (s.res == RES_ONE) {
       if (out == in) return fail(JV_ERR_STATE, "flow: the whole-resnet launch cannot run in place");
       RowResArgs a{};
+      a.np = rt.np;
       a.A = in; a.lda = ldin; a.a_rows = g.a_rows; a.M = (int)g.M; a.Cin = ldin; a.rowmask = w.rowmask;
       a.amax_in = slots_of(in); a.slot_G = FLOW_G; a.slot_S = g.uoff ? -1 : g.S; a.slot_nb = g.B2; a.row_slot = w.row_sample;
       a.Wf1 = r.wf4; a.wf1_plane = 256L * 4 * ldin;
@@ -246,7 +254,7 @@ struct Est {
       a = base_args(g, in, ldin, r.res, w.res, 256);
       a.rowmask_in = w.rowmask;
       h3m(a, r.res);
-      JV_TRY(conv_gemm(a, 1, st));
+      JV_TRY(conv(a));
     }
     a = base_args(g, w.h2, 256, r.block2, out, 256);
     causal3(a);
@@ -276,8 +284,9 @@ struct Est {
     ConvGemmArgs a = base_args(g, w.ln, 256, b.qkv, w.qkv, 1536);
     h3(a, b.qkv);
     if (pre(b.qkv)) planes_in(a, w.ln, 256);
-    JV_TRY(conv_gemm(a, 1, st));
+    JV_TRY(conv(a));
     AttnArgs at{};
+    at.np = rt.np;
     at.qkv = w.qkv; at.ld = 1536; at.k_off = 512; at.v_off = 1024; at.out = w.att; at.ldo = 512;
     at.B = g.B2; at.H = EST_HEADS; at.G = FLOW_G; at.S = g.S; at.L = g.T; at.lens = w.lens2;
     at.chunk = rt.attn_chunk;
@@ -292,7 +301,7 @@ struct Est {
     if (sk) {
       JV_TRY(splitk(a, &b.n3, w.ln));      // h += to_out(att); ln = LayerNorm3(h)
     } else {
-      JV_TRY(conv_gemm(a, 1, st));
+      JV_TRY(conv(a));
       JV_TRY(ln_to(b.n3, b.ff1, h));
     }
     a = base_args(g, w.ln, 256, b.ff1, w.ff, 1024);
@@ -303,14 +312,14 @@ struct Est {
       a.out2 = reinterpret_cast<unsigned short*>(w.ff); a.out2_plane = R * 1024; a.ldo2 = 1024; a.out2_scale = b.ff2.a_scale;
     }
     const bool ff_planes = a.out2 != nullptr;
-    JV_TRY(conv_gemm(a, 1, st));
+    JV_TRY(conv(a));
     a = base_args(g, w.ff, 1024, b.ff2, out, ldo);
     a.res1 = h; a.ldr1 = 256;
     track(a);      // -> h / cat
     h3(a, b.ff2);
     if (ff_planes) planes_in(a, w.ff, 1024);
     if (sk) return splitk(a, (next && out == h) ? &next->n1 : nullptr, w.ln);      // + the next block's norm1
-    return conv_gemm(a, 1, st);
+    return conv(a);
   }
 
   // ---- the same block on the row-owning GEMM (rowgemm_kernel.h) when the batch fills the chip: every linear takes its A
@@ -326,6 +335,7 @@ struct Est {
     a.Wf = m.wf; a.wf_plane = (long)m.N * m.Cin;
     a.bias = m.bias; a.ln_eps = 1e-5f; a.out2_scale = 1.f;
     a.alg_rows = g.frames();
+    a.np = rt.np;
     return a;
   }
   void rg_track(RowGemmArgs& a) const { a.amax_out = slots_of(a.out); a.row_slot = w.row_sample; a.row_mask = w.rowmask; }
@@ -350,6 +360,7 @@ struct Est {
       JV_TRY(rowgemm(a, RG_QKV, st));
     }
     AttnArgs at{};
+    at.np = rt.np;
     at.qkv = w.qkv; at.out = w.att; at.ldo = 512;
     at.B = g.B2; at.H = EST_HEADS; at.G = FLOW_G; at.S = g.S; at.L = g.T; at.lens = w.lens2; at.uoff = g.uoff;
     at.chunk = rt.attn_chunk;
@@ -357,11 +368,12 @@ struct Est {
     at.out2 = reinterpret_cast<unsigned short*>(w.att); at.out2_plane = R * 512; at.out2_scale = b.out.a_scale;
     at.ld = 512; at.kv2 = kv2; at.kv2_plane = R * 1024; at.kv_ld = 1024;
     // whole-utterance attention of a batch that fills its rounds: one wave per SIMD, 160 queries per wave; else attn64_pl
-    if (attention64_single_fits(at)) JV_TRY(attention64_single(at, st));
+    if (rt.attn_single && attention64_single_fits(at)) JV_TRY(attention64_single(at, st));
     else JV_TRY(attention64_planes(at, st));
     const bool follows = next && out == h;
     if (fused(b)) {      // the LayerNorm planes never leave LDS (rowblock_kernel.h)
       RowBlockArgs f{};
+      f.np = rt.np;
       f.A2 = reinterpret_cast<const unsigned short*>(w.att); f.a2_plane = R * 512; f.a_rows = g.a_rows; f.M = (int)g.M;
       f.Wof = b.out.wf; f.wof_plane = (long)b.out.N * b.out.Cin; f.cso = b.out.colscale; f.bo = b.out.bias; f.a_scale_o = b.out.a_scale;
       f.h = h; f.ln3_g = b.n3.g; f.ln3_b = b.n3.b;
@@ -393,6 +405,7 @@ struct Est {
     if (rt.ffn_fuse && b.ffn_wf) {
       // the feed-forward pair in one launch (rowffn_kernel): the 1024-wide hidden tile never leaves LDS
       RowFfnArgs f{};
+      f.np = rt.np;
       f.A2 = reinterpret_cast<const unsigned short*>(w.ln); f.a2_plane = R * 256; f.a_rows = g.a_rows; f.lda2 = 256; f.M = (int)g.M;
       f.W1f = b.ff1.wf; f.w1f_plane = (long)b.ff1.N * b.ff1.Cin; f.cs1 = b.ff1.colscale; f.b1 = b.ff1.bias; f.a_scale1 = b.ff1.a_scale;
       f.h_scale = b.ff2.a_scale;
@@ -480,7 +493,7 @@ struct Est {
     a.rowmask_in = w.rowmask;
     a.rowmask_out = w.rowmask;
     h3m(a, e.final_proj);
-    return conv_gemm(a, 1, st);
+    return conv(a);
   }
 };
 

@@ -93,6 +93,8 @@ struct Geo {
 enum ResRoute : int { RES_TILES, RES_ROWS, RES_ONE };
 struct EstRoute {
   bool exact = false;        // bf16x6 everywhere: no fp16x3 operands, no bound tracking
+  int np = 3;                // products per step of every fp16x3 contraction of the call: 3, or 1 = hi x hi alone (Context::est_fp16); Est hands it to every launcher
+  bool attn_single = true;   // row-owning stages: attention_s.hip where the batch fills its rounds; false (np = 1: that kernel writes its three terms out as asm) always attention_pl.hip
   bool rows = false;         // the batch fills the chip: row-owning kernels (else the tile kernels)
   int ksplit = 1;            // > 1: short M, K split over this many workgroups per tile
   bool sk_blocks = false;    // every block's to_out / ff.net.2 splits K and its reduce tail writes the next LayerNorm

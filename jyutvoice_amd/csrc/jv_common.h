@@ -164,6 +164,7 @@ struct ConvGemmArgs {
   // rows, channel padding or the zero taps of a polyphase transposed conv
   long alg_rows;
   int alg_k;
+  int np;             // fp16x3 route (W2): products per step: 1 = hi x hi alone (the estimator's FP16 mode, EstRoute::np); 0 / 3: all three
   unsigned long long* stamps;   // tuning aid (JV_STAMPS): per-workgroup s_memtime at start / loop / epilogue / end
   int ablate;   // tuning aid (JV_ABLATE): 1 no global loads in loop, 2 no LDS stores, 4 no barrier, 16 no epilogue
 };
@@ -204,6 +205,7 @@ struct AttnArgs {
   long kv2_plane;
   int kv_ld;
   int chunk;          // > 0: chunk-causal (streaming) mask -- query i sees keys j < (i / chunk + 1) * chunk; 0: all keys
+  int np;             // fp16x3 forms (attention64 with q_scale > 0, attention64_planes): products per step: 1 = hi x hi alone (the estimator's FP16 mode, EstRoute::np); 0 / 3: all three
   int ablate;         // tuning aid (JV_ABLATE): 1 no K/V loads, 2 no split + LDS stores, 4 no barriers, 8 no PV, 16 no QK^T, 32 no softmax
 };
 int attention64(const AttnArgs& a, hipStream_t st);

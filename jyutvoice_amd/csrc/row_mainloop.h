@@ -56,9 +56,16 @@ struct WFragBuf {
 };
 
 // ---- fp16x3: acc + (a_hi + a_lo)(b_hi + b_lo) without the lo lo term, smallest terms first (as the tile kernels do) ----
+// NP = 1 (the estimator's FP16 mode, EstRoute::np): the hi hi product alone.  The kernels load, wait and fence exactly as at
+// NP = 3 -- the lo planes of the weight fragments still arrive in WFragBuf and are simply not multiplied, so the three rules
+// above and every kernel's wait derivation hold unchanged.  The vocoder's kernels take the default.
+template <int NP = 3>
 __device__ __forceinline__ rg_f32x4 h3_mma(rg_f32x4 acc, const rg_u32x4& a_hi, const rg_u32x4& a_lo, const rg_u32x4& b_hi, const rg_u32x4& b_lo) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, a_lo), __builtin_bit_cast(rg_f16x8, b_hi), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, a_hi), __builtin_bit_cast(rg_f16x8, b_lo), acc, 0, 0, 0);
+  static_assert(NP == 3 || NP == 1, "three products or the hi hi product alone");
+  if constexpr (NP == 3) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, a_lo), __builtin_bit_cast(rg_f16x8, b_hi), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, a_hi), __builtin_bit_cast(rg_f16x8, b_lo), acc, 0, 0, 0);
+  }
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rg_f16x8, a_hi), __builtin_bit_cast(rg_f16x8, b_hi), acc, 0, 0, 0);
 }
 

@@ -5,11 +5,11 @@
 namespace jv {
 
 namespace {
-template <int RT, bool QKV, bool STAG>
+template <int RT, bool QKV, bool STAG, int NP = 3>
 int rb_launch(const RowBlockArgs& a, hipStream_t st) {
-  return launch_lds<rowblock_kernel<RT, QKV, STAG>>(dim3(cdiv(a.M, 16 * RT)), dim3(512), rb_lds_bytes<RT>(), st, a, [&]() {
-    static const std::string name_plain = std::string("rowblock_h3<") + std::to_string(16 * RT) + "x256" + (QKV ? ",qkv>" : ">");
-    static const std::string name_ln = std::string("rowblock_h3<") + std::to_string(16 * RT) + "x256,ln>";
+  return launch_lds<rowblock_kernel<RT, QKV, STAG, NP>>(dim3(cdiv(a.M, 16 * RT)), dim3(512), rb_lds_bytes<RT>(), st, a, [&]() {
+    static const std::string name_plain = std::string("rowblock_h3<") + std::to_string(16 * RT) + "x256" + (QKV ? ",qkv" : "") + (NP == 1 ? ",np1>" : ">");
+    static const std::string name_ln = std::string("rowblock_h3<") + std::to_string(16 * RT) + "x256,ln" + (NP == 1 ? ",np1>" : ">");
     const std::string& name = (!QKV && a.ln_out) ? name_ln : name_plain;
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     // algorithmic work: to_out (512 -> 256) + ff.net.0 (256 -> 1024) + ff.net.2 (1024 -> 256) (+ q|k|v: 256 -> 1536);
@@ -33,7 +33,11 @@ bool ff_stagger() {
 
 template <int RT>
 int rb_launch1(const RowBlockArgs& a, bool qkv, hipStream_t st) {
-  if (ff_stagger()) return qkv ? rb_launch<RT, true, true>(a, st) : rb_launch<RT, false, true>(a, st);
+  if (ff_stagger()) {      // (an opt-in experiment: three products only)
+    if (a.np == 1) return fail(JV_ERR_STATE, "rowblock: the staggered feed-forward (JV_FF_STAGGER) has no one-product form");
+    return qkv ? rb_launch<RT, true, true>(a, st) : rb_launch<RT, false, true>(a, st);
+  }
+  if (a.np == 1) return qkv ? rb_launch<RT, true, false, 1>(a, st) : rb_launch<RT, false, false, 1>(a, st);
   return qkv ? rb_launch<RT, true, false>(a, st) : rb_launch<RT, false, false>(a, st);
 }
 }  // namespace

@@ -74,6 +74,7 @@ struct RowBlockArgs {
   unsigned short* ln_out;
   long ln_out_plane;
   long alg_rows;
+  int np;             // fp16x3 products per step: 1 = hi x hi alone (the estimator's FP16 mode, EstRoute::np); 0 / 3: all three
   unsigned long long* stamps;      // tuning aid (JV_RB_STAMPS, tuning builds): [workgroup][48] s_memtime at the phase boundaries
   // tuning aid (JV_RB_ABLATE, tuning builds; results are wrong by design): 1 GELU pass without its arithmetic, 2 no GELU pass at all,
   // 4 phase C without global stores, 8 phase C without chunk epilogues, 16 residual epilogues without their row passes
@@ -85,7 +86,7 @@ template <int RT> constexpr int rb_lds_bytes() { return 16 * rgw_stage_bytes<RT>
 // element (row, col) of the swizzled slab, in floats
 __device__ __forceinline__ int rb_slab(int row, int col) { return row * 256 + (col ^ (((row >> 2) & 3) << 4)); }
 
-template <int RT, bool QKV, bool STAG>
+template <int RT, bool QKV, bool STAG, int NP = 3>
 __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
   constexpr int R = 16 * RT;
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(512, 2) void rowblock_kernel(const RowBlockArgs p) 
   };
   auto mfma_block = [&](auto par_tag, auto nttag, rg_f32x4 (&acc)[RT][2], auto mt_tag) {
     constexpr int par = decltype(par_tag)::value, nt = decltype(nttag)::value, mt = decltype(mt_tag)::value;
-    acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
+    acc[mt][nt] = h3_mma<NP>(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
   };
 
   // ---- prologue: ring stages 0..2, W of steps 0 and 1; everything waited for once ----

@@ -60,6 +60,7 @@ struct RowConvArgs {
   float* res_out;
   const float *res_cs, *res_bias;
   long alg_rows;
+  int np;             // fp16x3 products per step: 1 = hi x hi alone (the estimator's FP16 mode, EstRoute::np); 0 / 3: all three
   int ablate;      // tuning aid (JV_RG_ABLATE, tuning builds): 1 no weight DMA in the loop, 2 no LDS reads + MFMAs, 4 no waits / barriers,
                    // 8 no A staging in the loop, 16 no epilogue
   unsigned long long* stamps;      // tuning aid (JV_RB_STAMPS, tuning builds; rowconv_wd_kernel): [workgroup][8] last-wave s_memtime per phase
@@ -74,7 +75,7 @@ template <int RT> constexpr int rc_a_plane() { return (16 * RT + 16) * 64; }
 template <int RT> constexpr int rc_lds_bytes() { return 3 * 32768 + 2 * 2 * rc_a_plane<RT>() + 16 * RT * 8; }
 static_assert(16 * 5 * RG_SLD * 4 <= 3 * 32768, "the epilogue slab of the tallest tile fits the weight ring");
 
-template <int RT>
+template <int RT, int NP = 3>
 __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rc_lds[];
   constexpr int R = 16 * RT, WR = R + 2;
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
         for (int pl = 0; pl < 2; ++pl) a[pl] = *reinterpret_cast<const rg_u32x4*>(sa + pl * A_PLANE + a_off);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          acc[mt][nt] = h3_mma(acc[mt][nt], a[0], a[1], b[nt][0], b[nt][1]);
+          acc[mt][nt] = h3_mma<NP>(acc[mt][nt], a[0], a[1], b[nt][0], b[nt][1]);
         }
         if (more) {
           if constexpr (mt < PPW) issue_piece(std::integral_constant<int, (mt < PPW ? mt : 0)>{}, nstage);
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_kernel(const RowConvArgs p) {
 template <int RT> constexpr int rcw_slab_off() { return (2 * 2 * rc_a_plane<RT>() + 16 * RT * 8 + 255) & ~255; }
 template <int RT> constexpr int rcw_lds_bytes() { return rcw_slab_off<RT>() + 16 * RT * RG_SLD * 4; }
 
-template <int RT, bool RES>
+template <int RT, bool RES, int NP = 3>
 __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rc_lds[];
   constexpr int R = 16 * RT, WR = R + 2;
@@ -570,7 +571,7 @@ __global__ __launch_bounds__(512, 2) void rowconv_wd_kernel(const RowConvArgs p)
       constexpr int nt = decltype(nttag)::value;
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt) {
-        ac[mt][nt] = h3_mma(ac[mt][nt], af[mt][0], af[mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
+        ac[mt][nt] = h3_mma<NP>(ac[mt][nt], af[mt][0], af[mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
       }
       __builtin_amdgcn_sched_barrier(0);
       load_w(par_tag, nttag);

@@ -21,11 +21,13 @@ __global__ void pack_wfrag_kernel(const unsigned short* __restrict__ w2, long w2
   *reinterpret_cast<uint4*>(wf + pl * wf_plane + (((long)ks * NB + nb) * 64 + lane) * 8) = v;
 }
 
-template <int RT, int EPI>
+// NP: fp16x3 products per step (RowGemmArgs::np and its twins in the other argument records) -- 3, or 1 in the estimator's FP16 mode
+template <int RT, int EPI, int NP>
 int rg_launch2(const RowGemmArgs& a, hipStream_t st) {
   auto prof_done = [&]() {
     static const std::string name = std::string("rowgemm_h3<") + std::to_string(16 * RT) + "x256" +
-                                    (EPI == RG_GELU_PL ? ",gelu" : EPI == RG_RES ? ",res" : EPI == RG_RES_LN ? ",res,ln" : EPI == RG_QKV ? ",qkv" : "") + ">";
+                                    (EPI == RG_GELU_PL ? ",gelu" : EPI == RG_RES ? ",res" : EPI == RG_RES_LN ? ",res,ln" : EPI == RG_QKV ? ",qkv" : "") +
+                                    (NP == 1 ? ",np1" : "") + ">";
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     const double bytes = 4.0 * (rows * a.K + (double)a.N * a.K + rows * a.N * ((EPI == RG_RES || EPI == RG_RES_LN) ? 2 : 1) +
                                 (EPI == RG_RES_LN ? rows * 256 : 0));
@@ -40,21 +42,21 @@ int rg_launch2(const RowGemmArgs& a, hipStream_t st) {
     if (wdir && a.N > 256 && lds <= 160 * 1024 && !dyn_env("JV_RG_NO_ARES")) {
       const int nc = a.N >> 8;
       const int ns = a.nsplit > 1 ? (a.nsplit < nc ? a.nsplit : nc) : 1;      // column chunks dealt over grid.y (RowGemmArgs::nsplit)
-      return launch_lds<rowgemm_wa_kernel<RT, EPI>>(dim3(tiles, ns), dim3(512), lds, st, a, prof_done);
+      return launch_lds<rowgemm_wa_kernel<RT, EPI, NP>>(dim3(tiles, ns), dim3(512), lds, st, a, prof_done);
     }
   }
-  if (wdir) return launch_lds<rowgemm_wd_kernel<RT, EPI>>(dim3(tiles), dim3(512), rgw_lds_bytes<RT>(), st, a, prof_done);
-  return launch_lds<rowgemm_kernel<RT, EPI>>(dim3(tiles), dim3(512), rg_lds_bytes<RT>(), st, a, prof_done);
+  if (wdir) return launch_lds<rowgemm_wd_kernel<RT, EPI, NP>>(dim3(tiles), dim3(512), rgw_lds_bytes<RT>(), st, a, prof_done);
+  return launch_lds<rowgemm_kernel<RT, EPI, NP>>(dim3(tiles), dim3(512), rg_lds_bytes<RT>(), st, a, prof_done);
 }
 
-template <int RT>
+template <int RT, int NP>
 int rg_launch1(const RowGemmArgs& a, int epi, hipStream_t st) {
   switch (epi) {
-    case RG_PLAIN: return rg_launch2<RT, RG_PLAIN>(a, st);
-    case RG_GELU_PL: return rg_launch2<RT, RG_GELU_PL>(a, st);
-    case RG_RES: return rg_launch2<RT, RG_RES>(a, st);
-    case RG_RES_LN: return rg_launch2<RT, RG_RES_LN>(a, st);
-    case RG_QKV: return rg_launch2<RT, RG_QKV>(a, st);
+    case RG_PLAIN: return rg_launch2<RT, RG_PLAIN, NP>(a, st);
+    case RG_GELU_PL: return rg_launch2<RT, RG_GELU_PL, NP>(a, st);
+    case RG_RES: return rg_launch2<RT, RG_RES, NP>(a, st);
+    case RG_RES_LN: return rg_launch2<RT, RG_RES_LN, NP>(a, st);
+    case RG_QKV: return rg_launch2<RT, RG_QKV, NP>(a, st);
     default: return fail(JV_ERR_ARG, "rowgemm: unknown epilogue");
   }
 }
@@ -105,23 +107,23 @@ int rowgemm_tile(int M) {
 bool rowconv_w_direct(const RowConvArgs& a) { return a.Wf && !((a.Cin >> 5) & 1) && !dyn_env("JV_RG_WLDS"); }
 
 namespace {
-template <int RT>
+template <int RT, int NP>
 int rc_launch(const RowConvArgs& a, hipStream_t st) {
   const bool wdir = rowconv_w_direct(a);
   if (a.ln2_out && !wdir) return fail(JV_ERR_ARG, "rowconv: the following LayerNorm exists on the W-direct kernel only");
   if (a.res_out && !wdir) return fail(JV_ERR_ARG, "rowconv: the folded res_conv exists on the W-direct kernel only");
   auto prof_done = [&]() {
-    static const std::string name = std::string("rowconv_h3<") + std::to_string(16 * RT) + "x256,k3>";
-    static const std::string name_res = std::string("rowconv_h3<") + std::to_string(16 * RT) + "x256,k3+res>";
+    static const std::string name = std::string("rowconv_h3<") + std::to_string(16 * RT) + "x256,k3" + (NP == 1 ? ",np1>" : ">");
+    static const std::string name_res = std::string("rowconv_h3<") + std::to_string(16 * RT) + "x256,k3+res" + (NP == 1 ? ",np1>" : ">");
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     const int taps = a.res_out ? 4 : 3;      // (the folded 1 x 1 res_conv is a fourth tap's worth of work and one more output)
     const double bytes = 4.0 * (rows * a.Cin + 256.0 * taps * a.Cin + rows * 256 * ((a.res ? 2 : 1) + (a.res_out ? 1 : 0)));
     prof_end(st, (a.res_out ? name_res : name).c_str(), 2.0 * rows * 256.0 * taps * a.Cin, bytes);
   };
   const dim3 grid(cdiv(a.M, 16 * RT)), block(512);
-  if (wdir && a.res_out) return launch_lds<rowconv_wd_kernel<RT, true>>(grid, block, rcw_lds_bytes<RT>(), st, a, prof_done);
-  if (wdir) return launch_lds<rowconv_wd_kernel<RT, false>>(grid, block, rcw_lds_bytes<RT>(), st, a, prof_done);
-  return launch_lds<rowconv_kernel<RT>>(grid, block, rc_lds_bytes<RT>(), st, a, prof_done);
+  if (wdir && a.res_out) return launch_lds<rowconv_wd_kernel<RT, true, NP>>(grid, block, rcw_lds_bytes<RT>(), st, a, prof_done);
+  if (wdir) return launch_lds<rowconv_wd_kernel<RT, false, NP>>(grid, block, rcw_lds_bytes<RT>(), st, a, prof_done);
+  return launch_lds<rowconv_kernel<RT, NP>>(grid, block, rc_lds_bytes<RT>(), st, a, prof_done);
 }
 }  // namespace
 
@@ -139,14 +141,17 @@ int rowconv(const RowConvArgs& a, hipStream_t st) {
     return fail(JV_ERR_ARG, "rowconv: the following LayerNorm needs gain, offset, a scale, a plane stride and 256-wide output rows");
   int rt = rowgemm_tile(a.M);
   if (rt == 0 || rt == 1) rt = 2;
-  return dispatch_rt(rt, "rowconv: bad tile height", [&](auto t) { return rc_launch<decltype(t)::value>(a, st); });
+  return dispatch_rt(rt, "rowconv: bad tile height", [&](auto t) {
+    constexpr int RT = decltype(t)::value;
+    return a.np == 1 ? rc_launch<RT, 1>(a, st) : rc_launch<RT, 3>(a, st);
+  });
 }
 
 namespace {
-template <int RT, bool QKV>
+template <int RT, bool QKV, int NP>
 int rr_launch(const RowResArgs& a, hipStream_t st) {
-  return launch_lds<rowres_kernel<RT, QKV>>(dim3(cdiv(a.M, 16 * RT - 2)), dim3(512), rr_lds_bytes<RT>(), st, a, [&]() {
-    static const std::string name = std::string("rowres_h3<") + std::to_string(16 * RT) + "x256" + (QKV ? ",qkv>" : ">");
+  return launch_lds<rowres_kernel<RT, QKV, NP>>(dim3(cdiv(a.M, 16 * RT - 2)), dim3(512), rr_lds_bytes<RT>(), st, a, [&]() {
+    static const std::string name = std::string("rowres_h3<") + std::to_string(16 * RT) + "x256" + (QKV ? ",qkv" : "") + (NP == 1 ? ",np1>" : ">");
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     // block1's three taps + res_conv, block2's three taps (+ the following block's to_q | to_k | to_v)
     const double macs = 256.0 * (4.0 * a.Cin + 3.0 * 256) + (QKV ? 256.0 * 1536 : 0.0);
@@ -185,15 +190,16 @@ int rowres(const RowResArgs& a, hipStream_t st) {
   // the kernel reads whole window rows up to the last tile's end: they must exist in the input buffer or read as masked (a_rows clamps)
   return dispatch_rt(rt, "rowres: no row-owning tile height for this row count", [&](auto t) {
     constexpr int RT = decltype(t)::value;
-    return qkv ? rr_launch<RT, true>(a, st) : rr_launch<RT, false>(a, st);
+    if (a.np == 1) return qkv ? rr_launch<RT, true, 1>(a, st) : rr_launch<RT, false, 1>(a, st);
+    return qkv ? rr_launch<RT, true, 3>(a, st) : rr_launch<RT, false, 3>(a, st);
   });
 }
 
 namespace {
-template <int RT>
+template <int RT, int NP>
 int rf_launch(const RowFfnArgs& a, hipStream_t st) {
-  return launch_lds<rowffn_kernel<RT>>(dim3(cdiv(a.M, 16 * RT)), dim3(512), rgf_lds_bytes<RT>(), st, a, [&]() {
-    static const std::string name = std::string("rowffn_h3<") + std::to_string(16 * RT) + "x256" + ">";
+  return launch_lds<rowffn_kernel<RT, NP>>(dim3(cdiv(a.M, 16 * RT)), dim3(512), rgf_lds_bytes<RT>(), st, a, [&]() {
+    static const std::string name = std::string("rowffn_h3<") + std::to_string(16 * RT) + "x256" + (NP == 1 ? ",np1>" : ">");
     const double rows = (double)(a.alg_rows > 0 ? a.alg_rows : a.M);
     // algorithmic bytes: LayerNorm planes in (rows x 256 x 4 B), both weight matrices, residual in, rows out (+ planes out)
     prof_end(st, name.c_str(), 2.0 * rows * 2.0 * 256.0 * 1024.0, 4.0 * (rows * 256 * (a.ln ? 4 : 3) + 2.0 * 256 * 1024));
@@ -210,7 +216,10 @@ int rowffn(const RowFfnArgs& a, hipStream_t st) {
     return fail(JV_ERR_ARG, "rowffn: aligned strides (and gain / offset / plane buffer for the LayerNorm epilogue) required");
   int rt = rowgemm_tile(a.M);
   if (rt == 0 || rt == 1) rt = 2;
-  return dispatch_rt(rt, "rowffn: bad tile height", [&](auto t) { return rf_launch<decltype(t)::value>(a, st); });
+  return dispatch_rt(rt, "rowffn: bad tile height", [&](auto t) {
+    constexpr int RT = decltype(t)::value;
+    return a.np == 1 ? rf_launch<RT, 1>(a, st) : rf_launch<RT, 3>(a, st);
+  });
 }
 
 int rowgemm(const RowGemmArgs& a, int epi, hipStream_t st) {
@@ -228,7 +237,10 @@ int rowgemm(const RowGemmArgs& a, int epi, hipStream_t st) {
   if (epi == RG_RES_LN && (!a.ln_g || !a.ln_b)) return fail(JV_ERR_ARG, "rowgemm: LayerNorm epilogue needs gain and offset");
   int rt = (a.rt >= 2 && a.rt <= 5) ? a.rt : rowgemm_tile(a.M);
   if (rt == 0 || rt == 1) rt = 2;      // callers ask rowgemm_tile() first; a direct call still works
-  return dispatch_rt(rt, "rowgemm: bad tile height", [&](auto t) { return rg_launch1<decltype(t)::value>(a, epi, st); });
+  return dispatch_rt(rt, "rowgemm: bad tile height", [&](auto t) {
+    constexpr int RT = decltype(t)::value;
+    return a.np == 1 ? rg_launch1<RT, 1>(a, epi, st) : rg_launch1<RT, 3>(a, epi, st);
+  });
 }
 
 }  // namespace jv

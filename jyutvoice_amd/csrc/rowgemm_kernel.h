@@ -73,6 +73,7 @@ struct RowGemmArgs {
   int nsplit;         // rowgemm_wa_kernel: the N / 256 column chunks are dealt to nsplit workgroups per row tile (grid.y); 0 / 1: one
   int rt;             // tile height in 16-row units, 2 .. 5; 0: rowgemm_tile(M).  A stand-alone launch need not take the fused block's:
                       // the L2 -> CU traffic of a launch is (row tiles) x (weight bytes), so few tall tiles x column split moves the least
+  int np;             // fp16x3 products per step: 1 = hi x hi alone (the estimator's FP16 mode, EstRoute::np); 0 / 3: all three
   int ablate;         // tuning aid (JV_RG_ABLATE, tuning builds): 1 no loads in the loop, 2 no MFMAs, 4 no barrier/wait (LDS kernel),
                       // W-direct kernel also: 8 no LDS fragment reads, 16 no W loads, 32 no A DMA, 64 no row pass
 };
@@ -83,7 +84,7 @@ constexpr int RG_SLAB_BYTES = RG_SLAB_ROWS * RG_SLD * 4;
 template <int RT> constexpr int rg_stage_bytes() { return 2 * 16 * RT * 64 + 2 * 256 * 64; }
 template <int RT> constexpr int rg_lds_bytes() { return 3 * rg_stage_bytes<RT>() + RG_SLAB_BYTES; }
 
-template <int RT, int EPI>
+template <int RT, int EPI, int NP = 3>
 __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
   constexpr int R = 16 * RT;
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const RowGemmArgs p) {
         for (int pl = 0; pl < 2; ++pl) a[pl] = *reinterpret_cast<const rg_u32x4*>(st + a_off + pl * A_PLANE + mt * 1024);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          acc[mt][nt] = h3_mma(acc[mt][nt], a[0], a[1], b[nt][0], b[nt][1]);
+          acc[mt][nt] = h3_mma<NP>(acc[mt][nt], a[0], a[1], b[nt][0], b[nt][1]);
         }
         // this group's share of the next-but-one step's DMA: pieces mt, mt + RT, ... of the wave's list
         if (more) {
@@ -393,7 +394,7 @@ constexpr int RGW_NST = 3;
 template <int RT> constexpr int rgw_stage_bytes() { return 2 * 16 * RT * 64; }
 template <int RT> constexpr int rgw_lds_bytes() { return RGW_NST * rgw_stage_bytes<RT>() + 16 * RT * RG_SLD * 4; }
 
-template <int RT, int EPI>
+template <int RT, int EPI, int NP = 3>
 __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
   constexpr int R = 16 * RT;
@@ -561,7 +562,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
       auto group = [&](auto mtag, auto nttag) {
         constexpr int mt = decltype(mtag)::value, nt = decltype(nttag)::value;
         if (!JV_ABLATE(p, 2)) {
-          acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
+          acc[mt][nt] = h3_mma<NP>(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         if constexpr (nt == 1 && mt < PPW) {
           if (more_a) issue_piece(std::integral_constant<int, (mt < PPW ? mt : 0)>{}, s3);
@@ -768,7 +769,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wd_kernel(const RowGemmArgs p)
 // of a chunk for the row-wise stores: no barrier in the chunk epilogues either -- the prologue's is the only one.
 template <int RT> constexpr int rgwa_lds_bytes(int KS) { return KS * rgw_stage_bytes<RT>() + 8 * 16 * 36 * 4; }
 
-template <int RT, int EPI>
+template <int RT, int EPI, int NP = 3>
 __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
   constexpr int R = 16 * RT;
@@ -887,7 +888,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wa_kernel(const RowGemmArgs p)
         constexpr int nt = decltype(nttag)::value;
 #pragma unroll
         for (int mt = 0; mt < RT; ++mt) {
-          acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
+          acc[mt][nt] = h3_mma<NP>(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         load_w(par_tag, nttag);
@@ -999,11 +1000,12 @@ struct RowFfnArgs {
   const int* row_slot;
   const unsigned char* row_mask;
   long alg_rows;
+  int np;             // fp16x3 products per step: 1 = hi x hi alone (the estimator's FP16 mode, EstRoute::np); 0 / 3: all three
 };
 
 template <int RT> constexpr int rgf_lds_bytes() { return 16 * rgw_stage_bytes<RT>() > 16 * RT * RG_SLD * 4 ? 16 * rgw_stage_bytes<RT>() : 16 * RT * RG_SLD * 4; }
 
-template <int RT>
+template <int RT, int NP = 3>
 __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rg_lds[];
   constexpr int R = 16 * RT;
@@ -1124,7 +1126,7 @@ __global__ __launch_bounds__(512, 2) void rowffn_kernel(const RowFfnArgs p) {
       constexpr int nt = decltype(nttag)::value;
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt) {
-        acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq[par][nt][0], bq[par][nt][1]);
+        acc[mt][nt] = h3_mma<NP>(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq[par][nt][0], bq[par][nt][1]);
       }
       __builtin_amdgcn_sched_barrier(0);
       load_w(par_tag, nttag);

@@ -78,11 +78,12 @@ struct RowResArgs {
   long kv2_plane;
   float k_scale, v_scale;
   long alg_rows;
+  int np;             // fp16x3 products per step: 1 = hi x hi alone (the estimator's FP16 mode, EstRoute::np); 0 / 3: all three
 };
 
 template <int RT> constexpr int rr_lds_bytes() { return 16 * rgw_stage_bytes<RT>(); }
 
-template <int RT, bool QKV>
+template <int RT, bool QKV, int NP = 3>
 __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rr_lds[];
   constexpr int R = 16 * RT, RO = R - 2, WR = R + 2;
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
         constexpr int nt = decltype(nttag)::value;
 #pragma unroll
         for (int mt = 0; mt < RT; ++mt) {
-          ac[mt][nt] = h3_mma(ac[mt][nt], af[mt][0], af[mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
+          ac[mt][nt] = h3_mma<NP>(ac[mt][nt], af[mt][0], af[mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         load_w(par_tag, nttag);
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
         constexpr int nt = decltype(nttag)::value;
 #pragma unroll
         for (int mt = 0; mt < RT; ++mt) {
-          acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
+          acc[mt][nt] = h3_mma<NP>(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         load_w(par_tag, nttag);
@@ -559,7 +560,7 @@ __global__ __launch_bounds__(512, 2) void rowres_kernel(const RowResArgs p) {
         constexpr int nt = decltype(nttag)::value;
 #pragma unroll
         for (int mt = 0; mt < RT; ++mt) {
-          acc[mt][nt] = h3_mma(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
+          acc[mt][nt] = h3_mma<NP>(acc[mt][nt], af[par][mt][0], af[par][mt][1], bq.q[par][nt][0], bq.q[par][nt][1]);
         }
         __builtin_amdgcn_sched_barrier(0);
         load_w(par_tag, nttag);

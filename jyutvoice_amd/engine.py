@@ -127,12 +127,26 @@ class Engine:
         at load time (jv_flow_set_contraction)"""
         check(self.lib.jv_flow_set_contraction(self._h, 1 if on else 0))
 
-    def contraction_info(self) -> dict:
+    PRECISIONS = {"fp32": 0, "fp16": 1}      # JV_PRECISION_FP32 / JV_PRECISION_FP16
+
+    def set_precision(self, precision: str = "fp32"):
+        """"fp32" (default): every contraction at fp32 accuracy.  "fp16": the estimator as the reference's fp16 TensorRT plan
+        runs it -- each contraction that would run fp16x3 issues its hi x hi product alone (operands rounded to 11 significant
+        bits under the same power-of-two scales, fp32 accumulation); layers without a usable bound, the encoders and the
+        vocoder are unchanged (jv_flow_set_precision).  Not together with set_exact_range(True)."""
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(self.PRECISIONS)}, not {precision!r}")
+        check(self.lib.jv_flow_set_precision(self._h, self.PRECISIONS[precision]))
+
+    def contraction_info(self, with_precision: bool = False) -> dict:
         """which of the estimator's transformer layers have a usable load-time bound (fp16x3) and which stay on bf16x6
-        (jv_flow_contraction_info)"""
-        out = (C.c_int32 * 4)()
-        check(self.lib.jv_flow_contraction_info(self._h, out, 4))
-        return {"blocks": out[0], "blocks_all_h3": out[1], "linears_h3": out[2], "attention_h3": out[3]}
+        (jv_flow_contraction_info); with_precision: also "precision", the mode set_precision() left ("fp32" / "fp16")"""
+        out = (C.c_int32 * 5)()
+        check(self.lib.jv_flow_contraction_info(self._h, out, 5))
+        info = {"blocks": out[0], "blocks_all_h3": out[1], "linears_h3": out[2], "attention_h3": out[3]}
+        if with_precision:
+            info["precision"] = "fp16" if out[4] else "fp32"
+        return info
 
     def flow_estimator(self, x, mask_lens, mu, t, spks, cond):
         """[B2,80,T] tensors on the device; mask_lens int32 [B2] or None."""
@@ -619,6 +633,12 @@ def op_conv_gemm(A, W, bias=None, ntaps=1, tap_row0=0, dil=1, M=None, act="none"
                               _lib.PRO[prologue], _ptr(alpha), float(slope), _ptr(g), _ptr(b), float(ln_eps), _ptr(rowmask),
                               _ptr(res), _ptr(out), _stream(A.device)))
     return out
+
+
+def op_set_products(np: int = 3) -> None:
+    """process-wide: fp16x3 products per step of the op_* hooks below (jv_op_set_products) -- 3, or 1 = the hi x hi product alone,
+    what Engine.set_precision("fp16") selects on a context.  Nothing on the production path reads it."""
+    check(_lib.load().jv_op_set_products(int(np)))
 
 
 def op_linear_h3(A, W, bias=None, act="none", res=None, a_bound=None, presplit=0):

@@ -14,8 +14,13 @@ leaves the reference's own Euler/CFG solver (solve_euler, :215-265) running unmo
 export is needed (or offered): the weights go in through load_state_dict, there is no engine file to build.
 
 Contract of the seam, stated because raw addresses carry none of it:
-  * fp32 only: the six inputs and the output are read and written as contiguous float32 (the reference's TRT profile,
-    scripts/export_onnx.py:343-346, and its `x.contiguous().data_ptr()` calls); a half-precision caller must cast first.
+  * fp32 at the addresses: the six inputs and the output are read and written as contiguous float32 (the reference's TRT
+    profile, scripts/export_onnx.py:343-346, and its `x.contiguous().data_ptr()` calls); a half-precision caller must cast
+    first.  That is the binding side only.  What runs between the bindings is the engine's precision mode: fp32-accurate
+    contractions by default, and with `HipEstimator(engine, fp16=True)` what the reference's fp16 plan
+    (scripts/export_onnx.py:342-361, `fp16 = True`) runs -- fp16 operands on the matrix cores, fp32 accumulation
+    (Engine.set_precision("fp16")).  A library context has one mode, as an engine file has one: fp16=True switches the
+    engine it is given; fp16=False leaves the engine's mode as it is.
   * stream order: the reference fills x / mask / mu / t on the caller's current stream and then launches on the pool's own
     non-blocking stream with nothing ordering the two (a latent race of the reference's seam).  Here `acquire_estimator()`
     records an event on the caller's current stream and makes the pool stream wait for it, so the estimator never reads
@@ -88,10 +93,13 @@ class HipEstimator:
     """`TrtContextWrapper`-shaped pool (utils/common.py:219-238): `trt_concurrent` contexts, each with its own torch stream
     context manager.  All of them drive ONE library context (one workspace), so the pool hands out one at a time."""
 
-    def __init__(self, engine, trt_concurrent: int = 1, device=None):
+    def __init__(self, engine, trt_concurrent: int = 1, device=None, fp16: bool = False):
         if trt_concurrent < 1:
             raise ValueError("trt_concurrent must be >= 1")
         self.engine = engine
+        self.fp16 = bool(fp16)
+        if self.fp16:
+            engine.set_precision("fp16")
         self.trt_engine = HipEstimatorEngine()
         self.device = engine.device if device is None else torch.device(device)
         self.trt_context_pool: "queue.Queue" = queue.Queue(maxsize=trt_concurrent)

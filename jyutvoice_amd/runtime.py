@@ -23,6 +23,7 @@ class Runtime:
         self.caps = (0, 0, 0)
         self.sds: Dict[int, Dict[str, torch.Tensor]] = {}
         self.noise = None
+        self.precision = "fp32"
 
     def set_weights(self, model: int, sd: Dict[str, torch.Tensor]):
         """validate + upload a state-dict (raises like nn.Module.load_state_dict)"""
@@ -62,6 +63,14 @@ class Runtime:
             self.caps = caps
         return self.engine
 
+    def set_precision(self, precision: str = "fp32"):
+        """Engine.set_precision on this runtime's context, kept across the contexts a weight reload creates"""
+        if precision not in Engine.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(Engine.PRECISIONS)}, not {precision!r}")
+        if self.engine is not None:
+            self.engine.set_precision(precision)      # (may refuse: exact_range is on)
+        self.precision = precision
+
     def _rebuild(self, caps):
         """new context + upload of every known state-dict: only when WEIGHTS change (the C ABI finalizes a model once)"""
         if self.engine is not None:
@@ -74,6 +83,8 @@ class Runtime:
         if self.noise is None:
             self.noise = synth.rand_noise()
         eng.load_noise(self.noise)
+        if self.precision != "fp32":
+            eng.set_precision(self.precision)
         self.engine = eng
         self.caps = caps
 

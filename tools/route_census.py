@@ -27,6 +27,8 @@ SWITCHES = ["JV_NO_ROWGEMM", "JV_DMA_A", "JV_NO_FFN_FUSE", "JV_NO_BLOCK_FUSE", "
 SETTINGS = {"default": {}}
 SETTINGS.update({s: {s: "1"} for s in SWITCHES})
 SETTINGS["set_exact_range"] = {}      # jv_flow_set_contraction(1) on a context created in the default mode
+SETTINGS["set_precision_fp16"] = {}   # jv_flow_set_precision(JV_PRECISION_FP16) on a context created in the default mode
+SETTINGS["JV_EST_FP16"] = {"JV_EST_FP16": "1"}
 SETTINGS["JV_ROWGEMM_RT=2"] = {"JV_DYNAMIC_ENV": "1", "JV_ROWGEMM_RT": "2"}
 SETTINGS["JV_ROWGEMM_RT=5"] = {"JV_DYNAMIC_ENV": "1", "JV_ROWGEMM_RT": "5"}
 
@@ -60,6 +62,8 @@ def child(setting, out_path):
         eng = get_runtime("cuda:0").ensure(batch, frames, tokens)
         if setting == "set_exact_range":
             eng.set_exact_range(True)
+        if setting == "set_precision_fp16":
+            eng.set_precision("fp16")
         return tts, eng
 
     def census(name, run):
