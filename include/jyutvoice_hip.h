@@ -167,6 +167,42 @@ int jv_cfm_solve(jv_context* ctx, const float* mu, const int32_t* lens, const fl
 int jv_cfm_solve_prompted(jv_context* ctx, const float* mu_y, const int32_t* y_lens, const float* prompt_h,
                           const float* prompt_feat, const int32_t* prompt_lens, const float* spks, int B, int Ty, int Ph, int Pf,
                           int n_timesteps, float temperature, const float* t_span_host, float* mel, void* stream);
+/* ---- in-flight batching: requests join and leave a running solve between two Euler steps ---------------------------------
+ * The solver's state between two steps of ConditionalCFM.solve_euler (flow_matching.py:230-265) is x, the running trunk maxima
+ * that the fp16x3 scales derive from, and a step counter; the estimator takes one t per sample.  So the utterances of one
+ * estimator evaluation need not be at the same step.  A request's state lives in caller-owned device pools, moved by descriptor
+ * like the pools of jv_slab_copy's callers; the library keeps nothing about a request between calls:
+ *   pool_x, pool_mu, pool_cond [slots, Tcap, 80] fp32, frame-major (the layout of prompt_h / prompt_feat), 16-byte aligned;
+ *   pool_spks [slots, 80], the projected speaker vector;  pool_amax [slots, 3, 2], the running maxima of the request and of its
+ *   CFG twin, one per tracked trunk buffer.
+ * A request served this way is DEFINED as jv_cfm_solve_prompted at B = 1 with its own n_timesteps and temperature, whatever else
+ * is in the pool and whenever the others joined or left; it meets it within the bound of any change of batch geometry (2e-5).
+ * Every per-request scalar is a HOST array (*_host): the caller decides them on the host anyway.  No call synchronises, and none
+ * keeps a pointer to a host array after it returns (the values travel as kernel arguments).  Every call validates all of its
+ * arguments before its first launch: a rejected call (JV_ERR_ARG / JV_ERR_SHAPE naming the request) leaves the pools unchanged.
+ *
+ * jv_cfm_pool_admit: packs B new requests into their slots.  mu_y [B,80,Ty], prompt_h [B,Ph,80], prompt_feat [B,Pf,80], spks
+ *   [B,80] on the device as for jv_cfm_solve_prompted; y_lens, prompt_lens, slots [B] int32 and temperature [B] float on the host.
+ *   Slot s receives mu = [prompt_h[b, :p_b] | mu_y[b, :, :y_b]], cond = [prompt_feat[b, :p_b] | 0], x = noise[:, :p_b + y_b] *
+ *   temperature[b], spks[b], and zeroed maxima.  0 <= p_b <= min(Ph, Pf), 0 <= y_b <= Ty, 1 <= p_b + y_b <= Tcap, 0 <= slot <
+ *   slots, no slot twice.  Rows of a slot behind p_b + y_b are neither written nor ever read.
+ * jv_cfm_pool_step: ONE Euler + CFG step (rate 0.7) for the B listed slots, request b at (t_host[b], dt_host[b]) with lens_host[b]
+ *   = p_b + y_b frames: x += dt_b ((1 + 0.7) v(x, t_b | mu, spks, cond) - 0.7 v(x, t_b)).  The rows are laid out by the rule of
+ *   jv_cfm_solve (compact where the estimator's route allows it, else uniform, padded to the step's longest request), always
+ *   two rows per frame (no shared first-step twin), always eager.  The context modes (jv_flow_set_streaming, _contraction,
+ *   _precision) apply as to any estimator call.  1 <= B <= max_batch, 1 <= lens_host[b] <= min(Tcap, max_frames), slots in range,
+ *   none twice.
+ * jv_cfm_pool_fetch: mel[b, :, t] = pool_x[slots_host[b], first_host[b] + t, :] for t < lens_host[b], zeros behind, mel [B,80,Tm]
+ *   -- the unpack of jv_cfm_solve_prompted with first = p_b, len = y_b.  0 <= first_b, 0 <= len_b <= Tm, first_b + len_b <= Tcap. */
+int jv_cfm_pool_admit(jv_context* ctx, const float* mu_y, const float* prompt_h, const float* prompt_feat, const float* spks,
+                      const int32_t* y_lens_host, const int32_t* prompt_lens_host, const int32_t* slots_host,
+                      const float* temperature_host, int B, int Ty, int Ph, int Pf, float* pool_x, float* pool_mu, float* pool_cond,
+                      float* pool_spks, float* pool_amax, int slots, int Tcap, void* stream);
+int jv_cfm_pool_step(jv_context* ctx, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks,
+                     float* pool_amax, int slots, int Tcap, const int32_t* slots_host, const int32_t* lens_host, const float* t_host,
+                     const float* dt_host, int B, void* stream);
+int jv_cfm_pool_fetch(jv_context* ctx, const float* pool_x, int slots, int Tcap, const int32_t* slots_host, const int32_t* first_host,
+                      const int32_t* lens_host, int B, int Tm, float* mel, void* stream);
 
 /* ---- prompt (voice-cloning) branch ---------------------------------------------------------------------
  * jv_prompt_encoder_fwd: FlowEncoder.forward of the reference's infer.py:35-83 -- Embedding(clamp(token, 0)) * mask ->

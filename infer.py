@@ -157,8 +157,14 @@ def synthesise_list(toks, args, tts, hift, device):
     if with_prompt:
         from jyutvoice_amd.flow.encoder import load_flow_encoder
         from jyutvoice_amd.utils.audio import extract_speech_feat_batch
-        print(f"Loading flow encoder from {args.flow_encoder}...")
-        flow_encoder = load_flow_encoder(args.flow_encoder, device)
+        if args.synthetic:
+            from jyutvoice_amd import synth
+            from jyutvoice_amd.flow.encoder import FlowEncoder
+            flow_encoder = FlowEncoder(device=device)
+            flow_encoder.load_state_dict(synth.prompt_state_dict())
+        else:
+            print(f"Loading flow encoder from {args.flow_encoder}...")
+            flow_encoder = load_flow_encoder(args.flow_encoder, device)
         plens = torch.tensor([len(toks[b]["prompt_token"]) for b in with_prompt], dtype=torch.int64)
         ptok = torch.zeros(len(with_prompt), int(plens.max()), dtype=torch.int64)
         for i, b in enumerate(with_prompt):
@@ -181,6 +187,8 @@ def synthesise_list(toks, args, tts, hift, device):
             if n_h != n_f:
                 print(f"utterance {b}: prompt_h has {n_h} frames, the prompt mel {n_f}: both trimmed to {p}")
             feats[b], hs[b] = f[:p].cpu(), h[i, :p].cpu()
+    if args.inflight:
+        return synthesise_inflight(toks, ids, spk, feats, hs, args, tts, hift)
     prompt_feat, prompt_h, prompt_lengths = pad_prompts(feats, hs)
 
     print(f"Running TTS synthesis of {B} utterances as one batch...")
@@ -193,6 +201,7 @@ def synthesise_list(toks, args, tts, hift, device):
     torch.cuda.synchronize()
     print(f"Synthesis time: {time.time() - start:.2f} s (rtf of synthesise(): {result['rtf']:.4f})")
     samples = result["mel_lengths"] * 480
+    dump_mels(args, [result["mel"][b, :, :n] for b, n in enumerate(result["mel_lengths"].tolist())])
     if args.sample_rate != 24000:      # the whole batch in one ragged call, each utterance at its own length
         from jyutvoice_amd.utils.audio import resample
         wav, samples = resample(wav, 24000, args.sample_rate, lengths=samples)
@@ -200,6 +209,64 @@ def synthesise_list(toks, args, tts, hift, device):
     for b, n in enumerate(samples.tolist()):
         path = f"{stem}_{b:03d}{ext}"
         write_wav(path, wav[b, :n], args.sample_rate)
+        print(f"Generated audio saved to: {path} ({n / args.sample_rate:.2f} seconds)")
+
+
+def dump_mels(args, mels):
+    """--dump-mel: mel b [80, y_b] -> DIR/mel_NNN.npy"""
+    if not args.dump_mel:
+        return
+    import numpy as np
+    os.makedirs(args.dump_mel, exist_ok=True)
+    for b, m in enumerate(mels):
+        np.save(os.path.join(args.dump_mel, f"mel_{b:03d}.npy"), m.cpu().numpy())
+
+
+def synthesise_inflight(toks, ids, spk, feats, hs, args, tts, hift):
+    """--tokens list.json --inflight S: the list through one SynthServer with at most S resident requests, a new request submitted
+    every --arrive-every steps; the same out_NNN files as the list route.  A request's own "n_timesteps", "temperature",
+    "length_scale" and "seed" keys override the command line's (seed: --seed + its index)."""
+    import torch
+
+    from jyutvoice_amd.serve import SynthServer
+    B = len(toks)
+    if args.inflight < 1 or args.arrive_every < 1:
+        raise SystemExit("--inflight and --arrive-every must be positive")
+    tokens = max(i["x"].shape[1] for i in ids)
+    # the pool's frame capacity is fixed up front, before any duration is known: room for 20 frames per token behind the longest prompt
+    frames = max(f.shape[0] for f in feats) + 20 * tokens
+    server = SynthServer(tts, hift, max_sessions=min(args.inflight, B), max_frames=frames, max_tokens=tokens)
+    print(f"Serving {B} requests through {server.max_sessions} slots, one arrival every {args.arrive_every} step(s)...")
+    start, out, step = time.time(), {}, 0
+    while len(out) < B:
+        b = step // args.arrive_every
+        if step % args.arrive_every == 0 and b < B:
+            t, p = toks[b], feats[b].shape[0]
+            try:
+                i = ids[b]
+                server.submit(i["x"], i["x_lengths"], i["lang"], i["tone"], i["word_pos"], i["syllable_pos"], spk[b:b + 1],
+                              prompt_feat=feats[b][None] if p else None, prompt_h=hs[b][None] if p else None,
+                              n_timesteps=int(t.get("n_timesteps", args.n_timesteps)), temperature=float(t.get("temperature", 1.0)),
+                              length_scale=float(t.get("length_scale", args.length_scale)), seed=int(t.get("seed", args.seed + b)))
+            except ValueError as e:
+                raise SystemExit(f"{args.tokens}: {e}")
+        out.update(server.step())
+        step += 1
+    torch.cuda.synchronize()
+    print(f"Synthesis time: {time.time() - start:.2f} s over {server.steps} pool steps")
+    bad = {rid: r["error"] for rid, r in out.items() if "error" in r}
+    if bad:
+        raise SystemExit(f"{args.tokens}: " + "; ".join(bad.values()))
+    dump_mels(args, [out[b]["mel"][0] for b in range(B)])
+    stem, ext = os.path.splitext(args.output)
+    for b in range(B):
+        wav, n = out[b]["wav"], 480 * out[b]["mel_length"]
+        if args.sample_rate != 24000:
+            from jyutvoice_amd.utils.audio import resample
+            wav, lens = resample(wav, 24000, args.sample_rate, lengths=torch.tensor([n]))
+            n = int(lens[0])
+        path = f"{stem}_{b:03d}{ext}"
+        write_wav(path, wav[0, :n], args.sample_rate)
         print(f"Generated audio saved to: {path} ({n / args.sample_rate:.2f} seconds)")
 
 
@@ -412,7 +479,13 @@ def main(argv=None):
                    help="--token2wav: a streaming session per request, its tokens pushed K at a time")
     p.add_argument("--stream-sessions", type=int, default=0, metavar="S",
                    help="--token2wav --stream-hop K: serve the list through one Token2WavServer, S sessions at a time")
-    p.add_argument("--synthetic", type=int, default=0, help="use N synthetic tokens and synthetic weights")
+    p.add_argument("--inflight", type=int, default=0, metavar="S",
+                   help="--tokens with a JSON list: serve the list through one SynthServer with at most S resident requests (in-flight "
+                        "batching); a request may carry its own n_timesteps, temperature, length_scale and seed keys")
+    p.add_argument("--arrive-every", type=int, default=1, metavar="K", help="--inflight: a new request is submitted every K steps")
+    p.add_argument("--dump-mel", default=None, metavar="DIR", help="--tokens with a JSON list: also save every mel as DIR/mel_NNN.npy")
+    p.add_argument("--synthetic", type=int, default=0, help="use N synthetic tokens and synthetic weights (with a --tokens list: the "
+                                                            "synthetic weights and the list's utterances)")
     p.add_argument("--synthetic-prompt", type=int, default=0, help="with --synthetic: K synthetic prompt tokens (voice-cloning path)")
     p.add_argument("--estimator-precision", default="fp32", choices=["fp32", "fp16"],
                    help="fp16: the CFM estimator as the reference's fp16 TensorRT plan runs it (fp16 operands, fp32 accumulation); "
@@ -445,9 +518,14 @@ def main(argv=None):
     tts, hift = jyutvoice_amd.build_default(device)
 
     prompt_feat = prompt_h = None
+    if args.inflight and not args.tokens:
+        raise SystemExit("--inflight needs --tokens with a JSON list")
     if args.synthetic:
         tts.load_state_dict(synth.tts_state_dict())
         hift.load_state_dict(synth.hift_state_dict())
+        if args.tokens and isinstance(json.load(open(args.tokens)), list):      # synthetic weights, the list's utterances
+            hift.manual_seed(args.seed)
+            return synthesise_list(json.load(open(args.tokens)), args, tts.eval().to(device), hift.eval().to(device), device)
         u = synth.batch(1, args.synthetic)
         ids = {k: u[k] for k in ("x", "lang", "tone", "word_pos", "syllable_pos")}
         spk = u["spk_embed"]

@@ -60,7 +60,10 @@ SIGNATURES = {
     "jv_flow_contraction_info": (_i, [_p, _p, _i]),
     "jv_cfm_solve": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p]),
     "jv_cfm_solve_prompted": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p]),
-    "jv_flow_encoder_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "jv_cfm_pool_admit": (_i, [_p] * 9 + [_i] * 4 + [_p] * 5 + [_i, _i, _p]),
+    "jv_cfm_pool_step": (_i, [_p] * 6 + [_i, _i] + [_p] * 4 + [_i, _p]),
+    "jv_cfm_pool_fetch": (_i, [_p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _p]),
+    "jv_flow_encoder_fwd": (_i,[_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "jv_flow_token2mel": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "jv_flow_encoder_fwd_partial": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "jv_flow_token2mel_partial": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),

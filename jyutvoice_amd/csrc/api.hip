@@ -409,6 +409,37 @@ int jv_cfm_solve_prompted(jv_context* ctx, const float* mu_y, const int32_t* y_l
                                 temperature, t_span_host, mel, static_cast<hipStream_t>(stream));
 }
 
+int jv_cfm_pool_admit(jv_context* ctx, const float* mu_y, const float* prompt_h, const float* prompt_feat, const float* spks,
+                      const int32_t* y_lens_host, const int32_t* prompt_lens_host, const int32_t* slots_host,
+                      const float* temperature_host, int B, int Ty, int Ph, int Pf, float* pool_x, float* pool_mu, float* pool_cond,
+                      float* pool_spks, float* pool_amax, int slots, int Tcap, void* stream) {
+  CTX_GUARD(ctx);
+  if (!spks || !y_lens_host || !prompt_lens_host || !slots_host || !temperature_host || !pool_x || !pool_mu || !pool_cond ||
+      !pool_spks || !pool_amax)
+    return jv::fail(JV_ERR_ARG, "jv_cfm_pool_admit: null argument");
+  if ((Ty > 0 && !mu_y) || (Ph > 0 && !prompt_h) || (Pf > 0 && !prompt_feat)) return jv::fail(JV_ERR_ARG, "jv_cfm_pool_admit: null tensor");
+  return jv::cfm_pool_admit(ctx->c, mu_y, prompt_h, prompt_feat, spks, y_lens_host, prompt_lens_host, slots_host, temperature_host, B,
+                            Ty, Ph, Pf, pool_x, pool_mu, pool_cond, pool_spks, pool_amax, slots, Tcap, static_cast<hipStream_t>(stream));
+}
+
+int jv_cfm_pool_step(jv_context* ctx, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks,
+                     float* pool_amax, int slots, int Tcap, const int32_t* slots_host, const int32_t* lens_host, const float* t_host,
+                     const float* dt_host, int B, void* stream) {
+  CTX_GUARD(ctx);
+  if (!pool_x || !pool_mu || !pool_cond || !pool_spks || !pool_amax || !slots_host || !lens_host || !t_host || !dt_host)
+    return jv::fail(JV_ERR_ARG, "jv_cfm_pool_step: null argument");
+  return jv::cfm_pool_step(ctx->c, pool_x, pool_mu, pool_cond, pool_spks, pool_amax, slots, Tcap, slots_host, lens_host, t_host,
+                           dt_host, B, static_cast<hipStream_t>(stream));
+}
+
+int jv_cfm_pool_fetch(jv_context* ctx, const float* pool_x, int slots, int Tcap, const int32_t* slots_host, const int32_t* first_host,
+                      const int32_t* lens_host, int B, int Tm, float* mel, void* stream) {
+  CTX_GUARD(ctx);
+  if (!pool_x || !slots_host || !first_host || !lens_host || !mel) return jv::fail(JV_ERR_ARG, "jv_cfm_pool_fetch: null argument");
+  return jv::cfm_pool_fetch(ctx->c, pool_x, slots, Tcap, slots_host, first_host, lens_host, B, Tm, mel,
+                            static_cast<hipStream_t>(stream));
+}
+
 // ---- operator-level entry points -------------------------------------------------------------------
 int jv_op_conv_gemm(const float* A, int64_t a_rows, int M, int Cin, int ntaps, int tap_row0, int dil, const float* W, int N,
                     const float* bias, int act, int prologue, const float* alpha, float slope, const float* ln_g,

@@ -57,6 +57,7 @@ int flow_ws_create(Context& c) {
   JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->h_sum), (size_t)B2 * sizeof(int), hipHostMallocDefault));
   JV_TRY(ws_alloc(c, (size_t)B2 * sizeof(int), reinterpret_cast<void**>(&w->t2m_lens)));
   JV_HIP(hipHostMalloc(reinterpret_cast<void**>(&w->h_y), (size_t)B2 * sizeof(int), hipHostMallocDefault));
+  JV_TRY(ws_alloc(c, (size_t)c.max_batch * sizeof(PoolStepReq), reinterpret_cast<void**>(&w->pool_req)));
   JV_TRY(ws_alloc(c, sizeof(int), reinterpret_cast<void**>(&w->step_ctr)));
   JV_TRY(F(&w->t_cur, 1));
   JV_TRY(F(&w->dt_cur, 1));
@@ -184,19 +185,26 @@ int solve_schedule(FlowWs& w, int n_timesteps, const float* t_span_host, std::ve
 // taken when it saves at least 8 % of the rows and the shorter batch still fills the row-owning kernels.  All per-row
 // arithmetic is the uniform geometry's (a row's sums do not depend on where the row sits): the same bits per utterance.
 // h_lens: the B sequence lengths on the host (after the solve's synchronisation).
-int solve_compact(Context& c, Geo& g, const int* h_lens, int B, int T, hipStream_t st) {
-  FlowWs& w = *c.flow;
+// the rule alone, on host arrays (cfm_pool_step lays a step out by it as well): uoff[2B + 1] receives the first rows; true = compact
+bool compact_plan(const Context& c, long M_uniform, const int* h_lens, int B, int T, int* uoff, long* rows, long* frames_out) {
   const int B2 = 2 * B;
   long r = FLOW_G, frames = 0;
   for (int b2 = 0; b2 < B2; ++b2) {
     const int len = std::min(std::max(h_lens[b2 % B], 0), T);
-    w.h_uoff[b2] = (int)r;
+    uoff[b2] = (int)r;
     r += len + FLOW_GAP;
     frames += len;
   }
-  w.h_uoff[B2] = (int)r;
-  if (r * 100 <= g.M * 92 && flow_compact_ok(c, r)) {
-    JV_HIP(hipMemcpyAsync(w.uoff, w.h_uoff, sizeof(int) * (B2 + 1), hipMemcpyHostToDevice, st));      // (pinned: stays valid)
+  uoff[B2] = (int)r;
+  *rows = r; *frames_out = frames;
+  return r * 100 <= M_uniform * 92 && flow_compact_ok(c, r);
+}
+
+int solve_compact(Context& c, Geo& g, const int* h_lens, int B, int T, hipStream_t st) {
+  FlowWs& w = *c.flow;
+  long r = 0, frames = 0;
+  if (compact_plan(c, g.M, h_lens, B, T, w.h_uoff, &r, &frames)) {
+    JV_HIP(hipMemcpyAsync(w.uoff, w.h_uoff, sizeof(int) * (2 * B + 1), hipMemcpyHostToDevice, st));      // (pinned: stays valid)
     g.M = r; g.uoff = w.uoff; g.alg_rows = frames;
   }
   return JV_OK;
@@ -423,7 +431,191 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
   return rows_to_cf_from(w.x, 80, FLOW_G, g.S, prompt_lens, y_lens, mel, 80L * Ty, B, 80, Ty, st, g.uoff);
 }
 
-constexpr int T2M_EST_CHUNK = 50;      // the estimator's static_chunk_size in frames (configs/base.yaml:98; decoder.py:951-954)
+// ---- in-flight batching (jv_cfm_pool_admit / _step / _fetch; kernels: cfmpool.hip) ---------------------------------------------
+// Between two Euler steps a solve's state is x, the running trunk maxima and a step counter, and the estimator takes one t per
+// sample: the utterances of one evaluation need not be at the same step.  A request's state lives in the caller's pools; a step
+// gathers the listed slots into the workspace rows, runs assemble_xin and estimator_body as solve_loop's step does -- with t per
+// sample, so without the precomputed embedding and therefore without the whole-resnet launch (est_route: RES_ONE needs temb_pre)
+// -- and applies the update with the request's own dt while scattering x back.  The maxima travel with the request: its scales
+// depend on that request alone, whoever held its slot or its workspace position before.
+// Every call checks all of its arguments before its first launch, never synchronises, and reads its host arrays only until it
+// returns (their values travel as kernel arguments).
+
+namespace {
+
+int pool_check_pools(const char* who, const void* a, const void* b, const void* c3, const void* d, const void* e, int slots, int Tcap) {
+  char msg[160];
+  if (slots < 1 || Tcap < 1) {
+    snprintf(msg, sizeof msg, "%s: slots and Tcap must be positive", who);
+    return fail(JV_ERR_ARG, msg);
+  }
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c3) | reinterpret_cast<uintptr_t>(d) |
+       reinterpret_cast<uintptr_t>(e)) & 15) {
+    snprintf(msg, sizeof msg, "%s: the pools must be 16-byte aligned", who);
+    return fail(JV_ERR_ARG, msg);
+  }
+  return JV_OK;
+}
+
+// slot in range and named once among the call's requests (seen: [slots], zeroed by the caller)
+int pool_check_slot(const char* who, int b, int slot, int slots, std::vector<char>& seen) {
+  char msg[160];
+  if (slot < 0 || slot >= slots) {
+    snprintf(msg, sizeof msg, "%s: request %d: slot %d outside [0, %d)", who, b, slot, slots);
+    return fail(JV_ERR_ARG, msg);
+  }
+  if (seen[slot]) {
+    snprintf(msg, sizeof msg, "%s: request %d: slot %d is named twice", who, b, slot);
+    return fail(JV_ERR_ARG, msg);
+  }
+  seen[slot] = 1;
+  return JV_OK;
+}
+
+}  // namespace
+
+int cfm_pool_admit(Context& c, const float* mu_y, const float* prompt_h, const float* prompt_feat, const float* spks,
+                   const int* h_ylens, const int* h_plens, const int* h_slots, const float* h_temps, int B, int Ty, int Ph, int Pf,
+                   float* pool_x, float* pool_mu, float* pool_cond, float* pool_spks, float* pool_amax, int slots, int Tcap,
+                   hipStream_t st) {
+  const char* who = "jv_cfm_pool_admit";
+  if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "tts weights not finalized");
+  if (!c.noise_loaded) return fail(JV_ERR_STATE, "CFM noise tensor not loaded (jv_load_noise)");
+  if (B < 1 || Ty < 0 || Ph < 0 || Pf < 0) return fail(JV_ERR_ARG, "jv_cfm_pool_admit: B must be positive, Ty, Ph, Pf non-negative");
+  JV_TRY(pool_check_pools(who, pool_x, pool_mu, pool_cond, pool_spks, spks, slots, Tcap));
+  if ((reinterpret_cast<uintptr_t>(prompt_h) | reinterpret_cast<uintptr_t>(prompt_feat)) & 15)
+    return fail(JV_ERR_ARG, "jv_cfm_pool_admit: prompt_h / prompt_feat must be 16-byte aligned");
+  const int Pmax = std::min(Ph, Pf);
+  std::vector<char> seen((size_t)slots, 0);
+  int tmax = 0;
+  char msg[200];
+  for (int b = 0; b < B; ++b) {
+    const int y = h_ylens[b], p = h_plens[b];
+    if (p < 0 || p > Pmax) {
+      snprintf(msg, sizeof msg, "%s: request %d: prompt length %d outside [0, min(Ph, Pf) = %d]", who, b, p, Pmax);
+      return fail(JV_ERR_ARG, msg);
+    }
+    if (y < 0 || y > Ty) {
+      snprintf(msg, sizeof msg, "%s: request %d: %d frames outside [0, Ty = %d]", who, b, y, Ty);
+      return fail(JV_ERR_ARG, msg);
+    }
+    if (p + y < 1 || p + y > Tcap || p + y > NOISE_FRAMES) {
+      snprintf(msg, sizeof msg, "%s: request %d: %d + %d frames outside [1, min(Tcap = %d, %d)]", who, b, p, y, Tcap, NOISE_FRAMES);
+      return fail(JV_ERR_ARG, msg);
+    }
+    if (!(h_temps[b] == h_temps[b])) {
+      snprintf(msg, sizeof msg, "%s: request %d: temperature is not a number", who, b);
+      return fail(JV_ERR_ARG, msg);
+    }
+    JV_TRY(pool_check_slot(who, b, h_slots[b], slots, seen));
+    tmax = std::max(tmax, p + y);
+  }
+  for (int b0 = 0; b0 < B; b0 += POOL_CHUNK) {
+    PoolAdmitChunk ch;
+    ch.n = std::min(POOL_CHUNK, B - b0); ch.b0 = b0;
+    int cmax = 0;
+    for (int i = 0; i < ch.n; ++i) {
+      ch.r[i] = {h_slots[b0 + i], h_plens[b0 + i], h_plens[b0 + i] + h_ylens[b0 + i], h_temps[b0 + i]};
+      cmax = std::max(cmax, ch.r[i].len);
+    }
+    for (int i = ch.n; i < POOL_CHUNK; ++i) ch.r[i] = {0, 0, 0, 0.f};
+    JV_TRY(pool_admit(ch, cmax, mu_y, Ty, prompt_h, Ph, prompt_feat, Pf, spks, c.noise, NOISE_FRAMES, pool_x, pool_mu, pool_cond,
+                      pool_spks, pool_amax, Tcap, st));
+  }
+  (void)tmax;
+  return JV_OK;
+}
+
+int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks, float* pool_amax,
+                  int slots, int Tcap, const int* h_slots, const int* h_lens, const float* h_t, const float* h_dt, int B,
+                  hipStream_t st) {
+  const char* who = "jv_cfm_pool_step";
+  if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "tts weights not finalized");
+  JV_TRY(pool_check_pools(who, pool_x, pool_mu, pool_cond, pool_spks, nullptr, slots, Tcap));
+  FlowWs& w = *c.flow;
+  char msg[200];
+  if (B < 1 || B > c.max_batch) {
+    snprintf(msg, sizeof msg, "%s: %d requests outside [1, max_batch = %d]: beyond the reservation (jv_reserve)", who, B, c.max_batch);
+    return fail(B < 1 ? JV_ERR_ARG : JV_ERR_SHAPE, msg);
+  }
+  std::vector<char> seen((size_t)slots, 0);
+  int T = 0;
+  for (int b = 0; b < B; ++b) {
+    JV_TRY(pool_check_slot(who, b, h_slots[b], slots, seen));
+    if (h_lens[b] < 1 || h_lens[b] > Tcap) {
+      snprintf(msg, sizeof msg, "%s: request %d: %d frames outside [1, Tcap = %d]", who, b, h_lens[b], Tcap);
+      return fail(JV_ERR_ARG, msg);
+    }
+    if (h_lens[b] > c.max_frames) {
+      snprintf(msg, sizeof msg, "%s: request %d: %d frames exceed the reservation (max_frames = %d)", who, b, h_lens[b], c.max_frames);
+      return fail(JV_ERR_SHAPE, msg);
+    }
+    if (!(h_t[b] == h_t[b]) || !(h_dt[b] == h_dt[b])) {
+      snprintf(msg, sizeof msg, "%s: request %d: t / dt is not a number", who, b);
+      return fail(JV_ERR_ARG, msg);
+    }
+    T = std::max(T, h_lens[b]);
+  }
+  // the step's rows, by cfm_solve's rule: compact where the route allows it and it saves rows, else uniform (padded to T)
+  const int B2 = 2 * B;
+  Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, w.t_dev, 1};
+  std::vector<int> uoff((size_t)B2 + 1);
+  long r = 0, frames = 0;
+  const bool compact = B > 1 && flow_compact_ok(c, g.M) && compact_plan(c, g.M, h_lens, B, T, uoff.data(), &r, &frames);
+  if (compact) { g.M = r; g.uoff = w.uoff; g.alg_rows = frames; }
+  if (g.M + 128 > w.rows_alloc) {      // (implied by the two limits above: the workspace holds 2 max_batch padded utterances)
+    snprintf(msg, sizeof msg, "%s: request %d: the step's %ld rows exceed the reservation (%ld)", who, B - 1, g.M, w.rows_alloc - 128);
+    return fail(JV_ERR_SHAPE, msg);
+  }
+  // ---- nothing was launched up to here ----
+  for (int b0 = 0; b0 < B; b0 += POOL_CHUNK) {
+    PoolStepChunk ch;
+    ch.n = std::min(POOL_CHUNK, B - b0); ch.b0 = b0;
+    for (int i = 0; i < POOL_CHUNK; ++i) {
+      const int b = b0 + i;
+      if (i < ch.n)
+        ch.r[i] = {h_slots[b], h_lens[b], compact ? uoff[b] : FLOW_G + b * g.S, compact ? uoff[B + b] : FLOW_G + (B + b) * g.S, h_t[b], h_dt[b]};
+      else
+        ch.r[i] = {0, 0, 0, 0, 0.f, 0.f};
+    }
+    JV_TRY(pool_publish(ch, B, w.pool_req, w.lens2, w.t_dev, compact ? w.uoff : nullptr, (int)g.M, st));
+  }
+  JV_TRY(row_meta(w.rowmask, w.row_sample, w.lens2, B2, 1, FLOW_G, g.S, T, w.rows_alloc, 1, 0, st, g.uoff));
+  JV_TRY(pool_gather(w.pool_req, B, T, compact ? 0 : T, pool_x, pool_mu, pool_cond, pool_spks, pool_amax, Tcap, w.x, w.mu, w.cond,
+                     w.spks, w.amax, w.amax_stride, st));
+  JV_TRY(assemble_xin(w.x, w.mu, w.spks, w.cond, w.xin, B, B, FLOW_G, g.S, T, g.M, st, g.uoff, w.row_sample, w.rowmask));
+  JV_TRY(estimator_body(c, g, est_route(c, g.M, /*temb_pre=*/false, compact, c.attn_chunk), st));
+  return pool_euler_scatter(w.pool_req, B, T, w.x, w.d, 0.7f, w.amax, w.amax_stride, pool_x, pool_amax, Tcap, st);
+}
+
+int cfm_pool_fetch(Context& c, const float* pool_x, int slots, int Tcap, const int* h_slots, const int* h_first, const int* h_lens,
+                   int B, int Tm, float* mel, hipStream_t st) {
+  (void)c;
+  const char* who = "jv_cfm_pool_fetch";
+  if (B < 1 || Tm < 1 || slots < 1 || Tcap < 1) return fail(JV_ERR_ARG, "jv_cfm_pool_fetch: B, Tm, slots and Tcap must be positive");
+  char msg[200];
+  for (int b = 0; b < B; ++b) {
+    if (h_slots[b] < 0 || h_slots[b] >= slots) {
+      snprintf(msg, sizeof msg, "%s: request %d: slot %d outside [0, %d)", who, b, h_slots[b], slots);
+      return fail(JV_ERR_ARG, msg);
+    }
+    if (h_first[b] < 0 || h_lens[b] < 0 || h_lens[b] > Tm || (long)h_first[b] + h_lens[b] > Tcap) {
+      snprintf(msg, sizeof msg, "%s: request %d: frames [%d, %d + %d) outside the slot (Tcap = %d) or longer than Tm = %d", who, b,
+               h_first[b], h_first[b], h_lens[b], Tcap, Tm);
+      return fail(JV_ERR_ARG, msg);
+    }
+  }
+  for (int b0 = 0; b0 < B; b0 += POOL_CHUNK) {
+    PoolFetchChunk ch;
+    ch.n = std::min(POOL_CHUNK, B - b0); ch.b0 = b0;
+    for (int i = 0; i < POOL_CHUNK; ++i)
+      ch.r[i] = i < ch.n ? PoolFetchReq{h_slots[b0 + i], h_first[b0 + i], h_lens[b0 + i]} : PoolFetchReq{0, 0, 0};
+    JV_TRY(pool_fetch(ch, pool_x, Tcap, mel, Tm, st));
+  }
+  return JV_OK;
+}
+
+constexpr int T2M_EST_CHUNK = 50;     // the estimator's static_chunk_size in frames (configs/base.yaml:98; decoder.py:951-954)
 
 // Token-to-mel (flow/flow.py:314-358 looped over the utterances): the flow encoder's h over [prompt tokens | tokens] is mu for the
 // whole sequence of T_b = 2 (p_b + n_b) frames, cond = [prompt_feat_b[:f_b] | 0], and frames f_b .. T_b - 1 come back.  The same

@@ -58,6 +58,7 @@ struct FlowWs {
   int* h_sum = nullptr;     // cfm_solve_prompted: p_b + y_b of every utterance and its CFG twin, [2*maxB] (pinned; goes up to lens2)
   int* t2m_lens = nullptr;  // flow_token2mel: T_b = 2 (p_b + n_b) in [0, maxB), y_b = T_b - f_b in [maxB, 2*maxB) (device)
   int* h_y = nullptr;       // ... and y_b on its way up, [maxB] (pinned)
+  PoolStepReq* pool_req = nullptr;      // cfm_pool_step: the step's requests (slot, length, rows, t, dt), [maxB] (device; cfmpool.hip)
   int max_steps = 1024;
   // One Euler step (step scalars -> input assembly -> estimator -> CFG update) captured as a hipGraph per (B, T,
   // attention mode): the step reads its (t, dt) through a device-side counter, so one executable graph replays for

@@ -209,6 +209,16 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
 int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const float* prompt_h, const float* prompt_feat,
                        const int* prompt_lens, const float* spks, int B, int Ty, int Ph, int Pf, int n_timesteps,
                        float temperature, const float* t_span_host, float* mel, hipStream_t st);
+// in-flight batching (jv_cfm_pool_*): requests in caller-owned pools join and leave a running solve between Euler steps
+int cfm_pool_admit(Context& c, const float* mu_y, const float* prompt_h, const float* prompt_feat, const float* spks,
+                   const int* h_ylens, const int* h_plens, const int* h_slots, const float* h_temps, int B, int Ty, int Ph, int Pf,
+                   float* pool_x, float* pool_mu, float* pool_cond, float* pool_spks, float* pool_amax, int slots, int Tcap,
+                   hipStream_t st);
+int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks, float* pool_amax,
+                  int slots, int Tcap, const int* h_slots, const int* h_lens, const float* h_t, const float* h_dt, int B,
+                  hipStream_t st);
+int cfm_pool_fetch(Context& c, const float* pool_x, int slots, int Tcap, const int* h_slots, const int* h_first, const int* h_lens,
+                   int B, int Tm, float* mel, hipStream_t st);
 
 int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const float* prompt_feat,
                    const int* feat_lens, const float* embedding, int B, int P, int N, int F, int streaming, int n_timesteps,

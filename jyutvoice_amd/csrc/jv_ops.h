@@ -37,6 +37,35 @@ int ln_epilogue_rows(float* x, const float* g, const float* b, float eps, long r
                      const unsigned char* rowmask, const float* rowvec, const int* row_sample, int rowvec_ld, const float* res,
                      long ldr, float scale, hipStream_t st, float* amax_out = nullptr, int amax_G = 0, int amax_S = 0,
                      int amax_nb = 1, const int* amax_rows = nullptr);
+// cfmpool.hip: in-flight batching (flow.hip cfm_pool_*).  A request's solver state lives in caller-owned pools, [slots, Tcap, 80]
+// frame-major x / mu / cond, [slots, 80] spks, [slots, 3, 2] running trunk maxima (buffer; request, CFG twin).  What the host
+// decides per call travels as kernel ARGUMENTS, POOL_CHUNK requests per launch: a launch snapshots its arguments, so a call needs
+// neither a synchronisation nor a staging buffer that the next call could rewrite under a copy still queued.
+constexpr int POOL_CHUNK = 64;
+struct PoolAdmitReq { int slot, p, len; float temp; };      // prompt frames, p + y frames, noise scale
+struct PoolAdmitChunk { int n, b0; PoolAdmitReq r[POOL_CHUNK]; };
+struct PoolStepReq { int slot, len, row, rowu; float t, dt; };      // first workspace row of the request and of its CFG twin
+struct PoolStepChunk { int n, b0; PoolStepReq r[POOL_CHUNK]; };
+struct PoolFetchReq { int slot, first, len; };
+struct PoolFetchChunk { int n, b0; PoolFetchReq r[POOL_CHUNK]; };
+// mu = [prompt_h[b, :p] | mu_y[b, :, :len - p]], cond = [prompt_feat[b, :p] | 0], x = noise[:, :len] * temp, spks, maxima = 0
+int pool_admit(const PoolAdmitChunk& ch, int tmax, const float* mu_y, int Ty, const float* prompt_h, int Ph, const float* prompt_feat,
+               int Pf, const float* spks, const float* noise, long noise_pitch, float* pool_x, float* pool_mu, float* pool_cond,
+               float* pool_spks, float* pool_amax, int Tcap, hipStream_t st);
+// the step's tables from the arguments: req[b], lens2[b] = lens2[B + b] = len, t_dev[b] = t_dev[B + b] = t and, with uoff (compact
+// geometry), uoff[b] = row, uoff[B + b] = rowu, uoff[2B] = rows_end
+int pool_publish(const PoolStepChunk& ch, int B, PoolStepReq* req, int* lens2, float* t_dev, int* uoff, int rows_end, hipStream_t st);
+// pools -> workspace rows of the B requests (x, mu, cond; zeros for frames len .. tfill - 1: the uniform geometry's padding), their
+// spks and the maxima of request and twin into amax[k * amax_stride + b] / [.. + B + b]
+int pool_gather(const PoolStepReq* req, int B, int tmax, int tfill, const float* pool_x, const float* pool_mu, const float* pool_cond,
+                const float* pool_spks, const float* pool_amax, int Tcap, float* x, float* mu, float* cond, float* spks, float* amax,
+                int amax_stride, hipStream_t st);
+// pool_x[slot, t] = x[row + t] + dt_b ((1 + rate) d[row + t] - rate d[rowu + t]) (euler_cfg with a dt per request), maxima back
+int pool_euler_scatter(const PoolStepReq* req, int B, int tmax, const float* x, const float* d, float rate, const float* amax,
+                       int amax_stride, float* pool_x, float* pool_amax, int Tcap, hipStream_t st);
+// mel[b, c, t] = pool_x[slot, first + t, c] for t < len, zeros up to Tm
+int pool_fetch(const PoolFetchChunk& ch, const float* pool_x, int Tcap, float* mel, int Tm, hipStream_t st);
+
 int fill(float* p, float v, long n, hipStream_t st);
 int fill_int(int* p, int v, long n, hipStream_t st);
 

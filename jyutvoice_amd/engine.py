@@ -26,6 +26,25 @@ def _f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+class CfmPool:
+    """The state of `slots` resident CFM solves (jv_cfm_pool_*), owned by the caller: x / mu / cond [slots, max_frames, 80]
+    frame-major, the projected speaker vectors [slots, 80] and the running trunk maxima [slots, 3, 2] (buffer; request, CFG
+    twin).  The library keeps nothing about a request between calls, so the pools survive jv_reserve and a new context."""
+
+    def __init__(self, slots: int, max_frames: int, device):
+        if not isinstance(slots, int) or slots < 1 or not isinstance(max_frames, int) or max_frames < 1:
+            raise ValueError(f"CfmPool: slots and max_frames must be positive ints, got {slots!r}, {max_frames!r}")
+        self.slots, self.max_frames = slots, max_frames
+        self.x = torch.zeros(slots, max_frames, spec.N_FEATS, device=device)
+        self.mu = torch.zeros_like(self.x)
+        self.cond = torch.zeros_like(self.x)
+        self.spks = torch.zeros(slots, spec.N_FEATS, device=device)
+        self.amax = torch.zeros(slots, 3, 2, device=device)
+
+    def tensors(self):
+        return self.x, self.mu, self.cond, self.spks, self.amax
+
+
 class Engine:
     """One library context = packed weights + workspace for up to `max_batch` utterances of
     `max_frames` mel frames / `max_tokens` tokens, bound to one GPU."""
@@ -190,6 +209,57 @@ class Engine:
         check(self.lib.jv_cfm_solve_prompted(self._h, _ptr(mu_y), _ptr(yl), _ptr(prompt_h), _ptr(prompt_feat), _ptr(pl), _ptr(spks),
                                              B, Ty, prompt_h.shape[1], prompt_feat.shape[1], int(n_timesteps), float(temperature),
                                              ts, _ptr(mel), _stream(self.device)))
+        return mel
+
+    # ---- in-flight batching: requests join and leave a running solve between Euler steps ---------------------
+    def cfm_pool(self, slots: int, max_frames: int) -> "CfmPool":
+        """the caller-owned state pools of `slots` resident solves of at most `max_frames` (prompt + generated) frames"""
+        return CfmPool(slots, max_frames, self.device)
+
+    @staticmethod
+    def _host_vec(who, name, values, ctype, B):
+        values = [v for v in (values.tolist() if isinstance(values, torch.Tensor) else values)]
+        if len(values) != B:
+            raise ValueError(f"{who}: {name} must hold {B} entries, got {len(values)}")
+        return (ctype * B)(*values)
+
+    def cfm_pool_admit(self, pool, mu_y, y_lens, prompt_h, prompt_feat, prompt_lens, spks, slots, temperatures):
+        """jv_cfm_pool_admit: pack B new requests into `slots` of `pool`.  mu_y [B,80,Ty], prompt_h [B,Ph,80] / prompt_feat
+        [B,Pf,80] (or None: no prompts), spks [B,80] on the device; y_lens, prompt_lens, slots, temperatures: B host values
+        each (lists or CPU tensors -- a device tensor would cost a synchronisation)"""
+        who = "cfm_pool_admit"
+        B, _, Ty = mu_y.shape
+        mu_y, spks = _f32(mu_y, self.device), _f32(spks, self.device)
+        if prompt_h is None or prompt_feat is None:
+            prompt_h = prompt_feat = torch.zeros(B, 0, spec.N_FEATS, device=self.device)
+        prompt_h, prompt_feat = _f32(prompt_h, self.device), _f32(prompt_feat, self.device)
+        check(self.lib.jv_cfm_pool_admit(
+            self._h, _ptr(mu_y) if Ty else None, _ptr(prompt_h) if prompt_h.shape[1] else None,
+            _ptr(prompt_feat) if prompt_feat.shape[1] else None, _ptr(spks),
+            self._host_vec(who, "y_lens", y_lens, C.c_int32, B), self._host_vec(who, "prompt_lens", prompt_lens, C.c_int32, B),
+            self._host_vec(who, "slots", slots, C.c_int32, B), self._host_vec(who, "temperatures", temperatures, C.c_float, B),
+            B, Ty, prompt_h.shape[1], prompt_feat.shape[1], _ptr(pool.x), _ptr(pool.mu), _ptr(pool.cond), _ptr(pool.spks),
+            _ptr(pool.amax), pool.slots, pool.max_frames, _stream(self.device)))
+
+    def cfm_pool_step(self, pool, slots, lens, t, dt):
+        """jv_cfm_pool_step: ONE Euler + CFG step of the listed slots, request b with lens[b] frames at (t[b], dt[b]); B host
+        values each.  Nothing comes back to the host."""
+        who, B = "cfm_pool_step", len(slots)
+        check(self.lib.jv_cfm_pool_step(
+            self._h, _ptr(pool.x), _ptr(pool.mu), _ptr(pool.cond), _ptr(pool.spks), _ptr(pool.amax), pool.slots, pool.max_frames,
+            self._host_vec(who, "slots", slots, C.c_int32, B), self._host_vec(who, "lens", lens, C.c_int32, B),
+            self._host_vec(who, "t", t, C.c_float, B), self._host_vec(who, "dt", dt, C.c_float, B), B, _stream(self.device)))
+
+    def cfm_pool_fetch(self, pool, slots, first, lens, frames=None):
+        """jv_cfm_pool_fetch: frames first[b] .. first[b] + lens[b] - 1 of the listed slots -> mel [B, 80, frames] (default: the
+        longest), left-aligned, zeros behind lens[b]"""
+        who, B = "cfm_pool_fetch", len(slots)
+        Tm = int(max(lens)) if frames is None else int(frames)
+        mel = torch.empty(B, spec.N_FEATS, Tm, device=self.device)
+        check(self.lib.jv_cfm_pool_fetch(
+            self._h, _ptr(pool.x), pool.slots, pool.max_frames, self._host_vec(who, "slots", slots, C.c_int32, B),
+            self._host_vec(who, "first", first, C.c_int32, B), self._host_vec(who, "lens", lens, C.c_int32, B), B, Tm, _ptr(mel),
+            _stream(self.device)))
         return mel
 
     # ---- prompt mel front-end --------------------------------------------------------------------------
