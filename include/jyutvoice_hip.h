@@ -363,6 +363,65 @@ int jv_fbank(jv_context* ctx, const float* wav, const int32_t* lens, int B, int 
 int jv_whisper_log_mel(jv_context* ctx, const float* wav, const int32_t* lens, int B, int n, float* out, int32_t* out_lens,
                        void* stream);
 
+/* ---- levels: prompt silence trim, peak, BS.1770 loudness, gain ----------------------------------------------
+ * What a CosyVoice2 front-end does to a reference recording before any feature is taken (energy trim 60 dB below the loudest frame,
+ * frame 440, hop 220; scale down to a peak of 0.8; append 0.2 s of silence) and the usual last step of a TTS service (programme
+ * loudness after ITU-R BS.1770-4 / EBU R 128).  The reference's infer.py does neither.  All definitions are restated here
+ * (unpinned: librosa, pyloudnorm and torchaudio are not part of this build).
+ *
+ * Energy trim: the contract of librosa.effects.trim(y, top_db, frame_length = F, hop_length = H) with zero centre padding, in the
+ *   linear domain.  x[0..N) padded with F / 2 zeros per side (xp); T = 1 + (N + 2 (F / 2) - F) / H frames (0 if that is negative or
+ *   N == 0); ms_t = (1 / F) sum_{i < F} xp[t H + i]^2, m_t = max(1e-10, ms_t), M = max_t m_t; frame t is non-silent iff
+ *   m_t > M 10^(-top_db / 10); start = H (first non-silent t), end = min(N, H (last non-silent t + 1)); none, or N == 0:
+ *   start = end = 0.  An all-zero recording has every m_t = M: nothing is trimmed.  fp32: a frame's sum is 64 interleaved fmaf
+ *   chains (i mod 64, i ascending) joined by a fixed butterfly; the threshold is evaluated in fp64 and rounded once.
+ * Peak: max |x| over the recording, or over [start, end) (each clamped into [0, len], end >= start); exact; 0 for an empty range.
+ * Integrated loudness (mono).  K-weighting = shelf then high-pass, two biquads whose coefficients follow from the standard's
+ *   48 kHz table by the usual re-derivation, evaluated in fp64: with K = tan(pi f0 / fs), a0 = 1 + K / Q + K^2,
+ *   a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0] for both;
+ *   shelf: f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196, Vh = 10^(G / 20), Vb = Vh^0.4996667741545416,
+ *     b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0];
+ *   high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1].
+ *   Zero state before sample 0, y = high-pass(shelf(x)).  h = (fs + 5) / 10 samples; block j covers [j h, j h + 4 h) for
+ *   j < nb = (N - 4 h) / h + 1 (0 when N < 4 h); z_j = mean(y^2) over the block.  Absolute gate: z_j > 10^((-70 + 0.691) / 10);
+ *   relative gate: also z_j > 0.1 mean(z over the blocks past the absolute gate); L = -0.691 + 10 log10(mean z over the blocks
+ *   past both); no block, or none past the absolute gate: L = -inf (never NaN).  The recurrence and every sum run in fp64 in an
+ *   order fixed by the sample index; L is rounded once to fp32.
+ * Gain: g = 10^((target - L) / 20); with a ceiling c > 0 and peak given, g = min(g, c / peak); L = -inf or peak == 0: g = 1.
+ *   Without lufs (the prompt rule): g = c / peak if peak > c, else 1.  Evaluated in fp64, rounded once.
+ * Apply: out[b, :e - s] = x[b, s:e] g_b (one fp32 multiply), then `tail` zeros, out_lens[b] = e - s + tail, exact zeros behind.
+ *
+ * jv_kweight_coeffs: out = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 for a rate.  jv_loudness_blocks: nb above (-1 for a bad
+ *   rate).  Both host only, no context.  Rates outside [8000, 192000]: JV_ERR_ARG.
+ * Common to the five device calls: wav [B, n] fp32; lens [B] int32 on the device or NULL (all n), clamped as under "Lengths" above:
+ *   it MEANS len_b = min(max(lens[b], 0), n), and what lies behind it is not read (it may be NaN); start / end / peak / lufs / gain
+ *   are [B] device vectors.  Every error is returned before anything is launched and leaves the context usable; results are
+ *   written to device memory and nothing comes back to the host.  A recording gives the same bits alone and in any ragged batch.
+ * jv_trim_bounds: 1 <= hop_length, 1 <= frame_length <= 8192, top_db > 0 and finite, else JV_ERR_ARG.  Four launches.
+ * jv_peak: start / end optional (NULL: the whole recording).  One memset and one launch.
+ * jv_loudness: fs in [8000, 192000] else JV_ERR_ARG.  Four launches (segment scan, carry, bins, gates).
+ * jv_level_gain: target_lufs and ceiling are doubles (0.8 means 0.8, not its fp32 neighbour); lufs == NULL is the prompt rule (needs peak and ceiling > 0, else JV_ERR_ARG); otherwise ceiling <= 0 means none,
+ *   and a ceiling > 0 needs peak.
+ * jv_level_apply: start / end / gain optional (NULL: 0 / len / 1); n_out >= n + tail else JV_ERR_SHAPE; tail >= 0; out_lens optional.
+ * The calls only enqueue on `stream` and never synchronise -- except that jv_loudness builds and uploads two 65 x 4 x 4 tables of
+ * powers of the filter's transition matrix on the first use of a sample rate (a cache of 8 rates in the context; a miss copies
+ * synchronously and, once full, waits for the device and frees the least recently used), and that jv_trim_bounds / jv_loudness
+ * with a larger B x n than any call before wait for the device and re-allocate their intermediates (one buffer per context: calls
+ * that use it must be ordered on one stream).  So under stream capture: make a call of the largest shape and of each sample rate
+ * OUTSIDE the capture first.  These buffers are not workspace: jv_reserve leaves them alone, jv_destroy frees them.
+ * One launch holds at most 2^24 workgroups (8192 samples or 4 trim frames each): beyond that JV_ERR_SHAPE. */
+int jv_kweight_coeffs(int fs, double* out /* 10 */);
+int64_t jv_loudness_blocks(int64_t n, int fs);
+int jv_trim_bounds(jv_context* ctx, const float* wav, const int32_t* lens, int B, int n, float top_db, int frame_length,
+                   int hop_length, int32_t* start, int32_t* end, void* stream);
+int jv_peak(jv_context* ctx, const float* wav, const int32_t* lens, const int32_t* start, const int32_t* end, int B, int n,
+            float* peak, void* stream);
+int jv_loudness(jv_context* ctx, const float* wav, const int32_t* lens, int B, int n, int fs, float* lufs, void* stream);
+int jv_level_gain(jv_context* ctx, const float* lufs, const float* peak, int B, double target_lufs, double ceiling, float* gain,
+                  void* stream);
+int jv_level_apply(jv_context* ctx, const float* wav, const int32_t* lens, const int32_t* start, const int32_t* end,
+                   const float* gain, int B, int n, int tail, float* out, int64_t n_out, int32_t* out_lens, void* stream);
+
 /* ---- evaluation forward(): alignment search and the three losses (no gradients) --------------------------------
  * What JyutVoiceTTS.forward (jyutvoice_tts.py:255-364) computes between the encoder and its return, around one call of
  * jv_flow_estimator_step.  Tensors are device pointers: mu_x [B,80,Tx], h = decoder_h [B,Ty,80] (batch, time, channel), x_lens and

@@ -26,6 +26,12 @@ mel extractor.  Instead this CLI takes their outputs directly:
                              extension.  Each utterance's prompt_h (2 frames per prompt token) and prompt mel are trimmed
                              to the shorter of the two first: the batch takes one prompt length per utterance
     --sample_rate R          write the audio at R Hz instead of 24000 (resampled on the GPU, the whole batch in one call)
+    --prompt-trim-db DB      every "prompt_wav" / "prompt_wav_24k" recording is conditioned on the GPU, at its own rate, before the
+    --prompt-peak V          resample, as the CosyVoice2 front-ends condition theirs: energy trim DB below the loudest frame (frame
+    --prompt-tail SECONDS    440, hop 220), scaled down to a peak of V, SECONDS of silence appended (upstream: 60, 0.8, 0.2)
+    --loudness LUFS          every output is brought to LUFS (ITU-R BS.1770-4 integrated loudness, measured and applied on the GPU
+    [--peak V]               before the output resample), the gain limited so that no sample exceeds V; the measured loudness and the
+                             applied gain are printed per output.  Not with --stream-hop: it needs the whole utterance
     --dump-ref-features DIR  every request with a "prompt_wav" (or "prompt_wav_24k") also gets what infer.py:98-163 feeds the two ONNX
                              front-ends from the recording's 16 kHz copy: DIR/ref_NNN_fbank.npy (kaldi fbank minus its mean over
                              frames, [T, 80]) and DIR/ref_NNN_logmel.npy (whisper log-mel, [128, T]), NNN the request's number; all
@@ -104,6 +110,38 @@ def read_prompt_wav(tok):
     return read_wav_24k(tok["prompt_wav_24k"]), 24000
 
 
+def prompt_conditioning(args):
+    """the --prompt-* flags as condition_prompt's arguments, or None when none of them is given"""
+    if args.prompt_trim_db is None and args.prompt_peak is None and args.prompt_tail is None:
+        return None
+    return dict(top_db=args.prompt_trim_db, peak=args.prompt_peak, tail_seconds=args.prompt_tail or 0.0)
+
+
+def prompt_mels(recs, args, device):
+    """the prompt mels of (recording, rate) pairs in one ragged pass at 24 kHz, conditioned first when a --prompt-* flag asks"""
+    from jyutvoice_amd.utils.audio import condition_prompt, extract_speech_feat_batch
+    wavs, rates = [w for w, _ in recs], [r for _, r in recs]
+    cond = prompt_conditioning(args)
+    if cond is None:
+        return extract_speech_feat_batch(wavs, device, sample_rates=rates)
+    try:
+        rows, lens = condition_prompt(wavs, rates, device=device, **cond)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    return extract_speech_feat_batch(rows, device, sample_rates=rates, lengths=lens)
+
+
+def output_loudness(wav, samples, args, first=0):
+    """--loudness: wav [B, n] at 24 kHz, utterance b in [:samples[b]] -> the same batch at args.loudness LUFS (one set of calls)"""
+    if args.loudness is None:
+        return wav
+    from jyutvoice_amd.utils.audio import normalize_loudness
+    wav, lufs, gain = normalize_loudness(wav, 24000, args.loudness, args.peak, lens=samples)
+    for b, (l, g) in enumerate(zip(lufs.tolist(), gain.tolist())):
+        print(f"output {first + b}: measured {l:.2f} LUFS, gain {g:.4f}")
+    return wav
+
+
 def dump_ref_features(toks, args, device):
     """--dump-ref-features: the speaker fbank and the tokenizer log-mel of every request's recording, one ragged batch per feature"""
     import numpy as np
@@ -171,9 +209,9 @@ def synthesise_list(toks, args, tts, hift, device):
             ptok[i, : plens[i]] = torch.tensor(toks[b]["prompt_token"], dtype=torch.int64)
         h, h_len = flow_encoder(ptok, plens)
         from_wav = [b for b in with_prompt if "prompt_wav_24k" in toks[b] or "prompt_wav" in toks[b]]
-        if any("prompt_wav" in toks[b] for b in from_wav):      # recordings at rates of their own: grouped by rate, resampled on the GPU
-            recs = [read_prompt_wav(toks[b]) for b in from_wav]
-            mel, mel_len = extract_speech_feat_batch([w for w, _ in recs], device, sample_rates=[r for _, r in recs])
+        if from_wav and (any("prompt_wav" in toks[b] for b in from_wav) or prompt_conditioning(args)):
+            # recordings at rates of their own: grouped by rate, (conditioned and) resampled on the GPU
+            mel, mel_len = prompt_mels([read_prompt_wav(toks[b]) for b in from_wav], args, device)
         elif from_wav:
             mel, mel_len = extract_speech_feat_batch([read_wav_24k(toks[b]["prompt_wav_24k"]) for b in from_wav], device)
         for i, b in enumerate(with_prompt):
@@ -202,6 +240,7 @@ def synthesise_list(toks, args, tts, hift, device):
     print(f"Synthesis time: {time.time() - start:.2f} s (rtf of synthesise(): {result['rtf']:.4f})")
     samples = result["mel_lengths"] * 480
     dump_mels(args, [result["mel"][b, :, :n] for b, n in enumerate(result["mel_lengths"].tolist())])
+    wav = output_loudness(wav, samples, args)
     if args.sample_rate != 24000:      # the whole batch in one ragged call, each utterance at its own length
         from jyutvoice_amd.utils.audio import resample
         wav, samples = resample(wav, 24000, args.sample_rate, lengths=samples)
@@ -247,7 +286,8 @@ def synthesise_inflight(toks, ids, spk, feats, hs, args, tts, hift):
                 server.submit(i["x"], i["x_lengths"], i["lang"], i["tone"], i["word_pos"], i["syllable_pos"], spk[b:b + 1],
                               prompt_feat=feats[b][None] if p else None, prompt_h=hs[b][None] if p else None,
                               n_timesteps=int(t.get("n_timesteps", args.n_timesteps)), temperature=float(t.get("temperature", 1.0)),
-                              length_scale=float(t.get("length_scale", args.length_scale)), seed=int(t.get("seed", args.seed + b)))
+                              length_scale=float(t.get("length_scale", args.length_scale)), seed=int(t.get("seed", args.seed + b)),
+                              loudness=args.loudness, peak=args.peak)
             except ValueError as e:
                 raise SystemExit(f"{args.tokens}: {e}")
         out.update(server.step())
@@ -261,6 +301,8 @@ def synthesise_inflight(toks, ids, spk, feats, hs, args, tts, hift):
     stem, ext = os.path.splitext(args.output)
     for b in range(B):
         wav, n = out[b]["wav"], 480 * out[b]["mel_length"]
+        if "lufs" in out[b]:
+            print(f"output {b}: measured {out[b]['lufs']:.2f} LUFS, gain {out[b]['gain']:.4f}")
         if args.sample_rate != 24000:
             from jyutvoice_amd.utils.audio import resample
             wav, lens = resample(wav, 24000, args.sample_rate, lengths=torch.tensor([n]))
@@ -319,9 +361,7 @@ def token2wav_list(reqs, args, device):
     feats = [torch.zeros(0, 80)] * B
     from_wav = [b for b, r in enumerate(reqs) if "prompt_wav" in r or "prompt_wav_24k" in r]
     if from_wav:
-        from jyutvoice_amd.utils.audio import extract_speech_feat_batch
-        recs = [read_prompt_wav(reqs[b]) for b in from_wav]
-        mel, mel_len = extract_speech_feat_batch([w for w, _ in recs], device, sample_rates=[r for _, r in recs])
+        mel, mel_len = prompt_mels([read_prompt_wav(reqs[b]) for b in from_wav], args, device)
         for j, b in enumerate(from_wav):
             feats[b] = mel[j, : int(mel_len[j])].cpu()
     for b, r in enumerate(reqs):
@@ -356,6 +396,7 @@ def token2wav_list(reqs, args, device):
         torch.cuda.synchronize()
         print(f"Synthesis time: {time.time() - start:.2f} s")
         samples = flow.mel_lengths.to(torch.int64) * 480
+    wav = output_loudness(wav, samples, args)
     if args.sample_rate != 24000:
         from jyutvoice_amd.utils.audio import resample
         wav, samples = resample(wav, 24000, args.sample_rate, lengths=samples)
@@ -494,7 +535,29 @@ def main(argv=None):
     p.add_argument("--sample_rate", type=int, default=24000, help="sample rate of the written audio (resampled on the GPU)")
     p.add_argument("--dump-ref-features", default=None, metavar="DIR",
                    help="also write each request's reference-recording features (fbank, whisper log-mel) as .npy files into DIR")
+    p.add_argument("--prompt-trim-db", type=float, default=None, metavar="DB",
+                   help="trim each prompt recording's leading / trailing silence, DB below its loudest frame (upstream: 60)")
+    p.add_argument("--prompt-peak", type=float, default=None, metavar="V",
+                   help="scale a prompt recording down to a peak of V when it exceeds it (upstream: 0.8)")
+    p.add_argument("--prompt-tail", type=float, default=None, metavar="SECONDS",
+                   help="append SECONDS of silence to each prompt recording (upstream: 0.2)")
+    p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                   help="bring every output to LUFS (ITU-R BS.1770-4 integrated loudness), on the GPU, before the output resample")
+    p.add_argument("--peak", type=float, default=None, metavar="V", help="--loudness: limit the gain so that no sample exceeds V")
     args = p.parse_args(argv)
+    if args.loudness is not None and (args.stream_hop or args.stream_sessions):
+        p.error("--loudness cannot be combined with --stream-hop / --stream-sessions: integrated loudness needs the whole utterance, "
+                "and a streaming session hands its audio out piece by piece")
+    if args.peak is not None and args.loudness is None:
+        p.error("--peak limits the gain of --loudness: give --loudness LUFS too")
+    if args.loudness is not None and not abs(args.loudness) < float("inf"):
+        p.error("--loudness must be finite")
+    for name in ("peak", "prompt_peak", "prompt_trim_db"):
+        v = getattr(args, name)
+        if v is not None and not 0 < v < float("inf"):
+            p.error(f"--{name.replace('_', '-')} must be positive and finite")
+    if args.prompt_tail is not None and not 0 <= args.prompt_tail < float("inf"):
+        p.error("--prompt-tail must be >= 0 and finite")
     if args.sample_rate <= 0:
         raise SystemExit("--sample_rate must be positive")
     if args.sample_rate != 24000:      # a rate whose filter table the library refuses: say so before anything is loaded
@@ -563,7 +626,10 @@ def main(argv=None):
             flow_encoder = load_flow_encoder(args.flow_encoder, device)
             ptok = torch.tensor(tok["prompt_token"], dtype=torch.int64).view(1, -1)
             prompt_h, _ = flow_encoder(ptok, torch.tensor([ptok.shape[1]], dtype=torch.int64))
-            if "prompt_wav" in tok:      # infer.py:368-382: the recording at its own rate -> 24 kHz on the GPU
+            if ("prompt_wav" in tok or "prompt_wav_24k" in tok) and prompt_conditioning(args):
+                mel, mel_len = prompt_mels([read_prompt_wav(tok)], args, device)
+                prompt_feat = mel[:, : int(mel_len[0])]
+            elif "prompt_wav" in tok:      # infer.py:368-382: the recording at its own rate -> 24 kHz on the GPU
                 from jyutvoice_amd.utils.audio import extract_speech_feat, resample
                 speech, rate = read_prompt_wav(tok)
                 prompt_feat, _ = extract_speech_feat(resample(speech, rate, 24000, device=device), device)
@@ -585,6 +651,7 @@ def main(argv=None):
     wav, _ = hift.inference(result["mel"])
     torch.cuda.synchronize()
     print(f"Synthesis time: {time.time() - start:.2f} s (rtf of synthesise(): {result['rtf']:.4f})")
+    wav = output_loudness(wav, None, args)
     if args.sample_rate != 24000:
         from jyutvoice_amd.utils.audio import resample
         wav = resample(wav, 24000, args.sample_rate)

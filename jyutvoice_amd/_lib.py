@@ -82,6 +82,13 @@ SIGNATURES = {
     "jv_load_whisper_filters": (_i, [_p, _p, _i64, _i, _p]),
     "jv_fbank": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "jv_whisper_log_mel": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
+    "jv_kweight_coeffs": (_i, [_i, C.POINTER(C.c_double)]),
+    "jv_loudness_blocks": (_i64, [_i64, _i]),
+    "jv_trim_bounds": (_i, [_p, _p, _p, _i, _i, _f, _i, _i, _p, _p, _p]),
+    "jv_peak": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p]),
+    "jv_loudness": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
+    "jv_level_gain": (_i, [_p, _p, _p, _i, C.c_double, C.c_double, _p, _p]),
+    "jv_level_apply": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i64, _p, _p]),
     "jv_log_prior": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "jv_maximum_path": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "jv_align": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),

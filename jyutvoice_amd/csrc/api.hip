@@ -246,6 +246,7 @@ void jv_destroy(jv_context* ctx) {
   jv::resample_ws_destroy(c);
   jv::feat16k_ws_destroy(c);
   jv::align_ws_destroy(c);
+  jv::level_ws_destroy(c);
   delete ctx;
 }
 

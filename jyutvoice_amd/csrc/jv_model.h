@@ -186,6 +186,7 @@ struct Context {
   struct AudioWs* aws = nullptr;
   struct ResampleWs* rws = nullptr;   // resampling tables per reduced rate pair (resample.hip): not workspace, survives jv_reserve
   struct FeatWs* fws = nullptr;       // windows, DFT bases, mel weights and per-tile partials of the 16 kHz features (feat16k.hip): not workspace, survives jv_reserve
+  struct LevelWs* lws = nullptr;      // K-weighting power tables per sample rate and the per-call intermediates of trim / loudness (level.hip): not workspace, survives jv_reserve
   struct AlignWs* alws = nullptr;     // transposed log prior, decision bits and loss partials of forward() (align.hip): not workspace, survives jv_reserve
   std::string last_error;
 };
@@ -256,6 +257,9 @@ void feat16k_ws_destroy(Context& c);
 
 // align.hip
 void align_ws_destroy(Context& c);
+
+// level.hip
+void level_ws_destroy(Context& c);
 
 }  // namespace jv
 

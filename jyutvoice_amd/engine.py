@@ -306,6 +306,98 @@ class Engine:
                                    _ptr(out_lens), _stream(self.device)))
         return out if lens is None else (out, out_lens)
 
+    # ---- levels: silence trim, peak, BS.1770 loudness, gain -------------------------------------------
+    def _level_in(self, who, wav, lens):
+        w = _f32(wav, self.device)
+        if w.dim() != 2:
+            raise ValueError(f"{who}: wav must be [B, n], got {tuple(w.shape)}")
+        return w, self._level_vec(who, "lens", lens, w.shape[0], torch.int32)
+
+    def _level_vec(self, who, name, v, B, dtype):
+        if v is None:
+            return None
+        v = v.to(device=self.device, dtype=dtype).contiguous()
+        if v.shape != (B,):
+            raise ValueError(f"{who}: {name} must have shape [{B}], got {tuple(v.shape)}")
+        return v
+
+    def trim_bounds(self, wav, lens=None, top_db=60.0, frame_length=440, hop_length=220):
+        """librosa.effects.trim's bounds with zero centre padding (jv_trim_bounds): wav [B, n], lens [B] sample counts or None
+        -> (start, end) int32 [B] on the device; recording b without its leading / trailing silence is wav[b, start[b]:end[b]]"""
+        who = "trim_bounds"
+        w, wl = self._level_in(who, wav, lens)
+        if not (isinstance(top_db, (int, float)) and top_db > 0 and top_db != float("inf")):
+            raise ValueError(f"{who}: top_db must be positive and finite, got {top_db!r}")
+        if not (isinstance(frame_length, int) and 1 <= frame_length <= 8192):
+            raise ValueError(f"{who}: frame_length must be an int in [1, 8192], got {frame_length!r}")
+        if not (isinstance(hop_length, int) and hop_length >= 1):
+            raise ValueError(f"{who}: hop_length must be an int >= 1, got {hop_length!r}")
+        B, n = w.shape
+        start = torch.empty(B, dtype=torch.int32, device=self.device)
+        end = torch.empty_like(start)
+        check(self.lib.jv_trim_bounds(self._h, _ptr(w), _ptr(wl), B, n, float(top_db), frame_length, hop_length, _ptr(start),
+                                      _ptr(end), _stream(self.device)))
+        return start, end
+
+    def peak(self, wav, lens=None, start=None, end=None):
+        """max |wav[b, start[b]:end[b]]| (the whole recording without bounds), exact (jv_peak) -> [B] fp32 on the device"""
+        who = "peak"
+        w, wl = self._level_in(who, wav, lens)
+        B, n = w.shape
+        s, e = self._level_vec(who, "start", start, B, torch.int32), self._level_vec(who, "end", end, B, torch.int32)
+        out = torch.empty(B, device=self.device)
+        check(self.lib.jv_peak(self._h, _ptr(w), _ptr(wl), _ptr(s), _ptr(e), B, n, _ptr(out), _stream(self.device)))
+        return out
+
+    def loudness(self, wav, sample_rate, lens=None):
+        """integrated loudness after ITU-R BS.1770-4, mono (jv_loudness): wav [B, n] at sample_rate -> [B] LUFS on the device;
+        -inf for a recording shorter than 400 ms or with no block above -70 LUFS"""
+        who = "loudness"
+        w, wl = self._level_in(who, wav, lens)
+        if not (isinstance(sample_rate, int) and 8000 <= sample_rate <= 192000):
+            raise ValueError(f"{who}: sample_rate must be an int in [8000, 192000], got {sample_rate!r}")
+        B, n = w.shape
+        out = torch.empty(B, device=self.device)
+        check(self.lib.jv_loudness(self._h, _ptr(w), _ptr(wl), B, n, sample_rate, _ptr(out), _stream(self.device)))
+        return out
+
+    def level_gain(self, lufs=None, peak=None, target=-23.0, ceiling=None):
+        """the gain that brings a recording of `lufs` to `target`, limited so that its peak stays at `ceiling` (None: no limit);
+        lufs None: the prompt rule, ceiling / peak where peak > ceiling, else 1 (jv_level_gain) -> [B] fp32 on the device"""
+        who = "level_gain"
+        if lufs is None and peak is None:
+            raise ValueError(f"{who}: needs lufs, peak or both")
+        B = (lufs if lufs is not None else peak).shape[0]
+        lu, pk = self._level_vec(who, "lufs", lufs, B, torch.float32), self._level_vec(who, "peak", peak, B, torch.float32)
+        if ceiling is not None and not (isinstance(ceiling, (int, float)) and 0 < ceiling < float("inf")):
+            raise ValueError(f"{who}: ceiling must be positive and finite (or None), got {ceiling!r}")
+        if ceiling is not None and pk is None:
+            raise ValueError(f"{who}: a ceiling needs peak")
+        if lu is None and ceiling is None:
+            raise ValueError(f"{who}: without lufs (the prompt rule) a ceiling is needed")
+        if lu is not None and not (isinstance(target, (int, float)) and abs(target) < float("inf")):
+            raise ValueError(f"{who}: target must be finite, got {target!r}")
+        out = torch.empty(B, device=self.device)
+        check(self.lib.jv_level_gain(self._h, _ptr(lu), _ptr(pk), B, float(target), float(ceiling or 0.0), _ptr(out),
+                                     _stream(self.device)))
+        return out
+
+    def level_apply(self, wav, lens=None, start=None, end=None, gain=None, tail=0):
+        """out[b, :e - s] = wav[b, s:e] * gain[b], then `tail` zeros, exact zeros behind (jv_level_apply; bounds default to the
+        recording, the gain to 1) -> (out [B, n + tail], out_lens int32 [B] = e - s + tail)"""
+        who = "level_apply"
+        w, wl = self._level_in(who, wav, lens)
+        B, n = w.shape
+        if not (isinstance(tail, int) and tail >= 0):
+            raise ValueError(f"{who}: tail must be an int >= 0, got {tail!r}")
+        s, e = self._level_vec(who, "start", start, B, torch.int32), self._level_vec(who, "end", end, B, torch.int32)
+        g = self._level_vec(who, "gain", gain, B, torch.float32)
+        out = torch.empty(B, n + tail, device=self.device)
+        out_lens = torch.empty(B, dtype=torch.int32, device=self.device)
+        check(self.lib.jv_level_apply(self._h, _ptr(w), _ptr(wl), _ptr(s), _ptr(e), _ptr(g), B, n, tail, _ptr(out), out.shape[1],
+                                      _ptr(out_lens), _stream(self.device)))
+        return out, out_lens
+
     # ---- reference-audio features at 16 kHz -----------------------------------------------------------
     def load_whisper_filters(self, filters: torch.Tensor):
         """the [128, 201] filterbank whisper ships (librosa.filters.mel(sr=16000, n_fft=400, n_mels=128)); jv_load_whisper_filters"""

@@ -73,8 +73,9 @@ def admit_plan(waiting: Sequence[int], active: Sequence[int], free_slots: int, r
 
 
 class _Request:
-    def __init__(self, rid, args, prompt_feat, prompt_h, n, temperature, length_scale, seed):
+    def __init__(self, rid, args, prompt_feat, prompt_h, n, temperature, length_scale, seed, loudness=None, peak=None):
         self.rid, self.args, self.prompt_feat, self.prompt_h = rid, args, prompt_feat, prompt_h
+        self.loudness, self.peak = loudness, peak      # target LUFS and peak ceiling of the output, or None
         self.n, self.temperature, self.length_scale, self.seed = n, temperature, length_scale, seed
         self.p = 0 if prompt_feat is None else int(prompt_feat.shape[1])
         self.tt, self.dts = step_table(n)
@@ -101,6 +102,10 @@ class SynthServer:
     `hift.inference` of that mel bit for bit in its source signal -- and frees their slots.
     -> {rid: {"wav" [1, 480 y], "mel" [1, 80, y], "mel_length": y, "source" [1, 1, 480 y]}}; a request that cannot be served (more
     frames than max_frames once its durations are known) comes back as {rid: {"error": message}}.
+    A request submitted with `loudness` (LUFS; optionally `peak`, a ceiling on |sample|) has its audio brought to that integrated
+    loudness (ITU-R BS.1770-4): the requests of a step that ask for it are measured and scaled together after the vocoder
+    (jv_loudness, jv_peak, jv_level_gain, jv_level_apply), and their results gain "lufs" (as measured) and "gain" (as applied); each
+    gets the bits `normalize_loudness` of its own audio gives, and a request without the option is untouched.
 
     One reservation at construction for max_sessions utterances of max_frames frames / max_tokens tokens: no step rebuilds a context.
     row_capacity (default: what that reservation holds) bounds the rows of a step.  `engine`: the library context to run on
@@ -140,7 +145,7 @@ class SynthServer:
 
     # ---- host only ------------------------------------------------------------------------------------------------------------------
     def submit(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed, prompt_feat=None, prompt_h=None, n_timesteps=10,
-               temperature=1.0, length_scale=1.0, seed=None) -> int:
+               temperature=1.0, length_scale=1.0, seed=None, loudness=None, peak=None) -> int:
         rid = self._next_rid
         who = f"SynthServer.submit(): request {rid}"
         ids = {"x": x, "lang": lang, "tone": tone, "word_pos": word_pos, "syllable_pos": syllable_pos}
@@ -175,6 +180,12 @@ class SynthServer:
             raise ValueError(f"{who}: temperature must be finite, got {temperature}")
         if not math.isfinite(length_scale) or length_scale <= 0:
             raise ValueError(f"{who}: length_scale must be positive, got {length_scale}")
+        if loudness is not None and not (isinstance(loudness, (int, float)) and math.isfinite(loudness)):
+            raise ValueError(f"{who}: loudness must be a finite number of LUFS (or None), got {loudness!r}")
+        if peak is not None and not (isinstance(peak, (int, float)) and math.isfinite(peak) and peak > 0):
+            raise ValueError(f"{who}: peak must be positive and finite (or None), got {peak!r}")
+        if peak is not None and loudness is None:
+            raise ValueError(f"{who}: peak limits the gain of loudness: give loudness too")
         p = 0 if prompt_feat is None else prompt_feat.shape[1]
         # every token gets at least one frame unless length_scale shortens it; the prompt alone must leave room for one
         least = p + max(1, int(xl[0]) if length_scale >= 1.0 else 1)
@@ -184,7 +195,8 @@ class SynthServer:
         if seed is None:      # (a host draw, as HiFTGenerator draws it)
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
         args = (x, xl.to(torch.int64), lang, tone, word_pos, syllable_pos, spk_embed)
-        self._waiting.append(_Request(rid, args, prompt_feat, prompt_h, n_timesteps, temperature, length_scale, int(seed)))
+        self._waiting.append(_Request(rid, args, prompt_feat, prompt_h, n_timesteps, temperature, length_scale, int(seed),
+                                      None if loudness is None else float(loudness), None if peak is None else float(peak)))
         self._next_rid += 1
         return rid
 
@@ -271,7 +283,31 @@ class SynthServer:
             self.vocoder.close(r.slot)
             del self._active[r.slot]
             self._free.append(r.slot)
+        self._normalize(eng, [r for r in fin if r.loudness is not None], done)
         return done
+
+    def _normalize(self, eng, reqs: List[_Request], done: Dict[int, dict]):
+        """the finished requests that asked for a loudness, as one ragged batch: one measurement, one gain per distinct
+        (loudness, peak), one scaling"""
+        if not reqs:
+            return
+        wavs = [done[r.rid]["wav"] for r in reqs]
+        lens = torch.tensor([w.shape[1] for w in wavs], dtype=torch.int32)
+        buf = torch.zeros(len(reqs), int(lens.max()), device=wavs[0].device)
+        for b, w in enumerate(wavs):
+            buf[b, : w.shape[1]] = w[0]
+        lens = lens.to(buf.device)
+        lufs, pk = eng.loudness(buf, spec.SAMPLE_RATE, lens), eng.peak(buf, lens)
+        gain = torch.ones(len(reqs), device=buf.device)
+        groups: Dict[tuple, List[int]] = {}
+        for b, r in enumerate(reqs):
+            groups.setdefault((r.loudness, r.peak), []).append(b)
+        for (target, ceiling), members in groups.items():
+            idx = torch.tensor(members, device=buf.device)
+            gain[idx] = eng.level_gain(lufs[idx], None if ceiling is None else pk[idx], target, ceiling)
+        out, _ = eng.level_apply(buf, lens, gain=gain)
+        for b, (r, l, g) in enumerate(zip(reqs, lufs.tolist(), gain.tolist())):
+            done[r.rid].update({"wav": out[b:b + 1, : wavs[b].shape[1]], "lufs": l, "gain": g})
 
     def drain(self) -> Dict[int, dict]:
         """step() until nothing is waiting or resident -> all results"""

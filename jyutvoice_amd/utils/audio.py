@@ -82,7 +82,7 @@ def extract_speech_feat(speech, device="cuda:0"):
     return feat, torch.tensor([feat.shape[1]], dtype=torch.int32, device=feat.device)
 
 
-def extract_speech_feat_batch(speeches, device="cuda:0", sample_rates=None):
+def extract_speech_feat_batch(speeches, device="cuda:0", sample_rates=None, lengths=None):
     """`extract_speech_feat` of several recordings of different durations in one GPU pass (jv_mel_spectrogram_ragged):
     speeches = list of [1, n_b] or [n_b] tensors at 24 kHz -> (speech_feat [B, Tmax, 80], zero behind each recording's frames,
     speech_feat_len [B] int32).  Recording b's frames are those of `extract_speech_feat(speeches[b])`, bit for bit.
@@ -90,13 +90,17 @@ def extract_speech_feat_batch(speeches, device="cuda:0", sample_rates=None):
     sample_rates (one int per recording): the recordings come at rates of their own (infer.py:368-382).  They are grouped by
     rate, each group goes through one ragged `jv_resample` call to 24 kHz, and the lengths it leaves on the device feed the
     ragged mel pass: recording b's frames are those of `extract_speech_feat(resample(speeches[b], sample_rates[b], 24000))`,
-    bit for bit.  None is the 24 kHz path above, untouched."""
+    bit for bit.  None is the 24 kHz path above, untouched.
+
+    lengths ([B] int32 on the device, what `condition_prompt` returns): recording b is speeches[b][:lengths[b]] and the rows may
+    be longer; the lengths never come down to the host here."""
     wavs = [s.reshape(-1).to(torch.float32) for s in speeches]
     if not wavs:
         raise ValueError("extract_speech_feat_batch: no recordings")
+    lengths = _device_lengths("extract_speech_feat_batch", lengths, len(wavs), torch.device(device))
     if sample_rates is not None:
-        return _extract_resampled(wavs, [int(r) for r in sample_rates], torch.device(device))
-    buf, lens = _pad_rows(wavs)
+        return _extract_resampled(wavs, [int(r) for r in sample_rates], torch.device(device), lengths)
+    buf, lens = _rows_of(wavs, range(len(wavs)), lengths)
     mel, mel_lens = _engine(torch.device(device)).mel_spectrogram(buf, lens)
     return mel.transpose(1, 2).contiguous(), mel_lens
 
@@ -109,7 +113,28 @@ def _pad_rows(wavs):
     return buf, lens
 
 
-def _extract_resampled(wavs, rates, dev):
+def _device_lengths(who, lengths, B, dev):
+    if lengths is None:
+        return None
+    lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32)
+    if lengths.shape != (B,):
+        raise ValueError(f"{who}: lengths must have shape [{B}], got {tuple(lengths.shape)}")
+    return lengths
+
+
+def _rows_of(wavs, members, lengths):
+    """the rows `members` as one padded batch and their lengths: from the rows' sizes on the host (`_pad_rows`), or -- with
+    device lengths -- stacked where the rows are, the lengths gathered on the device"""
+    members = list(members)
+    if lengths is None:
+        return _pad_rows([wavs[b] for b in members])
+    buf = torch.zeros(len(members), max(wavs[b].numel() for b in members), device=lengths.device)
+    for i, b in enumerate(members):
+        buf[i, : wavs[b].numel()] = wavs[b]
+    return buf, lengths[torch.tensor(members, device=lengths.device)]
+
+
+def _extract_resampled(wavs, rates, dev, lengths=None):
     if len(rates) != len(wavs):
         raise ValueError(f"extract_speech_feat_batch: {len(wavs)} recordings, {len(rates)} sample rates")
     eng = _engine(dev)
@@ -118,7 +143,7 @@ def _extract_resampled(wavs, rates, dev):
         groups.setdefault(r, []).append(b)
     done = []
     for r, members in groups.items():      # one ragged launch per rate; nothing comes back to the host
-        buf, lens = _pad_rows([wavs[b] for b in members])
+        buf, lens = _rows_of(wavs, members, lengths)
         out, out_lens = eng.resample(buf, r, _PARAMS["sampling_rate"], lens)
         done.append((torch.tensor(members, device=out.device), out, out_lens))
     wav24 = torch.zeros(len(wavs), max(out.shape[1] for _, out, _ in done), device=done[0][1].device)
@@ -153,6 +178,94 @@ def resample(waveform, orig_freq, new_freq, lengths=None, device="cuda:0"):
     if lengths is not None:
         return res
     return res if waveform.dim() == 2 else res.squeeze(0)
+
+
+# ---- levels: what a CosyVoice2 front-end does to a prompt before any feature, and programme loudness of the output ------------
+def _level_rows(who, wavs, lens, device):
+    if not isinstance(wavs, torch.Tensor):
+        wavs = torch.as_tensor(np.asarray(wavs))
+    if wavs.dim() not in (1, 2):
+        raise ValueError(f"{who}: wavs must be [n] or [B, n], got {tuple(wavs.shape)}")
+    if wavs.dim() == 1 and lens is not None:
+        raise ValueError(f"{who}: lens needs wavs as [B, n]")
+    dev = wavs.device if wavs.is_cuda else torch.device(device)
+    return get_runtime(dev).ensure(1, 64, 1), wavs.reshape(-1, wavs.shape[-1]).to(dev), wavs.dim() == 1
+
+
+def trim_silence(wavs, lens=None, top_db=60, frame_length=440, hop_length=220, device="cuda:0"):
+    """`librosa.effects.trim(y, top_db, frame_length, hop_length)` (zero centre padding) of every row on the GPU (jv_trim_bounds,
+    jv_level_apply): wavs [n] or [B, n], lens ([B] sample counts) or None -> (out, out_lens int32 [B] on the device); recording b
+    is out[b, :out_lens[b]], exact zeros behind.  Nothing comes back to the host."""
+    eng, w, single = _level_rows("trim_silence", wavs, lens, device)
+    start, end = eng.trim_bounds(w, lens, top_db, frame_length, hop_length)
+    out, out_lens = eng.level_apply(w, lens, start, end)
+    return (out[0] if single else out), out_lens
+
+
+def loudness(wavs, sample_rate, lens=None, device="cuda:0"):
+    """integrated loudness after ITU-R BS.1770-4, mono, on the GPU (jv_loudness): wavs [n] or [B, n] -> [B] LUFS on the device
+    (-inf for fewer than 400 ms or nothing above -70 LUFS)"""
+    eng, w, _ = _level_rows("loudness", wavs, lens, device)
+    return eng.loudness(w, sample_rate, lens)
+
+
+def normalize_loudness(wavs, sample_rate, target=-23.0, peak=None, lens=None, device="cuda:0"):
+    """bring every row to `target` LUFS, the gain limited so that no sample exceeds `peak` (None: no limit); a row without a
+    loudness (-inf) or all zeros keeps gain 1 -> (out like wavs, lufs [B] as measured, gain [B] as applied), all on the device"""
+    eng, w, single = _level_rows("normalize_loudness", wavs, lens, device)
+    lufs = eng.loudness(w, sample_rate, lens)
+    pk = eng.peak(w, lens) if peak is not None else None
+    gain = eng.level_gain(lufs, pk, target, peak)
+    out, _ = eng.level_apply(w, lens, gain=gain)
+    return (out[0] if single else out), lufs, gain
+
+
+def condition_prompt(speeches, sample_rates=None, top_db=60, peak=0.8, tail_seconds=0.2, device="cuda:0"):
+    """what the CosyVoice2 front-ends do to a reference recording before any feature is taken: energy trim (`top_db` below the
+    loudest frame, frame 440, hop 220 samples at whatever rate), scale down to a peak of `peak` (never up), append
+    `tail_seconds` of silence.  Either of top_db / peak may be None to skip that part.
+
+    speeches: a list of [n_b] / [1, n_b] recordings with sample_rates (one int per recording, or one int for all; None: one
+    rate, tail at 24 kHz) -> (list of rows, lens int32 [B] on the device): row b holds the conditioned recording in
+    [:lens[b]] and exact zeros behind.  A [B, n] tensor comes back as one padded batch [B, n + tail].  Grouped by rate, five
+    launches' worth of calls per rate, nothing comes back to the host: rows and lens go to `extract_speech_feat_batch`,
+    `extract_spk_feat_batch` and `extract_token_feat_batch` as (speeches, sample_rates, lengths=lens)."""
+    who = "condition_prompt"
+    batch = isinstance(speeches, torch.Tensor) and speeches.dim() == 2
+    wavs = [torch.as_tensor(s).reshape(-1).to(torch.float32) for s in speeches]
+    if not wavs:
+        raise ValueError(f"{who}: no recordings")
+    if sample_rates is None or isinstance(sample_rates, int):
+        rates = [24000 if sample_rates is None else sample_rates] * len(wavs)
+    else:
+        rates = [int(r) for r in sample_rates]
+    if len(rates) != len(wavs):
+        raise ValueError(f"{who}: {len(wavs)} recordings, {len(rates)} sample rates")
+    if any(r < 1 for r in rates):
+        raise ValueError(f"{who}: sample rates must be positive, got {rates}")
+    if not (isinstance(tail_seconds, (int, float)) and 0 <= tail_seconds < float("inf")):
+        raise ValueError(f"{who}: tail_seconds must be >= 0 and finite, got {tail_seconds!r}")
+    if peak is not None and not (isinstance(peak, (int, float)) and 0 < peak < float("inf")):
+        raise ValueError(f"{who}: peak must be positive and finite (or None), got {peak!r}")
+    if top_db is not None and not (isinstance(top_db, (int, float)) and 0 < top_db < float("inf")):
+        raise ValueError(f"{who}: top_db must be positive and finite (or None), got {top_db!r}")
+    dev = wavs[0].device if wavs[0].is_cuda else torch.device(device)
+    eng = get_runtime(dev).ensure(1, 64, 1)
+    groups = {}
+    for b, r in enumerate(rates):
+        groups.setdefault(r, []).append(b)
+    rows = [None] * len(wavs)
+    lens_out = torch.zeros(len(wavs), dtype=torch.int32, device=dev)
+    for r, members in groups.items():
+        buf, lens = _pad_rows([wavs[b] for b in members])
+        buf = buf.to(dev)
+        start, end = eng.trim_bounds(buf, lens, top_db) if top_db is not None else (None, None)
+        gain = eng.level_gain(None, eng.peak(buf, lens, start, end), ceiling=peak) if peak is not None else None
+        out, out_lens = eng.level_apply(buf, lens, start, end, gain, int(round(tail_seconds * r)))
+        lens_out[torch.tensor(members, device=dev)] = out_lens
+        for i, b in enumerate(members):
+            rows[b] = out[i]
+    return (torch.stack(rows) if batch else rows), lens_out
 
 
 _PCM, _FLOAT, _EXTENSIBLE = 1, 3, 0xFFFE
@@ -288,7 +401,7 @@ def extract_spk_feat(speech, device="cuda:0"):
     return _engine16k(dev).fbank(w, subtract_mean=True)[0]
 
 
-def _to16k_batch(who, speeches, sample_rates, dev, min_len):
+def _to16k_batch(who, speeches, sample_rates, dev, min_len, lengths=None):
     """recordings at rates of their own -> ([B, n] at 16 kHz on the device, lens int32 [B] on the device); grouped by rate, one
     ragged `jv_resample` per rate, nothing comes back to the host (as `_extract_resampled` does for 24 kHz)"""
     wavs = [torch.as_tensor(s).reshape(-1).to(torch.float32) for s in speeches]
@@ -297,19 +410,20 @@ def _to16k_batch(who, speeches, sample_rates, dev, min_len):
     rates = [16000] * len(wavs) if sample_rates is None else [int(r) for r in sample_rates]
     if len(rates) != len(wavs):
         raise ValueError(f"{who}: {len(wavs)} recordings, {len(rates)} sample rates")
+    lengths = _device_lengths(who, lengths, len(wavs), dev)
     for b, (w, r) in enumerate(zip(wavs, rates)):      # the lengths are on the host here: refuse what the reference would
-        if min_len and resample_length(w.numel(), r, 16000) < min_len:
+        if lengths is None and min_len and resample_length(w.numel(), r, 16000) < min_len:
             raise ValueError(f"{who}: recording {b}: {w.numel()} samples at {r} Hz are fewer than {min_len} at 16 kHz")
     eng = _engine16k(dev)
     if all(r == 16000 for r in rates):
-        buf, lens = _pad_rows(wavs)
+        buf, lens = _rows_of(wavs, range(len(wavs)), lengths)
         return eng, buf.to(dev), lens.to(dev)
     groups = {}
     for b, r in enumerate(rates):
         groups.setdefault(r, []).append(b)
     done = []
     for r, members in groups.items():
-        buf, lens = _pad_rows([wavs[b] for b in members])
+        buf, lens = _rows_of(wavs, members, lengths)
         out, out_lens = eng.resample(buf, r, 16000, lens)
         done.append((torch.tensor(members, device=out.device), out, out_lens))
     wav16 = torch.zeros(len(wavs), max(out.shape[1] for _, out, _ in done), device=done[0][1].device)
@@ -320,19 +434,21 @@ def _to16k_batch(who, speeches, sample_rates, dev, min_len):
     return eng, wav16, lens16
 
 
-def extract_spk_feat_batch(speeches, sample_rates=None, device="cuda:0"):
+def extract_spk_feat_batch(speeches, sample_rates=None, device="cuda:0", lengths=None):
     """`extract_spk_feat` of several recordings in one GPU pass: -> (spk_feat [B, Tmax, 80], exact zeros behind each recording's
     frames, lens int32 [B]).  sample_rates (one int per recording; None: all 16 kHz): grouped by rate and resampled to 16 kHz
     on the GPU; recording b's rows are those of `extract_spk_feat(resample(speeches[b], sample_rates[b], 16000))`, bit for bit.
-    A recording of fewer than 400 samples at 16 kHz has no frame: a zero row and length 0, as the reference's empty feature."""
-    eng, wav16, lens16 = _to16k_batch("extract_spk_feat_batch", speeches, sample_rates, torch.device(device), 0)
+    A recording of fewer than 400 samples at 16 kHz has no frame: a zero row and length 0, as the reference's empty feature.
+    lengths: as in `extract_speech_feat_batch`."""
+    eng, wav16, lens16 = _to16k_batch("extract_spk_feat_batch", speeches, sample_rates, torch.device(device), 0, lengths)
     return eng.fbank(wav16, lens16, subtract_mean=True)
 
 
-def extract_token_feat_batch(speeches, sample_rates=None, device="cuda:0"):
+def extract_token_feat_batch(speeches, sample_rates=None, device="cuda:0", lengths=None):
     """`log_mel_spectrogram` of several recordings in one GPU pass: -> (feat [B, 128, Tmax], zeros behind, lens int32 [B]); the
-    max - 8 clamp is each recording's own.  sample_rates as in `extract_spk_feat_batch`."""
-    eng, wav16, lens16 = _to16k_batch("extract_token_feat_batch", speeches, sample_rates, torch.device(device), 201)
+    max - 8 clamp is each recording's own.  sample_rates as in `extract_spk_feat_batch`; lengths as in `extract_speech_feat_batch`
+    (with them a recording too short for the reflect padding is not refused here: it gets a zero row and length 0)."""
+    eng, wav16, lens16 = _to16k_batch("extract_token_feat_batch", speeches, sample_rates, torch.device(device), 201, lengths)
     return eng.whisper_log_mel(wav16, lens16)
 
 
