@@ -112,6 +112,23 @@ int jv_flow_set_streaming(jv_context* ctx, int chunk_frames);
  * the GPU.  The in-library profiler (jv_profile_enable) forces the eager path because it brackets every
  * launch with events.  Results are bit-identical either way. */
 int jv_flow_set_graph(jv_context* ctx, int on);
+/* jv_flow_set_guidance: the classifier-free-guidance rate of ConditionalCFM.solve_euler (flow_matching.py:215-265,
+ * `inference_cfg_rate` of configs/base.yaml: x += dt ((1 + r) v(x, t | mu, spks, cond) - r v(x, t))), a context mode like
+ * jv_flow_set_streaming.  rates_host: n host floats, read before the call returns.  n = 0 (or rates_host = NULL): the default,
+ * 0.7 in every step.  n = 1: that rate in every step.  n > 1: one rate per Euler step -- a guidance window is the usual form --
+ * and a solve whose n_timesteps != n fails with JV_ERR_ARG naming both numbers before its first launch.  A rate must be finite
+ * and >= 0, else JV_ERR_ARG (the mode is then unchanged).  Read by every closed solve: jv_cfm_solve, jv_cfm_solve_prompted,
+ * jv_flow_token2mel, _partial and _ctx; not by jv_flow_estimator_step / _masked, which have no solver, nor by jv_cfm_pool_step
+ * (jv_cfm_pool_step_g takes a rate per request).  The rate reaches the update through a device table stepped with the step
+ * counter, as dt does, so a captured step (jv_flow_set_graph) replays with the rate of ITS step.
+ * NO-TWIN STEPS.  A step whose rate is exactly 0 needs no unconditional evaluation and runs on B samples, x += dt v(x, t | ...):
+ * a solve whose rates are all 0 never lays out, packs or computes a twin; a solve with mixed rates changes between the 2B- and
+ * the B-sample rows from step to step where both take the same estimator route (both beyond the 2048-row split-K seam, the same
+ * resnet launches, uniform rows) and otherwise keeps the twins in that step, where the update with rate 0 gives the same x.
+ * Either way the result meets the twin-keeping one within the bound of any change of batch geometry (2e-5).  Such solves are
+ * always eager.  JV_NO_TWIN_DROP=1 in the environment at jv_create keeps the twins in every step (for A/B runs).  With the
+ * default and with 0.7 set explicitly the update is the same fp32 operations in the same order as before this mode existed. */
+int jv_flow_set_guidance(jv_context* ctx, const float* rates_host, int n);
 /* jv_flow_set_contraction: how fp32 contractions are carried out on the 16-bit matrix cores.  exact_range = 0
  * (default): fp16x3 -- each operand split into two fp16 planes after an exact power-of-two scaling (22 significant bits,
  * three MFMA products, fp32 accumulate) -- wherever an upper bound of the operand is known, so that fp16's range cannot be
@@ -193,7 +210,12 @@ int jv_cfm_solve_prompted(jv_context* ctx, const float* mu_y, const int32_t* y_l
  *   _precision) apply as to any estimator call.  1 <= B <= max_batch, 1 <= lens_host[b] <= min(Tcap, max_frames), slots in range,
  *   none twice.
  * jv_cfm_pool_fetch: mel[b, :, t] = pool_x[slots_host[b], first_host[b] + t, :] for t < lens_host[b], zeros behind, mel [B,80,Tm]
- *   -- the unpack of jv_cfm_solve_prompted with first = p_b, len = y_b.  0 <= first_b, 0 <= len_b <= Tm, first_b + len_b <= Tcap. */
+ *   -- the unpack of jv_cfm_solve_prompted with first = p_b, len = y_b.  0 <= first_b, 0 <= len_b <= Tm, first_b + len_b <= Tcap.
+ * jv_cfm_pool_step_g: jv_cfm_pool_step with cfg_host[B], the guidance rate of each listed request in THIS step (finite and >= 0;
+ *   flow_matching.py:215-265 with the request's own inference_cfg_rate, or its guidance window's rate at this t): x += dt_b ((1 +
+ *   cfg_b) v(x, t_b | ...) - cfg_b v(x, t_b)).  jv_cfm_pool_step is this call with 0.7 for all, bit for bit.  A pool step always
+ *   carries two rows per frame, also for a request at rate 0: its twin is computed and (1 + 0) v_c - 0 v_u is v_c.  Dropping the
+ *   twins of individual requests inside a step (a mixed twin map) is a follow-up. */
 int jv_cfm_pool_admit(jv_context* ctx, const float* mu_y, const float* prompt_h, const float* prompt_feat, const float* spks,
                       const int32_t* y_lens_host, const int32_t* prompt_lens_host, const int32_t* slots_host,
                       const float* temperature_host, int B, int Ty, int Ph, int Pf, float* pool_x, float* pool_mu, float* pool_cond,
@@ -201,6 +223,9 @@ int jv_cfm_pool_admit(jv_context* ctx, const float* mu_y, const float* prompt_h,
 int jv_cfm_pool_step(jv_context* ctx, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks,
                      float* pool_amax, int slots, int Tcap, const int32_t* slots_host, const int32_t* lens_host, const float* t_host,
                      const float* dt_host, int B, void* stream);
+int jv_cfm_pool_step_g(jv_context* ctx, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks,
+                       float* pool_amax, int slots, int Tcap, const int32_t* slots_host, const int32_t* lens_host, const float* t_host,
+                       const float* dt_host, const float* cfg_host, int B, void* stream);
 int jv_cfm_pool_fetch(jv_context* ctx, const float* pool_x, int slots, int Tcap, const int32_t* slots_host, const int32_t* first_host,
                       const int32_t* lens_host, int B, int Tm, float* mel, void* stream);
 

@@ -165,6 +165,27 @@ def dump_ref_features(toks, args, device):
     print(f"Reference features of {len(idx)} recordings saved to: {args.dump_ref_features}")
 
 
+def guidance_kw(args, decoder):
+    """--cfg-rate / --cfg-window / --t-scheduler as the keywords of synthesise(), of the flow's inference calls and of the streaming
+    sessions.  A flag that was not given says nothing: `decoder`'s own inference_cfg_rate / t_scheduler hold (the window is placed on
+    the t of the schedule the solve will run)."""
+    from jyutvoice_amd.flow.flow_matching import decoder_settings
+    kw = {}
+    if args.t_scheduler is not None:
+        kw["t_scheduler"] = args.t_scheduler
+    if args.cfg_window is not None:
+        from jyutvoice_amd.serve import guidance_rates
+        conf_rate, conf_sched = decoder_settings(decoder)
+        try:
+            kw["cfg_schedule"] = guidance_rates(args.n_timesteps, conf_rate if args.cfg_rate is None else args.cfg_rate,
+                                                tuple(args.cfg_window), args.t_scheduler or conf_sched)
+        except ValueError as e:
+            raise SystemExit(f"--cfg-rate / --cfg-window: {e}")
+    elif args.cfg_rate is not None:
+        kw["cfg_rate"] = args.cfg_rate
+    return kw
+
+
 def synthesise_list(toks, args, tts, hift, device):
     """--tokens with a JSON list: all utterances in one batch through synthesise(batched=True, prompt_lengths=...)"""
     import torch
@@ -234,7 +255,7 @@ def synthesise_list(toks, args, tts, hift, device):
     result = tts.synthesise(x=batch["x"], x_lengths=x_lengths, lang=batch["lang"], tone=batch["tone"], word_pos=batch["word_pos"],
                             syllable_pos=batch["syllable_pos"], prompt_feat=prompt_feat, prompt_h=prompt_h, spk_embed=spk,
                             n_timesteps=args.n_timesteps, length_scale=args.length_scale, batched=True,
-                            prompt_lengths=prompt_lengths)
+                            prompt_lengths=prompt_lengths, **guidance_kw(args, tts.decoder))
     wav, _ = hift.inference(result["mel"], lengths=result["mel_lengths"])
     torch.cuda.synchronize()
     print(f"Synthesis time: {time.time() - start:.2f} s (rtf of synthesise(): {result['rtf']:.4f})")
@@ -264,7 +285,7 @@ def dump_mels(args, mels):
 def synthesise_inflight(toks, ids, spk, feats, hs, args, tts, hift):
     """--tokens list.json --inflight S: the list through one SynthServer with at most S resident requests, a new request submitted
     every --arrive-every steps; the same out_NNN files as the list route.  A request's own "n_timesteps", "temperature",
-    "length_scale" and "seed" keys override the command line's (seed: --seed + its index)."""
+    "length_scale", "seed", "cfg_rate" and "cfg_window" keys override the command line's (seed: --seed + its index)."""
     import torch
 
     from jyutvoice_amd.serve import SynthServer
@@ -287,7 +308,8 @@ def synthesise_inflight(toks, ids, spk, feats, hs, args, tts, hift):
                               prompt_feat=feats[b][None] if p else None, prompt_h=hs[b][None] if p else None,
                               n_timesteps=int(t.get("n_timesteps", args.n_timesteps)), temperature=float(t.get("temperature", 1.0)),
                               length_scale=float(t.get("length_scale", args.length_scale)), seed=int(t.get("seed", args.seed + b)),
-                              loudness=args.loudness, peak=args.peak)
+                              loudness=args.loudness, peak=args.peak, cfg_rate=t.get("cfg_rate", args.cfg_rate),
+                              cfg_window=t.get("cfg_window", args.cfg_window), t_scheduler=args.t_scheduler)
             except ValueError as e:
                 raise SystemExit(f"{args.tokens}: {e}")
         out.update(server.step())
@@ -389,7 +411,7 @@ def token2wav_list(reqs, args, device):
         start = time.time()
         try:
             mel, _ = flow.inference(token, token_len, prompt_token, prompt_token_len, prompt_feat, feat_len, embedding, args.streaming,
-                                    True, batched=True, n_timesteps=args.n_timesteps)
+                                    True, batched=True, n_timesteps=args.n_timesteps, **guidance_kw(args, flow.decoder))
         except ValueError as e:
             raise SystemExit(f"{args.token2wav}: {e}")
         wav, _ = hift.inference(mel, lengths=flow.mel_lengths)
@@ -423,7 +445,7 @@ def token2wav_sessions(args, flow, hift, token, token_len, prompt_token, prompt_
         first = None
         try:
             session = Token2WavStream(flow, hift, prompt_token[b:b + 1, :p], prompt_feat[b:b + 1, :f], embedding[b:b + 1], max(n, 1),
-                                      n_timesteps=args.n_timesteps)
+                                      n_timesteps=args.n_timesteps, **guidance_kw(args, flow.decoder))
             pieces = []
             for i in range(0, n, args.stream_hop):
                 pieces.append(session.push(token[b, i:min(i + args.stream_hop, n)]))
@@ -458,7 +480,7 @@ def token2wav_server(args, flow, hift, token, token_len, prompt_token, prompt_to
     B = token.shape[0]
     try:
         server = Token2WavServer(flow, hift, min(args.stream_sessions, B), max(int(token_len.max()), 1), n_timesteps=args.n_timesteps,
-                                 max_prompt_tokens=max(int(prompt_token_len.max()), (int(feat_len.max()) + 1) // 2))
+                                 max_prompt_tokens=max(int(prompt_token_len.max()), (int(feat_len.max()) + 1) // 2), **guidance_kw(args, flow.decoder))
     except ValueError as e:
         raise SystemExit(f"{args.token2wav}: {e}")
     pieces, live, pos, waiting, steps = [[] for _ in range(B)], {}, {}, list(range(B)), 0
@@ -531,6 +553,13 @@ def main(argv=None):
     p.add_argument("--estimator-precision", default="fp32", choices=["fp32", "fp16"],
                    help="fp16: the CFM estimator as the reference's fp16 TensorRT plan runs it (fp16 operands, fp32 accumulation); "
                         "encoders and vocoder unchanged (every route: ids, --token2wav, streaming, server)")
+    p.add_argument("--cfg-rate", type=float, default=None, metavar="R",
+                   help="classifier-free-guidance rate of the CFM solve, >= 0 (default: the decoder's inference_cfg_rate, 0.7); 0 runs "
+                        "the solve without unconditional twins.  Every mode takes it")
+    p.add_argument("--cfg-window", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="guide only the Euler steps whose t lies in [LO, HI); the others run at rate 0, without twins")
+    p.add_argument("--t-scheduler", default=None, choices=["cosine", "linear"],
+                   help="time schedule of the Euler steps (default: the decoder's t_scheduler, cosine in configs/base.yaml)")
     p.add_argument("--seed", type=int, default=0, help="seed of the vocoder's source-noise draws")
     p.add_argument("--sample_rate", type=int, default=24000, help="sample rate of the written audio (resampled on the GPU)")
     p.add_argument("--dump-ref-features", default=None, metavar="DIR",
@@ -647,7 +676,7 @@ def main(argv=None):
     start = time.time()
     result = tts.synthesise(x=ids["x"], x_lengths=x_lengths, lang=ids["lang"], tone=ids["tone"], word_pos=ids["word_pos"],
                             syllable_pos=ids["syllable_pos"], prompt_feat=prompt_feat, prompt_h=prompt_h, spk_embed=spk,
-                            n_timesteps=args.n_timesteps, length_scale=args.length_scale)
+                            n_timesteps=args.n_timesteps, length_scale=args.length_scale, **guidance_kw(args, tts.decoder))
     wav, _ = hift.inference(result["mel"])
     torch.cuda.synchronize()
     print(f"Synthesis time: {time.time() - start:.2f} s (rtf of synthesise(): {result['rtf']:.4f})")

@@ -55,6 +55,7 @@ SIGNATURES = {
     "jv_flow_estimator_masked": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
     "jv_flow_set_streaming": (_i, [_p, _i]),
     "jv_flow_set_graph": (_i, [_p, _i]),
+    "jv_flow_set_guidance": (_i, [_p, _p, _i]),
     "jv_flow_set_contraction": (_i, [_p, _i]),
     "jv_flow_set_precision": (_i, [_p, _i]),
     "jv_flow_contraction_info": (_i, [_p, _p, _i]),
@@ -62,6 +63,7 @@ SIGNATURES = {
     "jv_cfm_solve_prompted": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p]),
     "jv_cfm_pool_admit": (_i, [_p] * 9 + [_i] * 4 + [_p] * 5 + [_i, _i, _p]),
     "jv_cfm_pool_step": (_i, [_p] * 6 + [_i, _i] + [_p] * 4 + [_i, _p]),
+    "jv_cfm_pool_step_g": (_i, [_p] * 6 + [_i, _i] + [_p] * 5 + [_i, _p]),
     "jv_cfm_pool_fetch": (_i, [_p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _p]),
     "jv_flow_encoder_fwd": (_i,[_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "jv_flow_token2mel": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),

@@ -1,4 +1,6 @@
 // extern "C" surface of libjyutvoice_hip.so (include/jyutvoice_hip.h).  Nothing throws across it.
+#include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -184,6 +186,7 @@ int jv_create(jv_context** out, int device, int max_batch, int max_frames, int m
   c.no_ln_fold = getenv("JV_NO_LN_FOLD") != nullptr;
   c.no_temb_pre = getenv("JV_NO_TEMB_PRE") != nullptr;
   c.no_cfg_share = getenv("JV_NO_CFG_SHARE") != nullptr;
+  c.no_twin_drop = getenv("JV_NO_TWIN_DROP") != nullptr;
   c.no_hiftconv = getenv("JV_NO_HIFTCONV") != nullptr;
   c.no_hift_pair = getenv("JV_NO_HIFT_PAIR") != nullptr;
   c.max_frames = max_frames;
@@ -334,6 +337,21 @@ int jv_flow_set_streaming(jv_context* ctx, int chunk_frames) {
   return JV_OK;
 }
 
+// (host state only: the rates reach the device with the next solve's schedule, so nothing in flight is touched)
+int jv_flow_set_guidance(jv_context* ctx, const float* rates_host, int n) {
+  CTX_GUARD(ctx);
+  if (n < 0) return jv::fail(JV_ERR_ARG, "jv_flow_set_guidance: n must be >= 0");
+  if (n > 0 && !rates_host) n = 0;
+  for (int i = 0; i < n; ++i)
+    if (!jv::guidance_rate_ok(rates_host[i])) {
+      char msg[160];
+      snprintf(msg, sizeof msg, "jv_flow_set_guidance: rate %d of %d is %g: a guidance rate must be finite and >= 0", i, n, (double)rates_host[i]);
+      return jv::fail(JV_ERR_ARG, msg);
+    }
+  ctx->c.guidance.assign(rates_host, rates_host + n);
+  return JV_OK;
+}
+
 int jv_flow_set_graph(jv_context* ctx, int on) {
   CTX_GUARD(ctx);
   ctx->c.step_graphs = on != 0;
@@ -431,6 +449,16 @@ int jv_cfm_pool_step(jv_context* ctx, float* pool_x, const float* pool_mu, const
     return jv::fail(JV_ERR_ARG, "jv_cfm_pool_step: null argument");
   return jv::cfm_pool_step(ctx->c, pool_x, pool_mu, pool_cond, pool_spks, pool_amax, slots, Tcap, slots_host, lens_host, t_host,
                            dt_host, B, static_cast<hipStream_t>(stream));
+}
+
+int jv_cfm_pool_step_g(jv_context* ctx, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks,
+                       float* pool_amax, int slots, int Tcap, const int32_t* slots_host, const int32_t* lens_host, const float* t_host,
+                       const float* dt_host, const float* cfg_host, int B, void* stream) {
+  CTX_GUARD(ctx);
+  if (!pool_x || !pool_mu || !pool_cond || !pool_spks || !pool_amax || !slots_host || !lens_host || !t_host || !dt_host || !cfg_host)
+    return jv::fail(JV_ERR_ARG, "jv_cfm_pool_step_g: null argument");
+  return jv::cfm_pool_step(ctx->c, pool_x, pool_mu, pool_cond, pool_spks, pool_amax, slots, Tcap, slots_host, lens_host, t_host,
+                           dt_host, B, static_cast<hipStream_t>(stream), cfg_host);
 }
 
 int jv_cfm_pool_fetch(jv_context* ctx, const float* pool_x, int slots, int Tcap, const int32_t* slots_host, const int32_t* first_host,

@@ -135,10 +135,10 @@ int pool_gather(const PoolStepReq* req, int B, int tmax, int tfill, const float*
   return JV_OK;
 }
 
-// ---- Euler step with classifier-free guidance and a dt per request, written back to the pool (rowops.hip euler_cfg_kernel's
+// ---- Euler step with classifier-free guidance, a dt and a guidance rate per request (PoolStepReq::cfg), written back to the pool (rowops.hip euler_cfg_kernel's
 // expressions), and the maxima the estimator's launches left in the request's and its twin's slots --------------------------------
 __global__ __launch_bounds__(256) void pool_euler_scatter_kernel(const PoolStepReq* __restrict__ req, int B, const float* __restrict__ x,
-                                                                 const float* __restrict__ d, float rate, const float* __restrict__ amax,
+                                                                 const float* __restrict__ d, const float* __restrict__ amax,
                                                                  int amax_stride, float* __restrict__ pool_x, float* __restrict__ pool_amax,
                                                                  int Tcap) {
   const int b = blockIdx.y;
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void pool_euler_scatter_kernel(const PoolStepR
   const int t = (int)(idx / 20), cc = (int)(idx - (long)t * 20) * 4;
   if (t >= len) return;
   const long r = (long)req[b].row + t, ru = (long)req[b].rowu + t;
-  const float dt = req[b].dt;
+  const float dt = req[b].dt, rate = req[b].cfg;
   const f32x4 dc = *reinterpret_cast<const f32x4*>(d + r * 80 + cc);
   const f32x4 du = *reinterpret_cast<const f32x4*>(d + ru * 80 + cc);
   f32x4 xv = *reinterpret_cast<const f32x4*>(x + r * 80 + cc);
@@ -160,10 +160,10 @@ __global__ __launch_bounds__(256) void pool_euler_scatter_kernel(const PoolStepR
   *reinterpret_cast<f32x4*>(pool_x + ((long)slot * Tcap + t) * 80 + cc) = xv;
 }
 
-int pool_euler_scatter(const PoolStepReq* req, int B, int tmax, const float* x, const float* d, float rate, const float* amax,
+int pool_euler_scatter(const PoolStepReq* req, int B, int tmax, const float* x, const float* d, const float* amax,
                        int amax_stride, float* pool_x, float* pool_amax, int Tcap, hipStream_t st) {
   if (B <= 0 || tmax <= 0) return JV_OK;
-  hipLaunchKernelGGL(pool_euler_scatter_kernel, dim3((unsigned)cdivl((long)tmax * 20, 256), B), dim3(256), 0, st, req, B, x, d, rate,
+  hipLaunchKernelGGL(pool_euler_scatter_kernel, dim3((unsigned)cdivl((long)tmax * 20, 256), B), dim3(256), 0, st, req, B, x, d,
                      amax, amax_stride, pool_x, pool_amax, Tcap);
   JV_HIP(hipGetLastError());
   return JV_OK;

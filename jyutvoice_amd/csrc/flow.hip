@@ -48,6 +48,7 @@ int flow_ws_create(Context& c) {
   JV_TRY(F(&w->ts_emb, (size_t)TS_MAX * EST_NRES * 256));
   JV_TRY(F(&w->t_table, (size_t)w->max_steps));
   JV_TRY(F(&w->dt_table, (size_t)w->max_steps));
+  JV_TRY(F(&w->cfg_table, (size_t)w->max_steps));
   JV_TRY(ws_alloc(c, R, reinterpret_cast<void**>(&w->rowmask)));
   JV_TRY(ws_alloc(c, R * sizeof(int), reinterpret_cast<void**>(&w->row_sample)));
   JV_TRY(ws_alloc(c, (size_t)B2 * sizeof(int), reinterpret_cast<void**>(&w->lens2)));
@@ -61,6 +62,7 @@ int flow_ws_create(Context& c) {
   JV_TRY(ws_alloc(c, sizeof(int), reinterpret_cast<void**>(&w->step_ctr)));
   JV_TRY(F(&w->t_cur, 1));
   JV_TRY(F(&w->dt_cur, 1));
+  JV_TRY(F(&w->cfg_cur, 1));
   JV_HIP(hipStreamCreateWithFlags(&w->gstream, hipStreamNonBlocking));
   JV_HIP(hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming));
   JV_HIP(hipEventCreateWithFlags(&w->ev_out, hipEventDisableTiming));
@@ -85,11 +87,12 @@ void flow_ws_forget_attention(Context& c, hipStream_t st) {
 
 namespace {
 
-// (t, dt) of the step the device-side counter points at, then advance it: the only step-dependent state of a solve
+// (t, dt, guidance rate) of the step the device-side counter points at, then advance it: the only step-dependent state of a solve
 // (256 threads; emb_steps != null: the step's precomputed timestep embedding, [EST_NRES * 256] floats, moves to the fixed
 // place the estimator's launches read it from -- their arguments are frozen inside a captured graph)
-__global__ void step_advance_kernel(const float* __restrict__ t_table, const float* __restrict__ dt_table, int* ctr,
-                                    float* t_cur, float* dt_cur, const float* __restrict__ emb_steps, float* __restrict__ emb_cur) {
+__global__ void step_advance_kernel(const float* __restrict__ t_table, const float* __restrict__ dt_table,
+                                    const float* __restrict__ cfg_table, int* ctr, float* t_cur, float* dt_cur, float* cfg_cur,
+                                    const float* __restrict__ emb_steps, float* __restrict__ emb_cur) {
   const int i = *ctr;
   if (emb_steps)
     for (int k = threadIdx.x; k < EST_NRES * 256; k += 256) emb_cur[k] = emb_steps[(long)i * EST_NRES * 256 + k];
@@ -97,6 +100,7 @@ __global__ void step_advance_kernel(const float* __restrict__ t_table, const flo
   if (threadIdx.x == 0) {
     *t_cur = t_table[i];
     *dt_cur = dt_table[i];
+    *cfg_cur = cfg_table[i];
     *ctr = i + 1;
   }
 }
@@ -149,13 +153,39 @@ namespace {
 // ---- the three parts of a solve that cfm_solve and cfm_solve_prompted share: schedule, geometry, Euler loop ----------------
 // The entries differ in what they pack into the row buffers before the loop and in what they unpack after it.
 
-// (t, dt) of every step -> w.t_table / w.dt_table.  tt / dts are the caller's: pageable staging that must live until the
-// solve's one synchronisation has consumed the copies.
-int solve_schedule(FlowWs& w, int n_timesteps, const float* t_span_host, std::vector<float>& tt, std::vector<float>& dts,
-                   hipStream_t st) {
+// The guidance mode of the context (jv_flow_set_guidance) against a solve of n_timesteps steps: a schedule has one rate per step.
+// Called by every entry before its first launch.
+int guidance_check(const Context& c, const char* who, int n_timesteps) {
+  if (c.guidance.size() > 1 && (int)c.guidance.size() != n_timesteps) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: n_timesteps = %d, but the guidance schedule (jv_flow_set_guidance) holds %d rates: one per Euler step",
+             who, n_timesteps, (int)c.guidance.size());
+    return fail(JV_ERR_ARG, msg);
+  }
+  return JV_OK;
+}
+
+// the rate of step k: 0.7 where no mode is set (flow_matching.py:252-258, inference_cfg_rate of configs/base.yaml)
+float guidance_rate(const Context& c, int k) {
+  return c.guidance.empty() ? 0.7f : c.guidance.size() == 1 ? c.guidance[0] : c.guidance[(size_t)k];
+}
+
+// Does the solve lay out unconditional twins at all?  Not where every step's rate is exactly 0 (JV_NO_TWIN_DROP=1: always)
+bool solve_twins(const Context& c, int n_timesteps) {
+  if (c.no_twin_drop) return true;
+  for (int k = 0; k < n_timesteps; ++k)
+    if (guidance_rate(c, k) != 0.f) return true;
+  return false;
+}
+
+// (t, dt, guidance rate) of every step -> w.t_table / w.dt_table / w.cfg_table.  tt / dts are the caller's: pageable staging
+// that must live until the solve's one synchronisation has consumed the copies (the rates ride behind dts in the same vector).
+int solve_schedule(const Context& c, FlowWs& w, int n_timesteps, const float* t_span_host, std::vector<float>& tt,
+                   std::vector<float>& dts, hipStream_t st) {
   std::vector<float> ts(n_timesteps + 1);
   tt.resize(n_timesteps);
-  dts.resize(n_timesteps);
+  dts.resize(2 * (size_t)n_timesteps);
+  for (int k = 0; k < n_timesteps; ++k) dts[(size_t)n_timesteps + k] = guidance_rate(c, k);
   // cosine schedule and the reference's running (t, dt) recurrence, in fp32 (flow_matching.py:230,260-263,387-389)
   if (t_span_host) {
     for (int i = 0; i <= n_timesteps; ++i) ts[i] = t_span_host[i];
@@ -178,6 +208,7 @@ int solve_schedule(FlowWs& w, int n_timesteps, const float* t_span_host, std::ve
   }
   JV_HIP(hipMemcpyAsync(w.t_table, tt.data(), sizeof(float) * n_timesteps, hipMemcpyHostToDevice, st));
   JV_HIP(hipMemcpyAsync(w.dt_table, dts.data(), sizeof(float) * n_timesteps, hipMemcpyHostToDevice, st));
+  JV_HIP(hipMemcpyAsync(w.cfg_table, dts.data() + n_timesteps, sizeof(float) * n_timesteps, hipMemcpyHostToDevice, st));
   return JV_OK;
 }
 
@@ -185,9 +216,9 @@ int solve_schedule(FlowWs& w, int n_timesteps, const float* t_span_host, std::ve
 // taken when it saves at least 8 % of the rows and the shorter batch still fills the row-owning kernels.  All per-row
 // arithmetic is the uniform geometry's (a row's sums do not depend on where the row sits): the same bits per utterance.
 // h_lens: the B sequence lengths on the host (after the solve's synchronisation).
-// the rule alone, on host arrays (cfm_pool_step lays a step out by it as well): uoff[2B + 1] receives the first rows; true = compact
-bool compact_plan(const Context& c, long M_uniform, const int* h_lens, int B, int T, int* uoff, long* rows, long* frames_out) {
-  const int B2 = 2 * B;
+// the rule alone, on host arrays (cfm_pool_step lays a step out by it as well): uoff[B2 + 1] receives the first rows; true = compact
+// B2: the samples laid out, 2B, or B for a solve without guidance (M_uniform is then that geometry's row count as well)
+bool compact_plan(const Context& c, long M_uniform, const int* h_lens, int B, int B2, int T, int* uoff, long* rows, long* frames_out) {
   long r = FLOW_G, frames = 0;
   for (int b2 = 0; b2 < B2; ++b2) {
     const int len = std::min(std::max(h_lens[b2 % B], 0), T);
@@ -203,8 +234,8 @@ bool compact_plan(const Context& c, long M_uniform, const int* h_lens, int B, in
 int solve_compact(Context& c, Geo& g, const int* h_lens, int B, int T, hipStream_t st) {
   FlowWs& w = *c.flow;
   long r = 0, frames = 0;
-  if (compact_plan(c, g.M, h_lens, B, T, w.h_uoff, &r, &frames)) {
-    JV_HIP(hipMemcpyAsync(w.uoff, w.h_uoff, sizeof(int) * (2 * B + 1), hipMemcpyHostToDevice, st));      // (pinned: stays valid)
+  if (compact_plan(c, g.M, h_lens, B, g.B2, T, w.h_uoff, &r, &frames)) {
+    JV_HIP(hipMemcpyAsync(w.uoff, w.h_uoff, sizeof(int) * (g.B2 + 1), hipMemcpyHostToDevice, st));      // (pinned: stays valid)
     g.M = r; g.uoff = w.uoff; g.alg_rows = frames;
   }
   return JV_OK;
@@ -230,8 +261,10 @@ bool lens_all_equal(const int* h_lens, int B, int T) {
 
 // the Euler loop on packed row buffers (w.mu, w.cond, w.x = z, w.lens2, row metadata): the result is left in w.x
 // lens_equal: the host knows that all B utterances have the same number of frames (it learns so without a copy of its own)
+// g.B2 = 2B: the rows hold every utterance's unconditional twin; g.B2 = B (solve_twins: every rate is 0): none was laid out
 int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timesteps, bool lens_equal, hipStream_t st) {
   FlowWs& w = *c.flow;
+  const bool twins = g.B2 == 2 * B;
   JV_HIP(hipMemsetAsync(w.step_ctr, 0, sizeof(int), st));
   JV_HIP(hipMemsetAsync(w.amax, 0, sizeof(float) * 3 * w.amax_stride, st));      // trunk bounds: maxima over the whole solve
   JV_HIP(hipMemcpyAsync(w.spks, spks, sizeof(float) * 80 * B, hipMemcpyDeviceToDevice, st));
@@ -242,21 +275,53 @@ int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timest
   g.temb_pre = !c.no_temb_pre && n_timesteps <= TS_MAX;
   if (g.temb_pre) JV_TRY(time_embedding(c, w.t_table, 1, n_timesteps, w.ts_sin, w.ts_1, w.ts_mish, w.ts_emb, st));
   const EstRoute route = est_route(c, g.M, g.temb_pre, g.uoff != nullptr, c.attn_chunk);      // one route for every step (and for a captured one)
-  // one Euler step over `gg` / `rt` with `ntwin` unconditional twins: B of them, or the one shared twin of step 0 (the row tables
-  // were built for 2B samples: the first B + 1 are a prefix of them), after which the slots it stands for take its maxima
+  // one Euler step over `gg` / `rt` with `ntwin` unconditional twins: B of them, the one shared twin of step 0 (after which the
+  // slots it stands for take its maxima), or none in a step whose guidance rate is 0 (the row tables were built for 2B samples:
+  // the first B + 1, or B, are a prefix of them).  The step's rate comes through w.cfg_cur as its dt comes through w.dt_cur
   auto euler_step = [&](hipStream_t s, const Geo& gg, const EstRoute& rt, int ntwin) -> int {
-    const bool one_twin = ntwin < B;
-    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(256), 0, s, w.t_table, w.dt_table, w.step_ctr, w.t_cur, w.dt_cur,
-                       g.temb_pre ? w.ts_emb : nullptr, w.temb);
+    const bool one_twin = ntwin == 1 && B > 1;
+    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(256), 0, s, w.t_table, w.dt_table, w.cfg_table, w.step_ctr, w.t_cur,
+                       w.dt_cur, w.cfg_cur, g.temb_pre ? w.ts_emb : nullptr, w.temb);
     JV_TRY(assemble_xin(w.x, w.mu, w.spks, w.cond, w.xin, B, ntwin, FLOW_G, gg.S, T, gg.M, s, gg.uoff, w.row_sample, w.rowmask));
     JV_TRY(estimator_body(c, gg, rt, s));
-    JV_TRY(euler_cfg(w.x, w.d, B, FLOW_G, gg.S, T, w.dt_cur, 0, 0.7f, s, gg.uoff, w.lens2, one_twin));
+    JV_TRY(euler_cfg(w.x, w.d, B, FLOW_G, gg.S, T, w.dt_cur, 0, w.cfg_cur, s, gg.uoff, w.lens2, one_twin, ntwin == 0));
     if (one_twin) {
       hipLaunchKernelGGL(amax_share_kernel, dim3((unsigned)cdiv(3 * (B - 1), 64)), dim3(64), 0, s, w.amax, w.amax_stride, B);
       JV_HIP(hipGetLastError());
     }
     return JV_OK;
   };
+  auto same_resnets = [](const EstRoute& a, const EstRoute& b) {
+    for (int i = 0; i < EST_NRES; ++i)
+      if (a.stage[i].res != b.stage[i].res || a.stage[i].rows != b.stage[i].rows) return false;
+    return true;
+  };
+  // NO twin in a step whose guidance rate is exactly 0: (1 + 0) d_c - 0 d_u needs no d_u, so the step runs on the B conditional
+  // samples -- the prefix of the 2B-sample rows, as the shared first step below runs on a prefix of B + 1 -- and x += dt d.
+  // A solve whose rates are ALL 0 arrives here with g laid out for B samples and takes every step that way on `route`.  A solve
+  // with mixed rates changes geometry between steps and is bound by the rule the shared first step states: both geometries on the
+  // row-owning side of the split-K seam, the same resnet launches in both (trunk buffers, running maxima), uniform rows.  Where
+  // the rule is not met the step keeps its twins and euler_cfg with rate 0 gives the same x: the only degradation.
+  // JV_NO_TWIN_DROP=1: twins in every step.  (DESIGN.md 5 "Guidance")
+  std::vector<char> drop((size_t)n_timesteps, twins ? 0 : 1);
+  Geo gB = g;
+  EstRoute routeB = route;
+  if (twins && !c.no_twin_drop) {
+    bool any = false;
+    for (int k = 0; k < n_timesteps; ++k) any = any || guidance_rate(c, k) == 0.f;
+    const long MB = flow_rows(B, T);
+    if (any && !g.uoff && MB > PARTIAL_ROWS && rowgemm_tile((int)MB) != 0) {
+      gB.B2 = B; gB.M = MB; gB.alg_rows = 0;      // (the profiler's frames: B T)
+      routeB = est_route(c, MB, g.temb_pre, false, c.attn_chunk);      // once per geometry, not per step
+      if (!same_resnets(routeB, route)) routeB = est_route(c, MB, g.temb_pre, false, c.attn_chunk, false);
+      if (same_resnets(routeB, route))
+        for (int k = 0; k < n_timesteps; ++k) drop[(size_t)k] = guidance_rate(c, k) == 0.f;
+    }
+  }
+  bool any_drop = false;
+  for (int k = 0; k < n_timesteps; ++k) any_drop = any_drop || drop[(size_t)k];
+  // step k in the form its rate allows (eager)
+  auto step_k = [&](int k) -> int { return drop[(size_t)k] ? euler_step(st, twins ? gB : g, twins ? routeB : route, 0) : euler_step(st, g, route, B); };
   int done = 0;      // steps enqueued so far
   // ONE unconditional twin for the first step.  Every utterance starts from the same noise prefix, a twin has mu = spks = cond = 0
   // and t is one scalar: with equal lengths the B twins of step 0 are one sample B times over, so the step runs on B + 1 samples
@@ -264,18 +329,13 @@ int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timest
   // not depend on the batch or the tile height, but they do differ across the split-K seam: the shorter geometry has to stay on
   // the row-owning side of it as well.  JV_NO_CFG_SHARE=1: 2B samples in every step.  
   const long M0 = flow_rows(B + 1, T);
-  if (!c.no_cfg_share && lens_equal && B >= 2 && !g.uoff && M0 > PARTIAL_ROWS && rowgemm_tile((int)M0) != 0) {
+  if (twins && !drop[0] && !c.no_cfg_share && lens_equal && B >= 2 && !g.uoff && M0 > PARTIAL_ROWS && rowgemm_tile((int)M0) != 0) {
     Geo g0 = g;
     g0.B2 = B + 1; g0.M = M0; g0.alg_rows = 0;      // (the profiler's frames: (B + 1) T)
     // ... and every resnet has to take the same launches in both geometries: the one-launch form (which has to fit its rounds,
     // rowres_fits: a function of the row count) alternates the trunk between w.h and w.h2, the others keep it in w.h, and the
     // running maxima are kept per BUFFER -- a step 0 on other buffers would leave other maxima, the conditional samples'
     // included, to the later steps.  Where only the shorter geometry would fit the one-launch form, step 0 does without it
-    auto same_resnets = [](const EstRoute& a, const EstRoute& b) {
-      for (int i = 0; i < EST_NRES; ++i)
-        if (a.stage[i].res != b.stage[i].res || a.stage[i].rows != b.stage[i].rows) return false;
-      return true;
-    };
     EstRoute route0 = est_route(c, M0, g.temb_pre, false, c.attn_chunk);
     if (!same_resnets(route0, route)) route0 = est_route(c, M0, g.temb_pre, false, c.attn_chunk, false);
     if (same_resnets(route0, route)) {      // (always eager: a captured step is a 2B step)
@@ -284,9 +344,10 @@ int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timest
     }
   }
   // The in-library profiler brackets every launch with events, which a capture would turn into graph nodes: eager then.
-  const bool use_graph = c.step_graphs && !prof_on() && n_timesteps > 1 && !g.uoff;      // (a captured step is keyed by (B, T): uniform geometry only)
+  // ... and a captured step is a 2B step: a solve with a step without twins is eager throughout, so no 2B graph ever replays for it
+  const bool use_graph = c.step_graphs && !prof_on() && n_timesteps > 1 && !g.uoff && !any_drop;      // (a captured step is keyed by (B, T): uniform geometry only)
   if (!use_graph) {
-    for (int s = done; s < n_timesteps; ++s) JV_TRY(euler_step(st, g, route, B));
+    for (int s = done; s < n_timesteps; ++s) JV_TRY(step_k(s));
   } else {
     FlowWs::StepGraph* sg = nullptr;
     for (auto& e : w.graphs)
@@ -341,11 +402,12 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
   if (T > NOISE_FRAMES) return fail(JV_ERR_SHAPE, "more frames than the fixed noise tensor holds (15000)");
   FlowWs& w = *c.flow;
   if (n_timesteps < 1 || n_timesteps > w.max_steps) return fail(JV_ERR_ARG, "n_timesteps out of range");
-  const int B2 = 2 * B;
+  JV_TRY(guidance_check(c, "jv_cfm_solve", n_timesteps));
+  const int B2 = solve_twins(c, n_timesteps) ? 2 * B : B;      // samples laid out: no twin where no step has guidance
   Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, nullptr, 0};
 
   std::vector<float> tt, dts;
-  JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
+  JV_TRY(solve_schedule(c, w, n_timesteps, t_span_host, tt, dts, st));
   // Ragged batch?  The lengths come down with the synchronisation below (which the staging vectors need anyway): B ints.
   const bool ragged_candidate = lens_dev && B > 1 && flow_compact_ok(c, g.M);
   if (ragged_candidate) JV_HIP(hipMemcpyAsync(w.h_lens, lens_dev, sizeof(int) * B, hipMemcpyDeviceToHost, st));
@@ -355,7 +417,7 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
 
   // pack: lengths (duplicated for the CFG twin rows), masks, row-layout mu / cond / z
   if (lens_dev) {
-    JV_TRY(clamp_lens(lens_dev, B, 2, T, w.lens2, st));      // (the layout above used the same clamp on the host copy)
+    JV_TRY(clamp_lens(lens_dev, B, B2 / B, T, w.lens2, st));      // (the layout above used the same clamp on the host copy)
   } else {
     JV_TRY(fill_int(w.lens2, T, B2, st));
   }
@@ -388,10 +450,11 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
   if (n_timesteps < 1 || n_timesteps > w.max_steps) return fail(JV_ERR_ARG, "n_timesteps out of range");
   if ((reinterpret_cast<uintptr_t>(prompt_h) | reinterpret_cast<uintptr_t>(prompt_feat)) & 15)
     return fail(JV_ERR_ARG, "jv_cfm_solve_prompted: prompt_h / prompt_feat must be 16-byte aligned");
-  const int B2 = 2 * B, Pmax = std::min(Ph, Pf);
+  JV_TRY(guidance_check(c, "jv_cfm_solve_prompted", n_timesteps));
+  const int B2 = solve_twins(c, n_timesteps) ? 2 * B : B, Pmax = std::min(Ph, Pf);
 
   std::vector<float> tt, dts;
-  JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
+  JV_TRY(solve_schedule(c, w, n_timesteps, t_span_host, tt, dts, st));
   // both length vectors always come down (2B ints): they are validated here, before anything is launched on them
   JV_HIP(hipMemcpyAsync(w.h_lens, y_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
   JV_HIP(hipMemcpyAsync(w.h_lens + B, prompt_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
@@ -413,7 +476,7 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
     w.h_sum[b] = w.h_sum[B + b] = p + y;
     T = std::max(T, p + y);
   }
-  JV_TRY(check_shape(c, B2, T));
+  JV_TRY(check_shape(c, 2 * B, T));      // (the capacity counts twins whether or not this solve lays them out)
   if (T > NOISE_FRAMES) return fail(JV_ERR_SHAPE, "more frames than the fixed noise tensor holds (15000)");
   Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, nullptr, 0};
   if (B > 1 && flow_compact_ok(c, g.M)) JV_TRY(solve_compact(c, g, w.h_sum, B, T, st));
@@ -528,8 +591,8 @@ int cfm_pool_admit(Context& c, const float* mu_y, const float* prompt_h, const f
 
 int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks, float* pool_amax,
                   int slots, int Tcap, const int* h_slots, const int* h_lens, const float* h_t, const float* h_dt, int B,
-                  hipStream_t st) {
-  const char* who = "jv_cfm_pool_step";
+                  hipStream_t st, const float* h_cfg) {
+  const char* who = h_cfg ? "jv_cfm_pool_step_g" : "jv_cfm_pool_step";
   if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "tts weights not finalized");
   JV_TRY(pool_check_pools(who, pool_x, pool_mu, pool_cond, pool_spks, nullptr, slots, Tcap));
   FlowWs& w = *c.flow;
@@ -554,6 +617,10 @@ int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* 
       snprintf(msg, sizeof msg, "%s: request %d: t / dt is not a number", who, b);
       return fail(JV_ERR_ARG, msg);
     }
+    if (h_cfg && !guidance_rate_ok(h_cfg[b])) {
+      snprintf(msg, sizeof msg, "%s: request %d: guidance rate %g must be finite and >= 0", who, b, (double)h_cfg[b]);
+      return fail(JV_ERR_ARG, msg);
+    }
     T = std::max(T, h_lens[b]);
   }
   // the step's rows, by cfm_solve's rule: compact where the route allows it and it saves rows, else uniform (padded to T)
@@ -561,7 +628,7 @@ int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* 
   Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, w.t_dev, 1};
   std::vector<int> uoff((size_t)B2 + 1);
   long r = 0, frames = 0;
-  const bool compact = B > 1 && flow_compact_ok(c, g.M) && compact_plan(c, g.M, h_lens, B, T, uoff.data(), &r, &frames);
+  const bool compact = B > 1 && flow_compact_ok(c, g.M) && compact_plan(c, g.M, h_lens, B, B2, T, uoff.data(), &r, &frames);
   if (compact) { g.M = r; g.uoff = w.uoff; g.alg_rows = frames; }
   if (g.M + 128 > w.rows_alloc) {      // (implied by the two limits above: the workspace holds 2 max_batch padded utterances)
     snprintf(msg, sizeof msg, "%s: request %d: the step's %ld rows exceed the reservation (%ld)", who, B - 1, g.M, w.rows_alloc - 128);
@@ -574,9 +641,10 @@ int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* 
     for (int i = 0; i < POOL_CHUNK; ++i) {
       const int b = b0 + i;
       if (i < ch.n)
-        ch.r[i] = {h_slots[b], h_lens[b], compact ? uoff[b] : FLOW_G + b * g.S, compact ? uoff[B + b] : FLOW_G + (B + b) * g.S, h_t[b], h_dt[b]};
+        ch.r[i] = {h_slots[b], h_lens[b], compact ? uoff[b] : FLOW_G + b * g.S, compact ? uoff[B + b] : FLOW_G + (B + b) * g.S, h_t[b], h_dt[b],
+                   h_cfg ? h_cfg[b] : 0.7f};
       else
-        ch.r[i] = {0, 0, 0, 0, 0.f, 0.f};
+        ch.r[i] = {0, 0, 0, 0, 0.f, 0.f, 0.f};
     }
     JV_TRY(pool_publish(ch, B, w.pool_req, w.lens2, w.t_dev, compact ? w.uoff : nullptr, (int)g.M, st));
   }
@@ -585,7 +653,8 @@ int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* 
                      w.spks, w.amax, w.amax_stride, st));
   JV_TRY(assemble_xin(w.x, w.mu, w.spks, w.cond, w.xin, B, B, FLOW_G, g.S, T, g.M, st, g.uoff, w.row_sample, w.rowmask));
   JV_TRY(estimator_body(c, g, est_route(c, g.M, /*temb_pre=*/false, compact, c.attn_chunk), st));
-  return pool_euler_scatter(w.pool_req, B, T, w.x, w.d, 0.7f, w.amax, w.amax_stride, pool_x, pool_amax, Tcap, st);
+  // (two rows per frame for every request, one at rate 0 included: its twin is computed and (1 + 0) d_c - 0 d_u = d_c)
+  return pool_euler_scatter(w.pool_req, B, T, w.x, w.d, w.amax, w.amax_stride, pool_x, pool_amax, Tcap, st);
 }
 
 int cfm_pool_fetch(Context& c, const float* pool_x, int slots, int Tcap, const int* h_slots, const int* h_first, const int* h_lens,
@@ -639,8 +708,9 @@ int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* t
   if (n_timesteps < 1 || n_timesteps > w.max_steps) return fail(JV_ERR_ARG, "n_timesteps out of range");
   if (reinterpret_cast<uintptr_t>(prompt_feat) & 15) return fail(JV_ERR_ARG, "jv_flow_token2mel: prompt_feat must be 16-byte aligned");
   if (ctx < 0 || P + N - ctx < 1) return fail(JV_ERR_ARG, "jv_flow_token2mel_partial: P + N must be at least 4 (one encoded token + 3 of context)");
-  const int B2 = 2 * B, Tm = 2 * (P + N - ctx);
-  JV_TRY(check_shape(c, B2, Tm));
+  JV_TRY(guidance_check(c, "jv_flow_token2mel", n_timesteps));
+  const int B2 = solve_twins(c, n_timesteps) ? 2 * B : B, Tm = 2 * (P + N - ctx);
+  JV_TRY(check_shape(c, 2 * B, Tm));
   if (Tm > NOISE_FRAMES) return fail(JV_ERR_SHAPE, "more frames than the fixed noise tensor holds (15000)");
 
   // h [B, Tm, 80] and the projected speaker vectors wait in buffers the estimator writes only once the loop runs: w.d (its
@@ -653,7 +723,7 @@ int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* t
   if (ctx_lens) {
     if (ctx != 0) return fail(JV_ERR_ARG, "jv_flow_token2mel_ctx: one context for the call or one per utterance, not both");
     std::vector<int> enc_lens, f_host;
-    JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
+    JV_TRY(solve_schedule(c, w, n_timesteps, t_span_host, tt, dts, st));
     JV_TRY(flow_ctx_lengths("jv_flow_token2mel_ctx", plen, len, ctx_lens, feat_lens, B, P, N, enc_lens, &f_host, st));
     for (int b = 0; b < B; ++b) {
       w.h_lens[b] = 2 * enc_lens[b];
@@ -665,7 +735,7 @@ int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* t
     JV_TRY(flow_encoder_fwd(c, ptok, plen, tok, len, B, P, N, streaming, h, hl, st, ctx));
     JV_TRY(speaker_projection(c, embedding, B, spks, st));
 
-    JV_TRY(solve_schedule(w, n_timesteps, t_span_host, tt, dts, st));
+    JV_TRY(solve_schedule(c, w, n_timesteps, t_span_host, tt, dts, st));
     JV_HIP(hipMemcpyAsync(w.h_lens, hl, sizeof(int) * B, hipMemcpyDeviceToHost, st));
     JV_HIP(hipMemcpyAsync(w.h_lens + B, feat_lens, sizeof(int) * B, hipMemcpyDeviceToHost, st));
     JV_HIP(hipStreamSynchronize(st));

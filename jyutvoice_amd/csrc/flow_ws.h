@@ -45,6 +45,7 @@ struct FlowWs {
   float *d = nullptr;                                                 // [rows,80]
   float *tsin = nullptr, *t1 = nullptr, *tmish = nullptr, *temb = nullptr;
   float *t_dev = nullptr, *t_table = nullptr, *dt_table = nullptr;
+  float *cfg_table = nullptr;      // the guidance rate of every Euler step of the solve, [max_steps] (jv_flow_set_guidance; solve_schedule)
   // cfm_solve: the timestep embedding of EVERY step of a solve, computed in three launches before the loop (the steps'
   // t are known up front and the same for all rows): [TS_MAX] rows of sinusoid / hidden / Mish / the 14 projections
   float *ts_sin = nullptr, *ts_1 = nullptr, *ts_mish = nullptr, *ts_emb = nullptr;
@@ -58,14 +59,14 @@ struct FlowWs {
   int* h_sum = nullptr;     // cfm_solve_prompted: p_b + y_b of every utterance and its CFG twin, [2*maxB] (pinned; goes up to lens2)
   int* t2m_lens = nullptr;  // flow_token2mel: T_b = 2 (p_b + n_b) in [0, maxB), y_b = T_b - f_b in [maxB, 2*maxB) (device)
   int* h_y = nullptr;       // ... and y_b on its way up, [maxB] (pinned)
-  PoolStepReq* pool_req = nullptr;      // cfm_pool_step: the step's requests (slot, length, rows, t, dt), [maxB] (device; cfmpool.hip)
+  PoolStepReq* pool_req = nullptr;      // cfm_pool_step: the step's requests (slot, length, rows, t, dt, guidance rate), [maxB] (device; cfmpool.hip)
   int max_steps = 1024;
   // One Euler step (step scalars -> input assembly -> estimator -> CFG update) captured as a hipGraph per (B, T,
-  // attention mode): the step reads its (t, dt) through a device-side counter, so one executable graph replays for
-  // every step of every solve of that geometry.  Replayed on a private stream (the caller's may be the legacy
+  // attention mode): the step reads its (t, dt, guidance rate) through a device-side counter, so one executable graph replays
+  // for every step of every solve of that geometry -- a solve with a step WITHOUT twins (rate 0) never replays it, it is eager.  Replayed on a private stream (the caller's may be the legacy
   // default stream, which cannot be captured), fenced against the caller's stream with events.
   int* step_ctr = nullptr;
-  float *t_cur = nullptr, *dt_cur = nullptr;
+  float *t_cur = nullptr, *dt_cur = nullptr, *cfg_cur = nullptr;      // (t, dt, guidance rate) of the running step (step_advance_kernel)
   struct StepGraph { int B, T, chunk, pre; hipGraph_t graph; hipGraphExec_t exec; };      // pre: captured with the embeddings precomputed
   std::vector<StepGraph> graphs;
   hipStream_t gstream = nullptr;

@@ -1,5 +1,6 @@
 // Context, weight registry and per-stage weight views of libjyutvoice_hip.so.
 #pragma once
+#include <cmath>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -163,6 +164,7 @@ struct Context {
   bool no_ffn_fuse = false;      // JV_NO_FFN_FUSE=1: ff.net.0 and ff.net.2 as two launches (the path rowffn_kernel is checked against)
   bool no_temb_pre = false;      // JV_NO_TEMB_PRE=1: the timestep embedding inside every Euler step instead of once per solve (flow.hip cfm_solve)
   bool no_cfg_share = false;     // JV_NO_CFG_SHARE=1: the first Euler step of an equal-length batch on all 2B samples instead of B + 1 (one shared unconditional twin; flow.hip solve_loop)
+  bool no_twin_drop = false;     // JV_NO_TWIN_DROP=1: an Euler step whose guidance rate is 0 keeps its unconditional twins (2B samples, CFG update with rate 0) instead of running on B samples (flow.hip solve_loop)
   bool no_ln_fold = false;       // JV_NO_LN_FOLD=1: a stage's first norm1 as its own launch (layernorm256_planes) instead of in the resnet's last convolution
   bool no_res_qkv = false;       // JV_NO_RES_QKV=1: a stage's first q | k | v as its own launch (rowgemm_wa) instead of inside the resnet's (rowres_kernel.h)
   bool no_res_pair = false;      // JV_NO_RES_PAIR=1: a resnet as two row-owning launches (block1 + res_conv, block2) instead of one (rowres_kernel.h)
@@ -176,6 +178,7 @@ struct Context {
   bool exact_range = false;      // true: bf16x6 everywhere (jv_flow_set_contraction); false: fp16x3 where the range is proven
   bool est_fp16 = false;         // jv_flow_set_precision(JV_PRECISION_FP16) / JV_EST_FP16=1: the estimator's fp16x3 contractions issue the hi x hi product alone (EstRoute::np)
   bool step_graphs = false;      // replay the Euler step as a captured hipGraph (jv_flow_set_graph; never under the profiler)
+  std::vector<float> guidance;   // jv_flow_set_guidance: empty = rate 0.7 in every Euler step; one entry = that rate in every step; more = one per step (a solve's n_timesteps must match)
   int attn_chunk = 0;            // > 0: streaming (chunk-causal) estimator attention, in frames (jv_flow_set_streaming)
   // workspace
   std::vector<void*> ws_allocs;
@@ -190,6 +193,9 @@ struct Context {
   struct AlignWs* alws = nullptr;     // transposed log prior, decision bits and loss partials of forward() (align.hip): not workspace, survives jv_reserve
   std::string last_error;
 };
+
+// a guidance rate (jv_flow_set_guidance, jv_cfm_pool_step_g): finite and >= 0
+inline bool guidance_rate_ok(float r) { return std::isfinite(r) && r >= 0.f; }
 
 // registry.hip
 void build_registry(Context& c);
@@ -217,7 +223,7 @@ int cfm_pool_admit(Context& c, const float* mu_y, const float* prompt_h, const f
                    hipStream_t st);
 int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks, float* pool_amax,
                   int slots, int Tcap, const int* h_slots, const int* h_lens, const float* h_t, const float* h_dt, int B,
-                  hipStream_t st);
+                  hipStream_t st, const float* h_cfg = nullptr);      // h_cfg: the guidance rate of every request in this step (null: 0.7)
 int cfm_pool_fetch(Context& c, const float* pool_x, int slots, int Tcap, const int* h_slots, const int* h_first, const int* h_lens,
                    int B, int Tm, float* mel, hipStream_t st);
 

@@ -24,15 +24,17 @@ int pack_prompted(const float* mu_y, int Ty, const float* prompt_h, int Ph, cons
                   const int* clens = nullptr);
 int rows_to_cf_from(const float* src, int ld, int G, int S, const int* first, const int* lens, float* dst, long dst_bstride,
                     int B, int C, int T, hipStream_t st, const int* uoff = nullptr);
-// ntwin: the unconditional twin slots to fill behind the B conditional ones (B, or 1: the twin a solve's first step shares)
+// ntwin: the unconditional twin slots to fill behind the B conditional ones (B; 1: the twin a solve's first step shares; 0: none)
 int assemble_xin(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int ntwin, int G,
                  int S, int L, long rows2, hipStream_t st, const int* uoff = nullptr, const int* row_sample = nullptr,
                  const unsigned char* rowmask = nullptr);
 int assemble_xin_plain(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int G,
                        int S, int L, long rows, hipStream_t st);
 int time_sinusoid(const float* t, int t_stride, float* out, int B, hipStream_t st);
-int euler_cfg(float* x, const float* d, int B, int G, int S, int L, const float* dt_table, int step, float rate,
-              hipStream_t st, const int* uoff = nullptr, const int* lens = nullptr, bool one_twin = false);      // one_twin: every utterance reads the twin at slot B
+// rate: the step's guidance rate, one float on the device.  one_twin: every utterance reads the twin at slot B.  no_twin: the
+// step of rate 0 on B utterances alone, x += dt d (rate is not read, no twin row is addressed)
+int euler_cfg(float* x, const float* d, int B, int G, int S, int L, const float* dt_table, int step, const float* rate,
+              hipStream_t st, const int* uoff = nullptr, const int* lens = nullptr, bool one_twin = false, bool no_twin = false);
 int ln_epilogue_rows(float* x, const float* g, const float* b, float eps, long rows, int C, int act,
                      const unsigned char* rowmask, const float* rowvec, const int* row_sample, int rowvec_ld, const float* res,
                      long ldr, float scale, hipStream_t st, float* amax_out = nullptr, int amax_G = 0, int amax_S = 0,
@@ -44,7 +46,7 @@ int ln_epilogue_rows(float* x, const float* g, const float* b, float eps, long r
 constexpr int POOL_CHUNK = 64;
 struct PoolAdmitReq { int slot, p, len; float temp; };      // prompt frames, p + y frames, noise scale
 struct PoolAdmitChunk { int n, b0; PoolAdmitReq r[POOL_CHUNK]; };
-struct PoolStepReq { int slot, len, row, rowu; float t, dt; };      // first workspace row of the request and of its CFG twin
+struct PoolStepReq { int slot, len, row, rowu; float t, dt, cfg; };      // first workspace row of the request and of its CFG twin; its guidance rate in this step
 struct PoolStepChunk { int n, b0; PoolStepReq r[POOL_CHUNK]; };
 struct PoolFetchReq { int slot, first, len; };
 struct PoolFetchChunk { int n, b0; PoolFetchReq r[POOL_CHUNK]; };
@@ -60,8 +62,8 @@ int pool_publish(const PoolStepChunk& ch, int B, PoolStepReq* req, int* lens2, f
 int pool_gather(const PoolStepReq* req, int B, int tmax, int tfill, const float* pool_x, const float* pool_mu, const float* pool_cond,
                 const float* pool_spks, const float* pool_amax, int Tcap, float* x, float* mu, float* cond, float* spks, float* amax,
                 int amax_stride, hipStream_t st);
-// pool_x[slot, t] = x[row + t] + dt_b ((1 + rate) d[row + t] - rate d[rowu + t]) (euler_cfg with a dt per request), maxima back
-int pool_euler_scatter(const PoolStepReq* req, int B, int tmax, const float* x, const float* d, float rate, const float* amax,
+// pool_x[slot, t] = x[row + t] + dt_b ((1 + cfg_b) d[row + t] - cfg_b d[rowu + t]) (euler_cfg with a dt and a rate per request), maxima back
+int pool_euler_scatter(const PoolStepReq* req, int B, int tmax, const float* x, const float* d, const float* amax,
                        int amax_stride, float* pool_x, float* pool_amax, int Tcap, hipStream_t st);
 // mel[b, c, t] = pool_x[slot, first + t, c] for t < len, zeros up to Tm
 int pool_fetch(const PoolFetchChunk& ch, const float* pool_x, int Tcap, float* mel, int Tm, hipStream_t st);

@@ -495,7 +495,7 @@ int rows_to_cf_from(const float* src, int ld, int G, int S, const int* first, co
 // rows of utterance b' < B are conditional; b' >= B are the unconditional twin of b' - B (mu = spks = cond = 0),
 // jyutvoice/flow/flow_matching.py:246-251.  x/mu/cond are row buffers of 80 columns with geometry (G,S).
 // ntwin: the twin slots to fill, B .. B + ntwin - 1 (B: one per utterance; 1: the one twin a solve's first step shares, x of
-// utterance 0 -- flow.hip solve_loop)
+// utterance 0; 0: a step without guidance, whose rows end behind utterance B - 1 -- flow.hip solve_loop)
 __global__ __launch_bounds__(256) void assemble_xin_kernel(const float* __restrict__ x, const float* __restrict__ mu,
                                                            const float* __restrict__ spks, const float* __restrict__ cond,
                                                            float* __restrict__ xin, int B, int ntwin, int G, int S, int L,
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(256) void assemble_xin_kernel(const float* __restri
 int assemble_xin(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int ntwin, int G,
                  int S, int L, long rows2, hipStream_t st, const int* uoff, const int* row_sample, const unsigned char* rowmask) {
   if (uoff && (!row_sample || !rowmask)) return fail(JV_ERR_ARG, "assemble_xin: the compact geometry needs the row tables");
-  if (ntwin < 1 || ntwin > B) return fail(JV_ERR_ARG, "assemble_xin: between one twin slot and one per utterance");
+  if (ntwin < 0 || ntwin > B) return fail(JV_ERR_ARG, "assemble_xin: between no twin slot and one per utterance");
   hipLaunchKernelGGL(assemble_xin_kernel, dim3((unsigned)cdivl(rows2 * 80, 256)), dim3(256), 0, st, x, mu, spks, cond, xin,
                      B, ntwin, G, S, L, rows2, uoff, row_sample, rowmask);
   JV_HIP(hipGetLastError());
@@ -588,11 +588,13 @@ int time_sinusoid(const float* t, int t_stride, float* out, int B, hipStream_t s
 }
 
 // ---- Euler step with classifier-free guidance: x += dt * ((1+r) d_cond - r d_uncond) ----------------------
-// d holds 2B utterances (geometry G,S); step scalars come from a device table so the loop never syncs.
+// d holds 2B utterances (geometry G,S); step scalars come from device memory so the loop never syncs: dt = dt_table[step] and
+// r = *rate, the guidance rate of this step (flow.hip step_advance_kernel moves both there -- a captured step replays with them).
 // one_twin (uniform geometry): every utterance reads the one twin at slot B (a solve's shared first step)
 __global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ x, const float* __restrict__ d, int B, int G, int S,
-                                                        int L, const float* __restrict__ dt_table, int step, float rate,
-                                                        const int* __restrict__ uoff, const int* __restrict__ lens, bool one_twin) {
+                                                        int L, const float* __restrict__ dt_table, int step,
+                                                        const float* __restrict__ rate_p, const int* __restrict__ uoff,
+                                                        const int* __restrict__ lens, bool one_twin) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;   // f32x4 index over B*L*20
   const long per_b = (long)L * 20;
   if (idx >= per_b * B) return;
@@ -604,6 +606,7 @@ __global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ x, c
   const long ru = uoff ? (long)uoff[b + B] + t : (long)G + (long)(B + (one_twin ? 0 : b)) * S + t;      // the unconditional twin's row
   const int cc = (int)(rem % 20) * 4;
   const float dt = dt_table[step];
+  const float rate = *rate_p;
   const f32x4 dc = *reinterpret_cast<const f32x4*>(d + r * 80 + cc);
   const f32x4 du = *reinterpret_cast<const f32x4*>(d + ru * 80 + cc);
   f32x4 xv = *reinterpret_cast<f32x4*>(x + r * 80 + cc);
@@ -612,12 +615,38 @@ __global__ __launch_bounds__(256) void euler_cfg_kernel(float* __restrict__ x, c
   *reinterpret_cast<f32x4*>(x + r * 80 + cc) = xv;
 }
 
-int euler_cfg(float* x, const float* d, int B, int G, int S, int L, const float* dt_table, int step, float rate,
-              hipStream_t st, const int* uoff, const int* lens, bool one_twin) {
+// the step of a guidance rate of exactly 0, x += dt * d, on B utterances WITHOUT twins (flow_matching.py:252-258 with
+// inference_cfg_rate = 0: (1 + 0) d_cond - 0 d_uncond): no row of a twin is addressed, none need exist
+__global__ __launch_bounds__(256) void euler_plain_kernel(float* __restrict__ x, const float* __restrict__ d, int B, int G, int S,
+                                                          int L, const float* __restrict__ dt_table, int step,
+                                                          const int* __restrict__ uoff, const int* __restrict__ lens) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;   // f32x4 index over B*L*20
+  const long per_b = (long)L * 20;
+  if (idx >= per_b * B) return;
+  const int b = (int)(idx / per_b);
+  const long rem = idx - (long)b * per_b;
+  const long t = rem / 20;
+  if (uoff && t >= lens[b]) return;
+  const long r = uoff ? (long)uoff[b] + t : (long)G + (long)b * S + t;
+  const int cc = (int)(rem % 20) * 4;
+  const float dt = dt_table[step];
+  const f32x4 dc = *reinterpret_cast<const f32x4*>(d + r * 80 + cc);
+  f32x4 xv = *reinterpret_cast<f32x4*>(x + r * 80 + cc);
+  xv = xv + dt * dc;
+  *reinterpret_cast<f32x4*>(x + r * 80 + cc) = xv;
+}
+
+int euler_cfg(float* x, const float* d, int B, int G, int S, int L, const float* dt_table, int step, const float* rate,
+              hipStream_t st, const int* uoff, const int* lens, bool one_twin, bool no_twin) {
   if (uoff && !lens) return fail(JV_ERR_ARG, "euler_cfg: the compact geometry needs the lengths");
   if (uoff && one_twin) return fail(JV_ERR_ARG, "euler_cfg: one shared twin exists in the uniform geometry only");
-  hipLaunchKernelGGL(euler_cfg_kernel, dim3((unsigned)cdivl((long)B * L * 20, 256)), dim3(256), 0, st, x, d, B, G, S, L,
-                     dt_table, step, rate, uoff, lens, one_twin);
+  if (no_twin && one_twin) return fail(JV_ERR_ARG, "euler_cfg: one shared twin or none");
+  if (!no_twin && !rate) return fail(JV_ERR_ARG, "euler_cfg: the guidance rate is read from the device");
+  const dim3 grid((unsigned)cdivl((long)B * L * 20, 256));
+  if (no_twin)
+    hipLaunchKernelGGL(euler_plain_kernel, grid, dim3(256), 0, st, x, d, B, G, S, L, dt_table, step, uoff, lens);
+  else
+    hipLaunchKernelGGL(euler_cfg_kernel, grid, dim3(256), 0, st, x, d, B, G, S, L, dt_table, step, rate, uoff, lens, one_twin);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

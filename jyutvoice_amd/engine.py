@@ -5,6 +5,7 @@ stream they are enqueued on.  Every numerical step of the hot path runs inside t
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, Optional
 
@@ -137,6 +138,32 @@ class Engine:
         """chunk-causal estimator attention (the reference's streaming=True); 0 = full attention"""
         check(self.lib.jv_flow_set_streaming(self._h, int(chunk_frames)))
 
+    def set_guidance(self, rates=None):
+        """the classifier-free-guidance rate of the closed solves on this context (jv_flow_set_guidance; flow_matching.py:215-265).
+        None: the default, 0.7 in every Euler step.  A number, or a sequence of one: that rate in every step.  A sequence of n:
+        one rate per step of a solve with n_timesteps = n (any other solve raises JvError).  A step whose rate is exactly 0 runs
+        without unconditional twins.  A negative or non-finite rate raises JvError and leaves the mode as it was."""
+        if rates is None:
+            check(self.lib.jv_flow_set_guidance(self._h, None, 0))
+            return
+        vals = [float(rates)] if isinstance(rates, (int, float)) else [float(r) for r in
+                                                                      (rates.tolist() if isinstance(rates, torch.Tensor) else rates)]
+        if not vals:
+            raise ValueError("set_guidance: an empty schedule; pass None for the default rate")
+        check(self.lib.jv_flow_set_guidance(self._h, (C.c_float * len(vals))(*vals), len(vals)))
+
+    @contextlib.contextmanager
+    def guidance(self, rates):
+        """`with eng.guidance(rates):` -- set_guidance(rates) for the block, the default again behind it (rates = None: nothing)"""
+        if rates is None:
+            yield
+            return
+        self.set_guidance(rates)
+        try:
+            yield
+        finally:
+            self.set_guidance(None)
+
     def set_step_graph(self, on: bool = True):
         """replay the Euler step of cfm_solve as a captured hipGraph (default off: measured no faster; same results)"""
         check(self.lib.jv_flow_set_graph(self._h, 1 if on else 0))
@@ -241,14 +268,18 @@ class Engine:
             B, Ty, prompt_h.shape[1], prompt_feat.shape[1], _ptr(pool.x), _ptr(pool.mu), _ptr(pool.cond), _ptr(pool.spks),
             _ptr(pool.amax), pool.slots, pool.max_frames, _stream(self.device)))
 
-    def cfm_pool_step(self, pool, slots, lens, t, dt):
+    def cfm_pool_step(self, pool, slots, lens, t, dt, cfg=None):
         """jv_cfm_pool_step: ONE Euler + CFG step of the listed slots, request b with lens[b] frames at (t[b], dt[b]); B host
-        values each.  Nothing comes back to the host."""
+        values each.  cfg: the guidance rate of every request in this step (jv_cfm_pool_step_g); None: 0.7 for all.  Nothing
+        comes back to the host."""
         who, B = "cfm_pool_step", len(slots)
-        check(self.lib.jv_cfm_pool_step(
-            self._h, _ptr(pool.x), _ptr(pool.mu), _ptr(pool.cond), _ptr(pool.spks), _ptr(pool.amax), pool.slots, pool.max_frames,
-            self._host_vec(who, "slots", slots, C.c_int32, B), self._host_vec(who, "lens", lens, C.c_int32, B),
-            self._host_vec(who, "t", t, C.c_float, B), self._host_vec(who, "dt", dt, C.c_float, B), B, _stream(self.device)))
+        args = (self._h, _ptr(pool.x), _ptr(pool.mu), _ptr(pool.cond), _ptr(pool.spks), _ptr(pool.amax), pool.slots, pool.max_frames,
+                self._host_vec(who, "slots", slots, C.c_int32, B), self._host_vec(who, "lens", lens, C.c_int32, B),
+                self._host_vec(who, "t", t, C.c_float, B), self._host_vec(who, "dt", dt, C.c_float, B))
+        if cfg is None:
+            check(self.lib.jv_cfm_pool_step(*args, B, _stream(self.device)))
+        else:
+            check(self.lib.jv_cfm_pool_step_g(*args, self._host_vec(who, "cfg", cfg, C.c_float, B), B, _stream(self.device)))
 
     def cfm_pool_fetch(self, pool, slots, first, lens, frames=None):
         """jv_cfm_pool_fetch: frames first[b] .. first[b] + lens[b] - 1 of the listed slots -> mel [B, 80, frames] (default: the

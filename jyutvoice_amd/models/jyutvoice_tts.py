@@ -23,7 +23,7 @@ import torch
 
 from .. import spec
 from ..engine import JV_MODEL_TTS
-from ..flow.flow_matching import CausalConditionalCFM
+from ..flow.flow_matching import CausalConditionalCFM, check_scheduler, decoder_settings, resolve_guidance, time_span
 from ..runtime import get_runtime
 from .duration_predictor import DurationPredictor
 from .text_encoder import TextEncoder
@@ -112,7 +112,12 @@ class JyutVoiceTTS:
     # ---- the hot path -----------------------------------------------------------------------------------------
     @torch.inference_mode()
     def synthesise(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed, prompt_feat, prompt_h=None,
-                   n_timesteps=10, temperature=1.0, length_scale=1.0, batched=False, prompt_lengths=None, streaming=False):
+                   n_timesteps=10, temperature=1.0, length_scale=1.0, batched=False, prompt_lengths=None, streaming=False,
+                   cfg_rate=None, cfg_schedule=None, t_scheduler=None):
+        """jyutvoice_tts.py:130-253.  Extensions beyond the reference's arguments: batched / prompt_lengths (a batch, one voice
+        prompt per utterance); cfg_rate (the guidance rate of this call; None: the decoder's inference_cfg_rate), cfg_schedule (a
+        sequence of n_timesteps rates, one per Euler step; wins over cfg_rate) and t_scheduler ("cosine" / "linear"; None: the
+        decoder's) -- flow_matching.py:215-265, 387-389."""
         if streaming:
             raise NotImplementedError("synthesise() runs the non-streaming decoder (jyutvoice_tts.py:239 passes streaming=False)"
                                       + ("; prompt_lengths has no streaming form" if prompt_lengths is not None else ""))
@@ -122,6 +127,9 @@ class JyutVoiceTTS:
         t0 = dt.datetime.now()
         B, Tt = x.shape
         p_host = None if prompt_lengths is None else self._check_prompt_lengths(prompt_lengths, prompt_feat, prompt_h, B)
+        conf_rate, conf_sched = decoder_settings(self.decoder)
+        rates = resolve_guidance("synthesise()", n_timesteps, conf_rate, cfg_rate, cfg_schedule)
+        t_span = time_span(n_timesteps, check_scheduler("synthesise()", conf_sched if t_scheduler is None else t_scheduler))   # flow_matching.py:387-389
         rt = get_runtime(self.device)
         eng = rt.ensure(B, 64, Tt)
         # stage_events (a list, set by bench.py for its per-stage pass; None otherwise): events on the launch stream at the
@@ -145,9 +153,9 @@ class JyutVoiceTTS:
             # voice-cloning batch, one prompt length per utterance: the glue of jyutvoice_tts.py:213-244 runs inside
             # jv_cfm_solve_prompted, the tensors go there as they came
             eng = rt.ensure(B, max(p + y for p, y in zip(p_host, eng.y_lengths_host)), Tt)
-            t_span = 1 - torch.cos(torch.linspace(0, 1, n_timesteps + 1) * 0.5 * torch.pi)   # flow_matching.py:387-389
-            dec = eng.cfm_solve_prompted(mu_y, y_lengths, prompt_h, prompt_feat, prompt_lengths, c, n_timesteps, temperature,
-                                         t_span=t_span)
+            with eng.guidance(rates):
+                dec = eng.cfm_solve_prompted(mu_y, y_lengths, prompt_h, prompt_feat, prompt_lengths, c, n_timesteps, temperature,
+                                             t_span=t_span)
             return self._result(t0, B, encoder_outputs, dec, attn, y_lengths, mark)
         mel_len1 = 0
         if prompt_feat is not None and prompt_h is not None:
@@ -165,8 +173,8 @@ class JyutVoiceTTS:
             lens = y_lengths
         T = mu_y.shape[2]
         eng = rt.ensure(B, T, Tt)
-        t_span = 1 - torch.cos(torch.linspace(0, 1, n_timesteps + 1) * 0.5 * torch.pi)   # flow_matching.py:387-389
-        dec = eng.cfm_solve(mu_y.contiguous(), lens if B > 1 else None, c, conds, n_timesteps, temperature, t_span=t_span)
+        with eng.guidance(rates):
+            dec = eng.cfm_solve(mu_y.contiguous(), lens if B > 1 else None, c, conds, n_timesteps, temperature, t_span=t_span)
         dec = dec[:, :, mel_len1:]
         return self._result(t0, B, encoder_outputs, dec, attn, y_lengths, mark)
 

@@ -12,7 +12,8 @@ steps a solve's state is only x, the running trunk maxima and a step counter, an
     server.drain()
 
 A request is DEFINED as that request run alone: its mel is `tts.synthesise(..., n_timesteps=n_r, temperature=tau_r,
-length_scale=s_r, batched=True, prompt_lengths=[p_r])` at B = 1, its audio `hift.inference(mel_r)` at B = 1 after
+length_scale=s_r, batched=True, prompt_lengths=[p_r], cfg_schedule=guidance_rates(n_r, rate_r, window_r, sched_r), t_scheduler=sched_r)`
+at B = 1, its audio `hift.inference(mel_r)` at B = 1 after
 `hift.manual_seed(seed_r)` -- whatever else is in the pool and whenever the others joined or left.  A request that arrives waits at
 most one Euler step, not up to a whole pass.
 
@@ -28,18 +29,21 @@ import numpy as np
 import torch
 
 from . import spec
+from .flow.flow_matching import check_rate, check_scheduler, decoder_settings, time_span
 
 FLOW_G, FLOW_GAP = 4, 4      # guard rows ahead of a step's first utterance / between two utterances (csrc/flow_ws.h)
 MAX_STEPS = 1024             # the solver's limit on n_timesteps (csrc/flow_ws.h: FlowWs::max_steps)
 
 
-def step_table(n: int) -> Tuple[List[float], List[float]]:
+def step_table(n: int, t_scheduler: str = "cosine") -> Tuple[List[float], List[float]]:
     """(t, dt) of the n Euler steps of a request, as fp32 values: the cosine schedule `1 - cos(linspace(0, 1, n + 1) pi / 2)` that
-    `synthesise` hands the solver and the reference's running recurrence over it (flow_matching.py:230, 260-263, 387-389), in fp32
-    -- what `solve_schedule` computes for a closed solve of n steps.  Step k of the request uses (tt[k], dts[k])."""
+    `synthesise` hands the solver (t_scheduler="linear": `linspace(0, 1, n + 1)` itself) and the reference's running recurrence
+    over it (flow_matching.py:230, 260-263, 387-389), in fp32 -- what `solve_schedule` computes for a closed solve of n steps.
+    Step k of the request uses (tt[k], dts[k])."""
     if not isinstance(n, int) or n < 1:
         raise ValueError(f"step_table(): n must be a positive int, got {n!r}")
-    ts = (1 - torch.cos(torch.linspace(0, 1, n + 1) * 0.5 * torch.pi)).numpy().astype(np.float32)
+    check_scheduler("step_table()", t_scheduler)
+    ts = time_span(n, t_scheduler).numpy().astype(np.float32)
     tt, dts = [], []
     t, dt = ts[0], np.float32(ts[1] - ts[0])
     for s in range(1, n + 1):
@@ -49,6 +53,29 @@ def step_table(n: int) -> Tuple[List[float], List[float]]:
         if s < n:
             dt = np.float32(ts[s + 1] - t)
     return tt, dts
+
+
+def guidance_rates(n: int, rate: float, window: Optional[Tuple[float, float]] = None, t_scheduler: str = "cosine") -> List[float]:
+    """The guidance rate of each of the n Euler steps (flow_matching.py:215-265 with a rate per step): `rate` in a step whose t --
+    tt[k] of `step_table(n, t_scheduler)` -- lies in window = (t_lo, t_hi), closed at t_lo and open at t_hi, and 0 outside it (such
+    a step runs without unconditional twins in a closed solve).  window = None: `rate` in every step.  Pure host function."""
+    who = "guidance_rates()"
+    rate = check_rate(who, rate, "rate")
+    window = check_window(who, window)
+    tt, _ = step_table(n, t_scheduler)
+    if window is None:
+        return [rate] * n
+    return [rate if window[0] <= t < window[1] else 0.0 for t in tt]
+
+
+def check_window(who: str, window, name: str = "window") -> Optional[Tuple[float, float]]:
+    """a guidance window: None, or a pair of finite numbers (t_lo, t_hi)"""
+    if window is None:
+        return None
+    if (not isinstance(window, (tuple, list)) or len(window) != 2 or
+            not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in window)):
+        raise ValueError(f"{who}: {name} must be a pair of finite numbers (t_lo, t_hi), got {window!r}")
+    return float(window[0]), float(window[1])
 
 
 def step_rows(lens: Sequence[int]) -> int:
@@ -73,12 +100,14 @@ def admit_plan(waiting: Sequence[int], active: Sequence[int], free_slots: int, r
 
 
 class _Request:
-    def __init__(self, rid, args, prompt_feat, prompt_h, n, temperature, length_scale, seed, loudness=None, peak=None):
+    def __init__(self, rid, args, prompt_feat, prompt_h, n, temperature, length_scale, seed, loudness=None, peak=None, rates=None,
+                 t_scheduler="cosine"):
         self.rid, self.args, self.prompt_feat, self.prompt_h = rid, args, prompt_feat, prompt_h
         self.loudness, self.peak = loudness, peak      # target LUFS and peak ceiling of the output, or None
         self.n, self.temperature, self.length_scale, self.seed = n, temperature, length_scale, seed
         self.p = 0 if prompt_feat is None else int(prompt_feat.shape[1])
-        self.tt, self.dts = step_table(n)
+        self.tt, self.dts = step_table(n, t_scheduler)
+        self.rates = [spec.CFG_RATE] * n if rates is None else rates      # the guidance rate of every step, beside tt / dts
         self.k = 0                 # Euler steps taken
         self.slot = None
         self.y = None              # generated frames, once the text encoder has run
@@ -145,7 +174,11 @@ class SynthServer:
 
     # ---- host only ------------------------------------------------------------------------------------------------------------------
     def submit(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed, prompt_feat=None, prompt_h=None, n_timesteps=10,
-               temperature=1.0, length_scale=1.0, seed=None, loudness=None, peak=None) -> int:
+               temperature=1.0, length_scale=1.0, seed=None, loudness=None, peak=None, cfg_rate=None, cfg_window=None,
+               t_scheduler="cosine") -> int:
+        """cfg_rate: the request's guidance rate (None: the decoder's inference_cfg_rate); cfg_window = (t_lo, t_hi): guidance in
+        the steps whose t lies in [t_lo, t_hi) only, rate 0 outside (`guidance_rates`); t_scheduler: "cosine" / "linear" (None: the
+        decoder's)."""
         rid = self._next_rid
         who = f"SynthServer.submit(): request {rid}"
         ids = {"x": x, "lang": lang, "tone": tone, "word_pos": word_pos, "syllable_pos": syllable_pos}
@@ -186,6 +219,10 @@ class SynthServer:
             raise ValueError(f"{who}: peak must be positive and finite (or None), got {peak!r}")
         if peak is not None and loudness is None:
             raise ValueError(f"{who}: peak limits the gain of loudness: give loudness too")
+        conf_rate, conf_sched = decoder_settings(getattr(self.tts, "decoder", None))
+        t_scheduler = check_scheduler(who, conf_sched if t_scheduler is None else t_scheduler)
+        cfg_rate = check_rate(who, conf_rate if cfg_rate is None else cfg_rate, "cfg_rate")
+        rates = guidance_rates(n_timesteps, cfg_rate, check_window(who, cfg_window, "cfg_window"), t_scheduler)
         p = 0 if prompt_feat is None else prompt_feat.shape[1]
         # every token gets at least one frame unless length_scale shortens it; the prompt alone must leave room for one
         least = p + max(1, int(xl[0]) if length_scale >= 1.0 else 1)
@@ -196,7 +233,8 @@ class SynthServer:
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
         args = (x, xl.to(torch.int64), lang, tone, word_pos, syllable_pos, spk_embed)
         self._waiting.append(_Request(rid, args, prompt_feat, prompt_h, n_timesteps, temperature, length_scale, int(seed),
-                                      None if loudness is None else float(loudness), None if peak is None else float(peak)))
+                                      None if loudness is None else float(loudness), None if peak is None else float(peak),
+                                      rates, t_scheduler))
         self._next_rid += 1
         return rid
 
@@ -264,8 +302,11 @@ class SynthServer:
         live = list(self._active.values())
         if not live:
             return done
+        cfg = [r.rates[r.k] for r in live]
+        # (all at the default rate: the entry without rates, jv_cfm_pool_step, which is the other one with 0.7 for all)
+        kw = {} if all(abs(v - spec.CFG_RATE) <= 1e-12 for v in cfg) else {"cfg": cfg}
         eng.cfm_pool_step(self.pool, [r.slot for r in live], [r.frames for r in live], [r.tt[r.k] for r in live],
-                          [r.dts[r.k] for r in live])
+                          [r.dts[r.k] for r in live], **kw)
         self.steps += 1
         for r in live:
             r.k += 1

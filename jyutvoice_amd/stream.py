@@ -68,7 +68,10 @@ class Token2WavStream:
     signal of the audio returned so far ([1, 1, samples so far])."""
 
     def __init__(self, flow, hift, prompt_token, prompt_feat, embedding, max_tokens: int, n_timesteps: int = 10,
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, cfg_rate=None, cfg_schedule=None, t_scheduler=None):
+        # cfg_rate / cfg_schedule: the guidance rate of every solve of the session / one rate per Euler step, handed to the flow's
+        # inference calls; t_scheduler: "cosine" / "linear" (None each: the flow decoder's configuration)
+        self._cfg = {k: v for k, v in (("cfg_rate", cfg_rate), ("cfg_schedule", cfg_schedule), ("t_scheduler", t_scheduler)) if v is not None}
         if prompt_token is None:
             prompt_token = torch.zeros(1, 0, dtype=torch.int64)
         if prompt_feat is None:
@@ -123,14 +126,14 @@ class Token2WavStream:
         solve, lo, hi = next_step(self.P + self.tokens.shape[1], self.F, self.L_done, self.done, False)
         if not solve:
             return torch.zeros(1, 0, device=self.hift.device)
-        mel, _ = self.flow.inference_partial(*self._args(solve - self.P), n_timesteps=self.n_timesteps)
+        mel, _ = self.flow.inference_partial(*self._args(solve - self.P), n_timesteps=self.n_timesteps, **self._cfg)
         return self._feed(mel, solve - spec.PROMPT_LOOKAHEAD, lo, hi, False)
 
     @torch.inference_mode()
     def finish(self, tokens=None) -> torch.Tensor:
         self._take(tokens, "finish()")
         solve, lo, hi = next_step(self.P + self.tokens.shape[1], self.F, self.L_done, self.done, True)
-        mel, _ = self.flow.inference(*self._args(solve - self.P), True, n_timesteps=self.n_timesteps)
+        mel, _ = self.flow.inference(*self._args(solve - self.P), True, n_timesteps=self.n_timesteps, **self._cfg)
         wav = self._feed(mel, solve, lo, hi, True)
         self.finished = True
         return wav
@@ -182,7 +185,10 @@ class Token2WavServer:
     `max_sessions` utterances of 2 (max_prompt_tokens + max_tokens) frames: no step rebuilds a context.  `mel(sid)`, `source(sid)`
     and `f0(sid)` are views of a session's records; those of a finished session stay valid until its slot is opened again."""
 
-    def __init__(self, flow, hift, max_sessions: int, max_tokens: int, n_timesteps: int = 10, max_prompt_tokens: int = 150):
+    def __init__(self, flow, hift, max_sessions: int, max_tokens: int, n_timesteps: int = 10, max_prompt_tokens: int = 150,
+                 cfg_rate=None, cfg_schedule=None, t_scheduler=None):
+        # cfg_rate / cfg_schedule: as for Token2WavStream, for every step of the server (one solve serves all its sessions)
+        self._cfg = {k: v for k, v in (("cfg_rate", cfg_rate), ("cfg_schedule", cfg_schedule), ("t_scheduler", t_scheduler)) if v is not None}
         for name, v in (("max_sessions", max_sessions), ("max_tokens", max_tokens)):
             if not isinstance(v, int) or v < 1:
                 raise ValueError(f"Token2WavServer: {name} must be a positive int, got {v!r}")
@@ -311,7 +317,7 @@ class Token2WavServer:
         mel, _ = self.flow.inference_partial_batch(
             self._tok.index_select(0, slots)[:, :N], torch.tensor(n_len), self._ptok.index_select(0, slots)[:, :P], torch.tensor(p_len),
             self._feat.index_select(0, slots)[:, :F], torch.tensor(f_len), self._emb.index_select(0, slots),
-            [ctx for *_, ctx, _, _ in rows], streaming=True, n_timesteps=self.n_timesteps)
+            [ctx for *_, ctx, _, _ in rows], streaming=True, n_timesteps=self.n_timesteps, **self._cfg)
         out = self.vocoder.advance(mel, [(s.slot, r, lo, hi, s.closing) for r, (_, s, _, _, lo, hi) in enumerate(rows)])
         res = {}
         for sid, s, solve, ctx, lo, hi in rows:
