@@ -502,10 +502,21 @@ int jv_masked_mse(jv_context* ctx, const float* a, const float* b, const int32_t
  * jv_encoder_fwd: spk_embed_affine_layer(normalize(spk)) + TextEncoder.forward + DurationPredictor.forward
  * (jyutvoice/models/jyutvoice_tts.py:175-182, text_encoder.py:406-451, duration_predictor.py:48-60).
  * ids: int64 [B,Tt] each; x_lengths: int64 [B]; spk: [B,192] (raw, un-normalised).
- * outputs: x [B,576,Tt], mu_x [B,80,Tt], logw [B,1,Tt], spks_proj [B,80]. */
+ * outputs: x [B,576,Tt], mu_x [B,80,Tt], logw [B,1,Tt], spks_proj [B,80].
+ * Tt is bounded by the max_tokens of jv_create / jv_reserve alone; which attention kernels run is jv_encoder_set_attention's. */
 int jv_encoder_fwd(jv_context* ctx, const int64_t* phone, const int64_t* lang, const int64_t* tone, const int64_t* word_pos,
                    const int64_t* syllable_pos, const int64_t* x_lengths, const float* spk, int B, int Tt, float* x,
                    float* mu_x, float* logw, float* spks_proj, void* stream);
+/* jv_encoder_set_attention: the route of the encoder layers' 2-head RoPE attention (text_encoder.py:216-248) in jv_encoder_fwd.
+ *   JV_ENC_ATTN_AUTO (default): the four-launch route (q k^T GEMM, masked softmax, V transpose, P V GEMM around a [B,2,Tt,Tt] score
+ *                        buffer) for Tt <= 512, the one-launch kernel of encattn.hip above that
+ *   JV_ENC_ATTN_FUSED:   encattn.hip at every length
+ *   JV_ENC_ATTN_GEMM:    the four-launch route; jv_encoder_fwd with Tt > 512 returns JV_ERR_SHAPE
+ * Another value: JV_ERR_ARG, and the mode stays as it was.  The workspace holds the score buffer for min(max_tokens, 512) tokens. */
+#define JV_ENC_ATTN_AUTO 0
+#define JV_ENC_ATTN_FUSED 1
+#define JV_ENC_ATTN_GEMM 2
+int jv_encoder_set_attention(jv_context* ctx, int mode);
 /* jv_length_regulate: w_ceil = ceil(exp(logw)*mask)*length_scale, y_lengths, generate_path, mu_y = attn^T mu_x
  * (jyutvoice_tts.py:184-203, utils/model.py:29-46).  Two-phase because T_max is data dependent:
  *   phase 1 (attn == NULL): writes w_ceil [B,1,Tt] and y_lengths [B] int64 (device); the caller reads max(y_lengths)
@@ -584,6 +595,14 @@ int jv_op_attention(const float* qkv, const int32_t* lens, int B, int G, int S, 
  * freed inside the call, which then synchronises). */
 int jv_op_rel_attention(const float* qkv, const float* p, const float* u, const float* v, const int64_t* lens, int B, int T, int G,
                         int S, int len_mul, int chunk, int fused, float* out, void* stream);
+/* jv_op_enc_attention: the text encoder's attention (text_encoder.py:235-248: scores, mask, softmax, P V; RoPE already applied) on
+ * caller-supplied buffers.  qkv [rows,1728] rows G + b*S + t, q of head h at columns h*288, k at 576 + h*288, v at 1152 + h*288;
+ * lens: int64 [B], utterance b has L_b = min(lens[b], T) rows.
+ *   out[row(b,i), h*288 ..] = softmax_j(q_i . k_j / sqrt(288)) V  over keys j < L_b, for queries i < L_b  ([rows,576])
+ * fused = 1: encattn.hip, one launch; rows L_b <= i < T are written as zeros, nothing at or behind L_b is read.  fused = 0: the
+ * four-launch sequence of jv_encoder_fwd (temporaries allocated and freed inside the call, which then synchronises), which reads
+ * all T rows and leaves the average of V in rows L_b <= i < T; T > 512: JV_ERR_SHAPE.  Rows of no utterance are not written. */
+int jv_op_enc_attention(const float* qkv, const int64_t* lens, int B, int T, int G, int S, int fused, float* out, void* stream);
 float jv_h3_scale_for_bound(float bound);   /* host only: the power of two chosen for a proven bound (0 = unusable) */
 /* process-wide (the jv_op_* hooks take no context): fp16x3 products per step of the hooks jv_op_linear_h3,
  * jv_op_conv_h3_measured, jv_op_attention_h3, jv_op_attention_planes, jv_op_rowgemm, jv_op_rowgemm_qkv, jv_op_rowconv, jv_op_rowres

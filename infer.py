@@ -51,6 +51,8 @@ mel extractor.  Instead this CLI takes their outputs directly:
                              the same files are written, and the time to the first audio is printed per request
     --synthetic N            no checkpoint / no tokens: N synthetic tokens, key-hashed weights (smoke / demo)
     --synthetic-prompt K     with --synthetic: also a synthetic K-token voice prompt through the prompt encoder
+    --enc-attention MODE     text encoder attention: auto (four launches up to 512 tokens, one online-softmax launch above), fused
+                             (that launch at every length) or gemm (the four launches; texts beyond 512 tokens fail)
 
 With --text and no --tokens it explains what is missing instead of guessing.
 """
@@ -553,6 +555,9 @@ def main(argv=None):
     p.add_argument("--estimator-precision", default="fp32", choices=["fp32", "fp16"],
                    help="fp16: the CFM estimator as the reference's fp16 TensorRT plan runs it (fp16 operands, fp32 accumulation); "
                         "encoders and vocoder unchanged (every route: ids, --token2wav, streaming, server)")
+    p.add_argument("--enc-attention", default="auto", choices=["auto", "fused", "gemm"],
+                   help="text encoder attention: auto = four launches around a score buffer up to 512 tokens, one online-softmax "
+                        "launch above; fused = that launch at every length; gemm = the four launches (texts beyond 512 tokens fail)")
     p.add_argument("--cfg-rate", type=float, default=None, metavar="R",
                    help="classifier-free-guidance rate of the CFM solve, >= 0 (default: the decoder's inference_cfg_rate, 0.7); 0 runs "
                         "the solve without unconditional twins.  Every mode takes it")
@@ -605,6 +610,7 @@ def main(argv=None):
     print(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
     from jyutvoice_amd.runtime import get_runtime
     get_runtime(device).set_precision(args.estimator_precision)      # every route below runs on this runtime's context
+    get_runtime(device).set_encoder_attention(args.enc_attention)
     if args.token2wav:
         return token2wav_list(json.load(open(args.token2wav)), args, device)
     tts, hift = jyutvoice_amd.build_default(device)

@@ -20,6 +20,10 @@ JV_MODEL_FLOW = 3      # the decoder.* / spk_embed_affine_layer.* part of JV_MOD
 JV_PRECISION_FP32 = 0
 JV_PRECISION_FP16 = 1     # jv_flow_set_precision: the estimator's fp16x3 contractions issue the hi x hi product alone
 
+JV_ENC_ATTN_AUTO = 0      # jv_encoder_set_attention: four launches up to 512 tokens, encattn.hip's one launch above
+JV_ENC_ATTN_FUSED = 1
+JV_ENC_ATTN_GEMM = 2
+
 ACT = {"none": 0, "relu": 1, "gelu": 2, "mish": 3, "elu": 4, "silu": 5}
 PRO = {"none": 0, "snake": 1, "lrelu": 2}
 
@@ -72,6 +76,7 @@ SIGNATURES = {
     "jv_flow_encoder_fwd_ctx": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "jv_flow_token2mel_ctx": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "jv_encoder_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "jv_encoder_set_attention": (_i, [_p, _i]),
     "jv_load_mel_basis": (_i, [_p, _p, _i64, _i, _p]),
     "jv_mel_spectrogram": (_i, [_p, _p, _i, _i, _p, _p]),
     "jv_mel_spectrogram_ragged": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
@@ -109,6 +114,7 @@ SIGNATURES = {
     "jv_op_conv_gemm": (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _p, _p, _f, _p, _p, _p, _p]),
     "jv_op_attention": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "jv_op_rel_attention": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "jv_op_enc_attention": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "jv_h3_scale_for_bound": (_f, [_f]),
     "jv_op_set_products": (_i, [_i]),
     "jv_op_conv_h3_measured": (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _p, _p, _p, _f, _p, _p, _p]),

@@ -583,6 +583,32 @@ int jv_op_rel_attention(const float* qkv, const float* p, const float* u, const 
   return rc;
 }
 
+// The text encoder's attention on caller-supplied buffers: encattn.hip's one launch (fused) or the layer's four-launch sequence
+// (encoder.hip enc_attention_gemm) with temporaries of this call (test hook)
+int jv_op_enc_attention(const float* qkv, const int64_t* lens, int B, int T, int G, int S, int fused, float* out, void* stream) {
+  if (!qkv || !lens || !out) return jv::fail(JV_ERR_ARG, "jv_op_enc_attention: null argument");
+  if (B < 1 || T < 1 || G < 0 || S < T) return jv::fail(JV_ERR_ARG, "jv_op_enc_attention: bad geometry");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long* len = reinterpret_cast<const long*>(lens);
+  if (fused) return jv::enc_attention(qkv, len, B, T, G, S, out, st);
+  if (T > jv::ENC_ATTN_GEMM_MAX) return jv::fail(JV_ERR_SHAPE, "jv_op_enc_attention: the four-launch route supports up to 512 tokens");
+  static bool inited = false;
+  if (!inited) {
+    JV_TRY(jv::conv_gemm_init());
+    inited = true;
+  }
+  const size_t ld = (size_t)jv::round_up(T, 32), n_sc = (size_t)B * 2 * T * ld, n_vt = (size_t)B * 2 * 288 * ld;
+  float* tmp = nullptr;
+  JV_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(float) * (n_sc + n_vt)));
+  int rc = JV_OK;
+  if (hipMemsetAsync(tmp, 0, sizeof(float) * (n_sc + n_vt), st) != hipSuccess) rc = jv::fail(JV_ERR_HIP, "jv_op_enc_attention: staging failed");
+  if (rc == JV_OK) rc = jv::enc_attention_gemm(qkv, tmp, tmp + n_sc, out, len, B, T, G, S, st);
+  const hipError_t se = hipStreamSynchronize(st);
+  (void)hipFree(tmp);
+  if (rc == JV_OK && se != hipSuccess) rc = jv::fail(JV_ERR_HIP, std::string("jv_op_enc_attention: ") + hipGetErrorString(se));
+  return rc;
+}
+
 int jv_flow_token2mel(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
                       const int64_t* token_lens, const float* prompt_feat, const int32_t* feat_lens, const float* embedding, int B,
                       int P, int N, int F, int streaming, int n_timesteps, float temperature, const float* t_span_host, float* mel,

@@ -3,9 +3,10 @@
 // :216-248 (2-head RoPE attention), :276-281 (conv FFN); jyutvoice/models/duration_predictor.py:48-60;
 // jyutvoice/models/jyutvoice_tts.py:175-176 (speaker projection), :184-203 (length regulation).
 //
-// ~1-2 % of the path's FLOPs: every contraction reuses the conv_gemm kernel -- the 288-wide attention heads as two
-// batched GEMMs (q k^T with the K rows as the "weight" operand; P V with a transposed V) around a masked-softmax
-// kernel -- so no second attention kernel has to be tuned for a stage this small.
+// ~1-2 % of the path's FLOPs: every contraction reuses the conv_gemm kernel.  Up to 512 tokens that includes the 288-wide
+// attention heads, as two batched GEMMs (q k^T with the K rows as the "weight" operand; P V with a transposed V) around a
+// masked-softmax kernel and a [B,2,Tt,Tt] score buffer (enc_attention_gemm); longer texts, whose score buffer would be what
+// bounds the batch, run the one-launch kernel of encattn.hip.  enc_attention_route decides, jv_encoder_set_attention overrides.
 #include "../../include/jyutvoice_hip.h"
 #include "jv_model.h"
 #include "jv_ops.h"
@@ -53,7 +54,8 @@ int enc_ws_create(Context& c) {
   const long rows = E_G + (long)c.max_batch * (c.max_tokens + E_GAP);
   w->rows_alloc = round_up((int)rows, 128) + 128;
   const size_t R = (size_t)w->rows_alloc;
-  const size_t ld = (size_t)round_up(c.max_tokens, 32);
+  const size_t tq = (size_t)std::min(c.max_tokens, ENC_ATTN_GEMM_MAX);   // the score buffer serves the four-launch route alone
+  const size_t ld = (size_t)round_up((int)tq, 32);
   auto F = [&](float** p, size_t floats) { return ws_alloc(c, floats * sizeof(float), reinterpret_cast<void**>(p)); };
   JV_TRY(F(&w->e0, R * 192));
   JV_TRY(F(&w->e1, R * 192));
@@ -68,7 +70,7 @@ int enc_ws_create(Context& c) {
   JV_TRY(F(&w->d2, R * 256));
   JV_TRY(F(&w->mu, R * 80));
   JV_TRY(F(&w->lw, R * 4));
-  JV_TRY(F(&w->scores, (size_t)c.max_batch * 2 * c.max_tokens * ld));
+  JV_TRY(F(&w->scores, (size_t)c.max_batch * 2 * tq * ld));
   JV_TRY(F(&w->vt, (size_t)c.max_batch * 2 * 288 * ld));
   JV_TRY(F(&w->spkn, (size_t)c.max_batch * 192));
   JV_TRY(F(&w->cond, (size_t)c.max_batch * 576));
@@ -85,6 +87,14 @@ void enc_ws_destroy(Context& c) {
 
 namespace {
 
+// The one place a call's attention route is decided: *fused = encattn.hip's one launch, else enc_attention_gemm.
+int enc_attention_route(const Context& c, int Tt, bool* fused) {
+  if (c.enc_attn == JV_ENC_ATTN_GEMM && Tt > ENC_ATTN_GEMM_MAX)
+    return fail(JV_ERR_SHAPE, "batch/tokens exceed the capacity given to jv_create (and the 512-token attention limit)");
+  *fused = c.enc_attn == JV_ENC_ATTN_FUSED || (c.enc_attn == JV_ENC_ATTN_AUTO && Tt > ENC_ATTN_GEMM_MAX);
+  return JV_OK;
+}
+
 ConvGemmArgs gemm_args(const float* A, int lda, long a_rows, long M, const GemmW& w, float* out, int ldo) {
   ConvGemmArgs a;
   conv_gemm_defaults(a);
@@ -97,6 +107,32 @@ ConvGemmArgs gemm_args(const float* A, int lda, long a_rows, long M, const GemmW
 }
 
 }  // namespace
+
+// scores = Q K^T, P = softmax(masked scores / sqrt(288)), V^T, att = P V: four launches on a qkv row buffer (rope_qk applied)
+int enc_attention_gemm(const float* qkv, float* scores, float* vt, float* att, const long* xlen, int B, int Tt, int G, int S,
+                       hipStream_t st) {
+  if (Tt > ENC_ATTN_GEMM_MAX) return fail(JV_ERR_SHAPE, "encoder attention supports up to 512 tokens");
+  const int ld = round_up(Tt, 32);
+  ConvGemmArgs a;
+  // scores[b,h] = Q_bh K_bh^T : the K rows are the K-contiguous "weight" operand
+  conv_gemm_defaults(a);
+  a.A = qkv + (long)G * 1728; a.lda = 1728; a.a_rows = Tt; a.M = Tt; a.Cin = 288; a.ntaps = 1;
+  a.W = qkv + (long)G * 1728 + 576; a.ldw = 1728; a.n_rows_w = Tt; a.N = Tt;
+  a.out = scores; a.ldo = ld;
+  a.nb2 = 2;
+  a.sA1 = (long)S * 1728; a.sA2 = 288; a.sW1 = (long)S * 1728; a.sW2 = 288; a.sO1 = 2L * Tt * ld; a.sO2 = (long)Tt * ld;
+  JV_TRY(conv_gemm(a, B * 2, st));
+  JV_TRY(enc_softmax(scores, xlen, B, 2, Tt, ld, st));
+  JV_TRY(transpose_v(qkv, vt, B, Tt, ld, G, S, st));
+  // att[b, :, h*288:(h+1)*288] = P_bh V_bh
+  conv_gemm_defaults(a);
+  a.A = scores; a.lda = ld; a.a_rows = Tt; a.M = Tt; a.Cin = ld; a.ntaps = 1;
+  a.W = vt; a.ldw = ld; a.n_rows_w = 288; a.N = 288;
+  a.out = att + (long)G * 576; a.ldo = 576;
+  a.nb2 = 2;
+  a.sA1 = 2L * Tt * ld; a.sA2 = (long)Tt * ld; a.sW1 = 2L * 288 * ld; a.sW2 = 288L * ld; a.sO1 = (long)S * 576; a.sO2 = 288;
+  return conv_gemm(a, B * 2, st);
+}
 
 // Linear(192 -> 80)(F.normalize(spk)): the speaker vector of the flow decoder (jyutvoice_tts.py:175-176, flow/flow.py:315-316)
 int speaker_projection(Context& c, const float* spk, int B, float* spks_out, hipStream_t st) {
@@ -116,8 +152,9 @@ int encoder_fwd(Context& c, const long* phone, const long* lang, const long* ton
                                                     "the text encoder (encoder.*) and the duration predictor (dp.*) are missing"
                                                   : "tts weights not finalized");
   if (B < 1 || Tt < 1) return fail(JV_ERR_ARG, "batch and token count must be positive");
-  if (B > c.max_batch || Tt > c.max_tokens || Tt > 512)
-    return fail(JV_ERR_SHAPE, "batch/tokens exceed the capacity given to jv_create (and the 512-token attention limit)");
+  if (B > c.max_batch || Tt > c.max_tokens) return fail(JV_ERR_SHAPE, "batch/tokens exceed the capacity given to jv_create");
+  bool fused = false;
+  JV_TRY(enc_attention_route(c, Tt, &fused));
   EncWs& w = *c.ews;
   const EncoderW& e = c.enc;
   const int S = Tt + E_GAP;
@@ -149,30 +186,13 @@ int encoder_fwd(Context& c, const long* phone, const long* lang, const long* ton
   JV_TRY(concat_fill(spk, lang, e.lang_emb, xlen, w.h, B, Tt, E_G, S, st));
 
   // 6 post-LN layers; every LayerNorm writes masked rows so "x * x_mask" never needs its own pass
-  const int ld = round_up(Tt, 32);
   for (int i = 0; i < ENC_LAYERS; ++i) {
     const EncLayerW& L = e.layer[i];
     ConvGemmArgs a = gemm_args(w.h, 576, AR, M, L.qkv, w.qkv, 1728);
     JV_TRY(conv_gemm(a, 1, st));
     JV_TRY(rope_qk(w.qkv, B, Tt, E_G, S, st));
-    // scores[b,h] = Q_bh K_bh^T : the K rows are the K-contiguous "weight" operand
-    conv_gemm_defaults(a);
-    a.A = w.qkv + (long)E_G * 1728; a.lda = 1728; a.a_rows = Tt; a.M = Tt; a.Cin = 288; a.ntaps = 1;
-    a.W = w.qkv + (long)E_G * 1728 + 576; a.ldw = 1728; a.n_rows_w = Tt; a.N = Tt;
-    a.out = w.scores; a.ldo = ld;
-    a.nb2 = 2;
-    a.sA1 = (long)S * 1728; a.sA2 = 288; a.sW1 = (long)S * 1728; a.sW2 = 288; a.sO1 = 2L * Tt * ld; a.sO2 = (long)Tt * ld;
-    JV_TRY(conv_gemm(a, B * 2, st));
-    JV_TRY(enc_softmax(w.scores, xlen, B, 2, Tt, ld, st));
-    JV_TRY(transpose_v(w.qkv, w.vt, B, Tt, ld, E_G, S, st));
-    // att[b, :, h*288:(h+1)*288] = P_bh V_bh
-    conv_gemm_defaults(a);
-    a.A = w.scores; a.lda = ld; a.a_rows = Tt; a.M = Tt; a.Cin = ld; a.ntaps = 1;
-    a.W = w.vt; a.ldw = ld; a.n_rows_w = 288; a.N = 288;
-    a.out = w.att + (long)E_G * 576; a.ldo = 576;
-    a.nb2 = 2;
-    a.sA1 = 2L * Tt * ld; a.sA2 = (long)Tt * ld; a.sW1 = 2L * 288 * ld; a.sW2 = 288L * ld; a.sO1 = (long)S * 576; a.sO2 = 288;
-    JV_TRY(conv_gemm(a, B * 2, st));
+    if (fused) JV_TRY(enc_attention(w.qkv, xlen, B, Tt, E_G, S, w.att, st));
+    else JV_TRY(enc_attention_gemm(w.qkv, w.scores, w.vt, w.att, xlen, B, Tt, E_G, S, st));
     a = gemm_args(w.att, 576, AR, M, L.o, w.y, 576);
     JV_TRY(conv_gemm(a, 1, st));
     JV_TRY(layernorm_rows(w.h, w.y, w.h, L.n1.g, L.n1.b, 1e-4f, M, 576, w.mask, st));
@@ -241,6 +261,14 @@ int jv_encoder_fwd(jv_context* ctx, const int64_t* phone, const int64_t* lang, c
                          reinterpret_cast<const long*>(tone), reinterpret_cast<const long*>(word_pos),
                          reinterpret_cast<const long*>(syllable_pos), reinterpret_cast<const long*>(x_lengths), spk, B, Tt, x,
                          mu_x, logw, spks_proj, static_cast<hipStream_t>(stream));
+}
+
+int jv_encoder_set_attention(jv_context* ctx, int mode) {
+  if (!ctx) return jv::fail(JV_ERR_ARG, "jv_encoder_set_attention: null context");
+  if (mode != JV_ENC_ATTN_AUTO && mode != JV_ENC_ATTN_FUSED && mode != JV_ENC_ATTN_GEMM)
+    return jv::fail(JV_ERR_ARG, "jv_encoder_set_attention: JV_ENC_ATTN_AUTO, JV_ENC_ATTN_FUSED or JV_ENC_ATTN_GEMM");
+  ctx->c.enc_attn = mode;      // read at the head of the next jv_encoder_fwd: launches already queued keep their route
+  return JV_OK;
 }
 
 int jv_length_regulate(jv_context* ctx, const float* logw, const int64_t* x_lengths, const float* mu_x, int B, int Tt,

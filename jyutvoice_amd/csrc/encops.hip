@@ -207,7 +207,7 @@ int l2_normalize(const float* x, float* out, int B, int C, hipStream_t st) {
 
 // ---- length regulation -------------------------------------------------------------------------------------
 // w_ceil = ceil(exp(logw) * mask) * length_scale; cum = torch.cumsum semantics on the CPU (sequential fp64
-// accumulation, every prefix rounded to fp32); y_len = max(long(sum), 1).  One lane per utterance (Tt <= 512).
+// accumulation, every prefix rounded to fp32); y_len = max(long(sum), 1).  One lane per utterance, one pass over its tokens.
 __global__ void durations_kernel(const float* __restrict__ logw, const long* __restrict__ xlen, float scale,
                                  float* __restrict__ w_ceil, float* __restrict__ cum, long* __restrict__ ylen, int B, int Tt) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;

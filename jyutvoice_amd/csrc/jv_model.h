@@ -179,6 +179,7 @@ struct Context {
   bool est_fp16 = false;         // jv_flow_set_precision(JV_PRECISION_FP16) / JV_EST_FP16=1: the estimator's fp16x3 contractions issue the hi x hi product alone (EstRoute::np)
   bool step_graphs = false;      // replay the Euler step as a captured hipGraph (jv_flow_set_graph; never under the profiler)
   std::vector<float> guidance;   // jv_flow_set_guidance: empty = rate 0.7 in every Euler step; one entry = that rate in every step; more = one per step (a solve's n_timesteps must match)
+  int enc_attn = 0;              // jv_encoder_set_attention: JV_ENC_ATTN_AUTO / _FUSED / _GEMM (encoder.hip enc_attention_route)
   int attn_chunk = 0;            // > 0: streaming (chunk-causal) estimator attention, in frames (jv_flow_set_streaming)
   // workspace
   std::vector<void*> ws_allocs;
@@ -234,6 +235,13 @@ int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* t
 
 // encoder.hip: Linear(192 -> 80)(F.normalize(spk)) (jyutvoice_tts.py:175-176, flow.py:315-316)
 int speaker_projection(Context& c, const float* spk, int B, float* spks_out, hipStream_t st);
+// the four-launch attention of a text-encoder layer on explicit buffers (encoder.hip): scores [B,2,Tt,ld], vt [B,2,288,ld],
+// ld = round_up(Tt, 32) <= 512; att rows are written for all Tt rows of every utterance
+constexpr int ENC_ATTN_GEMM_MAX = 512;
+int enc_attention_gemm(const float* qkv, float* scores, float* vt, float* att, const long* xlen, int B, int Tt, int G, int S,
+                       hipStream_t st);
+// encattn.hip: the same attention in one launch (online softmax, no [Tt, Tt] buffer); rows L_b <= i < Tt are written as zeros
+int enc_attention(const float* qkv, const long* len, int B, int T, int G, int S, float* att, hipStream_t st);
 
 // prompt.hip
 int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int Tk, float* h_out, hipStream_t st);

@@ -597,6 +597,19 @@ class Engine:
         return mel, ml
 
     # ---- encoder --------------------------------------------------------------------------------------
+    ENC_ATTENTION = {"auto": 0, "fused": 1, "gemm": 2}      # JV_ENC_ATTN_AUTO / _FUSED / _GEMM
+    encoder_attention = "auto"                              # what set_encoder_attention() left on this context
+
+    def set_encoder_attention(self, mode: str = "auto"):
+        """the route of the text encoder's attention (jv_encoder_set_attention).  "auto" (default): four launches around a
+        [B, 2, Tt, Tt] score buffer up to 512 tokens, the one-launch online-softmax kernel (encattn.hip) above; "fused": that kernel
+        at every length; "gemm": the four launches, and texts beyond 512 tokens raise JvError.  Another name raises ValueError
+        and leaves the mode as it was."""
+        if mode not in self.ENC_ATTENTION:
+            raise ValueError(f"encoder attention must be one of {sorted(self.ENC_ATTENTION)}, not {mode!r}")
+        check(self.lib.jv_encoder_set_attention(self._h, self.ENC_ATTENTION[mode]))
+        self.encoder_attention = mode
+
     def encoder(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed):
         B, Tt = x.shape
         ids = [v.to(device=self.device, dtype=torch.int64).contiguous() for v in (x, lang, tone, word_pos, syllable_pos)]
@@ -863,6 +876,18 @@ def op_rel_attention(qkv, p, u, v, lens, B, T, G, S, len_mul=1, chunk=0, fused=T
     lens = lens.to(device=qkv.device, dtype=torch.int64).contiguous()
     check(lib.jv_op_rel_attention(_ptr(qkv), _ptr(p), _ptr(u), _ptr(v), _ptr(lens), int(B), int(T), int(G), int(S), int(len_mul),
                                   int(chunk), 1 if fused else 0, _ptr(out), _stream(qkv.device)))
+    return out
+
+
+def op_enc_attention(qkv, lens, B, T, G, S, fused=True):
+    """the text encoder's attention (jv_op_enc_attention): qkv [rows, 1728] (rows G + b*S + t; q | k | v, 2 heads of 288 each, RoPE
+    applied), lens int64 [B] -> out [rows, 576]; fused: encattn.hip's one launch (rows at and behind a length are zeros), else the
+    four-launch sequence (T <= 512; those rows hold an average of V).  Rows the call does not own come back NaN."""
+    lib = _lib.load()
+    out = torch.full((qkv.shape[0], 576), float("nan"), device=qkv.device)
+    lens = lens.to(device=qkv.device, dtype=torch.int64).contiguous()
+    check(lib.jv_op_enc_attention(_ptr(qkv), _ptr(lens), int(B), int(T), int(G), int(S), 1 if fused else 0, _ptr(out),
+                                  _stream(qkv.device)))
     return out
 
 

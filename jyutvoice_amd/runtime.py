@@ -24,6 +24,7 @@ class Runtime:
         self.sds: Dict[int, Dict[str, torch.Tensor]] = {}
         self.noise = None
         self.precision = "fp32"
+        self.encoder_attention = "auto"
 
     def set_weights(self, model: int, sd: Dict[str, torch.Tensor]):
         """validate + upload a state-dict (raises like nn.Module.load_state_dict)"""
@@ -71,6 +72,14 @@ class Runtime:
             self.engine.set_precision(precision)      # (may refuse: exact_range is on)
         self.precision = precision
 
+    def set_encoder_attention(self, mode: str = "auto"):
+        """Engine.set_encoder_attention on this runtime's context, kept across the contexts a weight reload creates"""
+        if mode not in Engine.ENC_ATTENTION:
+            raise ValueError(f"encoder attention must be one of {sorted(Engine.ENC_ATTENTION)}, not {mode!r}")
+        if self.engine is not None:
+            self.engine.set_encoder_attention(mode)
+        self.encoder_attention = mode
+
     def _rebuild(self, caps):
         """new context + upload of every known state-dict: only when WEIGHTS change (the C ABI finalizes a model once)"""
         if self.engine is not None:
@@ -85,6 +94,8 @@ class Runtime:
         eng.load_noise(self.noise)
         if self.precision != "fp32":
             eng.set_precision(self.precision)
+        if self.encoder_attention != "auto":
+            eng.set_encoder_attention(self.encoder_attention)
         self.engine = eng
         self.caps = caps
 
