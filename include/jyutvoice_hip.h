@@ -605,14 +605,31 @@ int jv_op_rel_attention(const float* qkv, const float* p, const float* u, const 
 int jv_op_enc_attention(const float* qkv, const int64_t* lens, int B, int T, int G, int S, int fused, float* out, void* stream);
 float jv_h3_scale_for_bound(float bound);   /* host only: the power of two chosen for a proven bound (0 = unusable) */
 /* process-wide (the jv_op_* hooks take no context): fp16x3 products per step of the hooks jv_op_linear_h3,
- * jv_op_conv_h3_measured, jv_op_attention_h3, jv_op_attention_planes, jv_op_rowgemm, jv_op_rowgemm_qkv, jv_op_rowconv, jv_op_rowres
- * and jv_op_rowblock -- 3 (default), or 1 = the hi x hi product alone, what JV_PRECISION_FP16 selects on a context.  Read by those
+ * jv_op_conv_h3_measured, jv_op_splitk, jv_op_attention_h3, jv_op_attention_planes, jv_op_rowgemm, jv_op_rowgemm_qkv, jv_op_rowconv,
+ * jv_op_rowres and jv_op_rowblock -- 3 (default), or 1 = the hi x hi product alone, what JV_PRECISION_FP16 selects on a context.  Read by those
  * hooks and by nothing on the production path. */
 int jv_op_set_products(int np);
 int jv_op_conv_h3_measured(const float* A, int64_t a_rows, int M, int Cin, int ntaps, int tap_row0, int dil, const float* W,
                            int N, const float* bias, int act, int prologue, const float* alpha, float slope,
                            const uint8_t* rowmask, const float* res, const float* amax_in, float a_extra, float* amax_out,
                            float* out, void* stream);
+/* jv_op_splitk: a contraction to 256 channels on the estimator's short-batch route (2048 rows or fewer): split-K tiles
+ * (ConvGemmArgs::ksplit) into partial sums, then ONE row-wise launch that sums them and runs the whole tail -- through the launcher
+ * the estimator itself calls (conv_splitk).  N must be 256.
+ *   v      = sum_j A[m + tap_row0 + j] W_j + bias                 A [a_rows, Cin] (rows with rowmask == 0 read as zero), W [256, ntaps Cin]
+ *   v      = act(LayerNorm_256(v) ln_g + ln_b), eps 1e-5          (ln_g != NULL; else act alone); rows with rowmask == 0 := 0
+ *   out[m] = v + rowvec[row_sample[m] * rowvec_ld] + res[m]       out [M, ldo], res [M, ldr] (may be out itself)
+ *   out2[m] = LayerNorm_256(out[m]) ln2_g + ln2_b                 (ln2_g != NULL) [M, 256]
+ * rowmask [a_rows] (optional) is the input mask, the output mask and the tracking mask; row_sample [a_rows]: a row's utterance.
+ * ksplit_max workgroups per tile, clamped to Cin / 32 (the estimator: 8).  mode: 0 bf16x6; 1 fp16x3 scaled per utterance by the
+ * measured bounds amax_in[slot_nb], slot(row) = clamp((row - slot_G) / slot_S, 0, slot_nb - 1) or, slot_S < 0, row_sample[row];
+ * 2 fp16x3 scaled by the caller's proven a_bound.  amax_out [slot_nb] (optional, zero it first): max |out| over the rows with
+ * rowmask != 0 is folded into slot row_sample[row]. */
+int jv_op_splitk(const float* A, int64_t a_rows, int M, int Cin, int ntaps, int tap_row0, const float* W, int N, const float* bias,
+                 const float* ln_g, const float* ln_b, int act, const uint8_t* rowmask, const float* rowvec,
+                 const int32_t* row_sample, int rowvec_ld, const float* res, int64_t ldr, float* out, int64_t ldo, const float* ln2_g,
+                 const float* ln2_b, float* out2, int ksplit_max, int mode, const float* amax_in, float a_bound, int slot_G,
+                 int slot_S, int slot_nb, float* amax_out, void* stream);
 int jv_op_attention_h3(const float* qkv, const int32_t* lens, int B, int G, int S, int L, float q_bound, float k_bound,
                        float v_bound, float* out, void* stream);
 int jv_op_linear_h3(const float* A, int64_t rows, int M, int K, const float* W, int N, const float* bias, int act,

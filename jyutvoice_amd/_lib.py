@@ -118,6 +118,8 @@ SIGNATURES = {
     "jv_h3_scale_for_bound": (_f, [_f]),
     "jv_op_set_products": (_i, [_i]),
     "jv_op_conv_h3_measured": (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _p, _p, _p, _f, _p, _p, _p]),
+    "jv_op_splitk": (_i, [_p, _i64, _i, _i, _i, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i64, _p, _i64, _p, _p, _p, _i, _i, _p, _f,
+                          _i, _i, _i, _p, _p]),
     "jv_op_attention_h3": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _f, _p, _p]),
     "jv_op_linear_h3": (_i, [_p, _i64, _i, _i, _p, _i, _p, _i, _p, _f, _i, _p, _p]),
     "jv_op_attention_planes": (_i, [_p, _i64, _p, _i, _i, _i, _i, _f, _f, _f, _i, _f, _p, _p, _p]),

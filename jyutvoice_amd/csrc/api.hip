@@ -89,7 +89,7 @@ static void workspaces_destroy(Context& c) {
 // looked up under a lock, so a buffer allocated on device A is never handed out after hipSetDevice(B) and two threads cannot
 // race the grow.  Calls of ONE hook on ONE device still share the buffer: the caller serialises those (stream order does).
 namespace {
-enum OpSlot { OPS_X6 = 0, OPS_H3, OPS_H3_A, OPS_CONV, OPS_RG, OPS_RG_A, OPS_RC, OPS_HIFT, OPS_ATTN, OPS_QKV, OPS_QKV_A, OPS_RR, OPS_HP, OPS_RB, OPS_COUNT };
+enum OpSlot { OPS_X6 = 0, OPS_H3, OPS_H3_A, OPS_CONV, OPS_RG, OPS_RG_A, OPS_RC, OPS_HIFT, OPS_ATTN, OPS_QKV, OPS_QKV_A, OPS_RR, OPS_HP, OPS_RB, OPS_SK, OPS_COUNT };
 int op_scratch(int slot, size_t need, void** out) {
   struct Buf { void* p = nullptr; size_t cap = 0; };
   static std::mutex mu;
@@ -687,6 +687,75 @@ int jv_op_conv_h3_measured(const float* A, int64_t a_rows, int M, int Cin, int n
   }
   a.np = g_op_products;
   return jv::conv_gemm(a, 1, st);
+}
+
+// A contraction to 256 channels on the estimator's short-M route, from fp32 operands: conv_splitk (rowops.hip) -- the split-K tiles
+// and splitk_reduce_rows' tail, the launcher Est::splitk calls -- with the weight planes and the partial sums in hook scratch.
+// mode: how A and W are scaled, as the estimator's three kinds of split launches: 0 bf16x6 (the first resnet's block1), 1 fp16x3
+// with the measured per-utterance bounds amax_in[slot_nb] (the other convolutions; slot(row) = clamp((row - slot_G) / slot_S), or
+// slot_S < 0: row_sample[row]), 2 fp16x3 with the proven a_bound (to_out, ff.net.2).  rowmask serves as rowmask_in, rowmask_out and
+// amax_mask (causal3 + ln_mish + track)
+int jv_op_splitk(const float* A, int64_t a_rows, int M, int Cin, int ntaps, int tap_row0, const float* W, int N, const float* bias,
+                 const float* ln_g, const float* ln_b, int act, const uint8_t* rowmask, const float* rowvec,
+                 const int32_t* row_sample, int rowvec_ld, const float* res, int64_t ldr, float* out, int64_t ldo, const float* ln2_g,
+                 const float* ln2_b, float* out2, int ksplit_max, int mode, const float* amax_in, float a_bound, int slot_G,
+                 int slot_S, int slot_nb, float* amax_out, void* stream) {
+  static bool inited = false;
+  if (!inited) {
+    JV_TRY(jv::conv_gemm_init());
+    inited = true;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (N != 256) return jv::fail(JV_ERR_ARG, "jv_op_splitk: the split-K tail exists for N = 256 only");
+  if (!A || !W || !out || M <= 0 || a_rows < M || Cin <= 0 || (Cin & 31) || ntaps < 1 || ksplit_max < 1 || ksplit_max > 64 ||
+      mode < 0 || mode > 2 || (ldo & 3) || ldo < 256 || (res && ((ldr & 3) || ldr < 256)) || (rowvec_ld & 3) || rowvec_ld < 0)
+    return jv::fail(JV_ERR_ARG, "jv_op_splitk: bad shape (Cin % 32, 1 <= ksplit_max <= 64, mode 0 .. 2, ldo / ldr / rowvec_ld % 4)");
+  if ((ln_g != nullptr) != (ln_b != nullptr) || (ln2_g && (!ln2_b || !out2)))
+    return jv::fail(JV_ERR_ARG, "jv_op_splitk: a LayerNorm needs gain and offset (and the second one out2)");
+  if (!row_sample && ((rowvec && rowvec_ld) || (amax_out && slot_nb > 1) || (mode == 1 && slot_S < 0)))
+    return jv::fail(JV_ERR_ARG, "jv_op_splitk: per-utterance vectors and slots need row_sample");
+  if (mode == 1 && (!amax_in || slot_nb < 1)) return jv::fail(JV_ERR_ARG, "jv_op_splitk: mode 1 needs amax_in[slot_nb]");
+  const float sc = mode == 2 ? jv::h3_scale_for_bound(a_bound) : 0.f;
+  if (mode == 2 && !(sc > 0.f)) return jv::fail(JV_ERR_ARG, "jv_op_splitk: unusable bound");
+  const size_t n = (size_t)N * ntaps * Cin;
+  const int ksplit = ksplit_max < (Cin >> 5) ? ksplit_max : (Cin >> 5);      // conv_splitk's clamp: the partials it will write
+  float* partial = nullptr;
+  unsigned short* planes = nullptr;
+  float *cs = nullptr, *stats = nullptr;
+  auto layout = [&](Bump& b) {
+    partial = b.take<float>((size_t)ksplit * M * 256);      // first: two calls at one M keep their partials at the same addresses
+    planes = b.take<unsigned short>((mode == 0 ? 3 : 2) * n);
+    cs = b.take<float>((size_t)N);
+    stats = b.take<float>(2 * (size_t)N);
+  };
+  void* scratch = nullptr;
+  { Bump b{nullptr}; layout(b); JV_TRY(op_scratch(OPS_SK, b.off, &scratch)); }
+  { Bump b{static_cast<char*>(scratch)}; layout(b); }
+  jv::ConvGemmArgs a;
+  jv::conv_gemm_defaults(a);
+  a.A = A; a.lda = Cin; a.a_rows = a_rows; a.M = M; a.Cin = Cin; a.ntaps = ntaps; a.tap_row0 = tap_row0; a.tap_dil = 1;
+  a.W = W; a.ldw = ntaps * Cin; a.n_rows_w = N; a.N = N; a.bias = bias; a.out = out; a.ldo = ldo;
+  if (ln_g) { a.ln = 1; a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = 1e-5f; }
+  a.act = act;
+  a.rowmask_in = rowmask; a.rowmask_out = rowmask;
+  a.rowvec = rowvec; a.row_sample = row_sample; a.rowvec_ld = rowvec_ld;
+  a.res1 = res; a.ldr1 = ldr;
+  a.amax_out = amax_out; a.amax_mask = rowmask;
+  if (mode == 0) {
+    JV_TRY(jv::split3_planes(W, planes, (long)n, st));
+    a.W3 = planes; a.w3_plane = (long)n;
+  } else {
+    JV_TRY(jv::split2h_planes(W, N, ntaps * Cin, stats, planes, cs, st));
+    a.W2 = planes; a.w2_plane = (long)n; a.colscale = cs;
+    if (mode == 2) {
+      a.a_scale = sc;
+    } else {
+      a.amax_in = amax_in; a.a_extra = 0.f;
+      a.amax_G = slot_G; a.amax_S = slot_S > 0 ? slot_S : 0; a.amax_nb = slot_nb; a.amax_rows = slot_S < 0 ? row_sample : nullptr;
+    }
+  }
+  a.np = g_op_products;
+  return jv::conv_splitk(a, ksplit_max, partial, row_sample, ln2_g, ln2_b, out2, st);
 }
 
 // the fp16x3 attention kernel; q_bound, k_bound, v_bound: the caller's proven bounds on |q|, |k|, |v| (test hook)

@@ -154,20 +154,9 @@ struct Est {
   void causal3(ConvGemmArgs& a) const { a.tap_row0 = -2; a.rowmask_in = w.rowmask; }   // CausalConv1d k=3: rows t-2, t-1, t of the masked input
   // `a`: the full-semantics launch (N = 256); ln2 / out2: optional LayerNorm of the stored row for the next GEMM
   int splitk(const ConvGemmArgs& a, const LnW* ln2, float* out2) {
-    ConvGemmArgs p = a;
-    p.ln = 0; p.act = ACT_NONE; p.bias = nullptr; p.rowmask_out = nullptr; p.rowvec = nullptr; p.row_sample = nullptr;
-    p.res1 = nullptr; p.amax_out = nullptr;
-    p.out = w.partial; p.ldo = 256;
-    p.ksplit = std::min(rt.ksplit, a.Cin >> 5); p.split_stride = (long)a.M * 256;
-    JV_TRY(conv(p));
-    SplitKReduceArgs r{};
-    r.partial = w.partial; r.ksplit = p.ksplit; r.split_stride = p.split_stride; r.rows = a.M;
-    r.bias = a.bias; r.ln = a.ln; r.ln_g = a.ln_g; r.ln_b = a.ln_b; r.ln_eps = a.ln_eps; r.act = a.act;
-    r.rowmask = a.rowmask_out; r.rowvec = a.rowvec; r.row_sample = w.row_sample; r.rowvec_ld = a.rowvec_ld;
-    r.res = a.res1; r.ldr = a.ldr1; r.out = a.out; r.ldo = a.ldo;
-    r.amax_out = a.amax_out; r.amax_mask = a.amax_mask;
-    if (ln2) { r.ln2_g = ln2->g; r.ln2_b = ln2->b; r.out2 = out2; }
-    return splitk_reduce_rows(r, st);
+    ConvGemmArgs f = a;
+    f.np = rt.np;
+    return conv_splitk(f, rt.ksplit, w.partial, w.row_sample, ln2 ? ln2->g : nullptr, ln2 ? ln2->b : nullptr, out2, st);
   }
   // A causal k = 3 convolution to 256 channels, by the route: split-K tiles at short M, the row-owning kernel where the batch
   // fills the chip and the input has a tracked bound, else the tile kernels.

@@ -232,6 +232,10 @@ struct SplitKReduceArgs {
   const float *ln2_g, *ln2_b; float* out2;              // optional: LayerNorm_256(out row) -> out2 [rows, 256]
 };
 int splitk_reduce_rows(const SplitKReduceArgs& a, hipStream_t st);
+// a contraction to 256 channels as split-K tiles + that tail (the estimator's short-M route): `full` = the launch with its whole
+// semantics; ksplit is clamped to Cin / 32; partial [ksplit][M][256]; row_sample: the tail's row -> utterance table
+int conv_splitk(const ConvGemmArgs& full, int ksplit, float* partial, const int* row_sample, const float* ln2_g, const float* ln2_b,
+                float* out2, hipStream_t st);
 // fp16 planes [2][N][ldw] (row n = output column n, K-contiguous) -> fragment order [2][K/32][N/16][64 lanes][8 halves] (k-step major: the
 // column blocks a workgroup loads in one step are contiguous): lane l of a v_mfma_f32_16x16x32_f16 B operand holds row
 // 16 nb + (l & 15), k = 32 ks + 8 (l >> 4) ... + 8 (rowgemm.hip)

@@ -298,6 +298,29 @@ int splitk_reduce_rows(const SplitKReduceArgs& a, hipStream_t st) {
   return JV_OK;
 }
 
+// The two launches of a split-K contraction to 256 channels (the estimator's short-M route, Est::splitk; jv_op_splitk).
+// `a`: the launch with its whole semantics (N = 256, np set); its contraction runs with the tail stripped, over
+// min(ksplit, Cin / 32) workgroups per tile into partial [ksplit][M][256], and splitk_reduce_rows does the tail.
+// row_sample: the row -> utterance table (the time embedding's row and the tracked slot); ln2_g / ln2_b / out2: optional LayerNorm
+// of the stored row for the next GEMM
+int conv_splitk(const ConvGemmArgs& a, int ksplit, float* partial, const int* row_sample, const float* ln2_g, const float* ln2_b,
+                float* out2, hipStream_t st) {
+  ConvGemmArgs p = a;
+  p.ln = 0; p.act = ACT_NONE; p.bias = nullptr; p.rowmask_out = nullptr; p.rowvec = nullptr; p.row_sample = nullptr;
+  p.res1 = nullptr; p.amax_out = nullptr;
+  p.out = partial; p.ldo = 256;
+  p.ksplit = ksplit < (a.Cin >> 5) ? ksplit : (a.Cin >> 5); p.split_stride = (long)a.M * 256;
+  JV_TRY(conv_gemm(p, 1, st));
+  SplitKReduceArgs r{};
+  r.partial = partial; r.ksplit = p.ksplit; r.split_stride = p.split_stride; r.rows = a.M;
+  r.bias = a.bias; r.ln = a.ln; r.ln_g = a.ln_g; r.ln_b = a.ln_b; r.ln_eps = a.ln_eps; r.act = a.act;
+  r.rowmask = a.rowmask_out; r.rowvec = a.rowvec; r.row_sample = row_sample; r.rowvec_ld = a.rowvec_ld;
+  r.res = a.res1; r.ldr = a.ldr1; r.out = a.out; r.ldo = a.ldo;
+  r.amax_out = a.amax_out; r.amax_mask = a.amax_mask;
+  if (ln2_g) { r.ln2_g = ln2_g; r.ln2_b = ln2_b; r.out2 = out2; }
+  return splitk_reduce_rows(r, st);
+}
+
 // ---- row metadata: rowmask[r] (1 = real frame) and row_sample[r] (utterance index) -----------------
 // Two geometries.  Uniform (uoff == null): utterance b, frame t at row G + b S + t.  COMPACT (uoff != null, ragged batches,
 // flow.hip): utterance b starts at row uoff[b] and owns lens[b % nb] rows + the gap up to uoff[b + 1] -- no row is spent on

@@ -906,6 +906,36 @@ def op_conv_h3_measured(A, W, bias=None, ntaps=1, tap_row0=0, dil=1, M=None, act
     return out
 
 
+def op_splitk(A, W, bias=None, M=None, ntaps=1, tap_row0=0, ln=None, act="none", rowmask=None, rowvec=None, row_sample=None,
+              rowvec_ld=0, res=None, out=None, ln2=None, out2=None, ksplit_max=8, mode=0, amax_in=None, a_bound=0.0,
+              slots=(0, 0, 1), amax_out=None):
+    """the estimator's short-batch route (jv_op_splitk): split-K tiles + the row-wise reduce tail, through the launcher the
+    estimator calls.  A [rows, Cin], W [256, ntaps * Cin]; ln / ln2 = (gain, offset); rowmask uint8 [rows] and row_sample int32 [rows];
+    res and out: row-major views whose row strides become ldr / ldo (res may be out: in place; out may be the right half of a
+    [rows, 512] buffer); mode 0 bf16x6, 1 fp16x3 from amax_in [nb] with slots = (G, S, nb) (S < 0: through row_sample), 2 fp16x3 from
+    a_bound.  -> (out, out2); buffers allocated here come back NaN outside the M rows the launch owns."""
+    lib = _lib.load()
+    rows, cin = A.shape
+    N = W.shape[0]
+    M = rows if M is None else M
+    if out is None:
+        out = torch.full((rows, 256), float("nan"), device=A.device)
+    g, b = (ln if ln is not None else (None, None))
+    g2, b2 = (ln2 if ln2 is not None else (None, None))
+    if ln2 is not None and out2 is None:
+        out2 = torch.full((rows, 256), float("nan"), device=A.device)
+    for t in (out, res):
+        if t is not None and (t.dim() != 2 or t.stride(1) != 1 or t.shape[1] < 256):
+            raise ValueError("op_splitk: out and res are row-major [rows, >= 256] views")
+    G, S, nb = slots
+    check(lib.jv_op_splitk(_ptr(A), rows, M, cin, ntaps, tap_row0, _ptr(W), N, _ptr(bias), _ptr(g), _ptr(b), _lib.ACT[act],
+                           _ptr(rowmask), _ptr(rowvec), _ptr(row_sample), int(rowvec_ld), _ptr(res),
+                           0 if res is None else res.stride(0), _ptr(out), out.stride(0), _ptr(g2), _ptr(b2), _ptr(out2),
+                           int(ksplit_max), int(mode), _ptr(amax_in), float(a_bound), int(G), int(S), int(nb), _ptr(amax_out),
+                           _stream(A.device)))
+    return out, out2
+
+
 def op_attention_h3(qkv, lens, B, G, S, L, bounds=None):
     """fp16x3 attention kernel; bounds = (|q|, |k|, |v|) maxima the caller vouches for (default: measured)"""
     lib = _lib.load()
