@@ -568,6 +568,30 @@ int jv_slab_copy(jv_context* ctx, const float* src, int src_rows, int src_width,
                  const int32_t* desc, int B, int span, int zero_fill, void* stream);
 int jv_hift_decode(jv_context* ctx, const float* mel, const float* s, const int32_t* lens, int B, int T, float* wav,
                    void* stream);
+/* jv_hift_decode_tap (used by the parity tests): jv_hift_decode's own launch sequence up to and including one stage, whose
+ * workspace buffer is then copied out channels-first as out [B, C, L] -- an early return inside the function jv_hift_decode
+ * runs, not a second sequence: the geometry decision, the masks and every launch ahead of the return are the whole decode's.
+ * No waveform is written.  Positions at or behind an utterance's clamped length (lens[b] frames = L-per-frame x lens[b]
+ * positions, + 1 at the x120 level) are zeros, an utterance of length 0 is all zeros.  out_floats < B*C*L: JV_ERR_SHAPE;
+ * an unknown tap: JV_ERR_ARG; both before the first launch.  Taps in execution order (C, L):
+ *   STFT   (18, 120 T + 1)  9 real | 9 imaginary bins of the source's 16-point STFT
+ *   PRE    (512, T)         conv_pre
+ *   UPi    (256, 8 T) / (128, 40 T) / (64, 120 T + 1)   the i-th ConvTranspose1d (i = 2: behind the reflection pad)
+ *   SIi    as UPi           the i-th source-down convolution, ahead of its ResBlock
+ *   XSi    as UPi           UPi + the source ResBlock
+ *   Xi     as UPi           the mean of the three ResBlocks (the stage's output)
+ *   POST   (18, 120 T + 1)  conv_post: 9 log-magnitudes | 9 phases
+ *   FRAMES (16, 120 T + 1)  the windowed inverse-DFT frames, ahead of overlap-add and clip */
+#define JV_HIFT_TAP_STFT 0
+#define JV_HIFT_TAP_PRE 1
+#define JV_HIFT_TAP_UP0 2    /* UP1 = 3, UP2 = 4 */
+#define JV_HIFT_TAP_SI0 5    /* SI1 = 6, SI2 = 7 */
+#define JV_HIFT_TAP_XS0 8    /* XS1 = 9, XS2 = 10 */
+#define JV_HIFT_TAP_X0 11    /* X1 = 12, X2 = 13 */
+#define JV_HIFT_TAP_POST 14
+#define JV_HIFT_TAP_FRAMES 15
+int jv_hift_decode_tap(jv_context* ctx, const float* mel, const float* s, const int32_t* lens, int B, int T, int tap, float* out,
+                       int64_t out_floats, void* stream);
 
 /* ---- operator-level entry points (used by the parity tests; same kernels the stages above launch) -------------
  * jv_op_conv_gemm: out[m,n] = act(sum_{j,ci} A[m + tap_row0 + j*dil, ci] * W[n, j*Cin + ci] + bias[n]) (+ res[m,n])

@@ -24,6 +24,12 @@ JV_ENC_ATTN_AUTO = 0      # jv_encoder_set_attention: four launches up to 512 to
 JV_ENC_ATTN_FUSED = 1
 JV_ENC_ATTN_GEMM = 2
 
+# jv_hift_decode_tap: tap name -> (id, channels, positions per mel frame, + positions) as include/jyutvoice_hip.h lists them
+HIFT_TAPS = {"STFT": (0, 18, 120, 1), "PRE": (1, 512, 1, 0), "POST": (14, 18, 120, 1), "FRAMES": (15, 16, 120, 1)}
+for _i_lvl, (_c, _m, _a) in enumerate(((256, 8, 0), (128, 40, 0), (64, 120, 1))):
+    for _k, _name in enumerate(("UP", "SI", "XS", "X")):
+        HIFT_TAPS[f"{_name}{_i_lvl}"] = (2 + 3 * _k + _i_lvl, _c, _m, _a)
+
 ACT = {"none": 0, "relu": 1, "gelu": 2, "mish": 3, "elu": 4, "silu": 5}
 PRO = {"none": 0, "snake": 1, "lrelu": 2}
 
@@ -111,6 +117,7 @@ SIGNATURES = {
     "jv_hift_source_cont_rows": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
     "jv_slab_copy": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p]),
     "jv_hift_decode": (_i, [_p, _p, _p, _p, _i, _i, _p, _p]),
+    "jv_hift_decode_tap": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _i64, _p]),
     "jv_op_conv_gemm": (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _f, _p, _p, _f, _p, _p, _p, _p]),
     "jv_op_attention": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "jv_op_rel_attention": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),

@@ -31,8 +31,11 @@ int sine_source_rows(const float* f0, const float* phase, const float* lin_w, co
 // (uoff3: optional first rows of the utterances at level 3 -- the compact geometry of ragged batches, below)
 int stft_rows(const float* s, float* out, const int* lens, int B, int T, int G3, int S3, long rows, hipStream_t st, const int* uoff3 = nullptr);
 int reflect_fix(float* x, int B, int G3, int S3, int C, hipStream_t st, const int* uoff3 = nullptr);
-int istft_head(const float* post, float* frames, float* wav, const int* lens, int B, int T, int G3, int S3, long rows,
-               hipStream_t st, const int* uoff3 = nullptr);
+int istft_frames(const float* post, float* frames, long rows, hipStream_t st);
+int istft_ola(const float* frames, float* wav, const int* lens, int B, int T, int G3, int S3, hipStream_t st, const int* uoff3 = nullptr);
+
+int hift_tap_copy(const float* src, int ld, int C, int G, int S, const int* uoff, int mul, int add, const int* lens, int B, int L,
+                  float* dst, hipStream_t st);
 
 constexpr int H_G0 = 4, H_GAP0 = 4;
 constexpr int UPS[3] = {8, 5, 3};
@@ -145,6 +148,26 @@ int check(Context& c, int B, int T) {
   if (B < 1 || T < 1) return fail(JV_ERR_ARG, "batch and frame count must be positive");
   if (B > c.max_batch || T > c.max_frames) return fail(JV_ERR_SHAPE, "batch/frames exceed the capacity given to jv_create");
   return JV_OK;
+}
+
+// jv_hift_decode_tap: the stage whose buffer hift_decode copies out before it returns early (null: the whole decode)
+struct HiftTap {
+  int id;
+  float* out;
+  long out_floats;
+};
+
+// channels and level of a tap's buffer (false: no such tap).  Levels as in HGeo: 0 mel, 1 x8, 2 x40, 3 x120 + 1
+bool tap_shape(int id, int* C, int* lvl) {
+  if (id == JV_HIFT_TAP_STFT || id == JV_HIFT_TAP_POST) { *C = 18; *lvl = 3; return true; }
+  if (id == JV_HIFT_TAP_FRAMES) { *C = 16; *lvl = 3; return true; }
+  if (id == JV_HIFT_TAP_PRE) { *C = HIFT_CH; *lvl = 0; return true; }
+  if (id >= JV_HIFT_TAP_UP0 && id < JV_HIFT_TAP_POST) {
+    *lvl = (id - JV_HIFT_TAP_UP0) % 3 + 1;
+    *C = HIFT_CH >> *lvl;
+    return true;
+  }
+  return false;
 }
 
 ConvGemmArgs conv_args(const float* A, int lda, long a_rows, long M, const GemmW& w, float* out, int ldo, int tap_row0,
@@ -315,11 +338,25 @@ int hift_source_rows(Context& c, const float* f0, const float* phase, const unsi
   return sine_source_rows(f0, phase, c.hift.src_lin_w, c.hift.src_lin_b, c.hws->frac, s, B, T, seeds, calls, sample0, lens, cum, st);
 }
 
-int hift_decode(Context& c, const float* mel, const float* s, const int* lens, int B, int T, float* wav, hipStream_t st) {
+// tap (jv_hift_decode_tap, else null): return behind the launches of that stage, its buffer copied out channels-first; nothing
+// ahead of the return depends on it
+int hift_decode(Context& c, const float* mel, const float* s, const int* lens, int B, int T, float* wav, hipStream_t st,
+                const HiftTap* tap = nullptr) {
   JV_TRY(check(c, B, T));
   HiftWs& w = *c.hws;
   const HiftW& h = c.hift;
   HGeo g = make_geo(c, B, T);
+  if (tap) {
+    int C = 0, lvl = 0;
+    if (!tap_shape(tap->id, &C, &lvl)) return fail(JV_ERR_ARG, "jv_hift_decode_tap: unknown tap");
+    if (tap->out_floats < (long)B * C * g.L[lvl]) return fail(JV_ERR_SHAPE, "jv_hift_decode_tap: out holds fewer than B*C*L floats");
+  }
+  auto at = [&](int id) { return tap && tap->id == id; };
+  auto tap_out = [&](const float* buf, int ld) {      // (g by reference: read where the tap is taken, behind the geometry decision)
+    int C = 0, lvl = 0;
+    tap_shape(tap->id, &C, &lvl);
+    return hift_tap_copy(buf, ld, C, g.G[lvl], g.S[lvl], g.uoff[lvl], LVL_MUL[lvl], lvl == 3 ? 1 : 0, w.lens, B, g.L[lvl], tap->out, st);
+  };
   // Ragged batch: the COMPACT geometry (HiftWs::uoff) when it saves at least 8 % of the rows -- every level's rows are the mel
   // level's times a factor, so laying the utterances end to end at the mel level lays them end to end everywhere.  The lengths
   // come down once (B ints, one synchronisation per decode); every per-row sum is the uniform geometry's: the same bits.
@@ -351,6 +388,7 @@ int hift_decode(Context& c, const float* mel, const float* s, const int* lens, i
   float* stft = w.stft_alloc + 16 * 32;
   JV_TRY(stft_rows(s, stft, w.lens, B, T, g.G[3], g.S[3], g.alloc[3], st, g.uoff[3]));
   JV_HIP(hipMemsetAsync(w.amax, 0, sizeof(float) * HiftWs::A_SLOTS * w.amax_stride, st));
+  if (at(JV_HIFT_TAP_STFT)) return tap_out(stft, 32);
   const bool h3 = !c.exact_range;
   auto am = [&](int slot) { return w.amax + (long)slot * w.amax_stride; };
 
@@ -361,6 +399,7 @@ int hift_decode(Context& c, const float* mel, const float* s, const int* lens, i
     amax_geo(a, g, 0, w.mask[0]);
     JV_TRY(conv_gemm(a, 1, st));
   }
+  if (at(JV_HIFT_TAP_PRE)) return tap_out(w.x0, 512);
   const float* prev = w.x0;
   float* am_prev = am(HiftWs::A_X0);
   int prevC = 512;
@@ -377,6 +416,7 @@ int hift_decode(Context& c, const float* mel, const float* s, const int* lens, i
       JV_TRY(conv_gemm(a, 1, st));
       if (i == 2) JV_TRY(reflect_fix(w.x[i], B, g.G[3], g.S[3], C, st, g.uoff[3]));
     }
+    if (at(JV_HIFT_TAP_UP0 + i)) return tap_out(w.x[i], C);
     // source branch: strided conv of the STFT rows, then a ResBlock whose last layer also adds the up-sampled trunk
     {
       ConvGemmArgs a = conv_args(stft + sd_off[i] * 32, sd_stride[i] * 32, g.rows[l], g.rows[l], h.src_down[i], w.si[i], C,
@@ -384,14 +424,17 @@ int hift_decode(Context& c, const float* mel, const float* s, const int* lens, i
       a.amax_out = h3 ? am(HiftWs::A_SI + i) : nullptr;
       amax_geo(a, g, l, w.mask[l]);
       JV_TRY(conv_gemm(a, 1, st));
+      if (at(JV_HIFT_TAP_SI0 + i)) return tap_out(w.si[i], C);
       JV_TRY(resblock(h.src_rb[i], g, l, C, g.rows[l], g.alloc[l], w.mask[l], w.si[i], w.r[i], w.tmp[i], w.xs[i], w.x[i], 1.f, 0,
                       am(HiftWs::A_SI + i), am(HiftWs::A_R + i), am(HiftWs::A_TMP + i), am(HiftWs::A_XS + i), h3, !c.no_hiftconv, !c.no_hift_pair, st));
     }
+    if (at(JV_HIFT_TAP_XS0 + i)) return tap_out(w.xs[i], C);
     // x = xs now holds x_up + si ; MRF: mean of the three ResBlocks, accumulated into w.x[i]
     for (int j = 0; j < 3; ++j)
       JV_TRY(resblock(h.rb[3 * i + j], g, l, C, g.rows[l], g.alloc[l], w.mask[l], w.xs[i], w.r[i], w.tmp[i], w.x[i], nullptr,
                       1.f / 3.f, j > 0 ? 1 : 0, am(HiftWs::A_XS + i), am(HiftWs::A_R + i), am(HiftWs::A_TMP + i),
                       am(HiftWs::A_X + i), h3, !c.no_hiftconv, !c.no_hift_pair, st));
+    if (at(JV_HIFT_TAP_X0 + i)) return tap_out(w.x[i], C);
     prev = w.x[i];
     am_prev = am(HiftWs::A_X + i);
     prevC = C;
@@ -402,7 +445,10 @@ int hift_decode(Context& c, const float* mel, const float* s, const int* lens, i
     a.pro = PRO_LRELU; a.pro_slope = 0.01f;
     JV_TRY(conv_gemm(a, 1, st));
   }
-  return istft_head(w.post, w.frames, wav, w.lens, B, T, g.G[3], g.S[3], g.rows[3], st, g.uoff[3]);
+  if (at(JV_HIFT_TAP_POST)) return tap_out(w.post, 32);
+  JV_TRY(istft_frames(w.post, w.frames, g.rows[3], st));
+  if (at(JV_HIFT_TAP_FRAMES)) return tap_out(w.frames, 16);
+  return istft_ola(w.frames, wav, w.lens, B, T, g.G[3], g.S[3], st, g.uoff[3]);
 }
 
 }  // namespace jv
@@ -455,6 +501,14 @@ int jv_hift_decode(jv_context* ctx, const float* mel, const float* s, const int3
   if (!ctx || !mel || !s || !wav) return jv::fail(JV_ERR_ARG, "jv_hift_decode: null argument");
   JV_HIP(hipSetDevice(ctx->c.device));
   return jv::hift_decode(ctx->c, mel, s, lens, B, T, wav, static_cast<hipStream_t>(stream));
+}
+
+int jv_hift_decode_tap(jv_context* ctx, const float* mel, const float* s, const int32_t* lens, int B, int T, int tap, float* out,
+                       int64_t out_floats, void* stream) {
+  if (!ctx || !mel || !s || !out) return jv::fail(JV_ERR_ARG, "jv_hift_decode_tap: null argument");
+  JV_HIP(hipSetDevice(ctx->c.device));
+  const jv::HiftTap t{tap, out, (long)out_floats};
+  return jv::hift_decode(ctx->c, mel, s, lens, B, T, nullptr, static_cast<hipStream_t>(stream), &t);
 }
 
 }  // extern "C"

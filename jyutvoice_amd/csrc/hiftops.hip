@@ -361,11 +361,40 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
   wav[idx] = v;
 }
 
-int istft_head(const float* post, float* frames, float* wav, const int* lens, int B, int T, int G3, int S3, long rows,
-               hipStream_t st, const int* uoff3) {
+int istft_frames(const float* post, float* frames, long rows, hipStream_t st) {
   hipLaunchKernelGGL(istft_frames_kernel, dim3((unsigned)cdivl(rows, 256)), dim3(256), 0, st, post, frames, rows);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
+int istft_ola(const float* frames, float* wav, const int* lens, int B, int T, int G3, int S3, hipStream_t st, const int* uoff3) {
   hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)cdivl((long)B * T * 480, 256)), dim3(256), 0, st, frames, wav, lens, B, T,
                      G3, S3, 0.99f, uoff3);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
+// ---- stage tap (jv_hift_decode_tap): a level's row buffer -> channels-first [B, C, L] ------------------------------------------
+// dst[b, c, t] = src[row0(b) + t][c] for t < lens[b] * mul + add (nothing for lens[b] = 0), zero behind; row0(b) = uoff[b] in the
+// compact geometry, G + b S otherwise.  lens: the clamped lengths (HiftWs::lens), so a live row lies inside the level's rows
+__global__ __launch_bounds__(256) void hift_tap_copy_kernel(const float* __restrict__ src, int ld, int C, int G, int S,
+                                                            const int* __restrict__ uoff, int mul, int add,
+                                                            const int* __restrict__ lens, int B, int L, float* __restrict__ dst) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)B * C * L) return;
+  const int t = (int)(idx % L);
+  const long bc = idx / L;
+  const int c = (int)(bc % C), b = (int)(bc / C);
+  const int len = lens[b];
+  const long live = len > 0 ? min((long)len * mul + add, (long)L) : 0;
+  const long row0 = uoff ? (long)uoff[b] : (long)G + (long)b * S;
+  dst[idx] = t < live ? src[(row0 + t) * ld + c] : 0.f;
+}
+
+int hift_tap_copy(const float* src, int ld, int C, int G, int S, const int* uoff, int mul, int add, const int* lens, int B, int L,
+                  float* dst, hipStream_t st) {
+  hipLaunchKernelGGL(hift_tap_copy_kernel, dim3((unsigned)cdivl((long)B * C * L, 256)), dim3(256), 0, st, src, ld, C, G, S, uoff, mul,
+                     add, lens, B, L, dst);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

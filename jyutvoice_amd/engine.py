@@ -824,6 +824,21 @@ class Engine:
         check(self.lib.jv_hift_decode(self._h, _ptr(mel), _ptr(s), _ptr(lens_d), B, T, _ptr(wav), _stream(self.device)))
         return wav
 
+    def hift_decode_tap(self, mel, s, lens, tap, out=None):
+        """jv_hift_decode_tap: hift_decode's own launches up to and including the stage `tap` (a name of _lib.HIFT_TAPS), that
+        stage's buffer as [B, C, L]: zeros at and behind every utterance's length.  (tap as a raw id, or `out` given: passed on as
+        they are -- the library rejects an id it does not know and a buffer that is too small)"""
+        B, _, T = mel.shape
+        mel, s = _f32(mel, self.device), _f32(s, self.device)
+        lens_d = None if lens is None else lens.to(device=self.device, dtype=torch.int32).contiguous()
+        tap_id = _lib.HIFT_TAPS[tap][0] if isinstance(tap, str) else int(tap)
+        if out is None:
+            _, C, mul, add = _lib.HIFT_TAPS[tap] if isinstance(tap, str) else (0, 1, 0, 1)
+            out = torch.empty(B, C, T * mul + add, device=self.device)
+        check(self.lib.jv_hift_decode_tap(self._h, _ptr(mel), _ptr(s), _ptr(lens_d), B, T, tap_id, _ptr(out), out.numel(),
+                                          _stream(self.device)))
+        return out
+
 
 # ---- operator-level helpers for the parity tests (same kernels the stages launch) ------------------------
 def op_conv_gemm(A, W, bias=None, ntaps=1, tap_row0=0, dil=1, M=None, act="none", prologue="none", alpha=None, slope=0.0,
