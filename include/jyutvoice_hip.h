@@ -129,6 +129,23 @@ int jv_flow_set_graph(jv_context* ctx, int on);
  * always eager.  JV_NO_TWIN_DROP=1 in the environment at jv_create keeps the twins in every step (for A/B runs).  With the
  * default and with 0.7 set explicitly the update is the same fp32 operations in the same order as before this mode existed. */
 int jv_flow_set_guidance(jv_context* ctx, const float* rates_host, int n);
+/* jv_flow_set_solver: the integrator of the closed solves, a context mode like jv_flow_set_guidance, read by the same entries
+ * (jv_cfm_solve, jv_cfm_solve_prompted, jv_flow_token2mel, _partial and _ctx).  With (t_k, dt_k) of step k exactly as before (the
+ * fp32 running recurrence over t_span) and g(x, t) = (1 + r_k) v(x, t | mu, spks, cond) - r_k v(x, t), in fp32 in this order:
+ *   JV_SOLVER_EULER (default): x <- x + dt g(x, t) -- ConditionalCFM.solve_euler (flow_matching.py:215-265), unchanged: the same
+ *     launches and the same bits as before this mode existed.
+ *   JV_SOLVER_MIDPOINT: xs = x + (0.5f dt) g(x, t);  x <- x + dt g(xs, t + 0.5f dt).
+ *   JV_SOLVER_HEUN:     k1 = g(x, t);  xs = x + dt k1;  x <- x + (0.5f dt) (k1 + g(xs, t + dt)).
+ * n_timesteps stays the number of STEPS: a second-order solve performs 2 n_timesteps estimator evaluations, and one whose
+ * evaluations exceed 1024 fails with JV_ERR_ARG naming both numbers before its first launch.  The guidance rate of step k (and
+ * so the step without twins behind a rate of exactly 0) holds for both of its evaluations; a guidance schedule still holds one rate
+ * per step.  Second-order solves always run eagerly on 2B (or B) samples: the captured graph of jv_flow_set_graph is an Euler step
+ * and replays for Euler solves only, and the shared twin of the first Euler step is not taken.  An unknown value fails with
+ * JV_ERR_ARG and leaves the mode unchanged.  Not read by jv_cfm_pool_step / _g (Euler); jv_cfm_pool_step_s takes a stage per request. */
+#define JV_SOLVER_EULER 0
+#define JV_SOLVER_MIDPOINT 1
+#define JV_SOLVER_HEUN 2
+int jv_flow_set_solver(jv_context* ctx, int solver);
 /* jv_flow_set_contraction: how fp32 contractions are carried out on the 16-bit matrix cores.  exact_range = 0
  * (default): fp16x3 -- each operand split into two fp16 planes after an exact power-of-two scaling (22 significant bits,
  * three MFMA products, fp32 accumulate) -- wherever an upper bound of the operand is known, so that fp16's range cannot be
@@ -215,7 +232,20 @@ int jv_cfm_solve_prompted(jv_context* ctx, const float* mu_y, const int32_t* y_l
  *   flow_matching.py:215-265 with the request's own inference_cfg_rate, or its guidance window's rate at this t): x += dt_b ((1 +
  *   cfg_b) v(x, t_b | ...) - cfg_b v(x, t_b)).  jv_cfm_pool_step is this call with 0.7 for all, bit for bit.  A pool step always
  *   carries two rows per frame, also for a request at rate 0: its twin is computed and (1 + 0) v_c - 0 v_u is v_c.  Dropping the
- *   twins of individual requests inside a step (a mixed twin map) is a follow-up. */
+ *   twins of individual requests inside a step (a mixed twin map) is a follow-up.
+ * jv_cfm_pool_step_s: jv_cfm_pool_step_g for requests with a solver of their own (jv_flow_set_solver's definitions): a request on
+ *   a second-order solver takes TWO pool steps per solver step, and every listed request is taken at its own stage_host[b] with
+ *   the coefficient coef_host[b], at time t_host[b].  With g = (1 + cfg_b) v(x, t_b | ...) - cfg_b v(x, t_b) and x = pool_x[slot]:
+ *     JV_STAGE_EULER  c = dt:      x <- x + c g                                   (jv_cfm_pool_step_g, bit for bit)
+ *     JV_STAGE_MID1   c = 0.5f dt: x0 <- x;  x <- x + c g                         (t_b = t)
+ *     JV_STAGE_MID2   c = dt:      x <- x0 + c g                                  (t_b = t + 0.5f dt)
+ *     JV_STAGE_HEUN1  c = dt:      x0 <- x;  k1 <- g;  x <- x + c g               (t_b = t)
+ *     JV_STAGE_HEUN2  c = 0.5f dt: x <- x0 + c (k1 + g)                           (t_b = t + dt)
+ *   pool_x0, pool_k1: [slots, Tcap, 80] like pool_x, caller-owned, 16-byte aligned; either may be NULL where no listed stage
+ *   touches it (Euler: neither, midpoint: pool_x0 only), else JV_ERR_ARG naming the request.  pool_x always holds the estimator's
+ *   next input, so between a step's two stages jv_cfm_pool_fetch would return the stage point: fetch after the last stage.  The
+ *   running maxima accumulate over all evaluations.  A request served this way is DEFINED as jv_cfm_solve_prompted at B = 1 under
+ *   jv_flow_set_solver with its solver, within the same 2e-5. */
 int jv_cfm_pool_admit(jv_context* ctx, const float* mu_y, const float* prompt_h, const float* prompt_feat, const float* spks,
                       const int32_t* y_lens_host, const int32_t* prompt_lens_host, const int32_t* slots_host,
                       const float* temperature_host, int B, int Ty, int Ph, int Pf, float* pool_x, float* pool_mu, float* pool_cond,
@@ -226,6 +256,15 @@ int jv_cfm_pool_step(jv_context* ctx, float* pool_x, const float* pool_mu, const
 int jv_cfm_pool_step_g(jv_context* ctx, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks,
                        float* pool_amax, int slots, int Tcap, const int32_t* slots_host, const int32_t* lens_host, const float* t_host,
                        const float* dt_host, const float* cfg_host, int B, void* stream);
+#define JV_STAGE_EULER 0
+#define JV_STAGE_MID1 1
+#define JV_STAGE_MID2 4
+#define JV_STAGE_HEUN1 3
+#define JV_STAGE_HEUN2 12
+int jv_cfm_pool_step_s(jv_context* ctx, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks,
+                       float* pool_amax, float* pool_x0, float* pool_k1, int slots, int Tcap, const int32_t* slots_host,
+                       const int32_t* lens_host, const float* t_host, const float* coef_host, const float* cfg_host,
+                       const int32_t* stage_host, int B, void* stream);
 int jv_cfm_pool_fetch(jv_context* ctx, const float* pool_x, int slots, int Tcap, const int32_t* slots_host, const int32_t* first_host,
                       const int32_t* lens_host, int B, int Tm, float* mel, void* stream);
 

@@ -168,16 +168,18 @@ def dump_ref_features(toks, args, device):
 
 
 def guidance_kw(args, decoder):
-    """--cfg-rate / --cfg-window / --t-scheduler as the keywords of synthesise(), of the flow's inference calls and of the streaming
-    sessions.  A flag that was not given says nothing: `decoder`'s own inference_cfg_rate / t_scheduler hold (the window is placed on
-    the t of the schedule the solve will run)."""
+    """--cfg-rate / --cfg-window / --t-scheduler / --solver as the keywords of synthesise(), of the flow's inference calls and of the
+    streaming sessions.  A flag that was not given says nothing: `decoder`'s own inference_cfg_rate / t_scheduler / solver hold (the
+    window is placed on the t of the schedule the solve will run)."""
     from jyutvoice_amd.flow.flow_matching import decoder_settings
     kw = {}
     if args.t_scheduler is not None:
         kw["t_scheduler"] = args.t_scheduler
+    if args.solver is not None:
+        kw["solver"] = args.solver
     if args.cfg_window is not None:
         from jyutvoice_amd.serve import guidance_rates
-        conf_rate, conf_sched = decoder_settings(decoder)
+        conf_rate, conf_sched, _ = decoder_settings(decoder)
         try:
             kw["cfg_schedule"] = guidance_rates(args.n_timesteps, conf_rate if args.cfg_rate is None else args.cfg_rate,
                                                 tuple(args.cfg_window), args.t_scheduler or conf_sched)
@@ -287,7 +289,7 @@ def dump_mels(args, mels):
 def synthesise_inflight(toks, ids, spk, feats, hs, args, tts, hift):
     """--tokens list.json --inflight S: the list through one SynthServer with at most S resident requests, a new request submitted
     every --arrive-every steps; the same out_NNN files as the list route.  A request's own "n_timesteps", "temperature",
-    "length_scale", "seed", "cfg_rate" and "cfg_window" keys override the command line's (seed: --seed + its index)."""
+    "length_scale", "seed", "cfg_rate", "cfg_window" and "solver" keys override the command line's (seed: --seed + its index)."""
     import torch
 
     from jyutvoice_amd.serve import SynthServer
@@ -311,7 +313,8 @@ def synthesise_inflight(toks, ids, spk, feats, hs, args, tts, hift):
                               n_timesteps=int(t.get("n_timesteps", args.n_timesteps)), temperature=float(t.get("temperature", 1.0)),
                               length_scale=float(t.get("length_scale", args.length_scale)), seed=int(t.get("seed", args.seed + b)),
                               loudness=args.loudness, peak=args.peak, cfg_rate=t.get("cfg_rate", args.cfg_rate),
-                              cfg_window=t.get("cfg_window", args.cfg_window), t_scheduler=args.t_scheduler)
+                              cfg_window=t.get("cfg_window", args.cfg_window), t_scheduler=args.t_scheduler,
+                              solver=t.get("solver", args.solver))
             except ValueError as e:
                 raise SystemExit(f"{args.tokens}: {e}")
         out.update(server.step())
@@ -565,6 +568,10 @@ def main(argv=None):
                    help="guide only the Euler steps whose t lies in [LO, HI); the others run at rate 0, without twins")
     p.add_argument("--t-scheduler", default=None, choices=["cosine", "linear"],
                    help="time schedule of the Euler steps (default: the decoder's t_scheduler, cosine in configs/base.yaml)")
+    p.add_argument("--solver", default=None, choices=["euler", "midpoint", "heun"],
+                   help="integrator of the CFM solve (default: the decoder's, euler): midpoint and heun take --n_timesteps second-order "
+                        "steps of two estimator evaluations each.  Every mode that takes --cfg-rate takes it; with --inflight a request "
+                        "of the list may carry its own \"solver\"")
     p.add_argument("--seed", type=int, default=0, help="seed of the vocoder's source-noise draws")
     p.add_argument("--sample_rate", type=int, default=24000, help="sample rate of the written audio (resampled on the GPU)")
     p.add_argument("--dump-ref-features", default=None, metavar="DIR",

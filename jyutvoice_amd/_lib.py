@@ -20,7 +20,11 @@ JV_MODEL_FLOW = 3      # the decoder.* / spk_embed_affine_layer.* part of JV_MOD
 JV_PRECISION_FP32 = 0
 JV_PRECISION_FP16 = 1     # jv_flow_set_precision: the estimator's fp16x3 contractions issue the hi x hi product alone
 
-JV_ENC_ATTN_AUTO = 0      # jv_encoder_set_attention: four launches up to 512 tokens, encattn.hip's one launch above
+SOLVERS = {"euler": 0, "midpoint": 1, "heun": 2}      # jv_flow_set_solver: JV_SOLVER_EULER / _MIDPOINT / _HEUN
+# jv_cfm_pool_step_s: JV_STAGE_* -- bit 0 saves x0, bit 1 saves k1, bit 2 starts from x0, bit 3 adds k1
+STAGE_EULER, STAGE_MID1, STAGE_MID2, STAGE_HEUN1, STAGE_HEUN2 = 0, 1, 4, 3, 12
+
+JV_ENC_ATTN_AUTO = 0    # jv_encoder_set_attention: four launches up to 512 tokens, encattn.hip's one launch above
 JV_ENC_ATTN_FUSED = 1
 JV_ENC_ATTN_GEMM = 2
 
@@ -66,6 +70,7 @@ SIGNATURES = {
     "jv_flow_set_streaming": (_i, [_p, _i]),
     "jv_flow_set_graph": (_i, [_p, _i]),
     "jv_flow_set_guidance": (_i, [_p, _p, _i]),
+    "jv_flow_set_solver": (_i, [_p, _i]),
     "jv_flow_set_contraction": (_i, [_p, _i]),
     "jv_flow_set_precision": (_i, [_p, _i]),
     "jv_flow_contraction_info": (_i, [_p, _p, _i]),
@@ -74,6 +79,7 @@ SIGNATURES = {
     "jv_cfm_pool_admit": (_i, [_p] * 9 + [_i] * 4 + [_p] * 5 + [_i, _i, _p]),
     "jv_cfm_pool_step": (_i, [_p] * 6 + [_i, _i] + [_p] * 4 + [_i, _p]),
     "jv_cfm_pool_step_g": (_i, [_p] * 6 + [_i, _i] + [_p] * 5 + [_i, _p]),
+    "jv_cfm_pool_step_s": (_i, [_p] * 8 + [_i, _i] + [_p] * 6 + [_i, _p]),
     "jv_cfm_pool_fetch": (_i, [_p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _p]),
     "jv_flow_encoder_fwd": (_i,[_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "jv_flow_token2mel": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),

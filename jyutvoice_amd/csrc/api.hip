@@ -352,6 +352,18 @@ int jv_flow_set_guidance(jv_context* ctx, const float* rates_host, int n) {
   return JV_OK;
 }
 
+// (host state only, like the guidance mode: the next solve's schedule and loop read it)
+int jv_flow_set_solver(jv_context* ctx, int solver) {
+  CTX_GUARD(ctx);
+  if (solver != JV_SOLVER_EULER && solver != JV_SOLVER_MIDPOINT && solver != JV_SOLVER_HEUN) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "jv_flow_set_solver: solver %d is none of JV_SOLVER_EULER, JV_SOLVER_MIDPOINT, JV_SOLVER_HEUN", solver);
+    return jv::fail(JV_ERR_ARG, msg);
+  }
+  ctx->c.solver = solver;
+  return JV_OK;
+}
+
 int jv_flow_set_graph(jv_context* ctx, int on) {
   CTX_GUARD(ctx);
   ctx->c.step_graphs = on != 0;
@@ -459,6 +471,20 @@ int jv_cfm_pool_step_g(jv_context* ctx, float* pool_x, const float* pool_mu, con
     return jv::fail(JV_ERR_ARG, "jv_cfm_pool_step_g: null argument");
   return jv::cfm_pool_step(ctx->c, pool_x, pool_mu, pool_cond, pool_spks, pool_amax, slots, Tcap, slots_host, lens_host, t_host,
                            dt_host, B, static_cast<hipStream_t>(stream), cfg_host);
+}
+
+int jv_cfm_pool_step_s(jv_context* ctx, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks,
+                       float* pool_amax, float* pool_x0, float* pool_k1, int slots, int Tcap, const int32_t* slots_host,
+                       const int32_t* lens_host, const float* t_host, const float* coef_host, const float* cfg_host,
+                       const int32_t* stage_host, int B, void* stream) {
+  CTX_GUARD(ctx);
+  if (!pool_x || !pool_mu || !pool_cond || !pool_spks || !pool_amax || !slots_host || !lens_host || !t_host || !coef_host || !cfg_host ||
+      !stage_host)
+    return jv::fail(JV_ERR_ARG, "jv_cfm_pool_step_s: null argument");
+  static_assert(JV_STAGE_EULER == jv::STAGE_EULER && JV_STAGE_MID1 == jv::STAGE_MID1 && JV_STAGE_MID2 == jv::STAGE_MID2 &&
+                JV_STAGE_HEUN1 == jv::STAGE_HEUN1 && JV_STAGE_HEUN2 == jv::STAGE_HEUN2, "the header's stage codes are jv_ops.h's");
+  return jv::cfm_pool_step(ctx->c, pool_x, pool_mu, pool_cond, pool_spks, pool_amax, slots, Tcap, slots_host, lens_host, t_host,
+                           coef_host, B, static_cast<hipStream_t>(stream), cfg_host, stage_host, pool_x0, pool_k1);
 }
 
 int jv_cfm_pool_fetch(jv_context* ctx, const float* pool_x, int slots, int Tcap, const int32_t* slots_host, const int32_t* first_host,

@@ -1,7 +1,8 @@
 // In-flight batching of the CFM solve (flow.hip cfm_pool_*; jv_cfm_pool_admit / _step / _fetch): the moves between the caller's
 // request pools and the solver's row buffers.  A request's state is its x, mu and cond rows ([slots, Tcap, 80], frame-major), its
 // projected speaker vector and six running maxima; a step gathers the listed slots into the workspace in either row geometry, and
-// after the estimator applies the Euler + CFG update with the request's OWN dt straight into the pool.  Bandwidth-trivial, 16 B
+// after the estimator applies the Euler + CFG update with the request's OWN dt -- or a stage of the request's own midpoint / Heun
+// step (pool_stage_scatter) -- straight into the pool.  Bandwidth-trivial, 16 B
 // per lane.  What the host decides per call arrives as kernel arguments (jv_ops.h: Pool*Chunk), one launch per POOL_CHUNK requests
 // where the arguments are read by the kernel itself; every index was validated on the host before the first launch.
 #include "jv_common.h"
@@ -165,6 +166,46 @@ int pool_euler_scatter(const PoolStepReq* req, int B, int tmax, const float* x, 
   if (B <= 0 || tmax <= 0) return JV_OK;
   hipLaunchKernelGGL(pool_euler_scatter_kernel, dim3((unsigned)cdivl((long)tmax * 20, 256), B), dim3(256), 0, st, req, B, x, d,
                      amax, amax_stride, pool_x, pool_amax, Tcap);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
+// ---- a stage of a request's OWN solver (jv_cfm_pool_step_s; rowops.hip solver_stage_kernel's expressions) with the stage and its
+// coefficient per request: requests on Euler, at a first and at a second stage share the launch.  pool_x always takes the estimator's
+// next input, so pool_gather serves every stage; x0 / k1 of a request live in pool_x0 / pool_k1 under its slot ---------------------
+__global__ __launch_bounds__(256) void pool_stage_scatter_kernel(const PoolStepReq* __restrict__ req, int B, const float* __restrict__ x,
+                                                                 const float* __restrict__ d, const float* __restrict__ amax,
+                                                                 int amax_stride, float* __restrict__ pool_x, float* __restrict__ pool_x0,
+                                                                 float* __restrict__ pool_k1, float* __restrict__ pool_amax, int Tcap) {
+  const int b = blockIdx.y;
+  const int slot = req[b].slot, len = req[b].len, stage = req[b].stage;
+  if (blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 70) {
+    const int k = (threadIdx.x - 64) >> 1, twin = (threadIdx.x - 64) & 1;
+    pool_amax[(long)slot * 6 + (threadIdx.x - 64)] = amax[k * amax_stride + (twin ? B + b : b)];
+  }
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  const int t = (int)(idx / 20), cc = (int)(idx - (long)t * 20) * 4;
+  if (t >= len) return;
+  const long r = (long)req[b].row + t, ru = (long)req[b].rowu + t;
+  const float c = req[b].dt, rate = req[b].cfg;
+  const f32x4 dc = *reinterpret_cast<const f32x4*>(d + r * 80 + cc);
+  const f32x4 du = *reinterpret_cast<const f32x4*>(d + ru * 80 + cc);
+  const f32x4 xin = *reinterpret_cast<const f32x4*>(x + r * 80 + cc);
+  const f32x4 g = (1.0f + rate) * dc - rate * du;
+  const long o = ((long)slot * Tcap + t) * 80 + cc;
+  f32x4 base = xin, inc = g;
+  if (stage & STAGE_SAVE_X0) *reinterpret_cast<f32x4*>(pool_x0 + o) = xin;
+  if (stage & STAGE_SAVE_K1) *reinterpret_cast<f32x4*>(pool_k1 + o) = g;
+  if (stage & STAGE_BASE_X0) base = *reinterpret_cast<const f32x4*>(pool_x0 + o);
+  if (stage & STAGE_ADD_K1) inc = *reinterpret_cast<const f32x4*>(pool_k1 + o) + g;
+  *reinterpret_cast<f32x4*>(pool_x + o) = base + c * inc;
+}
+
+int pool_stage_scatter(const PoolStepReq* req, int B, int tmax, const float* x, const float* d, const float* amax, int amax_stride,
+                       float* pool_x, float* pool_x0, float* pool_k1, float* pool_amax, int Tcap, hipStream_t st) {
+  if (B <= 0 || tmax <= 0) return JV_OK;
+  hipLaunchKernelGGL(pool_stage_scatter_kernel, dim3((unsigned)cdivl((long)tmax * 20, 256), B), dim3(256), 0, st, req, B, x, d,
+                     amax, amax_stride, pool_x, pool_x0, pool_k1, pool_amax, Tcap);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

@@ -23,6 +23,8 @@ int flow_ws_create(Context& c) {
   JV_TRY(F(&w->x, R * 80));
   JV_TRY(F(&w->mu, R * 80));
   JV_TRY(F(&w->cond, R * 80));
+  JV_TRY(F(&w->x0, R * 80));
+  JV_TRY(F(&w->k1, R * 80));
   JV_TRY(F(&w->spks, (size_t)B2 * 80));
   JV_TRY(F(&w->xin, R * 320));
   JV_TRY(F(&w->h, R * 256));
@@ -165,6 +167,18 @@ int guidance_check(const Context& c, const char* who, int n_timesteps) {
   return JV_OK;
 }
 
+// The solver mode of the context (jv_flow_set_solver) against a solve of n_timesteps steps: the tables hold one slot per estimator
+// evaluation, two per step of a second-order solver.  Called by every entry before its first launch, after its own range check.
+int solver_check(const Context& c, const char* who, int n_timesteps) {
+  if (c.solver != JV_SOLVER_EULER && 2L * n_timesteps > c.flow->max_steps) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: n_timesteps = %d with the %s solver (jv_flow_set_solver) is %ld estimator evaluations, the limit is %d",
+             who, n_timesteps, c.solver == JV_SOLVER_MIDPOINT ? "midpoint" : "Heun", 2L * n_timesteps, c.flow->max_steps);
+    return fail(JV_ERR_ARG, msg);
+  }
+  return JV_OK;
+}
+
 // the rate of step k: 0.7 where no mode is set (flow_matching.py:252-258, inference_cfg_rate of configs/base.yaml)
 float guidance_rate(const Context& c, int k) {
   return c.guidance.empty() ? 0.7f : c.guidance.size() == 1 ? c.guidance[0] : c.guidance[(size_t)k];
@@ -206,9 +220,28 @@ int solve_schedule(const Context& c, FlowWs& w, int n_timesteps, const float* t_
       if (s < n_timesteps) dt = ts[s + 1] - t;
     }
   }
-  JV_HIP(hipMemcpyAsync(w.t_table, tt.data(), sizeof(float) * n_timesteps, hipMemcpyHostToDevice, st));
-  JV_HIP(hipMemcpyAsync(w.dt_table, dts.data(), sizeof(float) * n_timesteps, hipMemcpyHostToDevice, st));
-  JV_HIP(hipMemcpyAsync(w.cfg_table, dts.data() + n_timesteps, sizeof(float) * n_timesteps, hipMemcpyHostToDevice, st));
+  // A second-order solver (jv_flow_set_solver): one table slot per EVALUATION, step k at slots 2k and 2k + 1 -- the second time
+  // is t + 0.5f dt (midpoint) or t + dt, the next step's t under the recurrence above (Heun); the coefficient of a stage's update
+  // is 0.5f dt in the half stage (midpoint's first, Heun's second), dt in the other; the step's rate holds for both evaluations
+  int n_evals = n_timesteps;
+  if (c.solver != JV_SOLVER_EULER) {
+    const bool mid = c.solver == JV_SOLVER_MIDPOINT;
+    n_evals = 2 * n_timesteps;
+    std::vector<float> t2((size_t)n_evals), c2(2 * (size_t)n_evals);
+    for (int k = 0; k < n_timesteps; ++k) {
+      const float t = tt[k], dt = dts[k], half = 0.5f * dt, rate = dts[(size_t)n_timesteps + k];
+      t2[2 * k] = t;
+      t2[2 * k + 1] = mid ? t + half : t + dt;
+      c2[2 * k] = mid ? half : dt;
+      c2[2 * k + 1] = mid ? dt : half;
+      c2[(size_t)n_evals + 2 * k] = c2[(size_t)n_evals + 2 * k + 1] = rate;
+    }
+    tt.swap(t2);
+    dts.swap(c2);
+  }
+  JV_HIP(hipMemcpyAsync(w.t_table, tt.data(), sizeof(float) * n_evals, hipMemcpyHostToDevice, st));
+  JV_HIP(hipMemcpyAsync(w.dt_table, dts.data(), sizeof(float) * n_evals, hipMemcpyHostToDevice, st));
+  JV_HIP(hipMemcpyAsync(w.cfg_table, dts.data() + n_evals, sizeof(float) * n_evals, hipMemcpyHostToDevice, st));
   return JV_OK;
 }
 
@@ -272,8 +305,11 @@ int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timest
   // Every step's t is on the device already and is the same for all rows: the n embeddings are three GEMMs of n rows HERE
   // instead of three GEMMs of 2B identical rows inside every step -- K = 1024 contractions of one row tile, 20 - 48 us each
   // at any batch size, 1.2 ms of serial launches per solve (JV_NO_TEMB_PRE=1: per step, as jv_flow_estimator_masked does)
-  g.temb_pre = !c.no_temb_pre && n_timesteps <= TS_MAX;
-  if (g.temb_pre) JV_TRY(time_embedding(c, w.t_table, 1, n_timesteps, w.ts_sin, w.ts_1, w.ts_mish, w.ts_emb, st));
+  // A second-order solver (jv_flow_set_solver) evaluates the estimator twice per step: solve_schedule laid the tables out per
+  // evaluation, so the embeddings ahead of the loop cover all 2n times where 2n <= TS_MAX
+  const int n_evals = c.solver == JV_SOLVER_EULER ? n_timesteps : 2 * n_timesteps;
+  g.temb_pre = !c.no_temb_pre && n_evals <= TS_MAX;
+  if (g.temb_pre) JV_TRY(time_embedding(c, w.t_table, 1, n_evals, w.ts_sin, w.ts_1, w.ts_mish, w.ts_emb, st));
   const EstRoute route = est_route(c, g.M, g.temb_pre, g.uoff != nullptr, c.attn_chunk);      // one route for every step (and for a captured one)
   // one Euler step over `gg` / `rt` with `ntwin` unconditional twins: B of them, the one shared twin of step 0 (after which the
   // slots it stands for take its maxima), or none in a step whose guidance rate is 0 (the row tables were built for 2B samples:
@@ -322,6 +358,33 @@ int solve_loop(Context& c, Geo& g, const float* spks, int B, int T, int n_timest
   for (int k = 0; k < n_timesteps; ++k) any_drop = any_drop || drop[(size_t)k];
   // step k in the form its rate allows (eager)
   auto step_k = [&](int k) -> int { return drop[(size_t)k] ? euler_step(st, twins ? gB : g, twins ? routeB : route, 0) : euler_step(st, g, route, B); };
+  // MIDPOINT / HEUN (jv_flow_set_solver; DESIGN.md 5 "Solver"): two evaluations per step, each the Euler step's launches with
+  // solver_stage in euler_cfg's place -- the first saves x (and, Heun, its slope) and leaves the stage point in w.x, the second
+  // forms the new x from the saved state.  step_advance_kernel advances per evaluation; the step's rate, and so its geometry
+  // (drop[k], by the rule above), holds for both.  Always eager, on 2B (or B) samples: step 0's first evaluation alone has
+  // identical twins, and the captured graph is a 2B EULER step -- it keeps replaying for Euler solves only.  The running maxima
+  // accumulate over all evaluations.
+  if (c.solver != JV_SOLVER_EULER) {
+    const bool mid = c.solver == JV_SOLVER_MIDPOINT;
+    for (int k = 0; k < n_timesteps; ++k) {
+      const bool no_twin = drop[(size_t)k];
+      const Geo& gg = no_twin && twins ? gB : g;
+      const EstRoute& rt = no_twin && twins ? routeB : route;
+      for (int e = 0; e < 2; ++e) {
+        hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(256), 0, st, w.t_table, w.dt_table, w.cfg_table, w.step_ctr, w.t_cur,
+                           w.dt_cur, w.cfg_cur, g.temb_pre ? w.ts_emb : nullptr, w.temb);
+        JV_TRY(assemble_xin(w.x, w.mu, w.spks, w.cond, w.xin, B, no_twin ? 0 : B, FLOW_G, gg.S, T, gg.M, st, gg.uoff, w.row_sample, w.rowmask));
+        JV_TRY(estimator_body(c, gg, rt, st));
+        const int stage = mid ? (e == 0 ? STAGE_MID1 : STAGE_MID2) : (e == 0 ? STAGE_HEUN1 : STAGE_HEUN2);
+        JV_TRY(solver_stage(w.x, w.x0, w.k1, w.d, B, FLOW_G, gg.S, T, w.dt_cur, w.cfg_cur, stage, no_twin ? SOLVER_TWIN_NONE : SOLVER_TWIN_EACH,
+                            st, gg.uoff, w.lens2));
+      }
+    }
+#ifdef JV_TUNING
+    JV_TRY(est_stamps_dump(c, g, st));
+#endif
+    return JV_OK;
+  }
   int done = 0;      // steps enqueued so far
   // ONE unconditional twin for the first step.  Every utterance starts from the same noise prefix, a twin has mu = spks = cond = 0
   // and t is one scalar: with equal lengths the B twins of step 0 are one sample B times over, so the step runs on B + 1 samples
@@ -403,6 +466,7 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
   FlowWs& w = *c.flow;
   if (n_timesteps < 1 || n_timesteps > w.max_steps) return fail(JV_ERR_ARG, "n_timesteps out of range");
   JV_TRY(guidance_check(c, "jv_cfm_solve", n_timesteps));
+  JV_TRY(solver_check(c, "jv_cfm_solve", n_timesteps));
   const int B2 = solve_twins(c, n_timesteps) ? 2 * B : B;      // samples laid out: no twin where no step has guidance
   Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, nullptr, 0};
 
@@ -451,6 +515,7 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
   if ((reinterpret_cast<uintptr_t>(prompt_h) | reinterpret_cast<uintptr_t>(prompt_feat)) & 15)
     return fail(JV_ERR_ARG, "jv_cfm_solve_prompted: prompt_h / prompt_feat must be 16-byte aligned");
   JV_TRY(guidance_check(c, "jv_cfm_solve_prompted", n_timesteps));
+  JV_TRY(solver_check(c, "jv_cfm_solve_prompted", n_timesteps));
   const int B2 = solve_twins(c, n_timesteps) ? 2 * B : B, Pmax = std::min(Ph, Pf);
 
   std::vector<float> tt, dts;
@@ -503,6 +568,10 @@ int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const f
 // depend on that request alone, whoever held its slot or its workspace position before.
 // Every call checks all of its arguments before its first launch, never synchronises, and reads its host arrays only until it
 // returns (their values travel as kernel arguments).
+// jv_cfm_pool_step_s: a request on a second-order solver takes two pool steps per solver step, and a pool step takes every request
+// at the stage of its OWN solver (PoolStepReq::stage and its coefficient).  pool_x always holds the estimator's next input -- the
+// stage point xs between a step's two stages -- so the gather is the same for every stage; only the scatter differs
+// (pool_stage_scatter: x0 and k1 of a request wait in the caller's pool_x0 / pool_k1).
 
 namespace {
 
@@ -591,10 +660,11 @@ int cfm_pool_admit(Context& c, const float* mu_y, const float* prompt_h, const f
 
 int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks, float* pool_amax,
                   int slots, int Tcap, const int* h_slots, const int* h_lens, const float* h_t, const float* h_dt, int B,
-                  hipStream_t st, const float* h_cfg) {
-  const char* who = h_cfg ? "jv_cfm_pool_step_g" : "jv_cfm_pool_step";
+                  hipStream_t st, const float* h_cfg, const int* h_stage, float* pool_x0, float* pool_k1) {
+  const char* who = h_stage ? "jv_cfm_pool_step_s" : h_cfg ? "jv_cfm_pool_step_g" : "jv_cfm_pool_step";
   if (!c.ready[MODEL_FLOW]) return fail(JV_ERR_STATE, "tts weights not finalized");
   JV_TRY(pool_check_pools(who, pool_x, pool_mu, pool_cond, pool_spks, nullptr, slots, Tcap));
+  if (h_stage) JV_TRY(pool_check_pools(who, pool_x0, pool_k1, nullptr, nullptr, nullptr, slots, Tcap));
   FlowWs& w = *c.flow;
   char msg[200];
   if (B < 1 || B > c.max_batch) {
@@ -621,6 +691,16 @@ int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* 
       snprintf(msg, sizeof msg, "%s: request %d: guidance rate %g must be finite and >= 0", who, b, (double)h_cfg[b]);
       return fail(JV_ERR_ARG, msg);
     }
+    if (h_stage) {      // a stage of the request's own solver (jv_ops.h STAGE_*), and the pools that stage saves to or reads from
+      if (!stage_ok(h_stage[b])) {
+        snprintf(msg, sizeof msg, "%s: request %d: stage %d is none of JV_STAGE_EULER, _MID1, _MID2, _HEUN1, _HEUN2", who, b, h_stage[b]);
+        return fail(JV_ERR_ARG, msg);
+      }
+      if ((h_stage[b] != STAGE_EULER && !pool_x0) || ((h_stage[b] & (STAGE_SAVE_K1 | STAGE_ADD_K1)) && !pool_k1)) {
+        snprintf(msg, sizeof msg, "%s: request %d: stage %d saves to or reads from pool_x0 / pool_k1, which is null", who, b, h_stage[b]);
+        return fail(JV_ERR_ARG, msg);
+      }
+    }
     T = std::max(T, h_lens[b]);
   }
   // the step's rows, by cfm_solve's rule: compact where the route allows it and it saves rows, else uniform (padded to T)
@@ -642,9 +722,9 @@ int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* 
       const int b = b0 + i;
       if (i < ch.n)
         ch.r[i] = {h_slots[b], h_lens[b], compact ? uoff[b] : FLOW_G + b * g.S, compact ? uoff[B + b] : FLOW_G + (B + b) * g.S, h_t[b], h_dt[b],
-                   h_cfg ? h_cfg[b] : 0.7f};
+                   h_cfg ? h_cfg[b] : 0.7f, h_stage ? h_stage[b] : STAGE_EULER};
       else
-        ch.r[i] = {0, 0, 0, 0, 0.f, 0.f, 0.f};
+        ch.r[i] = {0, 0, 0, 0, 0.f, 0.f, 0.f, STAGE_EULER};
     }
     JV_TRY(pool_publish(ch, B, w.pool_req, w.lens2, w.t_dev, compact ? w.uoff : nullptr, (int)g.M, st));
   }
@@ -654,6 +734,7 @@ int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* 
   JV_TRY(assemble_xin(w.x, w.mu, w.spks, w.cond, w.xin, B, B, FLOW_G, g.S, T, g.M, st, g.uoff, w.row_sample, w.rowmask));
   JV_TRY(estimator_body(c, g, est_route(c, g.M, /*temb_pre=*/false, compact, c.attn_chunk), st));
   // (two rows per frame for every request, one at rate 0 included: its twin is computed and (1 + 0) d_c - 0 d_u = d_c)
+  if (h_stage) return pool_stage_scatter(w.pool_req, B, T, w.x, w.d, w.amax, w.amax_stride, pool_x, pool_x0, pool_k1, pool_amax, Tcap, st);
   return pool_euler_scatter(w.pool_req, B, T, w.x, w.d, w.amax, w.amax_stride, pool_x, pool_amax, Tcap, st);
 }
 
@@ -709,6 +790,7 @@ int flow_token2mel(Context& c, const long* ptok, const long* plen, const long* t
   if (reinterpret_cast<uintptr_t>(prompt_feat) & 15) return fail(JV_ERR_ARG, "jv_flow_token2mel: prompt_feat must be 16-byte aligned");
   if (ctx < 0 || P + N - ctx < 1) return fail(JV_ERR_ARG, "jv_flow_token2mel_partial: P + N must be at least 4 (one encoded token + 3 of context)");
   JV_TRY(guidance_check(c, "jv_flow_token2mel", n_timesteps));
+  JV_TRY(solver_check(c, "jv_flow_token2mel", n_timesteps));
   const int B2 = solve_twins(c, n_timesteps) ? 2 * B : B, Tm = 2 * (P + N - ctx);
   JV_TRY(check_shape(c, 2 * B, Tm));
   if (Tm > NOISE_FRAMES) return fail(JV_ERR_SHAPE, "more frames than the fixed noise tensor holds (15000)");

@@ -23,11 +23,14 @@ int rowblock(const RowBlockArgs& a, bool qkv, hipStream_t st);      // rowblock.
 constexpr int FLOW_G = 4;      // leading guard rows (>= causal left context 2)
 constexpr int FLOW_GAP = 4;    // rows between utterances
 constexpr int PARTIAL_ROWS = 2048, PARTIAL_SPLITS = 8;      // split-K is for short M only (est_route)
-constexpr int TS_MAX = 64;      // steps whose timestep embeddings cfm_solve computes ahead of the loop (more: per step, as the seam does)
+constexpr int TS_MAX = 64;      // evaluations whose timestep embeddings cfm_solve computes ahead of the loop (more: per evaluation, as the seam does)
 
 struct FlowWs {
   long rows_alloc = 0;      // rows every [*,C] buffer below can hold
   float *x = nullptr, *mu = nullptr, *cond = nullptr, *spks = nullptr;   // [rows,80] x3, [maxB,80]
+  // second-order solves (jv_flow_set_solver; flow.hip solve_loop): the state x0 a step started from (midpoint, Heun) and its first
+  // slope k1 (Heun), saved by the first stage for the second while x holds the stage point xs; [rows,80] each, untouched by Euler
+  float *x0 = nullptr, *k1 = nullptr;
   float *xin = nullptr;                                               // [rows,320]
   float *h = nullptr, *h2 = nullptr, *res = nullptr, *cat = nullptr;  // [rows,256] x3, [rows,512]
   float *ln = nullptr, *qkv = nullptr, *att = nullptr, *ff = nullptr; // 256, 1536, 512, 1024
@@ -45,7 +48,9 @@ struct FlowWs {
   float *d = nullptr;                                                 // [rows,80]
   float *tsin = nullptr, *t1 = nullptr, *tmish = nullptr, *temb = nullptr;
   float *t_dev = nullptr, *t_table = nullptr, *dt_table = nullptr;
-  float *cfg_table = nullptr;      // the guidance rate of every Euler step of the solve, [max_steps] (jv_flow_set_guidance; solve_schedule)
+  // (t_table, dt_table, cfg_table hold one entry per estimator EVALUATION: an Euler step is one, a midpoint / Heun step two, and
+  // dt_table holds the coefficient of the evaluation's update -- dt, or 0.5f dt in a half stage; solve_schedule)
+  float *cfg_table = nullptr;      // the guidance rate of every evaluation of the solve, [max_steps] (jv_flow_set_guidance; solve_schedule)
   // cfm_solve: the timestep embedding of EVERY step of a solve, computed in three launches before the loop (the steps'
   // t are known up front and the same for all rows): [TS_MAX] rows of sinusoid / hidden / Mish / the 14 projections
   float *ts_sin = nullptr, *ts_1 = nullptr, *ts_mish = nullptr, *ts_emb = nullptr;
@@ -60,7 +65,7 @@ struct FlowWs {
   int* t2m_lens = nullptr;  // flow_token2mel: T_b = 2 (p_b + n_b) in [0, maxB), y_b = T_b - f_b in [maxB, 2*maxB) (device)
   int* h_y = nullptr;       // ... and y_b on its way up, [maxB] (pinned)
   PoolStepReq* pool_req = nullptr;      // cfm_pool_step: the step's requests (slot, length, rows, t, dt, guidance rate), [maxB] (device; cfmpool.hip)
-  int max_steps = 1024;
+  int max_steps = 1024;      // estimator evaluations of one solve (the tables' length): n_timesteps, twice that for a second-order solver
   // One Euler step (step scalars -> input assembly -> estimator -> CFG update) captured as a hipGraph per (B, T,
   // attention mode): the step reads its (t, dt, guidance rate) through a device-side counter, so one executable graph replays
   // for every step of every solve of that geometry -- a solve with a step WITHOUT twins (rate 0) never replays it, it is eager.  Replayed on a private stream (the caller's may be the legacy

@@ -21,6 +21,10 @@
 #define JV_ERR_HIP 3
 #define JV_ERR_SHAPE 4
 #define JV_ERR_NAME 5
+// jv_flow_set_solver (include/jyutvoice_hip.h holds the same values)
+#define JV_SOLVER_EULER 0
+#define JV_SOLVER_MIDPOINT 1
+#define JV_SOLVER_HEUN 2
 
 // Tuning aids (ablation switches, in-kernel phase stamps) compile to nothing unless the library is built with
 // JV_TUNING=1 python -m jyutvoice_amd.build --force (tools/gemm_bench.py documents the switches).

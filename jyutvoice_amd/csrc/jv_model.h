@@ -179,6 +179,7 @@ struct Context {
   bool est_fp16 = false;         // jv_flow_set_precision(JV_PRECISION_FP16) / JV_EST_FP16=1: the estimator's fp16x3 contractions issue the hi x hi product alone (EstRoute::np)
   bool step_graphs = false;      // replay the Euler step as a captured hipGraph (jv_flow_set_graph; never under the profiler)
   std::vector<float> guidance;   // jv_flow_set_guidance: empty = rate 0.7 in every Euler step; one entry = that rate in every step; more = one per step (a solve's n_timesteps must match)
+  int solver = 0;                // jv_flow_set_solver: JV_SOLVER_EULER (one estimator evaluation per step) / _MIDPOINT / _HEUN (two; flow.hip solve_loop)
   int enc_attn = 0;              // jv_encoder_set_attention: JV_ENC_ATTN_AUTO / _FUSED / _GEMM (encoder.hip enc_attention_route)
   int attn_chunk = 0;            // > 0: streaming (chunk-causal) estimator attention, in frames (jv_flow_set_streaming)
   // workspace
@@ -224,7 +225,10 @@ int cfm_pool_admit(Context& c, const float* mu_y, const float* prompt_h, const f
                    hipStream_t st);
 int cfm_pool_step(Context& c, float* pool_x, const float* pool_mu, const float* pool_cond, const float* pool_spks, float* pool_amax,
                   int slots, int Tcap, const int* h_slots, const int* h_lens, const float* h_t, const float* h_dt, int B,
-                  hipStream_t st, const float* h_cfg = nullptr);      // h_cfg: the guidance rate of every request in this step (null: 0.7)
+                  hipStream_t st, const float* h_cfg = nullptr,      // h_cfg: the guidance rate of every request in this step (null: 0.7)
+                  // h_stage (jv_cfm_pool_step_s): the stage of every request's own solver in this step (STAGE_*, jv_ops.h), of which
+                  // h_dt is then the coefficient; pool_x0 / pool_k1: the pools the stages save to and read from
+                  const int* h_stage = nullptr, float* pool_x0 = nullptr, float* pool_k1 = nullptr);
 int cfm_pool_fetch(Context& c, const float* pool_x, int slots, int Tcap, const int* h_slots, const int* h_first, const int* h_lens,
                    int B, int Tm, float* mel, hipStream_t st);
 

@@ -35,6 +35,20 @@ int time_sinusoid(const float* t, int t_stride, float* out, int B, hipStream_t s
 // step of rate 0 on B utterances alone, x += dt d (rate is not read, no twin row is addressed)
 int euler_cfg(float* x, const float* d, int B, int G, int S, int L, const float* dt_table, int step, const float* rate,
               hipStream_t st, const int* uoff = nullptr, const int* lens = nullptr, bool one_twin = false, bool no_twin = false);
+// One stage of a second-order CFM step (flow.hip solve_loop; DESIGN.md 5 "Solver"), with g = (1 + r) d_cond - r d_uncond as euler_cfg
+// forms it (twin: SOLVER_TWIN_*; none: g = d_cond, no twin row is addressed) and c = coef[0], the stage's coefficient:
+//   base = stage & STAGE_BASE_X0 ? x0 : x;   inc = stage & STAGE_ADD_K1 ? k1 + g : g;   x <- base + c inc
+// and before that x0 <- x (STAGE_SAVE_X0), k1 <- g (STAGE_SAVE_K1).  x afterwards is the estimator's next input.
+//   midpoint: STAGE_MID1 with c = 0.5f dt (xs = x + c g, x0 kept), then STAGE_MID2 with c = dt (x = x0 + c g(xs))
+//   Heun:     STAGE_HEUN1 with c = dt (k1 = g, xs = x + c k1), then STAGE_HEUN2 with c = 0.5f dt (x = x0 + c (k1 + g(xs)))
+// STAGE_EULER (0, c = dt) is euler_cfg's update.  Also the stage codes of PoolStepReq::stage and jv_cfm_pool_step_s.
+constexpr int STAGE_SAVE_X0 = 1, STAGE_SAVE_K1 = 2, STAGE_BASE_X0 = 4, STAGE_ADD_K1 = 8;
+constexpr int STAGE_EULER = 0, STAGE_MID1 = STAGE_SAVE_X0, STAGE_MID2 = STAGE_BASE_X0, STAGE_HEUN1 = STAGE_SAVE_X0 | STAGE_SAVE_K1,
+              STAGE_HEUN2 = STAGE_BASE_X0 | STAGE_ADD_K1;
+inline bool stage_ok(int s) { return s == STAGE_EULER || s == STAGE_MID1 || s == STAGE_MID2 || s == STAGE_HEUN1 || s == STAGE_HEUN2; }
+constexpr int SOLVER_TWIN_NONE = 0, SOLVER_TWIN_SHARED = 1, SOLVER_TWIN_EACH = 2;      // shared: every utterance reads the twin at slot B
+int solver_stage(float* x, float* x0, float* k1, const float* d, int B, int G, int S, int L, const float* coef, const float* rate,
+                 int stage, int twin, hipStream_t st, const int* uoff = nullptr, const int* lens = nullptr);
 int ln_epilogue_rows(float* x, const float* g, const float* b, float eps, long rows, int C, int act,
                      const unsigned char* rowmask, const float* rowvec, const int* row_sample, int rowvec_ld, const float* res,
                      long ldr, float scale, hipStream_t st, float* amax_out = nullptr, int amax_G = 0, int amax_S = 0,
@@ -46,7 +60,9 @@ int ln_epilogue_rows(float* x, const float* g, const float* b, float eps, long r
 constexpr int POOL_CHUNK = 64;
 struct PoolAdmitReq { int slot, p, len; float temp; };      // prompt frames, p + y frames, noise scale
 struct PoolAdmitChunk { int n, b0; PoolAdmitReq r[POOL_CHUNK]; };
-struct PoolStepReq { int slot, len, row, rowu; float t, dt, cfg; };      // first workspace row of the request and of its CFG twin; its guidance rate in this step
+// first workspace row of the request and of its CFG twin; its guidance rate in this step; stage: STAGE_* above, of which dt is the
+// coefficient (jv_cfm_pool_step / _g: STAGE_EULER and the step's dt)
+struct PoolStepReq { int slot, len, row, rowu; float t, dt, cfg; int stage; };
 struct PoolStepChunk { int n, b0; PoolStepReq r[POOL_CHUNK]; };
 struct PoolFetchReq { int slot, first, len; };
 struct PoolFetchChunk { int n, b0; PoolFetchReq r[POOL_CHUNK]; };
@@ -65,6 +81,12 @@ int pool_gather(const PoolStepReq* req, int B, int tmax, int tfill, const float*
 // pool_x[slot, t] = x[row + t] + dt_b ((1 + cfg_b) d[row + t] - cfg_b d[rowu + t]) (euler_cfg with a dt and a rate per request), maxima back
 int pool_euler_scatter(const PoolStepReq* req, int B, int tmax, const float* x, const float* d, const float* amax,
                        int amax_stride, float* pool_x, float* pool_amax, int Tcap, hipStream_t st);
+// pool_euler_scatter's stage-aware sibling (jv_cfm_pool_step_s): solver_stage per request, stage and coefficient from req[b], on
+// the caller's pools -- base and the saved k1 are read from pool_x0 / pool_k1, x0 <- the step's input (x[row + t], what pool_x held)
+// and k1 <- g are saved there, and pool_x takes the estimator's next input (xs or the new x), so the gather is pool_gather for
+// every stage.  pool_x0 / pool_k1 may be null where no listed stage touches them (checked by the caller)
+int pool_stage_scatter(const PoolStepReq* req, int B, int tmax, const float* x, const float* d, const float* amax, int amax_stride,
+                       float* pool_x, float* pool_x0, float* pool_k1, float* pool_amax, int Tcap, hipStream_t st);
 // mel[b, c, t] = pool_x[slot, first + t, c] for t < len, zeros up to Tm
 int pool_fetch(const PoolFetchChunk& ch, const float* pool_x, int Tcap, float* mel, int Tm, hipStream_t st);
 

@@ -674,6 +674,54 @@ int euler_cfg(float* x, const float* d, int B, int G, int S, int L, const float*
   return JV_OK;
 }
 
+// ---- one stage of a second-order step (midpoint / Heun; jv_ops.h solver_stage): x <- (x | x0) + c (g | k1 + g) ---------------
+// euler_cfg_kernel's indexing and its g; c = *coef and r = *rate come from the device as there (flow.hip step_advance_kernel).
+// stage / twin are uniform over the launch: a stage touches only the buffers it names, SOLVER_TWIN_NONE addresses no twin row
+__global__ __launch_bounds__(256) void solver_stage_kernel(float* __restrict__ x, float* __restrict__ x0, float* __restrict__ k1,
+                                                           const float* __restrict__ d, int B, int G, int S, int L,
+                                                           const float* __restrict__ coef, const float* __restrict__ rate_p,
+                                                           int stage, int twin, const int* __restrict__ uoff,
+                                                           const int* __restrict__ lens) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;   // f32x4 index over B*L*20
+  const long per_b = (long)L * 20;
+  if (idx >= per_b * B) return;
+  const int b = (int)(idx / per_b);
+  const long rem = idx - (long)b * per_b;
+  const long t = rem / 20;
+  if (uoff && t >= lens[b]) return;      // compact geometry: the rows behind an utterance's frames are the next utterance's
+  const long r = uoff ? (long)uoff[b] + t : (long)G + (long)b * S + t;
+  const int cc = (int)(rem % 20) * 4;
+  const float c = *coef;
+  f32x4 g = *reinterpret_cast<const f32x4*>(d + r * 80 + cc);
+  if (twin != SOLVER_TWIN_NONE) {
+    const long ru = uoff ? (long)uoff[b + B] + t : (long)G + (long)(B + (twin == SOLVER_TWIN_SHARED ? 0 : b)) * S + t;
+    const float rate = *rate_p;
+    const f32x4 du = *reinterpret_cast<const f32x4*>(d + ru * 80 + cc);
+    g = (1.0f + rate) * g - rate * du;
+  }
+  const f32x4 xin = *reinterpret_cast<const f32x4*>(x + r * 80 + cc);
+  f32x4 base = xin, inc = g;
+  if (stage & STAGE_SAVE_X0) *reinterpret_cast<f32x4*>(x0 + r * 80 + cc) = xin;
+  if (stage & STAGE_SAVE_K1) *reinterpret_cast<f32x4*>(k1 + r * 80 + cc) = g;
+  if (stage & STAGE_BASE_X0) base = *reinterpret_cast<const f32x4*>(x0 + r * 80 + cc);
+  if (stage & STAGE_ADD_K1) inc = *reinterpret_cast<const f32x4*>(k1 + r * 80 + cc) + g;
+  *reinterpret_cast<f32x4*>(x + r * 80 + cc) = base + c * inc;
+}
+
+int solver_stage(float* x, float* x0, float* k1, const float* d, int B, int G, int S, int L, const float* coef, const float* rate,
+                 int stage, int twin, hipStream_t st, const int* uoff, const int* lens) {
+  if (!stage_ok(stage) || stage == STAGE_EULER) return fail(JV_ERR_ARG, "solver_stage: a stage of the midpoint or the Heun step");
+  if (twin < SOLVER_TWIN_NONE || twin > SOLVER_TWIN_EACH) return fail(JV_ERR_ARG, "solver_stage: no twin, the shared one or one each");
+  if (uoff && !lens) return fail(JV_ERR_ARG, "solver_stage: the compact geometry needs the lengths");
+  if (uoff && twin == SOLVER_TWIN_SHARED) return fail(JV_ERR_ARG, "solver_stage: one shared twin exists in the uniform geometry only");
+  if (twin != SOLVER_TWIN_NONE && !rate) return fail(JV_ERR_ARG, "solver_stage: the guidance rate is read from the device");
+  if (!x0 || ((stage & (STAGE_SAVE_K1 | STAGE_ADD_K1)) && !k1)) return fail(JV_ERR_ARG, "solver_stage: the stage's state buffer is missing");
+  hipLaunchKernelGGL(solver_stage_kernel, dim3((unsigned)cdivl((long)B * L * 20, 256)), dim3(256), 0, st, x, x0, k1, d, B, G, S, L,
+                     coef, rate, stage, twin, uoff, lens);
+  JV_HIP(hipGetLastError());
+  return JV_OK;
+}
+
 __global__ void fill_int_kernel(int* p, int v, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;

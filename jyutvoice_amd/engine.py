@@ -41,6 +41,12 @@ class CfmPool:
         self.cond = torch.zeros_like(self.x)
         self.spks = torch.zeros(slots, spec.N_FEATS, device=device)
         self.amax = torch.zeros(slots, 3, 2, device=device)
+        self.x0 = self.k1 = None      # second-order requests (jv_cfm_pool_step_s): the state a step started from / its first slope
+
+    def ensure_stage_pools(self):
+        """x0 / k1, sized like x: allocated when the first request with a second-order solver is admitted"""
+        if self.x0 is None:
+            self.x0, self.k1 = torch.zeros_like(self.x), torch.zeros_like(self.x)
 
     def tensors(self):
         return self.x, self.mu, self.cond, self.spks, self.amax
@@ -164,6 +170,26 @@ class Engine:
         finally:
             self.set_guidance(None)
 
+    def set_solver(self, name: str = "euler"):
+        """the integrator of the closed solves on this context (jv_flow_set_solver): "euler" (default; flow_matching.py:215-265),
+        "midpoint" or "heun" -- second-order steps of two estimator evaluations each, `n_timesteps` staying the number of steps.
+        An unknown name raises ValueError naming the choices and leaves the mode as it was."""
+        if name not in _lib.SOLVERS:
+            raise ValueError(f"set_solver: solver must be one of {list(_lib.SOLVERS)}, got {name!r}")
+        check(self.lib.jv_flow_set_solver(self._h, _lib.SOLVERS[name]))
+
+    @contextlib.contextmanager
+    def solver(self, name):
+        """`with eng.solver(name):` -- set_solver(name) for the block, Euler again behind it (name = None or "euler": nothing)"""
+        if name is None or name == "euler":
+            yield
+            return
+        self.set_solver(name)
+        try:
+            yield
+        finally:
+            self.set_solver("euler")
+
     def set_step_graph(self, on: bool = True):
         """replay the Euler step of cfm_solve as a captured hipGraph (default off: measured no faster; same results)"""
         check(self.lib.jv_flow_set_graph(self._h, 1 if on else 0))
@@ -268,11 +294,22 @@ class Engine:
             B, Ty, prompt_h.shape[1], prompt_feat.shape[1], _ptr(pool.x), _ptr(pool.mu), _ptr(pool.cond), _ptr(pool.spks),
             _ptr(pool.amax), pool.slots, pool.max_frames, _stream(self.device)))
 
-    def cfm_pool_step(self, pool, slots, lens, t, dt, cfg=None):
+    def cfm_pool_step(self, pool, slots, lens, t, dt, cfg=None, stage=None):
         """jv_cfm_pool_step: ONE Euler + CFG step of the listed slots, request b with lens[b] frames at (t[b], dt[b]); B host
-        values each.  cfg: the guidance rate of every request in this step (jv_cfm_pool_step_g); None: 0.7 for all.  Nothing
-        comes back to the host."""
+        values each.  cfg: the guidance rate of every request in this step (jv_cfm_pool_step_g); None: 0.7 for all.  stage
+        (jv_cfm_pool_step_s): the stage of every request's own solver in this step (_lib.STAGE_*), of which dt[b] is then the
+        coefficient; the pool's x0 / k1 are allocated on first use.  Nothing comes back to the host."""
         who, B = "cfm_pool_step", len(slots)
+        if stage is not None:
+            pool.ensure_stage_pools()
+            check(self.lib.jv_cfm_pool_step_s(
+                self._h, _ptr(pool.x), _ptr(pool.mu), _ptr(pool.cond), _ptr(pool.spks), _ptr(pool.amax), _ptr(pool.x0), _ptr(pool.k1),
+                pool.slots, pool.max_frames, self._host_vec(who, "slots", slots, C.c_int32, B),
+                self._host_vec(who, "lens", lens, C.c_int32, B), self._host_vec(who, "t", t, C.c_float, B),
+                self._host_vec(who, "dt", dt, C.c_float, B),
+                self._host_vec(who, "cfg", [spec.CFG_RATE] * B if cfg is None else cfg, C.c_float, B),
+                self._host_vec(who, "stage", stage, C.c_int32, B), B, _stream(self.device)))
+            return
         args = (self._h, _ptr(pool.x), _ptr(pool.mu), _ptr(pool.cond), _ptr(pool.spks), _ptr(pool.amax), pool.slots, pool.max_frames,
                 self._host_vec(who, "slots", slots, C.c_int32, B), self._host_vec(who, "lens", lens, C.c_int32, B),
                 self._host_vec(who, "t", t, C.c_float, B), self._host_vec(who, "dt", dt, C.c_float, B))

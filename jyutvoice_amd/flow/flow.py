@@ -32,7 +32,7 @@ import torch
 from .. import spec
 from ..engine import JV_MODEL_FLOW, JV_MODEL_PROMPT, JV_MODEL_TTS
 from .encoder import DIV_TERM_KEY, div_term, extract_flow_weights
-from .flow_matching import check_scheduler, decoder_settings, resolve_guidance, time_span
+from .flow_matching import check_scheduler, decoder_settings, resolve_guidance, resolve_solver, time_span
 
 _NAME = "CausalMaskedDiffWithXvec"
 
@@ -88,11 +88,13 @@ class CausalMaskedDiffWithXvec:
             self._runtime = get_runtime(self.device)
         return self._runtime
 
-    def _solver_settings(self, who, n_timesteps, cfg_rate, cfg_schedule, t_scheduler):
-        """(what Engine.guidance takes, t_span) of a call: the decoder's inference_cfg_rate / t_scheduler unless overridden"""
-        conf_rate, conf_sched = decoder_settings(self.decoder)
+    def _solver_settings(self, who, n_timesteps, cfg_rate, cfg_schedule, t_scheduler, solver=None):
+        """(what Engine.guidance takes, t_span, what Engine.solver takes) of a call: the decoder's inference_cfg_rate / t_scheduler /
+        solver unless overridden"""
+        conf_rate, conf_sched, conf_solver = decoder_settings(self.decoder)
         sched = check_scheduler(who, conf_sched if t_scheduler is None else t_scheduler)
-        return resolve_guidance(who, n_timesteps, conf_rate, cfg_rate, cfg_schedule), time_span(n_timesteps, sched)
+        return (resolve_guidance(who, n_timesteps, conf_rate, cfg_rate, cfg_schedule), time_span(n_timesteps, sched),
+                resolve_solver(who, conf_solver, solver))
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True, decoder: str = "own"):
         """The reference module's 1121 keys, split with `extract_flow_weights` into the flow encoder (JV_MODEL_PROMPT) and the
@@ -130,7 +132,7 @@ class CausalMaskedDiffWithXvec:
     @torch.inference_mode()
     def inference(self, token, token_len, prompt_token, prompt_token_len, prompt_feat, prompt_feat_len, embedding, streaming,
                   finalize, batched: bool = False, n_timesteps: int = 10, temperature: float = 1.0, cfg_rate=None, cfg_schedule=None,
-                  t_scheduler=None):
+                  t_scheduler=None, solver=None):
         """flow.py:300-358 -> (mel [B, 80, T_mel] float32, None).  token [B, N], prompt_token [B, P] int; prompt_feat [B, F, 80];
         embedding [B, 192] (raw: F.normalize and the affine layer run in the library); streaming: the chunk masks of the encoder
         (25 tokens / 50 frames) and of the estimator (50 frames).
@@ -139,7 +141,8 @@ class CausalMaskedDiffWithXvec:
         consulted, as in flow.py:337 -- so the mel has 2 (P + N) - prompt_feat.shape[1] frames.  With `batched=True` utterance b
         uses f_b = prompt_feat_len[b] frames of its prompt mel (see the module docstring).  The solve runs at the decoder's
         inference_cfg_rate and t_scheduler (flow_matching.py:215-265, 387-389); cfg_rate / cfg_schedule override the rate for this
-        call (one rate / one per Euler step) and t_scheduler the schedule ("cosine" / "linear"), here and in inference_partial / inference_partial_batch."""
+        call (one rate / one per Euler step), t_scheduler the schedule ("cosine" / "linear") and solver the integrator ("euler" /
+        "midpoint" / "heun"; None: the decoder's `solver`, "euler" unless set), here and in inference_partial / inference_partial_batch."""
         B = token.shape[0]
         if not batched:
             assert B == 1
@@ -184,8 +187,8 @@ class CausalMaskedDiffWithXvec:
         if not self._loaded:
             raise RuntimeError(f"{_NAME}: load_state_dict() has not been called")
         eng = self._rt().ensure(B, spec.PROMPT_UP_STRIDE * (P + N), 1)
-        rates, t_span = self._solver_settings("inference()", n_timesteps, cfg_rate, cfg_schedule, t_scheduler)
-        with eng.guidance(rates):
+        rates, t_span, solver = self._solver_settings("inference()", n_timesteps, cfg_rate, cfg_schedule, t_scheduler, solver)
+        with eng.guidance(rates), eng.solver(solver):
             mel, lens = eng.flow_token2mel(prompt_token if P > 0 else None, torch.tensor(p_host), token, torch.tensor(n_host),
                                            prompt_feat if F > 0 else None, torch.tensor(f_host, dtype=torch.int32), embedding,
                                            streaming=bool(streaming), n_timesteps=n_timesteps, temperature=temperature, t_span=t_span)
@@ -197,7 +200,8 @@ class CausalMaskedDiffWithXvec:
 
     @torch.inference_mode()
     def inference_partial(self, token, token_len, prompt_token, prompt_token_len, prompt_feat, prompt_feat_len, embedding, streaming,
-                          n_timesteps: int = 10, temperature: float = 1.0, cfg_rate=None, cfg_schedule=None, t_scheduler=None):
+                          n_timesteps: int = 10, temperature: float = 1.0, cfg_rate=None, cfg_schedule=None, t_scheduler=None,
+                          solver=None):
         """flow.py:327-336 as intended, B = 1 -> (mel [1, 80, 2 L - F] float32, None).  Of the m = P + N tokens the encoder runs on
         the first L = m - 3 (every length and mask uses L); the last three are embedded like the others (upsample_encoder.py:446-453)
         and read by PreLookaheadLayer.conv1 alone, in place of its zero padding (upsample_encoder.py:110-121).  F = prompt_feat.shape[1]
@@ -230,8 +234,8 @@ class CausalMaskedDiffWithXvec:
         if not self._loaded:
             raise RuntimeError(f"{_NAME}: load_state_dict() has not been called")
         eng = self._rt().ensure(1, spec.PROMPT_UP_STRIDE * (P + N), 1)
-        rates, t_span = self._solver_settings("inference_partial()", n_timesteps, cfg_rate, cfg_schedule, t_scheduler)
-        with eng.guidance(rates):
+        rates, t_span, solver = self._solver_settings("inference_partial()", n_timesteps, cfg_rate, cfg_schedule, t_scheduler, solver)
+        with eng.guidance(rates), eng.solver(solver):
             mel, lens = eng.flow_token2mel_partial(prompt_token if P > 0 else None, torch.tensor([P]), token, torch.tensor([m - P]),
                                                    prompt_feat if F > 0 else None, torch.tensor([F], dtype=torch.int32), embedding,
                                                    streaming=bool(streaming), n_timesteps=n_timesteps, temperature=temperature,
@@ -243,7 +247,7 @@ class CausalMaskedDiffWithXvec:
     @torch.inference_mode()
     def inference_partial_batch(self, token, token_len, prompt_token, prompt_token_len, prompt_feat, prompt_feat_len, embedding,
                                 ctx_lens, streaming=True, n_timesteps: int = 10, temperature: float = 1.0, cfg_rate=None,
-                                cfg_schedule=None, t_scheduler=None):
+                                cfg_schedule=None, t_scheduler=None, solver=None):
         """A batch that mixes partial and whole sequences -> (mel [B, 80, max_b y_b] float32, mel_lens int32 [B] on the device).
         Defined as the B = 1 calls looped over the utterances, every tensor cut to the utterance's own length as in
         `inference(batched=True)`: `inference_partial` where ctx_lens[b] = 3 (the last three of the p_b + n_b tokens are look-ahead
@@ -293,8 +297,8 @@ class CausalMaskedDiffWithXvec:
         if not self._loaded:
             raise RuntimeError(f"{_NAME}: load_state_dict() has not been called")
         eng = self._rt().ensure(B, spec.PROMPT_UP_STRIDE * (P + N), 1)
-        rates, t_span = self._solver_settings(who, n_timesteps, cfg_rate, cfg_schedule, t_scheduler)
-        with eng.guidance(rates):
+        rates, t_span, solver = self._solver_settings(who, n_timesteps, cfg_rate, cfg_schedule, t_scheduler, solver)
+        with eng.guidance(rates), eng.solver(solver):
             mel, lens = eng.flow_token2mel_ctx(prompt_token if P > 0 else None, torch.tensor(p_host), token, torch.tensor(n_host),
                                                torch.tensor(c_host, dtype=torch.int32), prompt_feat if F > 0 else None,
                                                torch.tensor(f_host, dtype=torch.int32), embedding, streaming=bool(streaming),

@@ -25,6 +25,16 @@ def check_scheduler(who: str, t_scheduler) -> str:
     return t_scheduler
 
 
+SOLVERS = ("euler", "midpoint", "heun")      # jv_flow_set_solver
+EVALS = {"euler": 1, "midpoint": 2, "heun": 2}      # estimator evaluations per step
+
+
+def check_solver(who: str, solver) -> str:
+    if not isinstance(solver, str) or solver not in SOLVERS:
+        raise ValueError(f"{who}: solver must be one of {list(SOLVERS)}, got {solver!r}")
+    return solver
+
+
 def check_rate(who: str, rate, name: str = "cfg_rate") -> float:
     """a guidance rate: finite and >= 0 (0: no guidance, the step needs no unconditional evaluation)"""
     if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not math.isfinite(rate) or rate < 0:
@@ -55,8 +65,15 @@ def resolve_guidance(who: str, n_timesteps: int, configured: float, cfg_rate=Non
 
 
 def decoder_settings(decoder):
-    """(inference_cfg_rate, t_scheduler) of a decoder object; the reference's defaults where it carries none"""
-    return (float(getattr(decoder, "inference_cfg_rate", spec.CFG_RATE)), getattr(decoder, "t_scheduler", "cosine") or "cosine")
+    """(inference_cfg_rate, t_scheduler, solver) of a decoder object; the reference's defaults where it carries none (its solver is
+    solve_euler: "euler")"""
+    return (float(getattr(decoder, "inference_cfg_rate", spec.CFG_RATE)), getattr(decoder, "t_scheduler", "cosine") or "cosine",
+            getattr(decoder, "solver", "euler") or "euler")
+
+
+def resolve_solver(who: str, configured: str, solver=None) -> str:
+    """the solver of a call: `solver`, or the decoder's setting where it is None; a bad name raises ValueError naming the choices"""
+    return check_solver(who, configured if solver is None else solver)
 
 
 class CausalConditionalCFM:
@@ -69,6 +86,10 @@ class CausalConditionalCFM:
             raise NotImplementedError(f"libjyutvoice_hip knows t_scheduler 'cosine' and 'linear' (flow_matching.py:387-389), got "
                                       f"{self.t_scheduler!r}")
         self.inference_cfg_rate = check_rate("CausalConditionalCFM", self.inference_cfg_rate, "inference_cfg_rate")
+        try:      # (an extension: the reference's only solver is solve_euler)
+            self.solver = check_solver("CausalConditionalCFM", _get(cfm_params, "solver"))
+        except (KeyError, AttributeError):
+            self.solver = "euler"
         try:      # used by JyutVoiceTTS.forward only (flow_matching.py:330-334); base.yaml: 0.2
             self.training_cfg_rate = float(_get(cfm_params, "training_cfg_rate"))
         except (KeyError, AttributeError):
@@ -78,15 +99,17 @@ class CausalConditionalCFM:
 
     @torch.inference_mode()
     def forward(self, mu, mask, n_timesteps, temperature=1.0, spks=None, cond=None, streaming=False, cfg_rate=None,
-                cfg_schedule=None):
+                cfg_schedule=None, solver=None):
         """flow_matching.py:356-401 -> (mel [B,80,T], None): fixed noise prefix * temperature, this decoder's t_scheduler, the
         Euler/CFG loop (solve_euler, :215-265) at this decoder's inference_cfg_rate -- all of it inside jv_cfm_solve.
         streaming=True: the estimator's chunk-causal attention (decoder.py:951-954) with this decoder's static_chunk_size, so
         frames of finished chunks do not change when more of the utterance arrives.  B > 1 is the batched extension (mask rows
-        = per-utterance lengths).  cfg_rate / cfg_schedule (extensions): another rate for this call / one rate per step."""
+        = per-utterance lengths).  cfg_rate / cfg_schedule (extensions): another rate for this call / one rate per step.
+        solver (extension): "euler" / "midpoint" / "heun" for this call (None: this decoder's `solver`)."""
         from ..runtime import get_runtime
         B, _, T = mu.shape
         rates = resolve_guidance("CausalConditionalCFM.forward()", n_timesteps, self.inference_cfg_rate, cfg_rate, cfg_schedule)
+        solver = resolve_solver("CausalConditionalCFM.forward()", self.solver, solver)
         eng = get_runtime(self.device).ensure(B, T, 1)
         chunk = getattr(self.estimator, "static_chunk_size", spec.EST_STATIC_CHUNK) if streaming else 0
         try:
@@ -96,7 +119,8 @@ class CausalConditionalCFM:
             lens = None if mask is None else mask.reshape(B, -1).ne(0).sum(dim=1)
             if cond is None:
                 cond = torch.zeros_like(mu)
-            mel = eng.cfm_solve(mu, lens, spks, cond, n_timesteps, temperature, t_span=time_span(n_timesteps, self.t_scheduler))
+            with eng.solver(solver):
+                mel = eng.cfm_solve(mu, lens, spks, cond, n_timesteps, temperature, t_span=time_span(n_timesteps, self.t_scheduler))
         finally:
             eng.set_streaming(0)
             if rates is not None:

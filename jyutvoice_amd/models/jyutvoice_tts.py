@@ -23,7 +23,7 @@ import torch
 
 from .. import spec
 from ..engine import JV_MODEL_TTS
-from ..flow.flow_matching import CausalConditionalCFM, check_scheduler, decoder_settings, resolve_guidance, time_span
+from ..flow.flow_matching import CausalConditionalCFM, check_scheduler, decoder_settings, resolve_guidance, resolve_solver, time_span
 from ..runtime import get_runtime
 from .duration_predictor import DurationPredictor
 from .text_encoder import TextEncoder
@@ -113,11 +113,13 @@ class JyutVoiceTTS:
     @torch.inference_mode()
     def synthesise(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed, prompt_feat, prompt_h=None,
                    n_timesteps=10, temperature=1.0, length_scale=1.0, batched=False, prompt_lengths=None, streaming=False,
-                   cfg_rate=None, cfg_schedule=None, t_scheduler=None):
+                   cfg_rate=None, cfg_schedule=None, t_scheduler=None, solver=None):
         """jyutvoice_tts.py:130-253.  Extensions beyond the reference's arguments: batched / prompt_lengths (a batch, one voice
         prompt per utterance); cfg_rate (the guidance rate of this call; None: the decoder's inference_cfg_rate), cfg_schedule (a
         sequence of n_timesteps rates, one per Euler step; wins over cfg_rate) and t_scheduler ("cosine" / "linear"; None: the
-        decoder's) -- flow_matching.py:215-265, 387-389."""
+        decoder's) -- flow_matching.py:215-265, 387-389; solver ("euler" / "midpoint" / "heun"; None: the decoder's `solver`, "euler"
+        unless set) -- n_timesteps second-order steps are 2 n_timesteps estimator evaluations.  The context is back on the default
+        rate and on Euler after the call."""
         if streaming:
             raise NotImplementedError("synthesise() runs the non-streaming decoder (jyutvoice_tts.py:239 passes streaming=False)"
                                       + ("; prompt_lengths has no streaming form" if prompt_lengths is not None else ""))
@@ -127,8 +129,9 @@ class JyutVoiceTTS:
         t0 = dt.datetime.now()
         B, Tt = x.shape
         p_host = None if prompt_lengths is None else self._check_prompt_lengths(prompt_lengths, prompt_feat, prompt_h, B)
-        conf_rate, conf_sched = decoder_settings(self.decoder)
+        conf_rate, conf_sched, conf_solver = decoder_settings(self.decoder)
         rates = resolve_guidance("synthesise()", n_timesteps, conf_rate, cfg_rate, cfg_schedule)
+        solver = resolve_solver("synthesise()", conf_solver, solver)
         t_span = time_span(n_timesteps, check_scheduler("synthesise()", conf_sched if t_scheduler is None else t_scheduler))   # flow_matching.py:387-389
         rt = get_runtime(self.device)
         eng = rt.ensure(B, 64, Tt)
@@ -153,7 +156,7 @@ class JyutVoiceTTS:
             # voice-cloning batch, one prompt length per utterance: the glue of jyutvoice_tts.py:213-244 runs inside
             # jv_cfm_solve_prompted, the tensors go there as they came
             eng = rt.ensure(B, max(p + y for p, y in zip(p_host, eng.y_lengths_host)), Tt)
-            with eng.guidance(rates):
+            with eng.guidance(rates), eng.solver(solver):
                 dec = eng.cfm_solve_prompted(mu_y, y_lengths, prompt_h, prompt_feat, prompt_lengths, c, n_timesteps, temperature,
                                              t_span=t_span)
             return self._result(t0, B, encoder_outputs, dec, attn, y_lengths, mark)
@@ -173,7 +176,7 @@ class JyutVoiceTTS:
             lens = y_lengths
         T = mu_y.shape[2]
         eng = rt.ensure(B, T, Tt)
-        with eng.guidance(rates):
+        with eng.guidance(rates), eng.solver(solver):
             dec = eng.cfm_solve(mu_y.contiguous(), lens if B > 1 else None, c, conds, n_timesteps, temperature, t_span=t_span)
         dec = dec[:, :, mel_len1:]
         return self._result(t0, B, encoder_outputs, dec, attn, y_lengths, mark)

@@ -17,6 +17,10 @@ at B = 1, its audio `hift.inference(mel_r)` at B = 1 after
 `hift.manual_seed(seed_r)` -- whatever else is in the pool and whenever the others joined or left.  A request that arrives waits at
 most one Euler step, not up to a whole pass.
 
+A request may run its own integrator (`submit(..., solver="midpoint" | "heun")`; DESIGN.md section 5, "Solver"): it then takes two
+pool steps per solver step, each at the stage of its own solver, beside requests on Euler or at other stages in the same step
+(jv_cfm_pool_step_s), finishes after its last stage, and is that request run alone with `synthesise(..., solver=...)`.
+
 Everything a step decides comes from host state, through `step_table` and `admit_plan` (pure functions, no device).
 """
 from __future__ import annotations
@@ -29,20 +33,39 @@ import numpy as np
 import torch
 
 from . import spec
-from .flow.flow_matching import check_rate, check_scheduler, decoder_settings, time_span
+from ._lib import STAGE_EULER, STAGE_HEUN1, STAGE_HEUN2, STAGE_MID1, STAGE_MID2
+from .flow.flow_matching import EVALS, check_rate, check_scheduler, check_solver, decoder_settings, time_span
 
 FLOW_G, FLOW_GAP = 4, 4      # guard rows ahead of a step's first utterance / between two utterances (csrc/flow_ws.h)
 MAX_STEPS = 1024             # the solver's limit on n_timesteps (csrc/flow_ws.h: FlowWs::max_steps)
 
 
-def step_table(n: int, t_scheduler: str = "cosine") -> Tuple[List[float], List[float]]:
+def step_table(n: int, t_scheduler: str = "cosine", solver: str = "euler"):
     """(t, dt) of the n Euler steps of a request, as fp32 values: the cosine schedule `1 - cos(linspace(0, 1, n + 1) pi / 2)` that
     `synthesise` hands the solver (t_scheduler="linear": `linspace(0, 1, n + 1)` itself) and the reference's running recurrence
     over it (flow_matching.py:230, 260-263, 387-389), in fp32 -- what `solve_schedule` computes for a closed solve of n steps.
-    Step k of the request uses (tt[k], dts[k])."""
+    Step k of the request uses (tt[k], dts[k]).
+
+    solver = "midpoint" / "heun": three lists of 2 n entries, one per estimator EVALUATION -- (t, coefficient, stage) as
+    jv_cfm_pool_step_s takes them and as `solve_schedule` lays them out for a closed solve of that solver.  Step k, with (t, dt)
+    its Euler row, is evaluations 2 k and 2 k + 1:
+        midpoint   (t, fp32(0.5 dt), STAGE_MID1),   (fp32(t + fp32(0.5 dt)), dt, STAGE_MID2)
+        heun       (t, dt, STAGE_HEUN1),            (fp32(t + dt), fp32(0.5 dt), STAGE_HEUN2)      -- t + dt is the next step's t
+    (for "euler" the coefficient is dt and the stage STAGE_EULER throughout: the two lists as ever).  Pure host function."""
     if not isinstance(n, int) or n < 1:
         raise ValueError(f"step_table(): n must be a positive int, got {n!r}")
     check_scheduler("step_table()", t_scheduler)
+    if check_solver("step_table()", solver) != "euler":
+        tt, dts = step_table(n, t_scheduler)
+        mid = solver == "midpoint"
+        t2, c2, s2 = [], [], []
+        for t, dt in zip(tt, dts):
+            t, dt = np.float32(t), np.float32(dt)
+            half = np.float32(np.float32(0.5) * dt)
+            t2 += [float(t), float(np.float32(t + half) if mid else np.float32(t + dt))]
+            c2 += [float(half), float(dt)] if mid else [float(dt), float(half)]
+            s2 += [STAGE_MID1, STAGE_MID2] if mid else [STAGE_HEUN1, STAGE_HEUN2]
+        return t2, c2, s2
     ts = time_span(n, t_scheduler).numpy().astype(np.float32)
     tt, dts = [], []
     t, dt = ts[0], np.float32(ts[1] - ts[0])
@@ -101,14 +124,21 @@ def admit_plan(waiting: Sequence[int], active: Sequence[int], free_slots: int, r
 
 class _Request:
     def __init__(self, rid, args, prompt_feat, prompt_h, n, temperature, length_scale, seed, loudness=None, peak=None, rates=None,
-                 t_scheduler="cosine"):
+                 t_scheduler="cosine", solver="euler"):
         self.rid, self.args, self.prompt_feat, self.prompt_h = rid, args, prompt_feat, prompt_h
         self.loudness, self.peak = loudness, peak      # target LUFS and peak ceiling of the output, or None
         self.n, self.temperature, self.length_scale, self.seed = n, temperature, length_scale, seed
         self.p = 0 if prompt_feat is None else int(prompt_feat.shape[1])
-        self.tt, self.dts = step_table(n, t_scheduler)
-        self.rates = [spec.CFG_RATE] * n if rates is None else rates      # the guidance rate of every step, beside tt / dts
-        self.k = 0                 # Euler steps taken
+        # one row per estimator evaluation = per pool step: an Euler step is one, a midpoint / Heun step two (`step_table`)
+        self.solver = solver
+        if solver == "euler":
+            self.tt, self.dts = step_table(n, t_scheduler)
+            self.stages = [STAGE_EULER] * n
+        else:
+            self.tt, self.dts, self.stages = step_table(n, t_scheduler, solver)
+        rates = [spec.CFG_RATE] * n if rates is None else rates
+        self.rates = [rates[k // EVALS[solver]] for k in range(len(self.tt))]      # a step's rate holds for both of its evaluations
+        self.k = 0                 # pool steps (evaluations) taken; the request is finished at len(tt)
         self.slot = None
         self.y = None              # generated frames, once the text encoder has run
         self.mu_y = self.spks = None      # [1, 80, y], [1, 80] on the device, between encoding and admission
@@ -175,8 +205,10 @@ class SynthServer:
     # ---- host only ------------------------------------------------------------------------------------------------------------------
     def submit(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed, prompt_feat=None, prompt_h=None, n_timesteps=10,
                temperature=1.0, length_scale=1.0, seed=None, loudness=None, peak=None, cfg_rate=None, cfg_window=None,
-               t_scheduler="cosine") -> int:
-        """cfg_rate: the request's guidance rate (None: the decoder's inference_cfg_rate); cfg_window = (t_lo, t_hi): guidance in
+               t_scheduler="cosine", solver=None) -> int:
+        """solver: the request's integrator, "euler" / "midpoint" / "heun" (None: the decoder's `solver`) -- n_timesteps second-order
+        steps take 2 n_timesteps pool steps, and the request is the one `synthesise(..., solver=solver)` runs alone at B = 1.
+        cfg_rate: the request's guidance rate (None: the decoder's inference_cfg_rate); cfg_window = (t_lo, t_hi): guidance in
         the steps whose t lies in [t_lo, t_hi) only, rate 0 outside (`guidance_rates`); t_scheduler: "cosine" / "linear" (None: the
         decoder's)."""
         rid = self._next_rid
@@ -219,7 +251,11 @@ class SynthServer:
             raise ValueError(f"{who}: peak must be positive and finite (or None), got {peak!r}")
         if peak is not None and loudness is None:
             raise ValueError(f"{who}: peak limits the gain of loudness: give loudness too")
-        conf_rate, conf_sched = decoder_settings(getattr(self.tts, "decoder", None))
+        conf_rate, conf_sched, conf_solver = decoder_settings(getattr(self.tts, "decoder", None))
+        solver = check_solver(who, conf_solver if solver is None else solver)
+        if n_timesteps * EVALS[solver] > MAX_STEPS:
+            raise ValueError(f"{who}: n_timesteps = {n_timesteps} with the {solver} solver is {n_timesteps * EVALS[solver]} estimator "
+                             f"evaluations, the limit is {MAX_STEPS}")
         t_scheduler = check_scheduler(who, conf_sched if t_scheduler is None else t_scheduler)
         cfg_rate = check_rate(who, conf_rate if cfg_rate is None else cfg_rate, "cfg_rate")
         rates = guidance_rates(n_timesteps, cfg_rate, check_window(who, cfg_window, "cfg_window"), t_scheduler)
@@ -234,7 +270,7 @@ class SynthServer:
         args = (x, xl.to(torch.int64), lang, tone, word_pos, syllable_pos, spk_embed)
         self._waiting.append(_Request(rid, args, prompt_feat, prompt_h, n_timesteps, temperature, length_scale, int(seed),
                                       None if loudness is None else float(loudness), None if peak is None else float(peak),
-                                      rates, t_scheduler))
+                                      rates, t_scheduler, solver))
         self._next_rid += 1
         return rid
 
@@ -305,12 +341,15 @@ class SynthServer:
         cfg = [r.rates[r.k] for r in live]
         # (all at the default rate: the entry without rates, jv_cfm_pool_step, which is the other one with 0.7 for all)
         kw = {} if all(abs(v - spec.CFG_RATE) <= 1e-12 for v in cfg) else {"cfg": cfg}
+        stages = [r.stages[r.k] for r in live]
+        if any(s != STAGE_EULER for s in stages):      # (all on Euler: the entries above, as before solvers per request existed)
+            kw = {"cfg": cfg, "stage": stages}
         eng.cfm_pool_step(self.pool, [r.slot for r in live], [r.frames for r in live], [r.tt[r.k] for r in live],
                           [r.dts[r.k] for r in live], **kw)
         self.steps += 1
         for r in live:
             r.k += 1
-        fin = [r for r in live if r.k == r.n]
+        fin = [r for r in live if r.k == len(r.tt)]
         if not fin:
             return done
         mel = eng.cfm_pool_fetch(self.pool, [r.slot for r in fin], [r.p for r in fin], [r.y for r in fin])

@@ -68,10 +68,11 @@ class Token2WavStream:
     signal of the audio returned so far ([1, 1, samples so far])."""
 
     def __init__(self, flow, hift, prompt_token, prompt_feat, embedding, max_tokens: int, n_timesteps: int = 10,
-                 seed: Optional[int] = None, cfg_rate=None, cfg_schedule=None, t_scheduler=None):
+                 seed: Optional[int] = None, cfg_rate=None, cfg_schedule=None, t_scheduler=None, solver=None):
         # cfg_rate / cfg_schedule: the guidance rate of every solve of the session / one rate per Euler step, handed to the flow's
-        # inference calls; t_scheduler: "cosine" / "linear" (None each: the flow decoder's configuration)
-        self._cfg = {k: v for k, v in (("cfg_rate", cfg_rate), ("cfg_schedule", cfg_schedule), ("t_scheduler", t_scheduler)) if v is not None}
+        # inference calls; t_scheduler: "cosine" / "linear"; solver: "euler" / "midpoint" / "heun" (None each: the flow decoder's configuration)
+        self._cfg = {k: v for k, v in (("cfg_rate", cfg_rate), ("cfg_schedule", cfg_schedule), ("t_scheduler", t_scheduler),
+                                       ("solver", solver)) if v is not None}
         if prompt_token is None:
             prompt_token = torch.zeros(1, 0, dtype=torch.int64)
         if prompt_feat is None:
@@ -186,9 +187,10 @@ class Token2WavServer:
     and `f0(sid)` are views of a session's records; those of a finished session stay valid until its slot is opened again."""
 
     def __init__(self, flow, hift, max_sessions: int, max_tokens: int, n_timesteps: int = 10, max_prompt_tokens: int = 150,
-                 cfg_rate=None, cfg_schedule=None, t_scheduler=None):
-        # cfg_rate / cfg_schedule: as for Token2WavStream, for every step of the server (one solve serves all its sessions)
-        self._cfg = {k: v for k, v in (("cfg_rate", cfg_rate), ("cfg_schedule", cfg_schedule), ("t_scheduler", t_scheduler)) if v is not None}
+                 cfg_rate=None, cfg_schedule=None, t_scheduler=None, solver=None):
+        # cfg_rate / cfg_schedule / solver: as for Token2WavStream, for every step of the server (one solve serves all its sessions)
+        self._cfg = {k: v for k, v in (("cfg_rate", cfg_rate), ("cfg_schedule", cfg_schedule), ("t_scheduler", t_scheduler),
+                                       ("solver", solver)) if v is not None}
         for name, v in (("max_sessions", max_sessions), ("max_tokens", max_tokens)):
             if not isinstance(v, int) or v < 1:
                 raise ValueError(f"Token2WavServer: {name} must be a positive int, got {v!r}")
