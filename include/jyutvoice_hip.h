@@ -546,6 +546,38 @@ int jv_masked_mse(jv_context* ctx, const float* a, const float* b, const int32_t
 int jv_encoder_fwd(jv_context* ctx, const int64_t* phone, const int64_t* lang, const int64_t* tone, const int64_t* word_pos,
                    const int64_t* syllable_pos, const int64_t* x_lengths, const float* spk, int B, int Tt, float* x,
                    float* mu_x, float* logw, float* spks_proj, void* stream);
+/* jv_encoder_fwd_tap (used by the parity tests): jv_encoder_fwd's own launch sequence up to and including one stage, whose
+ * workspace buffer is then copied out channels-first as out [B, C, Tt] -- an early return inside the function jv_encoder_fwd runs
+ * (the prenet buffers ping-pong and the hidden state is updated in place, so a stage can only be read where it stands), not a
+ * second sequence: the route decision, the row mask and every launch ahead of the return are the whole forward's.  Outputs whose
+ * launches lie behind the tap are not written (logw never; x and mu_x only by XD, D1, D2; spks_proj, the first stage, always).  Positions at or behind an utterance's clamped length are zeros.
+ * out_floats < B*C*Tt: JV_ERR_SHAPE; an unknown tap: JV_ERR_ARG; both before the first launch.  One id per tap, in execution
+ * order; the five taps of encoder layer i are the layer-0 ids + JV_ENC_TAP_PER_LAYER * i (38 ids, 0 .. 37).  Taps (C):
+ *   EMB   (192)   the four embeddings' sum x sqrt(192)
+ *   PREk  (192)   behind the k-th prenet conv k5 + channel LayerNorm + ReLU, k = 0 .. 2
+ *   H0    (576)   prenet projection + residual, masked | raw speaker vector | language embedding: the layers' input
+ *   QKVi  (1728)  q | k | v of layer i, RoPE applied to q and k
+ *   ATTi  (576)   the attention's output, ahead of conv_o
+ *   N1i   (576)   LayerNorm 1 of (h + conv_o(att))
+ *   FFi   (768)   ReLU(conv_1)
+ *   N2i   (576)   LayerNorm 2 of (h + conv_2(ff)): the layer's output
+ *   XD    (576)   x + cond(spk): the duration predictor's input
+ *   D1, D2 (256)  behind each of its conv k3 + ReLU + LayerNorm */
+#define JV_ENC_TAP_EMB 0
+#define JV_ENC_TAP_PRE0 1    /* PRE1 = 2, PRE2 = 3 */
+#define JV_ENC_TAP_H0 4
+#define JV_ENC_TAP_QKV0 5    /* layer i: + JV_ENC_TAP_PER_LAYER * i */
+#define JV_ENC_TAP_ATT0 6
+#define JV_ENC_TAP_N10 7
+#define JV_ENC_TAP_FF0 8
+#define JV_ENC_TAP_N20 9
+#define JV_ENC_TAP_PER_LAYER 5
+#define JV_ENC_TAP_XD 35
+#define JV_ENC_TAP_D1 36
+#define JV_ENC_TAP_D2 37
+int jv_encoder_fwd_tap(jv_context* ctx, const int64_t* phone, const int64_t* lang, const int64_t* tone, const int64_t* word_pos,
+                       const int64_t* syllable_pos, const int64_t* x_lengths, const float* spk, int B, int Tt, float* x,
+                       float* mu_x, float* logw, float* spks_proj, int tap, float* out, int64_t out_floats, void* stream);
 /* jv_encoder_set_attention: the route of the encoder layers' 2-head RoPE attention (text_encoder.py:216-248) in jv_encoder_fwd.
  *   JV_ENC_ATTN_AUTO (default): the four-launch route (q k^T GEMM, masked softmax, V transpose, P V GEMM around a [B,2,Tt,Tt] score
  *                        buffer) for Tt <= 512, the one-launch kernel of encattn.hip above that

@@ -34,6 +34,14 @@ for _i_lvl, (_c, _m, _a) in enumerate(((256, 8, 0), (128, 40, 0), (64, 120, 1)))
     for _k, _name in enumerate(("UP", "SI", "XS", "X")):
         HIFT_TAPS[f"{_name}{_i_lvl}"] = (2 + 3 * _k + _i_lvl, _c, _m, _a)
 
+# jv_encoder_fwd_tap: tap name -> (id, channels), in execution order, as include/jyutvoice_hip.h lists them (JV_ENC_TAP_*: the five
+# taps of encoder layer i are the layer-0 ids + 5 i)
+ENC_TAPS = {"EMB": (0, 192), "PRE0": (1, 192), "PRE1": (2, 192), "PRE2": (3, 192), "H0": (4, 576)}
+for _i_layer in range(6):
+    for _k, (_name, _c) in enumerate((("QKV", 1728), ("ATT", 576), ("N1", 576), ("FF", 768), ("N2", 576))):
+        ENC_TAPS[f"{_name}{_i_layer}"] = (5 + 5 * _i_layer + _k, _c)
+ENC_TAPS.update({"XD": (35, 576), "D1": (36, 256), "D2": (37, 256)})
+
 ACT = {"none": 0, "relu": 1, "gelu": 2, "mish": 3, "elu": 4, "silu": 5}
 PRO = {"none": 0, "snake": 1, "lrelu": 2}
 
@@ -88,6 +96,7 @@ SIGNATURES = {
     "jv_flow_encoder_fwd_ctx": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "jv_flow_token2mel_ctx": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "jv_encoder_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "jv_encoder_fwd_tap": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _i64, _p]),
     "jv_encoder_set_attention": (_i, [_p, _i]),
     "jv_load_mel_basis": (_i, [_p, _p, _i64, _i, _p]),
     "jv_mel_spectrogram": (_i, [_p, _p, _i, _i, _p, _p]),

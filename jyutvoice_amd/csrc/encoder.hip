@@ -18,7 +18,8 @@ int embed_sum(const long* x, const long* tone, const long* wp, const long* sp, c
 int concat_fill(const float* spk, const long* lang, const float* lang_emb, const long* xlen, float* h, int B, int Tt, int G,
                 int S, hipStream_t st);
 int lens_to_i32(const long* a, int* o, int n, int cap, hipStream_t st);
-int rope_qk(float* qkv, int B, int Tt, int G, int S, hipStream_t st);
+void rope_theta_table(float* theta);   // [72], host
+int rope_qk(float* qkv, const float* theta, int B, int Tt, int G, int S, hipStream_t st);
 int enc_softmax(float* sc, const long* xlen, int B, int H, int Tt, int ld, hipStream_t st);
 int transpose_v(const float* qkv, float* vt, int B, int Tt, int ld, int G, int S, hipStream_t st);
 int add_rowvec(const float* x, const float* vec, float* out, int B, int Tt, int G, int S, int C, hipStream_t st);
@@ -44,6 +45,7 @@ struct EncWs {
   float* vt = nullptr;                                 // [B,2,288,ld]
   float *spkn = nullptr, *cond = nullptr;              // [B,192], [B,576]
   float* cum = nullptr;                                // [B,Tt]
+  float* rope_theta = nullptr;                         // [72] RoPE's fp32 theta table (rope_theta_table)
   unsigned char* mask = nullptr;
   int* lens = nullptr;
 };
@@ -75,6 +77,12 @@ int enc_ws_create(Context& c) {
   JV_TRY(F(&w->spkn, (size_t)c.max_batch * 192));
   JV_TRY(F(&w->cond, (size_t)c.max_batch * 576));
   JV_TRY(F(&w->cum, (size_t)c.max_batch * c.max_tokens));
+  JV_TRY(F(&w->rope_theta, 72));
+  {
+    float theta[72];
+    rope_theta_table(theta);
+    JV_HIP(hipMemcpy(w->rope_theta, theta, sizeof(theta), hipMemcpyHostToDevice));
+  }
   JV_TRY(ws_alloc(c, R, reinterpret_cast<void**>(&w->mask)));
   JV_TRY(ws_alloc(c, sizeof(int) * c.max_batch, reinterpret_cast<void**>(&w->lens)));
   return JV_OK;
@@ -144,9 +152,28 @@ int speaker_projection(Context& c, const float* spk, int B, float* spks_out, hip
   return conv_gemm(a, 1, st);
 }
 
+// jv_encoder_fwd_tap: the stage whose buffer encoder_fwd copies out before it returns early (null: the whole forward)
+struct EncTap {
+  int id;
+  float* out;
+  long out_floats;
+};
+
+// channels of a tap's buffer (0: no such tap)
+static int enc_tap_channels(int id) {
+  if (id < JV_ENC_TAP_EMB || id > JV_ENC_TAP_D2) return 0;
+  if (id <= JV_ENC_TAP_PRE0 + 2) return 192;
+  if (id >= JV_ENC_TAP_D1) return 256;
+  if (id == JV_ENC_TAP_H0 || id == JV_ENC_TAP_XD) return 576;
+  const int kind = (id - JV_ENC_TAP_QKV0) % JV_ENC_TAP_PER_LAYER + JV_ENC_TAP_QKV0;
+  return kind == JV_ENC_TAP_QKV0 ? 1728 : kind == JV_ENC_TAP_FF0 ? 768 : 576;
+}
+
+// tap (jv_encoder_fwd_tap, else null): return behind the launches of that stage, its buffer copied out channels-first (e1 / e2
+// ping-pong and h is updated in place, so a stage can only be read where it stands); nothing ahead of the return depends on it
 int encoder_fwd(Context& c, const long* phone, const long* lang, const long* tone, const long* wpos, const long* spos,
                 const long* xlen, const float* spk, int B, int Tt, float* x_out, float* mu_out, float* logw_out,
-                float* spks_out, hipStream_t st) {
+                float* spks_out, hipStream_t st, const EncTap* tap = nullptr) {
   if (!c.ready[MODEL_TTS])
     return fail(JV_ERR_STATE, c.ready[MODEL_FLOW] ? "tts weights not finalized: this context holds the flow decoder only (JV_MODEL_FLOW); "
                                                     "the text encoder (encoder.*) and the duration predictor (dp.*) are missing"
@@ -160,6 +187,16 @@ int encoder_fwd(Context& c, const long* phone, const long* lang, const long* ton
   const int S = Tt + E_GAP;
   const long M = E_G + (long)B * S;
   const long AR = w.rows_alloc;
+  if (tap) {
+    const int C = enc_tap_channels(tap->id);
+    if (!C) return fail(JV_ERR_ARG, "jv_encoder_fwd_tap: unknown tap");
+    if (tap->out_floats < (long)B * C * Tt) return fail(JV_ERR_SHAPE, "jv_encoder_fwd_tap: out holds fewer than B*C*Tt floats");
+  }
+  auto at = [&](int id) { return tap && tap->id == id; };
+  auto tap_out = [&](const float* buf) {
+    const int C = enc_tap_channels(tap->id);
+    return rows_to_cf(buf, C, 0, E_G, S, tap->out, (long)C * Tt, B, C, Tt, w.lens, st);
+  };
 
   JV_TRY(lens_to_i32(xlen, w.lens, B, Tt, st));
   JV_TRY(row_meta(w.mask, nullptr, w.lens, B, 1, E_G, S, Tt, AR, 1, 0, st));
@@ -169,6 +206,7 @@ int encoder_fwd(Context& c, const long* phone, const long* lang, const long* ton
 
   // embeddings -> prenet (3 x conv k5 + channel-LN(eps 1e-4) + ReLU, 1x1 proj, residual, mask)
   JV_TRY(embed_sum(phone, tone, wpos, spos, e.emb, e.tone_emb, e.wpos_emb, e.spos_emb, w.e0, B, Tt, E_G, S, st));
+  if (at(JV_ENC_TAP_EMB)) return tap_out(w.e0);
   const float* cur = w.e0;
   for (int i = 0; i < 3; ++i) {
     ConvGemmArgs a = gemm_args(cur, 192, AR, M, e.pre_conv[i], w.e1, 192);
@@ -176,6 +214,7 @@ int encoder_fwd(Context& c, const long* phone, const long* lang, const long* ton
     JV_TRY(conv_gemm(a, 1, st));
     JV_TRY(layernorm_rows(w.e1, nullptr, w.e2, e.pre_ln[i].g, e.pre_ln[i].b, 1e-4f, M, 192, nullptr, st, 1));
     cur = w.e2;
+    if (at(JV_ENC_TAP_PRE0 + i)) return tap_out(w.e2);
   }
   {
     ConvGemmArgs a = gemm_args(w.e2, 192, AR, M, e.pre_proj, w.h, 576);   // columns [0,192) of the 576-wide concat
@@ -184,27 +223,34 @@ int encoder_fwd(Context& c, const long* phone, const long* lang, const long* ton
     JV_TRY(conv_gemm(a, 1, st));
   }
   JV_TRY(concat_fill(spk, lang, e.lang_emb, xlen, w.h, B, Tt, E_G, S, st));
+  if (at(JV_ENC_TAP_H0)) return tap_out(w.h);
 
   // 6 post-LN layers; every LayerNorm writes masked rows so "x * x_mask" never needs its own pass
   for (int i = 0; i < ENC_LAYERS; ++i) {
     const EncLayerW& L = e.layer[i];
+    const int lt = JV_ENC_TAP_PER_LAYER * i;
     ConvGemmArgs a = gemm_args(w.h, 576, AR, M, L.qkv, w.qkv, 1728);
     JV_TRY(conv_gemm(a, 1, st));
-    JV_TRY(rope_qk(w.qkv, B, Tt, E_G, S, st));
+    JV_TRY(rope_qk(w.qkv, w.rope_theta, B, Tt, E_G, S, st));
+    if (at(JV_ENC_TAP_QKV0 + lt)) return tap_out(w.qkv);
     if (fused) JV_TRY(enc_attention(w.qkv, xlen, B, Tt, E_G, S, w.att, st));
     else JV_TRY(enc_attention_gemm(w.qkv, w.scores, w.vt, w.att, xlen, B, Tt, E_G, S, st));
+    if (at(JV_ENC_TAP_ATT0 + lt)) return tap_out(w.att);
     a = gemm_args(w.att, 576, AR, M, L.o, w.y, 576);
     JV_TRY(conv_gemm(a, 1, st));
     JV_TRY(layernorm_rows(w.h, w.y, w.h, L.n1.g, L.n1.b, 1e-4f, M, 576, w.mask, st));
+    if (at(JV_ENC_TAP_N10 + lt)) return tap_out(w.h);
     a = gemm_args(w.h, 576, AR, M, L.ffn1, w.ffn, 768);
     a.rowmask_in = w.mask;
     a.act = ACT_RELU;
     JV_TRY(conv_gemm(a, 1, st));
+    if (at(JV_ENC_TAP_FF0 + lt)) return tap_out(w.ffn);
     a = gemm_args(w.ffn, 768, AR, M, L.ffn2, w.y, 576);
     a.rowmask_in = w.mask;
     a.rowmask_out = w.mask;
     JV_TRY(conv_gemm(a, 1, st));
     JV_TRY(layernorm_rows(w.h, w.y, w.h, L.n2.g, L.n2.b, 1e-4f, M, 576, w.mask, st));
+    if (at(JV_ENC_TAP_N20 + lt)) return tap_out(w.h);
   }
   // outputs: x (masked), mu = proj(x) * mask
   JV_TRY(rows_to_cf(w.h, 576, 0, E_G, S, x_out, 576L * Tt, B, 576, Tt, w.lens, st));
@@ -219,14 +265,17 @@ int encoder_fwd(Context& c, const long* phone, const long* lang, const long* ton
     ConvGemmArgs a = gemm_args(spk, 192, B, B, e.dp_cond, w.cond, 576);
     JV_TRY(conv_gemm(a, 1, st));
     JV_TRY(add_rowvec(w.h, w.cond, w.xd, B, Tt, E_G, S, 576, st));
+    if (at(JV_ENC_TAP_XD)) return tap_out(w.xd);
     a = gemm_args(w.xd, 576, AR, M, e.dp_conv1, w.d1, 256);
     a.rowmask_in = w.mask; a.act = ACT_RELU;
     JV_TRY(conv_gemm(a, 1, st));
     JV_TRY(layernorm_rows(w.d1, nullptr, w.d2, e.dp_ln1.g, e.dp_ln1.b, 1e-4f, M, 256, nullptr, st));
+    if (at(JV_ENC_TAP_D1)) return tap_out(w.d2);
     a = gemm_args(w.d2, 256, AR, M, e.dp_conv2, w.d1, 256);
     a.rowmask_in = w.mask; a.act = ACT_RELU;
     JV_TRY(conv_gemm(a, 1, st));
     JV_TRY(layernorm_rows(w.d1, nullptr, w.d2, e.dp_ln2.g, e.dp_ln2.b, 1e-4f, M, 256, nullptr, st));
+    if (at(JV_ENC_TAP_D2)) return tap_out(w.d2);
     a = gemm_args(w.d2, 256, AR, M, e.dp_proj, w.lw, 1);
     a.rowmask_in = w.mask; a.rowmask_out = w.mask;
     JV_TRY(conv_gemm(a, 1, st));
@@ -261,6 +310,20 @@ int jv_encoder_fwd(jv_context* ctx, const int64_t* phone, const int64_t* lang, c
                          reinterpret_cast<const long*>(tone), reinterpret_cast<const long*>(word_pos),
                          reinterpret_cast<const long*>(syllable_pos), reinterpret_cast<const long*>(x_lengths), spk, B, Tt, x,
                          mu_x, logw, spks_proj, static_cast<hipStream_t>(stream));
+}
+
+int jv_encoder_fwd_tap(jv_context* ctx, const int64_t* phone, const int64_t* lang, const int64_t* tone, const int64_t* word_pos,
+                       const int64_t* syllable_pos, const int64_t* x_lengths, const float* spk, int B, int Tt, float* x,
+                       float* mu_x, float* logw, float* spks_proj, int tap, float* out, int64_t out_floats, void* stream) {
+  if (!ctx || !phone || !lang || !tone || !word_pos || !syllable_pos || !x_lengths || !spk || !x || !mu_x || !logw || !spks_proj ||
+      !out)
+    return jv::fail(JV_ERR_ARG, "jv_encoder_fwd_tap: null argument");
+  JV_HIP(hipSetDevice(ctx->c.device));
+  const jv::EncTap t{tap, out, (long)out_floats};
+  return jv::encoder_fwd(ctx->c, reinterpret_cast<const long*>(phone), reinterpret_cast<const long*>(lang),
+                         reinterpret_cast<const long*>(tone), reinterpret_cast<const long*>(word_pos),
+                         reinterpret_cast<const long*>(syllable_pos), reinterpret_cast<const long*>(x_lengths), spk, B, Tt, x,
+                         mu_x, logw, spks_proj, static_cast<hipStream_t>(stream), &t);
 }
 
 int jv_encoder_set_attention(jv_context* ctx, int mode) {

@@ -73,17 +73,24 @@ int lens_to_i32(const long* a, int* o, int n, int cap, hipStream_t st) {
   return JV_OK;
 }
 
+// theta_i = 1 / 10000^(2i/144), i = 0 .. 71, as fp32 (text_encoder.py:119): the exponent and the quotient in fp32, the power
+// correctly rounded (fp64 pow, rounded once).  The device's powf may land an ulp from that, and the angle t theta carries t times
+// the difference: 3e-5 rad at t = 512 for the low pairs, fifteen times the fp32 floor of the rotated rows
+// (tests/test_gpu_textenc_stages.py, QKV0 of long513).  The table is made on the host, once per context (encoder.hip).
+void rope_theta_table(float* theta) {
+  for (int i = 0; i < 72; ++i) theta[i] = 1.0f / (float)pow(10000.0, (double)((float)(2 * i) / 144.0f));
+}
+
 // RoPE on q and k of a fused [rows,1728] qkv buffer: 2 heads x 288, first 144 dims, pairs (i, i+72), position = t
-__global__ __launch_bounds__(256) void rope_kernel(float* __restrict__ qkv, int B, int Tt, int G, int S) {
+__global__ __launch_bounds__(256) void rope_kernel(float* __restrict__ qkv, const float* __restrict__ theta_tab, int B, int Tt,
+                                                   int G, int S) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;   // over B*Tt*(2 tensors * 2 heads * 72)
   if (idx >= (long)B * Tt * 288) return;
   const int i = (int)(idx % 72);
   const int hh = (int)((idx / 72) % 4);                   // 0,1: q heads; 2,3: k heads
   const long bt = idx / 288;
   const int b = (int)(bt / Tt), t = (int)(bt - (long)b * Tt);
-  // theta_i = 1 / 10000^(2i/144), in fp32 like torch (text_encoder.py:119)
-  const float theta = 1.0f / powf(10000.0f, (float)(2 * i) / 144.0f);
-  const float ang = (float)t * theta;
+  const float ang = (float)t * theta_tab[i];             // in fp32 like torch (text_encoder.py:119)
   const float cs = cosf(ang), sn = sinf(ang);
   float* p = qkv + ((long)G + (long)b * S + t) * 1728 + (hh >> 1) * 576 + (hh & 1) * 288;
   const float a = p[i], c = p[i + 72];
@@ -91,8 +98,8 @@ __global__ __launch_bounds__(256) void rope_kernel(float* __restrict__ qkv, int 
   p[i + 72] = c * cs + a * sn;
 }
 
-int rope_qk(float* qkv, int B, int Tt, int G, int S, hipStream_t st) {
-  hipLaunchKernelGGL(rope_kernel, dim3((unsigned)cdivl((long)B * Tt * 288, 256)), dim3(256), 0, st, qkv, B, Tt, G, S);
+int rope_qk(float* qkv, const float* theta, int B, int Tt, int G, int S, hipStream_t st) {
+  hipLaunchKernelGGL(rope_kernel, dim3((unsigned)cdivl((long)B * Tt * 288, 256)), dim3(256), 0, st, qkv, theta, B, Tt, G, S);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

@@ -660,6 +660,25 @@ class Engine:
                                       _ptr(logw), _ptr(c), _stream(self.device)))
         return h, mu_x, logw, c
 
+    def encoder_tap(self, x, x_lengths, lang, tone, word_pos, syllable_pos, spk_embed, tap, out=None):
+        """jv_encoder_fwd_tap: encoder()'s own launches up to and including the stage `tap` (a name of _lib.ENC_TAPS), that stage's
+        buffer as [B, C, Tt]: zeros at and behind every utterance's length.  (tap as a raw id, or `out` given: passed on as they
+        are -- the library rejects an id it does not know and a buffer that is too small)"""
+        B, Tt = x.shape
+        ids = [v.to(device=self.device, dtype=torch.int64).contiguous() for v in (x, lang, tone, word_pos, syllable_pos)]
+        xl = x_lengths.to(device=self.device, dtype=torch.int64).contiguous()
+        spk = _f32(spk_embed, self.device)
+        tap_id, C = _lib.ENC_TAPS[tap] if isinstance(tap, str) else (int(tap), 1)
+        if out is None:
+            out = torch.empty(B, C, Tt, device=self.device)
+        h = torch.empty(B, spec.ENC_HIDDEN, Tt, device=self.device)      # (scratch: the call returns ahead of some or all of the outputs)
+        mu_x = torch.empty(B, spec.N_FEATS, Tt, device=self.device)
+        logw = torch.empty(B, 1, Tt, device=self.device)
+        c = torch.empty(B, spec.N_FEATS, device=self.device)
+        check(self.lib.jv_encoder_fwd_tap(self._h, *[_ptr(v) for v in ids], _ptr(xl), _ptr(spk), B, Tt, _ptr(h), _ptr(mu_x),
+                                          _ptr(logw), _ptr(c), tap_id, _ptr(out), out.numel(), _stream(self.device)))
+        return out
+
     def length_regulate(self, logw, x_lengths, mu_x, length_scale=1.0, host_lengths=False):
         """host_lengths: also leave y_lengths as a list of ints in self.y_lengths_host (the voice-cloning batch sizes its
         workspace by max(p_b + y_b) without a synchronisation of its own)"""
