@@ -327,6 +327,61 @@ int jv_flow_token2mel_partial(jv_context* ctx, const int64_t* prompt_tokens, con
 int jv_flow_encoder_fwd_ctx(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
                             const int64_t* token_lens, const int32_t* ctx_lens, int B, int P, int N, int streaming, float* h,
                             int32_t* h_lens, void* stream);
+/* jv_upsample_encoder_tap (used by the parity tests): the launch sequence of one of the four entries above up to and including one
+ * stage of the UpsampleConformerEncoder, whose workspace buffer is then copied out -- an early return inside the function those
+ * entries run (the buffers ping-pong and the hidden state is updated in place, so a stage can only be read where it stands), not
+ * a second sequence: the argument checks, the lengths, the row masks and every launch ahead of the return are the entry's own.
+ * mode selects the entry: JV_UPS_MODE_PROMPT (jv_prompt_encoder_fwd: P must be 0 and streaming 0, the three-GEMM attention),
+ * JV_UPS_MODE_FLOW (jv_flow_encoder_fwd), JV_UPS_MODE_PARTIAL (jv_flow_encoder_fwd_partial: B must be 1) and JV_UPS_MODE_CTX
+ * (jv_flow_encoder_fwd_ctx; ctx_lens is read by this mode alone).  Another mode or an unknown tap: JV_ERR_ARG; out_floats too
+ * small for the tap: JV_ERR_SHAPE; both behind the entry's own checks and ahead of its first launch.
+ * Layout, with W = P + N (the width of the whole sequence in every mode) and L_b the encoded length (p_b + n_b less the context):
+ *   row taps   out [B, C, W] (token rate) or [B, C, 2 W] (mel rate), channels first; exact zeros at and behind L_b / 2 L_b.  E0 alone
+ *              also shows the look-ahead context rows conv1 reads: its live length is L_b + ctx_b
+ *   tables     PE1 / PE2 / POS: out [2 T - 1, 512], T = the encoded width (W, in the partial mode W - 3) at token rate, twice that
+ *              at mel rate; no batch geometry
+ * One id per tap, in execution order; the eight taps of block i are the block-0 ids + JV_UPS_TAP_PER_BLOCK * i (93 ids, 0 .. 92):
+ *   EMB  (512)  the embedded tokens                          EL   (512)  embed.out.0 (Linear)
+ *   E0   (512)  its LayerNorm x sqrt(512)                    PE1  table  relative positions T - 1 .. -(T - 1), sin | cos interleaved
+ *   C1   (512)  look-ahead conv1 + bias (LeakyReLU is conv2's prologue)
+ *   LA   (512)  conv2 + bias + E0: the blocks' input
+ *   per block (six at token rate from JV_UPS_TAP_LN1_0, four at mel rate from JV_UPS_TAP_ULN1_0):
+ *     LN1 (512) norm_mha   QKV (1536) q | k | v   POS table linear_pos(PE)   ATT (512) the attention, ahead of linear_out
+ *     X1  (512) x + linear_out(att)   LN2 (512) norm_ff   FF (2048) SiLU(w_1)   X2 (512) X1 + w_2(FF): the block's output
+ *   REP  (512)  nearest x 2            UP   (512)  up_layer.conv (k5, causal)
+ *   UL   (512)  up_embed.out.0         U0   (512)  its LayerNorm x sqrt(512)     PE2  table
+ *   AN   (512)  after_norm             H    (80)   encoder_proj: the entry's output, here channels first */
+#define JV_UPS_MODE_PROMPT 0
+#define JV_UPS_MODE_FLOW 1
+#define JV_UPS_MODE_PARTIAL 2
+#define JV_UPS_MODE_CTX 3
+#define JV_UPS_TAP_EMB 0
+#define JV_UPS_TAP_EL 1
+#define JV_UPS_TAP_E0 2
+#define JV_UPS_TAP_PE1 3
+#define JV_UPS_TAP_C1 4
+#define JV_UPS_TAP_LA 5
+#define JV_UPS_TAP_LN1_0 6     /* token-rate block i < 6: + JV_UPS_TAP_PER_BLOCK * i */
+#define JV_UPS_TAP_QKV_0 7
+#define JV_UPS_TAP_POS_0 8
+#define JV_UPS_TAP_ATT_0 9
+#define JV_UPS_TAP_X1_0 10
+#define JV_UPS_TAP_LN2_0 11
+#define JV_UPS_TAP_FF_0 12
+#define JV_UPS_TAP_X2_0 13
+#define JV_UPS_TAP_PER_BLOCK 8
+#define JV_UPS_TAP_REP 54
+#define JV_UPS_TAP_UP 55
+#define JV_UPS_TAP_UL 56
+#define JV_UPS_TAP_U0 57
+#define JV_UPS_TAP_PE2 58
+#define JV_UPS_TAP_ULN1_0 59   /* mel-rate block i < 4: the same eight, + JV_UPS_TAP_PER_BLOCK * i */
+#define JV_UPS_TAP_AN 91
+#define JV_UPS_TAP_H 92
+#define JV_UPS_TAP_COUNT 93
+int jv_upsample_encoder_tap(jv_context* ctx, int mode, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                            const int64_t* token_lens, const int32_t* ctx_lens, int B, int P, int N, int streaming, int tap,
+                            float* out, int64_t out_floats, void* stream);
 int jv_flow_token2mel_ctx(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
                           const int64_t* token_lens, const int32_t* ctx_lens, const float* prompt_feat, const int32_t* feat_lens,
                           const float* embedding, int B, int P, int N, int F, int streaming, int n_timesteps, float temperature,

@@ -42,6 +42,22 @@ for _i_layer in range(6):
         ENC_TAPS[f"{_name}{_i_layer}"] = (5 + 5 * _i_layer + _k, _c)
 ENC_TAPS.update({"XD": (35, 576), "D1": (36, 256), "D2": (37, 256)})
 
+# jv_upsample_encoder_tap: tap name -> (id, channels, rate), in execution order, as include/jyutvoice_hip.h lists them (JV_UPS_TAP_*).
+# rate 1: token rows, out [B, C, P + N]; rate 2: mel rows, out [B, C, 2 (P + N)].  The eight taps of token-rate block i are NAME_i
+# (block-0 id + 8 i), of mel-rate block i NAME_ui.  UPS_TABLES (PE1, PE2, POS_*): [2T - 1, 512] with T the encoded width x rate
+UPS_MODES = {"prompt": 0, "flow": 1, "partial": 2, "ctx": 3}
+UPS_BLOCK_TAPS = (("LN1", 512), ("QKV", 1536), ("POS", 512), ("ATT", 512), ("X1", 512), ("LN2", 512), ("FF", 2048), ("X2", 512))
+UPS_TAPS = {"EMB": (0, 512, 1), "EL": (1, 512, 1), "E0": (2, 512, 1), "PE1": (3, 512, 1), "C1": (4, 512, 1), "LA": (5, 512, 1)}
+for _i_blk in range(6):
+    for _k, (_name, _c) in enumerate(UPS_BLOCK_TAPS):
+        UPS_TAPS[f"{_name}_{_i_blk}"] = (6 + 8 * _i_blk + _k, _c, 1)
+UPS_TAPS.update({"REP": (54, 512, 2), "UP": (55, 512, 2), "UL": (56, 512, 2), "U0": (57, 512, 2), "PE2": (58, 512, 2)})
+for _i_blk in range(4):
+    for _k, (_name, _c) in enumerate(UPS_BLOCK_TAPS):
+        UPS_TAPS[f"{_name}_u{_i_blk}"] = (59 + 8 * _i_blk + _k, _c, 2)
+UPS_TAPS.update({"AN": (91, 512, 2), "H": (92, 80, 2)})
+UPS_TABLES = frozenset(k for k in UPS_TAPS if k.startswith(("PE", "POS_")))
+
 ACT = {"none": 0, "relu": 1, "gelu": 2, "mish": 3, "elu": 4, "silu": 5}
 PRO = {"none": 0, "snake": 1, "lrelu": 2}
 
@@ -94,6 +110,7 @@ SIGNATURES = {
     "jv_flow_encoder_fwd_partial": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "jv_flow_token2mel_partial": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "jv_flow_encoder_fwd_ctx": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "jv_upsample_encoder_tap": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i64, _p]),
     "jv_flow_token2mel_ctx": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "jv_encoder_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "jv_encoder_fwd_tap": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _i64, _p]),

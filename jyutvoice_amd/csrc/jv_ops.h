@@ -13,8 +13,9 @@ int clamp_lens(const int* src, int nb, int reps, int T, int* dst, hipStream_t st
 // src[b*src_bstride + c*pitch + t] (channels-first) -> dst[(G + b*S + t)*ld + col0 + c]
 int cf_to_rows(const float* src, long src_bstride, long pitch, int B, int C, int T, float* dst, int ld, int col0, int G,
                int S, float scale, const int* lens, hipStream_t st, const int* uoff = nullptr);
+// (the inverse; positions at and behind min(lens[b] * len_mul + len_add, T) are written as zeros)
 int rows_to_cf(const float* src, int ld, int col0, int G, int S, float* dst, long dst_bstride, int B, int C, int T,
-               const int* lens, hipStream_t st, const int* uoff = nullptr);
+               const int* lens, hipStream_t st, const int* uoff = nullptr, int len_mul = 1, int len_add = 0);
 // cfm_solve_prompted's pack and unpack (rowops.hip): row-layout mu / cond of [prompt_b | text_b] sequences in one launch; the
 // generated frames first[b] .. first[b] + lens[b] - 1 back to channels-first, zero-filled to T.  clens (optional): the condition
 // prefix has a length of its own, cond = [prompt_feat_b[:clens[b]] | 0] while mu = [prompt_h[b, :plens[b]] | mu_y] (token-to-mel:

@@ -172,30 +172,86 @@ int rel_attention_gemm(const float* qkv, const float* p, const float* u, const f
 
 namespace {
 
+// jv_upsample_encoder_tap: the stage whose buffer encoder_stages copies out before it returns early (null: the whole encoder)
+struct UpsTap {
+  int id;
+  float* out;
+  long out_floats;
+};
+
+struct UpsTapShape {
+  int C;        // channels of a row tap
+  int rate;     // 1: token rows, 2: mel rows
+  bool table;   // [2T - 1, 512], no batch geometry (the position tables and linear_pos of them)
+};
+
+// false: no such tap
+bool ups_tap_shape(int id, UpsTapShape& s) {
+  if (id < 0 || id >= JV_UPS_TAP_COUNT) return false;
+  s.C = 512;
+  s.rate = id >= JV_UPS_TAP_REP ? 2 : 1;
+  s.table = id == JV_UPS_TAP_PE1 || id == JV_UPS_TAP_PE2;
+  if (id == JV_UPS_TAP_H) s.C = 80;
+  int kind = -1;
+  if (id >= JV_UPS_TAP_LN1_0 && id < JV_UPS_TAP_REP) kind = (id - JV_UPS_TAP_LN1_0) % JV_UPS_TAP_PER_BLOCK;
+  if (id >= JV_UPS_TAP_ULN1_0 && id < JV_UPS_TAP_AN) kind = (id - JV_UPS_TAP_ULN1_0) % JV_UPS_TAP_PER_BLOCK;
+  if (kind == JV_UPS_TAP_QKV_0 - JV_UPS_TAP_LN1_0) s.C = 1536;
+  if (kind == JV_UPS_TAP_FF_0 - JV_UPS_TAP_LN1_0) s.C = 2048;
+  if (kind == JV_UPS_TAP_POS_0 - JV_UPS_TAP_LN1_0) s.table = true;
+  return true;
+}
+
+// ahead of an entry's first launch.  W: tokens of the whole sequence (P + N), Tenc: the encoded width (W less a scalar context)
+int check_tap(const UpsTap* tap, int B, int W, int Tenc) {
+  if (!tap) return JV_OK;
+  UpsTapShape s;
+  if (!ups_tap_shape(tap->id, s)) return fail(JV_ERR_ARG, "jv_upsample_encoder_tap: unknown tap");
+  const long need = s.table ? (2L * s.rate * Tenc - 1) * 512 : (long)B * s.C * s.rate * W;
+  if (tap->out_floats < need)
+    return fail(JV_ERR_SHAPE, "jv_upsample_encoder_tap: out holds fewer floats than the tap ([B, C, rate (P + N)], a table [2T - 1, 512])");
+  return JV_OK;
+}
+
 // one pre-LN block on T rows per utterance (geometry G, S): x += MHA_rel(LN(x)); x += W2 silu(W1 LN(x)).  fused: the attention
 // as relattn.hip's one launch instead of the three GEMMs; chunk > 0: the streaming mask (keys j < (i / chunk + 1) * chunk)
+// tap_kind (jv_upsample_encoder_tap; -1: none): return behind the launches of that one of the block's eight stages, *tap_buf = the
+// buffer it stands in (x is updated in place: a stage can only be read where it stands)
 int conformer_block(Context& c, const ConfBlockW& k, int B, int T, int G, int S, long M, const long* len, int len_mul, bool fused,
-                    int chunk, hipStream_t st) {
+                    int chunk, hipStream_t st, int tap_kind = -1, const float** tap_buf = nullptr) {
   PromptWs& w = *c.pws;
   const long AR = w.rows;
   const int npos = 2 * T - 1;
+  auto at = [&](int id, const float* buf) {
+    if (tap_kind != id - JV_UPS_TAP_LN1_0) return false;
+    *tap_buf = buf;
+    return true;
+  };
   JV_TRY(layernorm_rows(w.x, nullptr, w.ln, k.n_mha.g, k.n_mha.b, 1e-5f, M, 512, nullptr, st));
+  if (at(JV_UPS_TAP_LN1_0, w.ln)) return JV_OK;
   ConvGemmArgs a = lin_args(w.ln, 512, AR, M, k.qkv, w.qkv, 1536);
   JV_TRY(conv_gemm(a, 1, st));
+  if (at(JV_UPS_TAP_QKV_0, w.qkv)) return JV_OK;
   a = lin_args(w.pe, 512, npos, npos, k.pos, w.p, 512);                       // p = linear_pos(pos_emb), shared by the batch
   JV_TRY(conv_gemm(a, 1, st));
+  if (at(JV_UPS_TAP_POS_0, w.p)) return JV_OK;
   if (fused) JV_TRY(rel_attention(w.qkv, w.p, npos, k.u, k.v, len, len_mul, B, T, G, S, chunk, w.att, st));
   else JV_TRY(rel_attention_gemm(w.qkv, w.p, k.u, k.v, w.qu, w.qv, w.ac, w.bd, w.vt, w.att, len, len_mul, B, T, G, S, chunk, st));
+  if (at(JV_UPS_TAP_ATT_0, w.att)) return JV_OK;
   a = lin_args(w.att, 512, AR, M, k.out, w.x, 512);
   a.res1 = w.x; a.ldr1 = 512;
   JV_TRY(conv_gemm(a, 1, st));
+  if (at(JV_UPS_TAP_X1_0, w.x)) return JV_OK;
   JV_TRY(layernorm_rows(w.x, nullptr, w.ln, k.n_ff.g, k.n_ff.b, 1e-5f, M, 512, nullptr, st));
+  if (at(JV_UPS_TAP_LN2_0, w.ln)) return JV_OK;
   a = lin_args(w.ln, 512, AR, M, k.w1, w.ffn, 2048);
   a.act = ACT_SILU;
   JV_TRY(conv_gemm(a, 1, st));
+  if (at(JV_UPS_TAP_FF_0, w.ffn)) return JV_OK;
   a = lin_args(w.ffn, 2048, AR, M, k.w2, w.x, 512);
   a.res1 = w.x; a.ldr1 = 512;
-  return conv_gemm(a, 1, st);
+  JV_TRY(conv_gemm(a, 1, st));
+  (void)at(JV_UPS_TAP_X2_0, w.x);
+  return JV_OK;
 }
 
 // Both stages for utterance b's ids [ptok[b, :p_b] | tok[b, :n_b]] (P = 0: one source), T1 = P + N token rows.  `len`: the int64
@@ -205,8 +261,11 @@ int conformer_block(Context& c, const ConfBlockW& k, int B, int T, int G, int S,
 // lens_c (with ctx = 0): every utterance has a context of its own, 0 or 3 tokens.  The buffers keep the width of the whole
 // sequence, T1 = P + N; utterance b's context rows sit right behind its L_b = len[b] encoded ones -- rows that are padding to
 // everything but conv1 -- and lens_c[b] = L_b + ctx_b is what mask1c marks
+// tap (jv_upsample_encoder_tap, else null): return behind the launches of that stage, its buffer copied out (the entry has checked
+// the tap and the size of its `out`); nothing ahead of the return depends on it, and h_out is not written
 int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const long* tok, const long* tlen, int N, const long* len,
-                   int B, bool fused, bool streaming, int ctx, float* h_out, hipStream_t st, const int* lens_c = nullptr) {
+                   int B, bool fused, bool streaming, int ctx, float* h_out, hipStream_t st, const int* lens_c = nullptr,
+                   const UpsTap* tap = nullptr) {
   PromptWs& w = *c.pws;
   const PromptW& e = c.prompt;
   const long AR = w.rows;
@@ -214,6 +273,26 @@ int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const 
   const int T1 = Tk, S1 = T1 + P_GAP, T2 = 2 * Tk, S2 = T2 + P_GAP;
   const long M1 = P_G + (long)B * S1, M2 = P_G + (long)B * S2;
   const int chunk1 = streaming ? PR_CHUNK : 0, chunk2 = 2 * chunk1;
+  auto at = [&](int id) { return tap && tap->id == id; };
+  // row taps: [B, C, rate (P + N)] channels first, zeros at and behind rate * lens[b] + add (lens_i holds the encoded lengths L_b)
+  auto tap_rows = [&](const float* buf, const int* lens, int add) -> int {
+    UpsTapShape s;
+    ups_tap_shape(tap->id, s);
+    const int Wd = s.rate * (P + N);
+    return rows_to_cf(buf, s.C, 0, P_G, s.rate == 1 ? S1 : S2, tap->out, (long)s.C * Wd, B, s.C, Wd, lens, st, nullptr, s.rate, add);
+  };
+  auto tap_table = [&](const float* buf, int T) -> int {
+    JV_HIP(hipMemcpyAsync(tap->out, buf, sizeof(float) * (2L * T - 1) * 512, hipMemcpyDeviceToDevice, st));
+    return JV_OK;
+  };
+  // the eight taps of block i of a stage whose block 0 starts at id0: which of them the block stops behind (-1: none)
+  auto block_tap = [&](int id0, int i) {
+    const int k = tap ? tap->id - (id0 + JV_UPS_TAP_PER_BLOCK * i) : -1;
+    return k >= 0 && k < JV_UPS_TAP_PER_BLOCK ? k : -1;
+  };
+  auto block_out = [&](int kind, const float* buf, int T) -> int {
+    return kind == JV_UPS_TAP_POS_0 - JV_UPS_TAP_LN1_0 ? tap_table(buf, T) : tap_rows(buf, w.lens_i, 0);
+  };
 
   JV_TRY(lens_to_i32(len, w.lens_i, B, Tk, st));
   JV_TRY(row_meta(w.mask1, nullptr, w.lens_i, B, 1, P_G, S1, T1, AR, 1, 0, st));
@@ -224,16 +303,21 @@ int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const 
   // ---- stage 1: embedding -> Linear + LayerNorm (* sqrt 512) -> look-ahead convs -> 6 blocks ---------------------------
   JV_TRY(fill(w.y, 0.f, M1 * 512, st));                     // gap rows of the embedding buffer must read as zero tokens
   JV_TRY(prompt_embed(ptok, plen, P, tok, tlen, N, e.emb, w.y, B, P_G, S1, PR_VOCAB, st));
+  if (at(JV_UPS_TAP_EMB)) return tap_rows(w.y, w.lens_i, 0);
   ConvGemmArgs a = lin_args(w.y, 512, AR, M1, e.emb_lin, w.ln, 512);
   JV_TRY(conv_gemm(a, 1, st));
+  if (at(JV_UPS_TAP_EL)) return tap_rows(w.ln, w.lens_i, 0);
   JV_TRY(layernorm_rows(w.ln, nullptr, w.x, e.emb_ln.g, e.emb_ln.b, 1e-5f, M1, 512, nullptr, st));
+  if (at(JV_UPS_TAP_E0)) return lens_c ? tap_rows(w.x, lens_c, 0) : tap_rows(w.x, w.lens_i, ctx);      // the rows conv1 reads
   JV_TRY(rel_pos_table(w.pe, e.div, T1, st));
+  if (at(JV_UPS_TAP_PE1)) return tap_table(w.pe, T1);
   // conv1: rows t .. t+3 of the valid frames (zeros beyond the end -- or, behind the last encoded frame of a partial sequence, the
   // embedded context rows), bias; LeakyReLU(0.01) is conv2's prologue
   a = lin_args(w.x, 512, AR, M1, e.look1, w.y, 512);
   a.tap_row0 = 0;
   a.rowmask_in = ctx > 0 || lens_c ? w.mask1c : w.mask1;
   JV_TRY(conv_gemm(a, 1, st));
+  if (at(JV_UPS_TAP_C1)) return tap_rows(w.y, w.lens_i, 0);
   // conv2: rows t-2 .. t of leaky(conv1) over the valid frames (zeros before the start), + bias + x
   a = lin_args(w.y, 512, AR, M1, e.look2, w.ln, 512);
   a.tap_row0 = -2;
@@ -242,23 +326,41 @@ int encoder_stages(Context& c, const long* ptok, const long* plen, int P, const 
   a.res1 = w.x; a.ldr1 = 512;
   JV_TRY(conv_gemm(a, 1, st));
   JV_HIP(hipMemcpyAsync(w.x, w.ln, sizeof(float) * M1 * 512, hipMemcpyDeviceToDevice, st));
-  for (int i = 0; i < PR_BLOCKS; ++i) JV_TRY(conformer_block(c, e.blk[i], B, T1, P_G, S1, M1, len, 1, fused, chunk1, st));
+  if (at(JV_UPS_TAP_LA)) return tap_rows(w.x, w.lens_i, 0);
+  for (int i = 0; i < PR_BLOCKS; ++i) {
+    const int kind = block_tap(JV_UPS_TAP_LN1_0, i);
+    const float* buf = nullptr;
+    JV_TRY(conformer_block(c, e.blk[i], B, T1, P_G, S1, M1, len, 1, fused, chunk1, st, kind, &buf));
+    if (kind >= 0) return block_out(kind, buf, T1);
+  }
 
   // ---- stage 2: nearest x2 -> conv k5 over rows u-4 .. u -> Linear + LayerNorm (* sqrt 512) -> 4 blocks -> LN -> proj ----
   JV_TRY(fill(w.y, 0.f, M2 * 512, st));
   JV_TRY(repeat_rows2(w.x, w.y, B, T1, P_G, S1, P_G, S2, st));
+  if (at(JV_UPS_TAP_REP)) return tap_rows(w.y, w.lens_i, 0);
   a = lin_args(w.y, 512, AR, M2, e.up_conv, w.ln, 512);
   a.tap_row0 = -4;
   a.rowmask_in = w.mask2;
   JV_TRY(conv_gemm(a, 1, st));
+  if (at(JV_UPS_TAP_UP)) return tap_rows(w.ln, w.lens_i, 0);
   a = lin_args(w.ln, 512, AR, M2, e.up_emb_lin, w.y, 512);
   JV_TRY(conv_gemm(a, 1, st));
+  if (at(JV_UPS_TAP_UL)) return tap_rows(w.y, w.lens_i, 0);
   JV_TRY(layernorm_rows(w.y, nullptr, w.x, e.up_emb_ln.g, e.up_emb_ln.b, 1e-5f, M2, 512, nullptr, st));
+  if (at(JV_UPS_TAP_U0)) return tap_rows(w.x, w.lens_i, 0);
   JV_TRY(rel_pos_table(w.pe, e.div, T2, st));
-  for (int i = 0; i < PR_UP_BLOCKS; ++i) JV_TRY(conformer_block(c, e.up[i], B, T2, P_G, S2, M2, len, 2, fused, chunk2, st));
+  if (at(JV_UPS_TAP_PE2)) return tap_table(w.pe, T2);
+  for (int i = 0; i < PR_UP_BLOCKS; ++i) {
+    const int kind = block_tap(JV_UPS_TAP_ULN1_0, i);
+    const float* buf = nullptr;
+    JV_TRY(conformer_block(c, e.up[i], B, T2, P_G, S2, M2, len, 2, fused, chunk2, st, kind, &buf));
+    if (kind >= 0) return block_out(kind, buf, T2);
+  }
   JV_TRY(layernorm_rows(w.x, nullptr, w.ln, e.after.g, e.after.b, 1e-5f, M2, 512, nullptr, st));
+  if (at(JV_UPS_TAP_AN)) return tap_rows(w.ln, w.lens_i, 0);
   a = lin_args(w.ln, 512, AR, M2, e.proj, w.o80, 80);
   JV_TRY(conv_gemm(a, 1, st));
+  if (at(JV_UPS_TAP_H)) return tap_rows(w.o80, w.lens_i, 0);
   return rows_to_btc(w.o80, len, 2, h_out, B, T2, 80, P_G, S2, st);
 }
 
@@ -270,27 +372,40 @@ int check_encoder_call(Context& c, int B, int Tk) {
   return JV_OK;
 }
 
-}  // namespace
-
-int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int Tk, float* h_out, hipStream_t st) {
+// The three entries, each with the optional tap of jv_upsample_encoder_tap (checked behind the entry's own checks, ahead of its
+// first launch); the functions the rest of the library calls pass none
+int prompt_encoder_run(Context& c, const long* tok, const long* len, int B, int Tk, float* h_out, hipStream_t st, const UpsTap* tap) {
   JV_TRY(check_encoder_call(c, B, Tk));
+  JV_TRY(check_tap(tap, B, Tk, Tk));
   JV_TRY(ensure_ws(c, B, Tk, true));
   // the three-GEMM attention, full context: this entry's launches and bits are what they were before relattn.hip existed
-  return encoder_stages(c, nullptr, nullptr, 0, tok, len, Tk, len, B, false, false, 0, h_out, st);
+  return encoder_stages(c, nullptr, nullptr, 0, tok, len, Tk, len, B, false, false, 0, h_out, st, nullptr, tap);
 }
 
 // flow.py:319-328, 338: [prompt tokens | tokens] -> h, on the fused attention (no ac / bd / vt in this route's workspace)
 // ctx = 3: flow.py:330-336, h over the first P + N - 3 tokens with the last three as look-ahead context ([B, 2 (P + N - 3), 80])
-int flow_encoder_fwd(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, int B, int P, int N,
-                     int streaming, float* h_out, int* h_lens, hipStream_t st, int ctx) {
+int flow_encoder_run(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, int B, int P, int N,
+                     int streaming, float* h_out, int* h_lens, hipStream_t st, int ctx, const UpsTap* tap) {
   if (P < 0 || N < 0) return fail(JV_ERR_ARG, "jv_flow_encoder_fwd: P and N must be non-negative");
   if (ctx != 0 && ctx != PR_LOOKAHEAD) return fail(JV_ERR_ARG, "flow encoder: the context is the look-ahead length (3 tokens) or nothing");
   if (ctx > 0 && (B != 1 || P + N <= ctx)) return fail(JV_ERR_ARG, "partial flow encoder: B must be 1 and P + N at least 4 (one encoded token + 3 of context)");
   JV_TRY(check_encoder_call(c, B, P + N));
+  JV_TRY(check_tap(tap, B, P + N, P + N - ctx));
   JV_TRY(ensure_ws(c, B, P + N, false));
   PromptWs& w = *c.pws;
   JV_TRY(sum_lens(plen, P, len, N, B, w.lens64, h_lens, 2, ctx, st));
-  return encoder_stages(c, ptok, plen, P, tok, len, N, w.lens64, B, true, streaming != 0, ctx, h_out, st);
+  return encoder_stages(c, ptok, plen, P, tok, len, N, w.lens64, B, true, streaming != 0, ctx, h_out, st, nullptr, tap);
+}
+
+}  // namespace
+
+int prompt_encoder_fwd(Context& c, const long* tok, const long* len, int B, int Tk, float* h_out, hipStream_t st) {
+  return prompt_encoder_run(c, tok, len, B, Tk, h_out, st, nullptr);
+}
+
+int flow_encoder_fwd(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, int B, int P, int N,
+                     int streaming, float* h_out, int* h_lens, hipStream_t st, int ctx) {
+  return flow_encoder_run(c, ptok, plen, tok, len, B, P, N, streaming, h_out, h_lens, st, ctx, nullptr);
 }
 
 // The lengths of a call with per-utterance contexts, on the host: the token counts and ctx_lens come down (one synchronisation, the
@@ -329,18 +444,45 @@ int flow_ctx_lengths(const char* who, const long* plen, const long* len, const i
 
 // jv_flow_encoder_fwd_ctx: flow_encoder_fwd with a context per utterance (ctx_lens: device int32 [B], each 0 or 3), h [B, 2 (P + N), 80]
 // with zeros behind 2 L_b.  checked: the caller has run flow_ctx_lengths on these vectors already
-int flow_encoder_fwd_ctx(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const int* ctx_lens, int B,
-                         int P, int N, int streaming, float* h_out, int* h_lens, hipStream_t st, bool checked) {
+static int flow_encoder_ctx_run(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const int* ctx_lens,
+                                int B, int P, int N, int streaming, float* h_out, int* h_lens, hipStream_t st, bool checked,
+                                const UpsTap* tap) {
   if (P < 0 || N < 0) return fail(JV_ERR_ARG, "jv_flow_encoder_fwd_ctx: P and N must be non-negative");
   JV_TRY(check_encoder_call(c, B, P + N));
   if (!checked) {
     std::vector<int> enc_lens;
     JV_TRY(flow_ctx_lengths("jv_flow_encoder_fwd_ctx", plen, len, ctx_lens, nullptr, B, P, N, enc_lens, nullptr, st));
   }
+  JV_TRY(check_tap(tap, B, P + N, P + N));
   JV_TRY(ensure_ws(c, B, P + N, false));
   PromptWs& w = *c.pws;
   JV_TRY(sum_lens_ctx(plen, P, len, N, B, w.lens64, h_lens, 2, ctx_lens, w.lens_c, st));
-  return encoder_stages(c, ptok, plen, P, tok, len, N, w.lens64, B, true, streaming != 0, 0, h_out, st, w.lens_c);
+  return encoder_stages(c, ptok, plen, P, tok, len, N, w.lens64, B, true, streaming != 0, 0, h_out, st, w.lens_c, tap);
+}
+
+int flow_encoder_fwd_ctx(Context& c, const long* ptok, const long* plen, const long* tok, const long* len, const int* ctx_lens, int B,
+                         int P, int N, int streaming, float* h_out, int* h_lens, hipStream_t st, bool checked) {
+  return flow_encoder_ctx_run(c, ptok, plen, tok, len, ctx_lens, B, P, N, streaming, h_out, h_lens, st, checked, nullptr);
+}
+
+// jv_upsample_encoder_tap: one of the entries above with a tap
+int upsample_encoder_tap(Context& c, int mode, const long* ptok, const long* plen, const long* tok, const long* len, const int* ctx_lens,
+                         int B, int P, int N, int streaming, int tap_id, float* out, long out_floats, hipStream_t st) {
+  const UpsTap tap{tap_id, out, out_floats};
+  switch (mode) {
+    case JV_UPS_MODE_PROMPT:
+      if (P != 0 || streaming != 0) return fail(JV_ERR_ARG, "jv_upsample_encoder_tap: the prompt entry has no prompt tokens (P = 0) and no streaming");
+      return prompt_encoder_run(c, tok, len, B, N, nullptr, st, &tap);
+    case JV_UPS_MODE_FLOW:
+      return flow_encoder_run(c, ptok, plen, tok, len, B, P, N, streaming, nullptr, nullptr, st, 0, &tap);
+    case JV_UPS_MODE_PARTIAL:
+      if (B != 1) return fail(JV_ERR_ARG, "jv_upsample_encoder_tap: the partial entry is B = 1");
+      return flow_encoder_run(c, ptok, plen, tok, len, 1, P, N, streaming, nullptr, nullptr, st, PR_LOOKAHEAD, &tap);
+    case JV_UPS_MODE_CTX:
+      if (!ctx_lens) return fail(JV_ERR_ARG, "jv_upsample_encoder_tap: the per-utterance mode needs ctx_lens");
+      return flow_encoder_ctx_run(c, ptok, plen, tok, len, ctx_lens, B, P, N, streaming, nullptr, nullptr, st, false, &tap);
+  }
+  return fail(JV_ERR_ARG, "jv_upsample_encoder_tap: mode is JV_UPS_MODE_PROMPT, _FLOW, _PARTIAL or _CTX");
 }
 
 }  // namespace jv
@@ -374,6 +516,17 @@ int jv_flow_encoder_fwd_ctx(jv_context* ctx, const int64_t* prompt_tokens, const
   return jv::flow_encoder_fwd_ctx(ctx->c, reinterpret_cast<const long*>(prompt_tokens), reinterpret_cast<const long*>(prompt_lens),
                                   reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_lens), ctx_lens, B, P, N,
                                   streaming, h, h_lens, static_cast<hipStream_t>(stream), false);
+}
+
+int jv_upsample_encoder_tap(jv_context* ctx, int mode, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,
+                            const int64_t* token_lens, const int32_t* ctx_lens, int B, int P, int N, int streaming, int tap,
+                            float* out, int64_t out_floats, void* stream) {
+  if (!ctx || !out || !token_lens || (N > 0 && !tokens) || (P > 0 && (!prompt_tokens || !prompt_lens)))
+    return jv::fail(JV_ERR_ARG, "jv_upsample_encoder_tap: null argument");
+  JV_HIP(hipSetDevice(ctx->c.device));
+  return jv::upsample_encoder_tap(ctx->c, mode, reinterpret_cast<const long*>(prompt_tokens), reinterpret_cast<const long*>(prompt_lens),
+                                  reinterpret_cast<const long*>(tokens), reinterpret_cast<const long*>(token_lens), ctx_lens, B, P, N,
+                                  streaming, tap, out, (long)out_floats, static_cast<hipStream_t>(stream));
 }
 
 int jv_flow_encoder_fwd_partial(jv_context* ctx, const int64_t* prompt_tokens, const int64_t* prompt_lens, const int64_t* tokens,

@@ -400,11 +400,12 @@ int cf_to_rows(const float* src, long src_bstride, long pitch, int B, int C, int
 
 __global__ __launch_bounds__(256) void rows_to_cf_kernel(const float* __restrict__ src, int ld, int col0, int G, int S,
                                                          float* __restrict__ dst, long dst_bstride, int C, int T,
-                                                         const int* __restrict__ lens, const int* __restrict__ uoff) {
+                                                         const int* __restrict__ lens, const int* __restrict__ uoff,
+                                                         int len_mul, int len_add) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int tmax = lens ? min(lens[b], T) : T;
+  const int tmax = lens ? min(lens[b] * len_mul + len_add, T) : T;
   const long row0 = uoff ? (long)uoff[b] : (long)G + (long)b * S;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -420,11 +421,11 @@ __global__ __launch_bounds__(256) void rows_to_cf_kernel(const float* __restrict
 }
 
 int rows_to_cf(const float* src, int ld, int col0, int G, int S, float* dst, long dst_bstride, int B, int C, int T,
-               const int* lens, hipStream_t st, const int* uoff) {
+               const int* lens, hipStream_t st, const int* uoff, int len_mul, int len_add) {
   if (B <= 0 || T <= 0) return JV_OK;
   if (uoff && !lens) return fail(JV_ERR_ARG, "rows_to_cf: the compact geometry needs the lengths");
   hipLaunchKernelGGL(rows_to_cf_kernel, dim3(cdiv(T, 32), cdiv(C, 32), B), dim3(256), 0, st, src, ld, col0, G, S, dst,
-                     dst_bstride, C, T, lens, uoff);
+                     dst_bstride, C, T, lens, uoff, len_mul, len_add);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

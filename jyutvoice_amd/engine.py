@@ -609,6 +609,27 @@ class Engine:
                                                1 if streaming else 0, _ptr(h), _ptr(hl), _stream(self.device)))
         return h, hl
 
+    def upsample_encoder_tap(self, mode, prompt_token, prompt_len, token, token_len, tap, streaming=False, ctx_lens=None, out=None):
+        """jv_upsample_encoder_tap: the launches of prompt_encoder ("prompt": prompt_token None), flow_encoder ("flow"),
+        flow_encoder_partial ("partial") or flow_encoder_ctx ("ctx", with ctx_lens) up to and including the stage `tap` (a name of
+        _lib.UPS_TAPS), that stage's buffer as [B, C, rate (P + N)] with zeros at and behind every utterance's live length -- for the
+        tables of _lib.UPS_TABLES [2T - 1, 512], T = rate x the encoded width (P + N, "partial": P + N - 3).  (tap as a raw id, or
+        `out` given: passed on as they are -- the library rejects an id it does not know and a buffer that is too small)"""
+        B, N = token.shape
+        P = 0 if prompt_token is None else prompt_token.shape[1]
+        tok, tl = self._tok(token), self._tok(token_len)
+        ptok, pl = (self._tok(prompt_token), self._tok(prompt_len)) if P > 0 else (None, None)
+        cl = None if ctx_lens is None else self._lens32("upsample_encoder_tap", ctx_lens, B)
+        tap_id, C_, rate = _lib.UPS_TAPS[tap] if isinstance(tap, str) else (int(tap), 1, 1)
+        if out is None:
+            T = rate * (P + N - (3 if mode == "partial" else 0))
+            out = (torch.empty(2 * T - 1, 512, device=self.device) if tap in _lib.UPS_TABLES
+                   else torch.empty(B, C_, rate * (P + N), device=self.device))
+        check(self.lib.jv_upsample_encoder_tap(self._h, _lib.UPS_MODES[mode] if isinstance(mode, str) else int(mode), _ptr(ptok),
+                                               _ptr(pl), _ptr(tok), _ptr(tl), _ptr(cl), B, P, N, 1 if streaming else 0, tap_id,
+                                               _ptr(out), out.numel(), _stream(self.device)))
+        return out
+
     def flow_token2mel_ctx(self, prompt_token, prompt_len, token, token_len, ctx_lens, prompt_feat, feat_len, embedding,
                            streaming=False, n_timesteps=10, temperature=1.0, t_span=None):
         """jv_flow_token2mel_ctx: flow_token2mel with a look-ahead context per utterance (ctx_lens [B], each 0 or 3) ->

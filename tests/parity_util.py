@@ -98,16 +98,33 @@ class Recorder:
     """measured figures -> <output directory>/<name> (JV_OUT as the tools/ scripts read it, default out/), rewritten after every
     entry (a later failure keeps what was measured)"""
 
-    def __init__(self, name, header):
-        self.name, self.doc = name, dict(header, measured={})
+    def __init__(self, name, header, columns=None):
+        self.name, self.doc, self.columns = name, dict(header, measured={}), columns
+        if columns:
+            self.doc["columns"] = list(columns)
 
     def __call__(self, key, **vals):
         self.doc["measured"].setdefault(key, {}).update({k: float(f"{v:.3e}") for k, v in vals.items()})
+        self.write()
+        print(f"[{self.name}] {key}: " + ", ".join(f"{k}={v:.3e}" for k, v in vals.items()))
+
+    def table(self, key, rows):
+        """a test that measures hundreds of figures: rows = {sub-key: {column: value}} become ONE entry, each row a list in the order
+        of `columns`, behind one rewrite of the file, which then keeps an entry on one line"""
+        self.doc["measured"][key] = {k: [float(f"{v[c]:.3e}") for c in self.columns] for k, v in rows.items()}
+        self.write()
+        print(f"[{self.name}] {key}: {len(rows)} rows of {self.columns}")
+
+    def write(self):
         out = os.environ.get("JV_OUT") or os.path.join(REPO, "out")
         os.makedirs(out, exist_ok=True)
         with open(os.path.join(out, self.name), "w") as fh:
-            json.dump(self.doc, fh, indent=1, sort_keys=True)
-        print(f"[{self.name}] {key}: " + ", ".join(f"{k}={v:.3e}" for k, v in vals.items()))
+            if not self.columns:
+                json.dump(self.doc, fh, indent=1, sort_keys=True)
+                return
+            head = json.dumps({k: v for k, v in self.doc.items() if k != "measured"}, indent=1, sort_keys=True)
+            lines = [f'  {json.dumps(k)}: {json.dumps(v, separators=(",", ":"))}' for k, v in sorted(self.doc["measured"].items())]
+            fh.write(head[:head.rindex("}")].rstrip() + ',\n "measured": {\n' + ",\n".join(lines) + "\n }\n}\n")
 
 
 # ---- which geometry / regime did a call take?  Read from the in-library profiler, as tools/route_census.py does -----------------
