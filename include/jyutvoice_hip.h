@@ -99,6 +99,49 @@ int jv_flow_estimator_step(jv_context* ctx, const float* x, const int32_t* lens,
  * into x (the seam passes x.data_ptr() as the output address).  jyutvoice_amd.flow.estimator.HipEstimator wraps it. */
 int jv_flow_estimator_masked(jv_context* ctx, const float* x, const float* mask, const float* mu, const float* t,
                              const float* spks, const float* cond, int B2, int T, float* out, void* stream);
+/* jv_flow_estimator_tap (used by the parity tests): the launch sequence of ONE estimator evaluation up to and including one stage,
+ * whose buffer is copied out channels-first.  It runs the function the production entries run (Est::run, estimator.hip) with a
+ * tap descriptor: the same argument checks, row layout and route decision, the same launches in the same order; the launches
+ * behind the tap are not run, and an untapped call launches what it launched without this entry.  Two modes:
+ *   JV_EST_MODE_ENTRY  jv_flow_estimator_step: B = B2 samples as the caller gives them, t [B] one timestep per sample, uniform rows,
+ *                      the time embedding made inside the evaluation.  x, mu, cond [B,80,T], spks [B,80], lens [B] or NULL.
+ *   JV_EST_MODE_STEP   one evaluation of a step of jv_cfm_solve: B utterances laid out with their B unconditional twins (2B
+ *                      samples: twin b at sample B + b carries x of utterance b and zeros for mu, spks, cond), t [1] one timestep
+ *                      for all, its embedding made ahead of the evaluation as the solve makes every step's, the compact geometry of
+ *                      ragged batches exactly where jv_cfm_solve takes it (its one synchronisation included).  x, mu, cond
+ *                      [B,80,T], spks [B,80], lens [B] or NULL.  The only way to the whole-resnet launch and the compact tables.
+ *                      It is a step of the DEFAULT solve: always 2B samples and the embedding always made ahead.  A solve whose
+ *                      guidance rates are all 0 lays out B samples, and one under JV_NO_TEMB_PRE=1 or with more than 64 evaluations
+ *                      makes the embedding inside every evaluation; neither form is reachable here (the latter is ENTRY's).
+ * The context modes (jv_flow_set_streaming, _contraction, _precision) apply as to the entry mirrored.  Another mode or an unknown
+ * tap: JV_ERR_ARG; out_floats too small for the tap: JV_ERR_SHAPE; both behind the entry's own checks and ahead of its first launch.
+ * With S = B (ENTRY) or 2B (STEP) samples and n = B (ENTRY) or 1 (STEP) timesteps, taps in execution order (79 ids, 0 .. 78):
+ *   TSIN [n,320]  sin | cos of 1000 t f_j      T1 [n,1024]  SiLU(linear_1)      TMISH [n,1024]  Mish(linear_2)
+ *   TEMB [n,14 x 256]  the 14 resnets' projections of it, stage i at columns 256 i
+ *   XIN [S,320,T]  x | mu | spks | cond
+ *   RESi [S,256,T]  the resnet of stage i = 0 .. 13 (0: down, 1 .. 12: mid, 13: up, which reads cat[BLK12_3, BLK0_3])
+ *   BLKi_j [S,256,T]  transformer block j = 0 .. 3 of stage i (BLK0_3 is the skip connection)
+ *   DOWN, UPC [S,256,T]  the causal convolutions behind stage 0 and stage 13;  FIN [S,256,T]  final conv + LayerNorm + Mish + mask
+ *   D [S,80,T]  the projection: the entry's output
+ * Row taps hold exact zeros at and behind every sample's clamped length.  Stage 0 owns ids JV_EST_TAP_RES0 .. + 4 (its resnet and
+ * four blocks), stage i >= 1 ids JV_EST_TAP_RES1 + JV_EST_TAP_PER_STAGE (i - 1) .. + 4. */
+#define JV_EST_MODE_ENTRY 0
+#define JV_EST_MODE_STEP 1
+#define JV_EST_TAP_TSIN 0
+#define JV_EST_TAP_T1 1
+#define JV_EST_TAP_TMISH 2
+#define JV_EST_TAP_TEMB 3
+#define JV_EST_TAP_XIN 4
+#define JV_EST_TAP_RES0 5      /* BLK0_j = 6 + j */
+#define JV_EST_TAP_DOWN 10
+#define JV_EST_TAP_RES1 11     /* stage i >= 1: RESi = 11 + JV_EST_TAP_PER_STAGE (i - 1), BLKi_j = RESi + 1 + j */
+#define JV_EST_TAP_PER_STAGE 5
+#define JV_EST_TAP_UPC 76
+#define JV_EST_TAP_FIN 77
+#define JV_EST_TAP_D 78
+#define JV_EST_TAP_COUNT 79
+int jv_flow_estimator_tap(jv_context* ctx, int mode, const float* x, const int32_t* lens, const float* mu, const float* t,
+                          const float* spks, const float* cond, int B, int T, int tap, float* out, int64_t out_floats, void* stream);
 /* jv_flow_set_streaming: the `streaming=True` mode of CausalConditionalDecoder.forward (decoder.py:951-954, 976-979,
  * 999-1002 -> utils/mask.py:91-126,192-198): chunk-causal attention with static_chunk_size = chunk_frames (50 in
  * configs/base.yaml:98) and all left chunks; 0 restores full attention.  Applies to the following estimator / solver

@@ -58,6 +58,22 @@ for _i_blk in range(4):
 UPS_TAPS.update({"AN": (91, 512, 2), "H": (92, 80, 2)})
 UPS_TABLES = frozenset(k for k in UPS_TAPS if k.startswith(("PE", "POS_")))
 
+# jv_flow_estimator_tap: tap name -> (id, channels), in execution order, as include/jyutvoice_hip.h lists them (JV_EST_TAP_*).  The
+# time taps (EST_TIME_TAPS) are [n, C] -- n = B2 samples in the "entry" mode, 1 in the "step" mode; every other tap is [samples, C, T]
+# with samples = B2 ("entry") or 2 B ("step": the B utterances, then their unconditional twins).  RESi / BLKi_j: stage i = 0 .. 13
+EST_MODES = {"entry": 0, "step": 1}
+EST_STAGES, EST_BLOCKS = 14, 4
+EST_TAPS = {"TSIN": (0, 320), "T1": (1, 1024), "TMISH": (2, 1024), "TEMB": (3, EST_STAGES * 256), "XIN": (4, 320)}
+for _i_stage in range(EST_STAGES):
+    _id0 = 5 if _i_stage == 0 else 11 + 5 * (_i_stage - 1)
+    EST_TAPS[f"RES{_i_stage}"] = (_id0, 256)
+    for _j in range(EST_BLOCKS):
+        EST_TAPS[f"BLK{_i_stage}_{_j}"] = (_id0 + 1 + _j, 256)
+    if _i_stage == 0:
+        EST_TAPS["DOWN"] = (10, 256)
+EST_TAPS.update({"UPC": (76, 256), "FIN": (77, 256), "D": (78, 80)})
+EST_TIME_TAPS = ("TSIN", "T1", "TMISH", "TEMB")
+
 ACT = {"none": 0, "relu": 1, "gelu": 2, "mish": 3, "elu": 4, "silu": 5}
 PRO = {"none": 0, "snake": 1, "lrelu": 2}
 
@@ -91,6 +107,7 @@ SIGNATURES = {
     "jv_finalize": (_i, [_p, _i, _p]),
     "jv_flow_estimator_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
     "jv_flow_estimator_masked": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
+    "jv_flow_estimator_tap": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i64, _p]),
     "jv_flow_set_streaming": (_i, [_p, _i]),
     "jv_flow_set_graph": (_i, [_p, _i]),
     "jv_flow_set_guidance": (_i, [_p, _p, _i]),

@@ -330,6 +330,14 @@ int jv_flow_estimator_masked(jv_context* ctx, const float* x, const float* mask,
   return jv::flow_estimator(ctx->c, x, nullptr, mu, t, spks, cond, B2, T, out, static_cast<hipStream_t>(stream), mask);
 }
 
+int jv_flow_estimator_tap(jv_context* ctx, int mode, const float* x, const int32_t* lens, const float* mu, const float* t,
+                          const float* spks, const float* cond, int B, int T, int tap, float* out, int64_t out_floats, void* stream) {
+  CTX_GUARD(ctx);
+  if (!x || !mu || !t || !spks || !cond || !out) return jv::fail(JV_ERR_ARG, "jv_flow_estimator_tap: null tensor");
+  return jv::flow_estimator_tap(ctx->c, mode, x, lens, mu, t, spks, cond, B, T, tap, out, (long)out_floats,
+                                static_cast<hipStream_t>(stream));
+}
+
 int jv_flow_set_streaming(jv_context* ctx, int chunk_frames) {
   CTX_GUARD(ctx);
   if (chunk_frames < 0) return jv::fail(JV_ERR_ARG, "jv_flow_set_streaming: chunk must be >= 0");

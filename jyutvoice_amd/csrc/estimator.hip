@@ -8,6 +8,7 @@
 
 #include <algorithm>
 
+#include "../../include/jyutvoice_hip.h"
 #include "flow_ws.h"
 
 namespace jv {
@@ -119,6 +120,8 @@ struct ConvStackScope {
 struct Est {
   Context& c; FlowWs& w; const EstimatorW& e;
   const Geo& g; const EstRoute& rt; hipStream_t st;
+  const EstTap* tap;      // jv_flow_estimator_tap (else null): run() returns behind this stage's launches
+  bool tapped = false;    // ... and has copied its buffer out
   const long R = w.rows_alloc;          // rows of every workspace buffer (plane stride of the fp16 images kept in them)
   // every launcher of a call takes the route's product count in its argument record (`np`: read only where the launch runs fp16x3)
   int conv(ConvGemmArgs& a) { a.np = rt.np; return conv_gemm(a, 1, st); }
@@ -423,6 +426,15 @@ struct Est {
     return rowgemm(a, RG_RES, st);
   }
 
+  // jv_flow_estimator_tap: stage `id` stands in columns [0, C) of `buf` -- if it is the tap, out it goes, channels first, zeros at and
+  // behind every sample's clamped length (either geometry)
+  int stage_done(int id, const float* buf, int ld, int C = 256) {
+    if (!tap || tap->id != id) return JV_OK;
+    tapped = true;
+    return rows_to_cf(buf, ld, 0, FLOW_G, g.S, tap->out, (long)C * g.T, g.B2, C, g.T, w.lens2, st, g.uoff);
+  }
+  static int tap_res(int i) { return i == 0 ? JV_EST_TAP_RES0 : JV_EST_TAP_RES1 + JV_EST_TAP_PER_STAGE * (i - 1); }
+
   // the four blocks of stage i on the trunk buffer h; the last one may retarget its output (skip / concat buffer)
   int blocks(int i, float* h, float* last_out, int last_ldo) {
     const EstRoute::Stage& s = rt.stage[i];
@@ -440,6 +452,8 @@ struct Est {
       } else {
         JV_TRY(block_tiles(blk[j], next, j > 0 || s.ln_fold, h, out, ldo));
       }
+      JV_TRY(stage_done(tap_res(i) + 1 + j, out, ldo));
+      if (tapped) return JV_OK;
     }
     return JV_OK;
   }
@@ -457,11 +471,22 @@ struct Est {
   // the network (decoder.py:917-1018)
   int run() {
     // timestep embedding: sinusoid -> Linear+SiLU -> Linear (+Mish, the only consumer) -> 14 projections
-    if (!g.temb_pre) JV_TRY(time_embedding(c, g.t_ptr, g.t_stride, g.B2, w.tsin, w.t1, w.tmish, w.temb, st));
+    if (!g.temb_pre) JV_TRY(time_embedding(c, g.t_ptr, g.t_stride, g.B2, w.tsin, w.t1, w.tmish, w.temb, st, est_tap_time_stages(tap)));
+    if (tap && tap->id <= JV_EST_TAP_TEMB) {      // [n, C] rows as they stand: one per sample, or the step's one (temb_pre)
+      float* const bufs[4] = {w.tsin, w.t1, w.tmish, w.temb};
+      JV_HIP(hipMemcpyAsync(tap->out, bufs[tap->id], sizeof(float) * (g.temb_pre ? 1 : g.B2) * est_tap_channels(tap->id),
+                            hipMemcpyDeviceToDevice, st));
+      return JV_OK;
+    }
     // down: resnet -> 4 blocks (result doubles as the skip) -> causal conv
     JV_TRY(resnet(0, w.xin, 320, w.h));
+    JV_TRY(stage_done(tap_res(0), w.h, 256));
+    if (tapped) return JV_OK;
     JV_TRY(blocks(0, w.h, skip, 512));
+    if (tapped) return JV_OK;
     { ConvStackScope scope; JV_TRY(trunk_conv(e.down_conv, skip, 512, w.h)); }
+    JV_TRY(stage_done(JV_EST_TAP_DOWN, w.h, 256));
+    if (tapped) return JV_OK;
     // mid x12; the last block writes straight into columns [0,256) of the concat buffer.  On the whole-resnet launch the trunk
     // alternates between w.h and w.h2 (est_route: all twelve or none), and is back in w.h after the twelfth
     float* trunk = w.h;
@@ -469,20 +494,31 @@ struct Est {
       float* const dst = rt.stage[i].res != RES_ONE ? trunk : trunk == w.h ? w.h2 : w.h;
       JV_TRY(resnet(i, trunk, 256, dst));
       trunk = dst;
+      JV_TRY(stage_done(tap_res(i), trunk, 256));
+      if (tapped) return JV_OK;
       JV_TRY(blocks(i, trunk, i == EST_NMID ? w.cat : trunk, i == EST_NMID ? 512 : 256));
+      if (tapped) return JV_OK;
     }
     if (trunk != w.h) return fail(JV_ERR_STATE, "flow: the mid stages left the trunk in the scratch buffer");
     // up: resnet(cat[x, skip]) -> 4 blocks -> causal conv -> final block -> 1x1 projection
     JV_TRY(resnet(EST_NRES - 1, w.cat, 512, w.h));
+    JV_TRY(stage_done(tap_res(EST_NRES - 1), w.h, 256));
+    if (tapped) return JV_OK;
     JV_TRY(blocks(EST_NRES - 1, w.h, w.h, 256));
+    if (tapped) return JV_OK;
     ConvStackScope scope;
     JV_TRY(trunk_conv(e.up_conv, w.h, 256, w.h2));
+    JV_TRY(stage_done(JV_EST_TAP_UPC, w.h2, 256));
+    if (tapped) return JV_OK;
     JV_TRY(trunk_conv(e.final_conv, w.h2, 256, w.h, &e.final_ln));
+    JV_TRY(stage_done(JV_EST_TAP_FIN, w.h, 256));
+    if (tapped) return JV_OK;
     ConvGemmArgs a = base_args(g, w.h, 256, e.final_proj, w.d, 80);
     a.rowmask_in = w.rowmask;
     a.rowmask_out = w.rowmask;
     h3m(a, e.final_proj);
-    return conv(a);
+    JV_TRY(conv(a));
+    return stage_done(JV_EST_TAP_D, w.d, 80, 80);
   }
 };
 
@@ -490,21 +526,53 @@ struct Est {
 
 // timestep embedding of n timesteps t[i * t_stride]: sinusoid -> Linear + SiLU -> Linear (+ Mish, the only consumer) -> the 14
 // resnets' projections, emb [n, 14 * 256] (decoder.py:917-935, 98-108).  Rows are independent: a row's bits do not depend on n.
-int time_embedding(Context& c, const float* t, int t_stride, int n, float* sin_buf, float* h1, float* hm, float* emb, hipStream_t st) {
+// stages < 4 (jv_flow_estimator_tap): the first so many of the four launches
+int time_embedding(Context& c, const float* t, int t_stride, int n, float* sin_buf, float* h1, float* hm, float* emb, hipStream_t st,
+                   int stages) {
   const EstimatorW& e = c.est;
-  JV_TRY(time_sinusoid(t, t_stride, sin_buf, n, st));
+  JV_TRY(time_sinusoid(t, t_stride, c.flow->tfreq, sin_buf, n, st));
+  if (stages < 2) return JV_OK;
   Geo tg{n, 1, 1, n, n, nullptr, 1};
   ConvGemmArgs a = base_args(tg, sin_buf, 320, e.time1, h1, 1024);
   a.act = ACT_SILU;
   JV_TRY(conv_gemm(a, 1, st));
+  if (stages < 3) return JV_OK;
   a = base_args(tg, h1, 1024, e.time2, hm, 1024);
   a.act = ACT_MISH;
   JV_TRY(conv_gemm(a, 1, st));
+  if (stages < 4) return JV_OK;
   a = base_args(tg, hm, 1024, e.temb_all, emb, EST_NRES * 256);
   return conv_gemm(a, 1, st);
 }
 
-int estimator_body(Context& c, const Geo& g, const EstRoute& rt, hipStream_t st) { return Est{c, *c.flow, c.est, g, rt, st}.run(); }
+// channels of a tap's buffer (0: no such tap)
+int est_tap_channels(int id) {
+  if (id < 0 || id >= JV_EST_TAP_COUNT) return 0;
+  switch (id) {
+    case JV_EST_TAP_TSIN: case JV_EST_TAP_XIN: return 320;
+    case JV_EST_TAP_T1: case JV_EST_TAP_TMISH: return 1024;
+    case JV_EST_TAP_TEMB: return EST_NRES * 256;
+    case JV_EST_TAP_D: return 80;
+  }
+  return 256;
+}
+
+int est_tap_time_stages(const EstTap* tap) { return tap && tap->id <= JV_EST_TAP_TEMB ? tap->id + 1 : 4; }
+
+int est_tap_check(const EstTap* tap, int ns, int nt, int T) {
+  if (!tap) return JV_OK;
+  const int C = est_tap_channels(tap->id);
+  if (!C) return fail(JV_ERR_ARG, "jv_flow_estimator_tap: unknown tap");
+  if (!tap->out) return fail(JV_ERR_ARG, "jv_flow_estimator_tap: null out");
+  const long need = tap->id <= JV_EST_TAP_TEMB ? (long)nt * C : (long)ns * C * T;
+  if (tap->out_floats < need)
+    return fail(JV_ERR_SHAPE, "jv_flow_estimator_tap: out holds fewer floats than the tap ([n, C] for the time taps, else [samples, C, T])");
+  return JV_OK;
+}
+
+int estimator_body(Context& c, const Geo& g, const EstRoute& rt, hipStream_t st, const EstTap* tap) {
+  return Est{c, *c.flow, c.est, g, rt, st, tap}.run();
+}
 
 #ifdef JV_TUNING
 // tuning aid (JV_RB_STAMPS): phase breakdown of the LAST rowblock launch (with and without q|k|v) and rowconv launch of a solve

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 
+#include "../../include/jyutvoice_hip.h"
 #include "flow_ws.h"
 
 namespace jv {
@@ -41,6 +42,12 @@ int flow_ws_create(Context& c) {
   JV_TRY(F(&w->t1, (size_t)B2 * 1024));
   JV_TRY(F(&w->tmish, (size_t)B2 * 1024));
   JV_TRY(F(&w->temb, (size_t)B2 * EST_NRES * 256));
+  JV_TRY(F(&w->tfreq, 160));
+  {
+    float freq[160];
+    time_freq_table(freq);
+    JV_HIP(hipMemcpy(w->tfreq, freq, sizeof(freq), hipMemcpyHostToDevice));
+  }
   w->amax_stride = B2;
   JV_TRY(F(&w->amax, (size_t)3 * B2));
   JV_TRY(F(&w->t_dev, (size_t)B2));
@@ -130,9 +137,12 @@ __global__ void mask_to_lens_kernel(const float* __restrict__ mask, int T, int* 
   if (threadIdx.x == 0) lens[b] = n;
 }
 
+// tap (jv_flow_estimator_tap's ENTRY mode, else null): return behind the launches of that stage, its buffer in tap->out; `out` is
+// then not written
 int flow_estimator(Context& c, const float* x, const int* lens_dev, const float* mu, const float* t_dev, const float* spks,
-                   const float* cond, int B2, int T, float* out, hipStream_t st, const float* mask_f32) {
+                   const float* cond, int B2, int T, float* out, hipStream_t st, const float* mask_f32, const EstTap* tap) {
   JV_TRY(check_shape(c, B2, T));
+  JV_TRY(est_tap_check(tap, B2, B2, T));
   FlowWs& w = *c.flow;
   Geo g{B2, T, T + FLOW_GAP, flow_rows(B2, T), w.rows_alloc, w.t_dev, 1};
   // channels-first [B2,80,T] inputs -> row buffers (reusing x/mu/cond, which hold 2B utterances here)
@@ -145,8 +155,10 @@ int flow_estimator(Context& c, const float* x, const int* lens_dev, const float*
   JV_TRY(row_meta(w.rowmask, w.row_sample, w.lens2, B2, 1, FLOW_G, g.S, T, w.rows_alloc, 1, 0, st));
   JV_HIP(hipMemcpyAsync(w.t_dev, t_dev, sizeof(float) * B2, hipMemcpyDeviceToDevice, st));
   JV_TRY(assemble_xin_plain(w.x, w.mu, spks, w.cond, w.xin, B2, FLOW_G, g.S, T, g.M, st));
+  if (tap && tap->id == JV_EST_TAP_XIN) return rows_to_cf(w.xin, 320, 0, FLOW_G, g.S, tap->out, 320L * T, B2, 320, T, w.lens2, st);
   JV_HIP(hipMemsetAsync(w.amax, 0, sizeof(float) * 3 * w.amax_stride, st));
-  JV_TRY(estimator_body(c, g, est_route(c, g.M, false, false, c.attn_chunk), st));
+  JV_TRY(estimator_body(c, g, est_route(c, g.M, false, false, c.attn_chunk), st, tap));
+  if (tap) return JV_OK;
   return rows_to_cf(w.d, 80, 0, FLOW_G, g.S, out, 80L * T, B2, 80, T, nullptr, st);
 }
 
@@ -290,6 +302,36 @@ bool lens_all_equal(const int* h_lens, int B, int T) {
   for (int b = 1; b < B; ++b)
     if (std::min(std::max(h_lens[b], 0), T) != l0) return false;
   return true;
+}
+
+// What cfm_solve does between its schedule and its noise, shared with jv_flow_estimator_tap's STEP mode: the geometry of a batch of
+// B utterances laid out as g.B2 samples (compact where compact_plan says so), the clamped lengths, the row tables, and mu / cond as
+// rows.  Synchronises `st` once (the lengths of a ragged candidate come down with it; a caller's pageable staging is consumed by
+// it).  *clens: the lengths a further cf_to_rows of the call takes (compact: only an utterance's own frames are written);
+// *lens_equal: the host knows the B lengths to be the same
+int solve_pack(Context& c, Geo& g, const float* mu, const int* lens_dev, const float* cond, int B, int T, const int** clens,
+               bool* lens_equal, hipStream_t st) {
+  FlowWs& w = *c.flow;
+  // Ragged batch?  The lengths come down with the synchronisation below (which the staging vectors need anyway): B ints.
+  const bool ragged_candidate = lens_dev && B > 1 && flow_compact_ok(c, g.M);
+  if (ragged_candidate) JV_HIP(hipMemcpyAsync(w.h_lens, lens_dev, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+  // pageable-host staging vectors die at scope exit: make sure the copies have been consumed
+  JV_HIP(hipStreamSynchronize(st));
+  if (ragged_candidate) JV_TRY(solve_compact(c, g, w.h_lens, B, T, st));
+
+  // pack: lengths (duplicated for the CFG twin rows), masks, row-layout mu / cond
+  if (lens_dev) {
+    JV_TRY(clamp_lens(lens_dev, B, g.B2 / B, T, w.lens2, st));      // (the layout above used the same clamp on the host copy)
+  } else {
+    JV_TRY(fill_int(w.lens2, T, g.B2, st));
+  }
+  *clens = g.uoff ? w.lens2 : nullptr;
+  JV_TRY(row_meta(w.rowmask, w.row_sample, w.lens2, g.B2, 1, FLOW_G, g.S, T, w.rows_alloc, 1, 0, st, g.uoff));
+  JV_TRY(cf_to_rows(mu, 80L * T, T, B, 80, T, w.mu, 80, 0, FLOW_G, g.S, 1.f, *clens, st, g.uoff));
+  JV_TRY(cf_to_rows(cond, 80L * T, T, B, 80, T, w.cond, 80, 0, FLOW_G, g.S, 1.f, *clens, st, g.uoff));
+  // (equal lengths: known where none were passed or where the ragged check brought them down)
+  *lens_equal = !lens_dev || (ragged_candidate && lens_all_equal(w.h_lens, B, T));
+  return JV_OK;
 }
 
 // the Euler loop on packed row buffers (w.mu, w.cond, w.x = z, w.lens2, row metadata): the result is left in w.x
@@ -472,31 +514,44 @@ int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spk
 
   std::vector<float> tt, dts;
   JV_TRY(solve_schedule(c, w, n_timesteps, t_span_host, tt, dts, st));
-  // Ragged batch?  The lengths come down with the synchronisation below (which the staging vectors need anyway): B ints.
-  const bool ragged_candidate = lens_dev && B > 1 && flow_compact_ok(c, g.M);
-  if (ragged_candidate) JV_HIP(hipMemcpyAsync(w.h_lens, lens_dev, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-  // pageable-host staging vectors die at scope exit: make sure the copies have been consumed
-  JV_HIP(hipStreamSynchronize(st));
-  if (ragged_candidate) JV_TRY(solve_compact(c, g, w.h_lens, B, T, st));
-
-  // pack: lengths (duplicated for the CFG twin rows), masks, row-layout mu / cond / z
-  if (lens_dev) {
-    JV_TRY(clamp_lens(lens_dev, B, B2 / B, T, w.lens2, st));      // (the layout above used the same clamp on the host copy)
-  } else {
-    JV_TRY(fill_int(w.lens2, T, B2, st));
-  }
-  const int* const clens = g.uoff ? w.lens2 : nullptr;      // (compact: only an utterance's own frames are written)
-  JV_TRY(row_meta(w.rowmask, w.row_sample, w.lens2, B2, 1, FLOW_G, g.S, T, w.rows_alloc, 1, 0, st, g.uoff));
-  JV_TRY(cf_to_rows(mu, 80L * T, T, B, 80, T, w.mu, 80, 0, FLOW_G, g.S, 1.f, clens, st, g.uoff));
-  JV_TRY(cf_to_rows(cond, 80L * T, T, B, 80, T, w.cond, 80, 0, FLOW_G, g.S, 1.f, clens, st, g.uoff));
+  bool lens_equal = false;
+  const int* clens = nullptr;
+  JV_TRY(solve_pack(c, g, mu, lens_dev, cond, B, T, &clens, &lens_equal, st));      // (its synchronisation has consumed tt / dts)
   // z = rand_noise[:, :, :T] * temperature, the same prefix for every utterance (flow_matching.py:385)
   JV_TRY(cf_to_rows(c.noise, 0, NOISE_FRAMES, B, 80, T, w.x, 80, 0, FLOW_G, g.S, temperature, clens, st, g.uoff));
 
-  // (equal lengths: known where none were passed or where the ragged check brought them down)
-  const bool lens_equal = !lens_dev || (ragged_candidate && lens_all_equal(w.h_lens, B, T));
   JV_TRY(solve_loop(c, g, spks, B, T, n_timesteps, lens_equal, st));
   // unpack
   return rows_to_cf(w.x, 80, 0, FLOW_G, g.S, mel, 80L * T, B, 80, T, lens_dev ? w.lens2 : nullptr, st, g.uoff);
+}
+
+// jv_flow_estimator_tap.  ENTRY: flow_estimator with the tap.  STEP: ONE evaluation as solve_loop's euler_step runs it inside
+// cfm_solve -- cfm_solve's checks and pack (solve_pack: the compact geometry exactly where a solve takes it), x as given in the
+// noise's place, B unconditional twins, one t whose embedding is made ahead of the evaluation (time_embedding over n = 1 straight
+// into w.temb, where step_advance_kernel would move the step's row), the maxima zeroed as at the head of a solve, the route of a
+// solve's steps -- up to the tap.  No CFG update: the tap is the evaluation's own
+int flow_estimator_tap(Context& c, int mode, const float* x, const int* lens_dev, const float* mu, const float* t_dev,
+                       const float* spks, const float* cond, int B, int T, int tap_id, float* out, long out_floats, hipStream_t st) {
+  const EstTap tap{tap_id, out, out_floats};
+  if (mode == JV_EST_MODE_ENTRY) return flow_estimator(c, x, lens_dev, mu, t_dev, spks, cond, B, T, nullptr, st, nullptr, &tap);
+  if (mode != JV_EST_MODE_STEP) return fail(JV_ERR_ARG, "jv_flow_estimator_tap: mode is JV_EST_MODE_ENTRY or JV_EST_MODE_STEP");
+  JV_TRY(check_shape(c, 2 * B, T));
+  JV_TRY(est_tap_check(&tap, 2 * B, 1, T));
+  FlowWs& w = *c.flow;
+  Geo g{2 * B, T, T + FLOW_GAP, flow_rows(2 * B, T), w.rows_alloc, nullptr, 0};
+  bool lens_equal = false;
+  const int* clens = nullptr;
+  JV_TRY(solve_pack(c, g, mu, lens_dev, cond, B, T, &clens, &lens_equal, st));
+  JV_TRY(cf_to_rows(x, 80L * T, T, B, 80, T, w.x, 80, 0, FLOW_G, g.S, 1.f, clens, st, g.uoff));
+  JV_HIP(hipMemsetAsync(w.amax, 0, sizeof(float) * 3 * w.amax_stride, st));
+  JV_HIP(hipMemcpyAsync(w.spks, spks, sizeof(float) * 80 * B, hipMemcpyDeviceToDevice, st));
+  g.t_ptr = w.t_cur;
+  g.temb_pre = true;
+  JV_TRY(time_embedding(c, t_dev, 1, 1, w.tsin, w.t1, w.tmish, w.temb, st, est_tap_time_stages(&tap)));
+  const EstRoute route = est_route(c, g.M, true, g.uoff != nullptr, c.attn_chunk);
+  JV_TRY(assemble_xin(w.x, w.mu, w.spks, w.cond, w.xin, B, B, FLOW_G, g.S, T, g.M, st, g.uoff, w.row_sample, w.rowmask));
+  if (tap.id == JV_EST_TAP_XIN) return rows_to_cf(w.xin, 320, 0, FLOW_G, g.S, tap.out, 320L * T, 2 * B, 320, T, w.lens2, st, g.uoff);
+  return estimator_body(c, g, route, st, &tap);
 }
 
 // The voice-cloning batch: utterance b's sequence is [prompt_b | text_b], p_b + y_b frames, with its own split point

@@ -47,6 +47,7 @@ struct FlowWs {
   unsigned long long* rc_stamps = nullptr;      // ... and rowconv_wd_kernel's
   float *d = nullptr;                                                 // [rows,80]
   float *tsin = nullptr, *t1 = nullptr, *tmish = nullptr, *temb = nullptr;
+  float* tfreq = nullptr;      // [160] the sinusoid's fp32 frequency table (time_freq_table)
   float *t_dev = nullptr, *t_table = nullptr, *dt_table = nullptr;
   // (t_table, dt_table, cfg_table hold one entry per estimator EVALUATION: an Euler step is one, a midpoint / Heun step two, and
   // dt_table holds the coefficient of the evaluation's update -- dt, or 0.5f dt in a half stage; solve_schedule)
@@ -126,9 +127,23 @@ struct EstRoute {
 // estimator.hip
 // res_one = false: no whole-resnet launch even where it fits (a solve's shared first step keeps the later steps' resnet route)
 EstRoute est_route(const Context& c, long M, bool temb_pre, bool compact, int attn_chunk, bool res_one = true);
-int time_embedding(Context& c, const float* t, int t_stride, int n, float* sin_buf, float* h1, float* hm, float* emb, hipStream_t st);
+// jv_flow_estimator_tap: the stage whose buffer an evaluation copies out before it returns early (null: the whole evaluation)
+struct EstTap {
+  int id;
+  float* out;
+  long out_floats;
+};
+int est_tap_channels(int id);      // channels of a tap's buffer (0: no such tap)
+// ahead of an entry's first launch: the tap exists and `out` holds it ([nt, C] for the time taps, [ns, C, T] for the row taps)
+int est_tap_check(const EstTap* tap, int ns, int nt, int T);
+// the launches up to the stage `tap` names alone (a tap behind TEMB, or none: all four)
+int est_tap_time_stages(const EstTap* tap);
+// stages: the first so many of the four launches (sinusoid, linear_1, linear_2, the projections)
+int time_embedding(Context& c, const float* t, int t_stride, int n, float* sin_buf, float* h1, float* hm, float* emb, hipStream_t st,
+                   int stages = 4);
 // the estimator body on prepared inputs: ws.xin [rows,320], ws.rowmask/row_sample/lens2, ws.t_dev [B2] -> ws.d [rows,80]
-int estimator_body(Context& c, const Geo& g, const EstRoute& rt, hipStream_t st);
+// tap: return behind the launches of that stage, its buffer copied out (the entry has run est_tap_check; XIN is the entry's own)
+int estimator_body(Context& c, const Geo& g, const EstRoute& rt, hipStream_t st, const EstTap* tap = nullptr);
 #ifdef JV_TUNING
 int est_stamps_dump(Context& c, const Geo& g, hipStream_t st);      // JV_RB_STAMPS: print the stamps the last launches left
 #endif

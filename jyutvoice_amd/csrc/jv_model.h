@@ -211,8 +211,12 @@ int flow_ws_create(Context& c);
 void flow_ws_forget_attention(Context& c, hipStream_t st);   // zero the attention buffer (new weights / contraction mode)
 bool flow_has_graphs(const Context& c);
 void flow_graphs_drop(Context& c);   // forget captured Euler-step graphs (weights or workspace pointers changed)
+struct EstTap;      // flow_ws.h
 int flow_estimator(Context& c, const float* x, const int* lens_dev, const float* mu, const float* t_dev, const float* spks,
-                   const float* cond, int B2, int T, float* out, hipStream_t st, const float* mask_f32 = nullptr);
+                   const float* cond, int B2, int T, float* out, hipStream_t st, const float* mask_f32 = nullptr,
+                   const EstTap* tap = nullptr);
+int flow_estimator_tap(Context& c, int mode, const float* x, const int* lens_dev, const float* mu, const float* t_dev,
+                       const float* spks, const float* cond, int B, int T, int tap_id, float* out, long out_floats, hipStream_t st);
 int cfm_solve(Context& c, const float* mu, const int* lens_dev, const float* spks, const float* cond, int B, int T,
               int n_timesteps, float temperature, const float* t_span_host, float* mel, hipStream_t st);
 int cfm_solve_prompted(Context& c, const float* mu_y, const int* y_lens, const float* prompt_h, const float* prompt_feat,

@@ -31,7 +31,8 @@ int assemble_xin(const float* x, const float* mu, const float* spks, const float
                  const unsigned char* rowmask = nullptr);
 int assemble_xin_plain(const float* x, const float* mu, const float* spks, const float* cond, float* xin, int B, int G,
                        int S, int L, long rows, hipStream_t st);
-int time_sinusoid(const float* t, int t_stride, float* out, int B, hipStream_t st);
+void time_freq_table(float* f);      // [160], host: the sinusoid's frequencies, correctly rounded
+int time_sinusoid(const float* t, int t_stride, const float* freq, float* out, int B, hipStream_t st);      // freq: that table on the device
 // rate: the step's guidance rate, one float on the device.  one_twin: every utterance reads the twin at slot B.  no_twin: the
 // step of rate 0 on B utterances alone, x += dt d (rate is not read, no twin row is addressed)
 int euler_cfg(float* x, const float* d, int B, int G, int S, int L, const float* dt_table, int step, const float* rate,

@@ -595,18 +595,26 @@ int assemble_xin_plain(const float* x, const float* mu, const float* spks, const
 }
 
 // ---- sinusoidal timestep embedding (jyutvoice/flow/decoder.py:21-30), 320 = 160 sin | 160 cos ------------
-__global__ void time_sinusoid_kernel(const float* __restrict__ t, int t_stride, float* __restrict__ out, int B) {
+// f_j = exp(j c), j = 0 .. 159, as fp32 (decoder.py:24): c = -(ln 10000) / 159 and the product j c in fp32 like torch, the
+// exponential correctly rounded (fp64 exp, rounded once).  The device's expf lands an ulp from that in some entries, and the angle
+// (1000 t) f carries 1000 t times the difference: 6.1e-6 in sin / cos at t = 0.3, 174 x the fp32 floor of the row
+// (tests/test_gpu_est_stages.py, TSIN; with this table: 1.6 x at the most).  The table is made on the host, once per context (flow.hip), as rope_theta_table is.
+void time_freq_table(float* f) {
+  const float c = (float)(-9.210340371976184 / 159.0);
+  for (int j = 0; j < 160; ++j) f[j] = (float)exp((double)((float)j * c));
+}
+
+__global__ void time_sinusoid_kernel(const float* __restrict__ t, int t_stride, const float* __restrict__ freq,
+                                     float* __restrict__ out, int B) {
   const int b = blockIdx.x, j = threadIdx.x;   // 160 threads
   if (b >= B || j >= 160) return;
-  const float c = (float)(-9.210340371976184 / 159.0);     // -(ln 10000)/(half-1), rounded to f32 like torch
-  const float f = expf((float)j * c);
-  const float a = (1000.0f * t[b * t_stride]) * f;
+  const float a = (1000.0f * t[b * t_stride]) * freq[j];      // in fp32 like torch
   out[b * 320 + j] = sinf(a);
   out[b * 320 + 160 + j] = cosf(a);
 }
 
-int time_sinusoid(const float* t, int t_stride, float* out, int B, hipStream_t st) {
-  hipLaunchKernelGGL(time_sinusoid_kernel, dim3(B), dim3(192), 0, st, t, t_stride, out, B);
+int time_sinusoid(const float* t, int t_stride, const float* freq, float* out, int B, hipStream_t st) {
+  hipLaunchKernelGGL(time_sinusoid_kernel, dim3(B), dim3(192), 0, st, t, t_stride, freq, out, B);
   JV_HIP(hipGetLastError());
   return JV_OK;
 }

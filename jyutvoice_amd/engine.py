@@ -231,6 +231,27 @@ class Engine:
                                               _ptr(out), _stream(self.device)))
         return out
 
+    def flow_estimator_tap(self, mode, x, mask_lens, mu, t, spks, cond, tap, out=None):
+        """jv_flow_estimator_tap: the launches of one estimator evaluation up to and including the stage `tap` (a name of
+        _lib.EST_TAPS), that stage's buffer channels first, zeros at and behind every sample's clamped length.  mode "entry":
+        flow_estimator's call (x, mu, cond [B2,80,T], t [B2], spks [B2,80]) -> [B2, C, T]; mode "step": one evaluation of a
+        cfm_solve step over B utterances and their B unconditional twins (x, mu, cond [B,80,T], t one scalar, spks [B,80]) ->
+        [2B, C, T], twin b at sample B + b.  The time taps (_lib.EST_TIME_TAPS) are [B2, C] / [1, C].  (mode or tap as a raw
+        id, or `out` given: passed on as they are -- the library rejects what it does not know and a buffer that is too small)"""
+        B, _, T = x.shape
+        x, mu, cond = (_f32(v, self.device) for v in (x, mu, cond))
+        t, spks = _f32(torch.as_tensor(t).reshape(-1), self.device), _f32(spks, self.device)
+        lens = None if mask_lens is None else mask_lens.to(device=self.device, dtype=torch.int32).contiguous()
+        step = mode in ("step", _lib.EST_MODES["step"])
+        tap_id, C_ = _lib.EST_TAPS[tap] if isinstance(tap, str) else (int(tap), 1)
+        if out is None:
+            out = (torch.empty(1 if step else B, C_, device=self.device) if tap in _lib.EST_TIME_TAPS
+                   else torch.empty(2 * B if step else B, C_, T, device=self.device))
+        check(self.lib.jv_flow_estimator_tap(self._h, _lib.EST_MODES[mode] if isinstance(mode, str) else int(mode), _ptr(x), _ptr(lens),
+                                             _ptr(mu), _ptr(t), _ptr(spks), _ptr(cond), B, T, tap_id, _ptr(out), out.numel(),
+                                             _stream(self.device)))
+        return out
+
     def cfm_solve(self, mu, lens, spks, cond, n_timesteps, temperature=1.0, t_span=None):
         B, _, T = mu.shape
         mu, cond, spks = _f32(mu, self.device), _f32(cond, self.device), _f32(spks, self.device)
